@@ -17,10 +17,16 @@ reference): un-fused, 64x128^3 of saved activations does not fit 288 GB (SURVEY 
 micro-batches of M chunks instead (M = 16: 123 GB, about +1 % throughput, statistics per 16 chunks).  Inputs are
 resident in HBM before the timed region.  Weak scaling: the per-GPU batch is fixed.
 
-Rank 0 prints one JSON line: metric/value (whole-job voxels/s), roofline of the dominant kernel
-(3x3x3 conv forward / backward-data as Winograd F(2x2,3x3)-over-(z,y) implicit GEMMs on fp32 MFMA, timed live with HIP
-events: `frac` prices the MFMA FLOPs the kernel really issues, 4/9 of the direct form's), cpu_baseline (the oracle's
-torch-CPU DC3D timed on this box's host cores).
+Rank 0 prints one JSON line: metric/value (whole-job voxels/s), ms_per_step, the losses of the timed steps.  A plain
+run does only what that headline needs: set-up, the fit probe, `--warmup` steps, `--steps` timed steps, the line.
+`--full` adds what takes time of its own: the roofline of the dominant kernel (3x3x3 conv forward / backward-data as
+Winograd F(2x2,3x3)-over-(z,y) implicit GEMMs on fp32 MFMA, timed live with HIP events inside the timed steps: `frac`
+prices the MFMA FLOPs the kernel really issues, 4/9 of the direct form's), cpu_baseline (the oracle's torch-CPU DC3D
+timed on this box's host cores), the measured ceilings, the reference-shape steps and the inference step.
+
+`--dump-outputs DIR` writes what the last timed step handed its caller (losses, parameters, gradients, BatchNorm
+running statistics) as DIR/<name>.npy; the inputs and the initial model are seeded, so two builds given the same
+arguments can be compared output for output.
 """
 import argparse
 import json
@@ -37,6 +43,8 @@ for _p in (ROOT, PKG):
 PEAK_FP32_MFMA_TFLOPS = 157.3   # MI355X_MICROARCH.md: v_mfma_f32_32x32x2_f32 / 16x16x4 dense peak
 PEAK_HBM_GBS = 8000.0
 PMC_MICRO = 64        # micro-batch of the rocprofv3 --pmc passes behind profiles/pmc_traffic.json (per-launch bytes scale with it)
+DUMP_SAMPLE = 1 << 18  # --dump-outputs: elements kept of a larger tensor (1 MB of float32 per file; ~22 MB for the whole model)
+DUMP_LIMIT = 64 << 20
 
 
 def wz_factor(kernel_name):
@@ -60,17 +68,23 @@ def parse():
     ap.add_argument("--norm", default="bn", help="norm_method of the model (reference default: bn)")
     ap.add_argument("--checkpoint-mode", default="stats", choices=["stats", "recompute"],
                     help="how checkpoint_layers flags are honoured (models.DC3D.checkpoint_mode)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true", help="also measure what the headline does not need: per-kernel HIP "
+                    "events and the roofline, the CPU baseline, measured ceilings, reference-shape and inference steps")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="write what the last timed step computed as DIR/<name>.npy")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="(--full) skip the CPU baseline")
     ap.add_argument("--cpu-seconds", type=float, default=90.0, help="budget for the CPU baseline sample (1 warm-up + 3 reps "
                     "at 2x64^3 and at 1x128^3: ~60 s on 16 threads)")
-    ap.add_argument("--no-kernel-timer", action="store_true", help="skip the per-kernel HIP-event pass")
-    ap.add_argument("--no-att", action="store_true", help="skip the side lines (reference-shape steps, inference step, "
-                    "measured ceilings) reported beside the headline")
+    ap.add_argument("--no-kernel-timer", action="store_true", help="(--full) skip the per-kernel HIP-event pass")
+    ap.add_argument("--no-att", action="store_true", help="(--full) skip the side lines (reference-shape steps, inference "
+                    "step, measured ceilings) reported beside the headline")
     ap.add_argument("--no-overlap", action="store_true", help="reduce the gradient buckets after backward instead of inside it "
                     "(A/B of the overlap; N > 1 only)")
     ap.add_argument("--backend", default="nccl", help="torch.distributed backend for N > 1 (nccl = RCCL over xGMI; "
                     "gloo only to rehearse the multi-rank path with several ranks on one GPU)")
-    return ap.parse_args()
+    args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    return args
 
 
 def ensure_built():
@@ -246,6 +260,33 @@ def inference_step(dev, shape=(300, 512, 512), reps=3):
             "lesion_ratio": res["lesion_ratio"], "mask_voxels": int(res["mask"].sum()), "mask_post_voxels": int(res["mask_post"].sum())}
 
 
+def dump_outputs(out_dir, model, last_loss):
+    """--dump-outputs: what the last timed step handed its caller, as DIR/<name>.npy -- `loss_reg` / `loss_seg` (float64,
+    this rank's shard as the step returned them), then the model after it: `param.<name>`, `grad.<name>` (the step's
+    gradients, all-reduced when N > 1) and `buffer.<name>` (BatchNorm running statistics) in float32.  A tensor of more than
+    DUMP_SAMPLE elements is written as DUMP_SAMPLE of its flat positions, drawn from a fixed seed and sorted: the same
+    positions on every run, so that two builds can be compared output for output."""
+    import numpy as np
+    import torch
+    os.makedirs(out_dir, exist_ok=True)
+    arrays = {"loss_reg": np.array([float(last_loss[0])]), "loss_seg": np.array([float(last_loss[1])])}
+    tensors = [(f"param.{n}", p) for n, p in model.named_parameters()]
+    tensors += [(f"grad.{n}", p.grad) for n, p in model.named_parameters() if p.grad is not None]
+    tensors += [(f"buffer.{n}", b) for n, b in model.named_buffers() if b.is_floating_point()]
+    with torch.no_grad():
+        for name, t in tensors:
+            t = t.detach()
+            if t.numel() > DUMP_SAMPLE:
+                pos = np.sort(np.random.default_rng(0).choice(t.numel(), DUMP_SAMPLE, replace=False))
+                t = t.reshape(-1)[torch.from_numpy(pos).to(t.device)]
+            arrays[name] = t.float().cpu().numpy()
+    total = sum(a.nbytes for a in arrays.values())
+    if total > DUMP_LIMIT:
+        raise RuntimeError(f"bench.py: --dump-outputs would write {total} bytes (limit {DUMP_LIMIT})")
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+
+
 def launch_ranks(n):
     """`python bench.py --gpus N` without a launcher: start the N ranks as fresh child processes (one per GPU,
     `python -m torch.distributed.run`), before this process has imported torch or touched the GPU, and return
@@ -373,8 +414,8 @@ def main():
     for i in range(args.warmup):
         trainer.step(batch, micro)
     args.micro = micro
-    # per-kernel HIP events (one pair per conv launch, on the launch stream) ride along in the timed region
-    use_timer = not args.no_kernel_timer
+    # --full: per-kernel HIP events (one pair per conv launch, on the launch stream) ride along in the timed region
+    use_timer = args.full and not args.no_kernel_timer
     sync()
     if use_timer:
         HF.TIMER = HF.KernelTimer()
@@ -393,6 +434,8 @@ def main():
         gfinite = all(bool(torch.isfinite(p.grad).all()) for p in model.parameters() if p.grad is not None)
         pfinite = all(bool(torch.isfinite(p).all()) for p in model.parameters())
     finite = bool(gfinite and pfinite and all(x == x and abs(x) != float("inf") for pair in loss_hist for x in pair))
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(args.dump_outputs, model, loss_hist[-1])
     if use_dist:
         t = torch.tensor([elapsed], dtype=torch.float64, device=dev)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
@@ -460,7 +503,9 @@ def main():
 
     cpu = None
     cpu_note = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if not args.full:
+        cpu_note = "not run (--full only)"
+    elif rank == 0 and world == 1 and not args.no_cpu_baseline:
         cpu = cpu_baseline(args.cpu_seconds)
     elif world > 1:
         cpu_note = "the CPU baseline is timed on rank 0 at N = 1 only (bench contract): see the n_gpus = 1 line"
@@ -473,7 +518,7 @@ def main():
     ck_mode = model.checkpoint_mode
     peak_alloc = torch.cuda.max_memory_allocated() / 2 ** 30
     peak_res = torch.cuda.max_memory_reserved() / 2 ** 30
-    if rank == 0 and world == 1 and not args.no_att:
+    if args.full and rank == 0 and world == 1 and not args.no_att:
         del trainer, opt, model, batch, losses
         torch.cuda.empty_cache()
         ceilings = measured_ceilings(dev)
@@ -489,13 +534,13 @@ def main():
         flops_per_voxel = 5415936.0     # fwd+bwd algorithmic FLOPs per input voxel
         tot_alg = sum(d["flops"] for d in summ.values())
         tot_ex = sum(d["flops"] * wz_factor(k) for k, d in summ.items())
-        exec_ratio = tot_ex / tot_alg if tot_alg else (2.0 / 3.0)
+        exec_ratio = tot_ex / tot_alg if tot_alg else (2.0 / 3.0) if args.full else None
         line = {
             "metric": "voxels/sec fwd+bwd (DC3D train step) on 64x128^3 CT chunks per GPU",
             "batchnorm_statistics_over_chunks": args.micro,
             "value": value, "unit": "voxels/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
             "ms_per_step": ms_per_step, "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
-            "dtype": "f32", "data": "synthetic",
+            "dtype": "f32", "data": "synthetic", "full": args.full,
             "config": {"workload": f"DC3D st_dram_ref (norm={args.norm}, checkpoint_layers as shipped, honoured as "
                                    f"'{ck_mode}') "
                                    f"fwd+loss+bwd+Adam, {args.chunks}x1x{args.size}^3 chunks per GPU, "
@@ -508,7 +553,8 @@ def main():
             "hbm_total_gb": torch.cuda.get_device_properties(dev).total_memory / 2 ** 30,
             # whole step against the fp32 peak: executed = what the kernels issue (conv FLOPs x 2/3 resp. 4/9 where the
             # Winograd kernels run: every layer but the first), algorithmic = the direct-conv count of SURVEY 8(d)
-            "network_executed_frac_of_fp32_peak": value / world * flops_per_voxel * exec_ratio / (PEAK_FP32_MFMA_TFLOPS * 1e12),
+            "network_executed_frac_of_fp32_peak": None if exec_ratio is None else
+            value / world * flops_per_voxel * exec_ratio / (PEAK_FP32_MFMA_TFLOPS * 1e12),
             "network_algorithmic_equiv_tflops": value / world * flops_per_voxel / 1e12,
             # the losses of the timed steps (rank 0's shard; reg summed over its chunks, seg weighted by its share of the
             # global batch), a checksum of the parameters after the last step, and whether everything is finite

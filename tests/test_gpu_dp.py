@@ -174,7 +174,7 @@ def test_bench_two_ranks_over_gloo_as_a_child_process():
     env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0")
     env.pop("WORLD_SIZE", None); env.pop("RANK", None); env.pop("LOCAL_RANK", None)
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--backend", "gloo", "--chunks", "2",
-                        "--size", "32", "--micro", "2", "--steps", "1", "--warmup", "1", "--no-cpu-baseline", "--no-att"],
+                        "--size", "32", "--micro", "2", "--steps", "1", "--warmup", "1", "--full", "--no-cpu-baseline", "--no-att"],
                        env=env, capture_output=True, text=True, timeout=420)
     assert r.returncode == 0, r.stdout[-1500:] + r.stderr[-3000:]
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
