@@ -9,14 +9,14 @@
 // Both only launch; bench.py brackets them with HIP events on the launch stream.  No result is consumed: `sink` receives one
 // float per thread so that the loop is not removed.
 #include "common.h"
-#include <stdlib.h>
 
 namespace dram {
 
 typedef float calib_f32x16 __attribute__((ext_vector_type(16)));
 typedef float calib_f32x4 __attribute__((ext_vector_type(4)));
 
-// U independent 16-byte loads per thread in flight before the first store; one pass, no loop (a block = 256 x U x 16 B)
+// U independent 16-byte loads per thread in flight before the first store; one pass, no loop (a block = 256 x U x 16 B).
+// dram_calibrate_hbm_copy launches <1, true>, the fastest form measured.
 template <int U, bool NT>
 __global__ __launch_bounds__(256) void calibrate_copy_kernel(const calib_f32x4* __restrict__ src, calib_f32x4* __restrict__ dst, size_t n16) {
     const size_t base = (size_t)blockIdx.x * (256 * U) + threadIdx.x;
@@ -65,18 +65,12 @@ extern "C" int dram_calibrate_hbm_copy(const void* src, void* dst, size_t nbytes
     DRAM_REQUIRE(src && dst && nbytes >= 16 && nbytes % 16 == 0, "calibrate_hbm_copy: need two buffers of a multiple of 16 bytes");
     DRAM_REQUIRE(((((unsigned long long)src) | ((unsigned long long)dst)) & 15ull) == 0, "calibrate_hbm_copy: buffers must be 16-byte aligned");
     const size_t n16 = nbytes / 16;
-    // Measured on MI355X (scripts/calib_sweep.py, 1 GiB, read + written bytes / time): one 16-byte load per thread, non-temporal:
-    // 6.64 TB/s; the same with default cache policy 6.24; four loads in flight per thread 5.68 / 6.21 (nt); eight 4.33 / 4.38.
-    static const int variant = getenv("DRAM_CALIB_COPY_VARIANT") ? atoi(getenv("DRAM_CALIB_COPY_VARIANT")) : 5;   // (sweeps only)
-    const int U = (variant & 3) == 1 ? 1 : ((variant & 3) == 2 ? 8 : 4);
-    const size_t blocks = (n16 + (size_t)256 * U - 1) / ((size_t)256 * U);
+    // Measured on MI355X (1 GiB, read + written bytes / time): one 16-byte load per thread, non-temporal: 6.64 TB/s; the same
+    // with default cache policy 6.24; four loads in flight per thread 5.68 / 6.21 (nt); eight 4.33 / 4.38.
+    const size_t blocks = (n16 + 255) / 256;
     DRAM_REQUIRE(blocks <= 0x7fffffffull, "calibrate_hbm_copy: buffer too large");
-    const dim3 grid((unsigned)blocks), blk(256);
-    hipStream_t st = (hipStream_t)stream;
-    const bool nt = (variant & 4) != 0;
-    if (U == 1) { if (nt) hipLaunchKernelGGL((calibrate_copy_kernel<1, true>), grid, blk, 0, st, (const calib_f32x4*)src, (calib_f32x4*)dst, n16); else hipLaunchKernelGGL((calibrate_copy_kernel<1, false>), grid, blk, 0, st, (const calib_f32x4*)src, (calib_f32x4*)dst, n16); }
-    else if (U == 8) { if (nt) hipLaunchKernelGGL((calibrate_copy_kernel<8, true>), grid, blk, 0, st, (const calib_f32x4*)src, (calib_f32x4*)dst, n16); else hipLaunchKernelGGL((calibrate_copy_kernel<8, false>), grid, blk, 0, st, (const calib_f32x4*)src, (calib_f32x4*)dst, n16); }
-    else { if (nt) hipLaunchKernelGGL((calibrate_copy_kernel<4, true>), grid, blk, 0, st, (const calib_f32x4*)src, (calib_f32x4*)dst, n16); else hipLaunchKernelGGL((calibrate_copy_kernel<4, false>), grid, blk, 0, st, (const calib_f32x4*)src, (calib_f32x4*)dst, n16); }
+    hipLaunchKernelGGL((calibrate_copy_kernel<1, true>), dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream,
+                       (const calib_f32x4*)src, (calib_f32x4*)dst, n16);
     return check_launch("calibrate_hbm_copy");
 }
 

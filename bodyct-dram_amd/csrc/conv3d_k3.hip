@@ -1073,10 +1073,6 @@ __device__ __forceinline__ float dpp_mov(float v) {
     return __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), CTRL, 0xF, 0xF, false));
 }
 
-#ifdef DRAM_WZY_STAMPS      // diagnostics build only (scripts/diag_wzy_stamps.py): s_memtime shares of the chunk loop
-__device__ unsigned long long g_wzy_stamps[32];      // [0 .. 15]: waves 0-3, [16 .. 31]: waves 4-7
-#endif
-
 // One instantiation serves plain and fused launches (lazy operands / statistics are runtime-uniform options): a separate
 // plain instantiation measured 2-4 % SLOWER than this one run without the options (241 vs 251, 258 vs 269 TFLOP/s
 // direct-equivalent at 64->64 / 192->64, 128^3), so it was dropped.
@@ -1239,12 +1235,6 @@ __device__ __forceinline__ void fwd_wzy_body(const ConvArgs& a, int total_items)
         // (measured: reading the two operand pairs of an iteration as four ds_read_b64 -- separate opaque bases, so that hipcc
         //  cannot merge them into ds_read2(st64)_b64 -- is 2-4 % SLOWER, although the merged form has half the LDS rate)
 
-#ifdef DRAM_WZY_STAMPS
-        unsigned long long ep_acc[6] = {};      // epilogue: transform, exchange write + barrier, read + combine + barrier, statistics, stores
-#define EP_STAMP(i_) { const unsigned long long tn_ = __builtin_readcyclecounter(); ep_acc[i_] += tn_ - ep_t; ep_t = tn_; }
-#else
-#define EP_STAMP(i_)
-#endif
         f32x16 acc[8];
     #pragma unroll
         for (int t = 0; t < 8; ++t)
@@ -1392,9 +1382,6 @@ __device__ __forceinline__ void fwd_wzy_body(const ConvArgs& a, int total_items)
             KArgs k = kargs();
             int n, x0, y0, z0, co0;
             decode(k, item, n, x0, y0, z0, co0);
-#ifdef DRAM_WZY_STAMPS
-            unsigned long long ep_t = __builtin_readcyclecounter();
-#endif
             // rows of A^T M (y part) for the wave's two xi_z: p[q][yy]
             float pq[2][2][16];
     #pragma unroll
@@ -1410,7 +1397,6 @@ __device__ __forceinline__ void fwd_wzy_body(const ConvArgs& a, int total_items)
                 for (int r = 0; r < 16; ++r) acc[t][r] = 0.f;
             // z part: Y[0] = (p0 + p1) + p2, Y[1] = (p1 - p2) - p3.  The xh = 0 wave (p0, p1) finishes plane 0 and needs p2;
             // the xh = 1 wave (p2, p3) finishes plane 1 and needs p1.  Slot layout [wave][register][lane]: conflict-free.
-            EP_STAMP(0)
             float* mine = xch + wave * 32 * 64 + lane;
             const float* theirs = xch + (wave ^ 4) * 32 * 64 + lane;
     #pragma unroll
@@ -1418,7 +1404,6 @@ __device__ __forceinline__ void fwd_wzy_body(const ConvArgs& a, int total_items)
     #pragma unroll
                 for (int r = 0; r < 16; ++r) mine[(16 * yy + r) * 64] = xh == 0 ? pq[1][yy][r] : pq[0][yy][r];
             __syncthreads();
-            EP_STAMP(1)
             float yv[2][16];
     #pragma unroll
             for (int yy = 0; yy < 2; ++yy)
@@ -1429,7 +1414,6 @@ __device__ __forceinline__ void fwd_wzy_body(const ConvArgs& a, int total_items)
                                         : (got - pq[0][yy][r]) - pq[1][yy][r];      // (p1 - p2) - p3
                 }
             __syncthreads();           // every wave has read: the stage may be filled again
-            EP_STAMP(2)
             const int gx = x0 + (BX == 32 ? j : (j & 15)), gz = z0 + (BX == 32 ? 0 : 2 * ty) + xh, gy = y0 + 2 * (BX == 32 ? ty : (j >> 4));
             const bool ok0 = gx < W && gz < D && gy < H;
             const bool ok1 = gx < W && gz < D && (gy + 1) < H;
@@ -1443,7 +1427,6 @@ __device__ __forceinline__ void fwd_wzy_body(const ConvArgs& a, int total_items)
                                   co0 + 32 * ct, kCout, k->nparts, box * 4 + 2 * ty + xh);
                 __builtin_amdgcn_sched_barrier(0);
             }
-            EP_STAMP(3)
             // stores: the wave's 32 channels lie in ONE destination tensor (host: dst.C1 % 32 == 0) -> one descriptor over
             // them, lane offset = (its 4 kh channels, its voxel), the register's channel as a scalar offset
             const int cw = co0 + 32 * ct;
@@ -1476,10 +1459,6 @@ __device__ __forceinline__ void fwd_wzy_body(const ConvArgs& a, int total_items)
                                                               (int)((unsigned)((r & 3) + 8 * (r >> 2)) * cstride), 0);
                 }
             }
-            EP_STAMP(4)
-#ifdef DRAM_WZY_STAMPS
-            ep_acc[5] += 1;
-#endif
         };
 
         // ---- the pipeline.  Cursors: (c_item, c_c0) = the chunk being multiplied, (s_item, s_c0) = the chunk being staged
@@ -1530,28 +1509,19 @@ __device__ __forceinline__ void fwd_wzy_body(const ConvArgs& a, int total_items)
         int c_item = item_lo, c_c0 = 0, cur = 0;
         bool pending = false;                       // the previous chunk's last four MFMAs are still to be issued
         f32x2 av[2][2], bv[2][2];
-    #ifdef DRAM_WZY_STAMPS
-        unsigned long long st_acc[10] = {};
-    #endif
         // The work that rides between the MFMAs of iteration `it`, in two pieces (after the 2nd / the 3rd MFMA), so that no
         // gap between two MFMAs of a wave is much longer than it has to be: the two waves of a SIMD run in step, and whatever
         // both do between two MFMAs is matrix-pipe idle time.  Staging slices run unconditionally: without a next chunk
         // they move stale data into the idle stage.
         auto ride = [&](int it, int half, bool has_next, bool has_fetch, float* nstage, int cur_) {
-    #ifndef DRAM_WZY_DIAG_NOPATCH       // (diagnostic builds, scripts/diag_wzy_stamps.py: what a part of the staging costs)
             if (it < 2 && has_fetch) fetch_issue(d_c0, raw0 + cur_ * G::RAW_STAGE, 2 * it + half);
-    #endif
             if (it == LD_IN && half == 1 && has_next && lazy) load_coef(s_c0);
-    #ifndef DRAM_WZY_DIAG_NOFILT
             if (it >= LD_W && it < LD_W + FPIECES / 2 && has_next) load_filters(s_c0, nstage, 2 * (it - LD_W) + half);
-    #endif
-    #ifndef DRAM_WZY_DIAG_NOSTAGE
             if (it == SL0 - 1 && half == 1) read_raw(raw0 + (cur_ ^ 1) * G::RAW_STAGE);
             if (it == SL0 && lazy && lc_has) activate(half);       // (a plain channel of a launch with a lazy source: nothing to do)
             if (it == SL0 + 1 && half == 0) transform_z();
             const int q = 2 * (it - SL0 - 1) + half - 1;            // SL0+1: -, 0;  SL0+2: 1, 2;  SL0+3: 3, -
             if (q >= 0 && q < 4) transform_y_store(nstage + st_idx, q);
-    #endif
         };
         for (;;) {
             const bool c_valid = c_item < item_hi;
@@ -1560,9 +1530,6 @@ __device__ __forceinline__ void fwd_wzy_body(const ConvArgs& a, int total_items)
             const bool boundary = pending && (c_c0 == 0);     // the previous chunk completed an item
             const float* stage = lds + cur * STAGE;
             float* nstage = lds + (cur ^ 1) * STAGE;
-    #ifdef DRAM_WZY_STAMPS
-            unsigned long long tp = __builtin_readcyclecounter();
-    #endif
     #pragma unroll
             for (int it = 0; it < 12; ++it) {
                 const int i0 = (it + 11) % 12;                // the MFMAs issued in this iteration belong to iteration i0
@@ -1588,36 +1555,16 @@ __device__ __forceinline__ void fwd_wzy_body(const ConvArgs& a, int total_items)
                     // (the MFMAs of the previous chunk's last iteration are queued behind the barrier: they cover the latency
                     //  of the operand reads above; the next chunk's filter loads follow in iteration LD_W)
                     if (boundary) epilogue(c_item - item_step, nstage);     // (the stage to fill is idle: its loads come after)
-    #ifdef DRAM_WZY_STAMPS
-                    if (!c_valid && lane == 0)
-                        for (int i = 0; i < 10; ++i) atomicAdd(&g_wzy_stamps[(EXTRA ? 16 : 0) + i], st_acc[i]);
-                    if (!c_valid && lane == 0)
-                        for (int i = 0; i < 6; ++i) atomicAdd(&g_wzy_stamps[(EXTRA ? 16 : 0) + 10 + i], ep_acc[i]);
-    #endif
                     if (!c_valid) return;
                     __builtin_amdgcn_sched_barrier(0);
                 }
-    #ifdef DRAM_WZY_STAMPS
-                if (it == 0 || it == 2 || it == 6 || it == 11) {
-                    const unsigned long long tn = __builtin_readcyclecounter();
-                    st_acc[it == 0 ? (boundary ? 6 : 0) : it == 2 ? 1 : it == 6 ? 2 : 3] += tn - tp;
-                    if (it == 0) st_acc[boundary ? 8 : 7] += 1;
-                    tp = tn;
-                }
-    #endif
             }
             // The last iteration's four MFMAs are issued behind the barrier, after the next chunk's first operand reads, whose
             // latency they cover (measured, MFMAs before / behind the barrier: 0/4 is 1-2 % faster than 2/2, 4/0 1 % slower).
             pending = true;
             if (has_next) advance_staging();
             if (has_fetch) advance_fetch();
-    #ifdef DRAM_WZY_STAMPS
-            { const unsigned long long tb = __builtin_readcyclecounter(); st_acc[4] += tb - tp; tp = tb; }
-    #endif
             __syncthreads();
-    #ifdef DRAM_WZY_STAMPS
-            st_acc[5] += __builtin_readcyclecounter() - tp;
-    #endif
             cur ^= 1;
             c_c0 += 4;
             if (c_c0 >= Cin) { c_c0 = 0; c_item += item_step; }
@@ -2082,10 +2029,6 @@ struct WgradWzGeom {
     static constexpr size_t LDS_BYTES = (DOUBLE ? 2 : 1) * (size_t)STAGE * sizeof(float);
 };
 
-#ifdef DRAM_WZY_STAMPS      // diagnostics build only (scripts/diag_wgrad_wz_stamps.py)
-__device__ unsigned long long g_wgrad_stamps[8];
-#endif
-
 template <int BX, int BY, int COS, int CIT, bool LAZY = false>
 __global__ __launch_bounds__(64 * COS * CIT, 2) void conv3d_k3_wgrad_wz_kernel(WgradArgs a) {
     using G = WgradWzGeom<BX, BY, COS, CIT>;
@@ -2325,25 +2268,14 @@ __global__ __launch_bounds__(64 * COS * CIT, 2) void conv3d_k3_wgrad_wz_kernel(W
     }
     __syncthreads();
     int cur = 0;
-#ifdef DRAM_WZY_STAMPS
-    unsigned long long st_acc[5] = {};
-#define WG_STAMP(i_) { const unsigned long long tn_ = __builtin_readcyclecounter(); st_acc[i_] += tn_ - tp_; tp_ = tn_; }
-#else
-#define WG_STAMP(i_)
-#endif
     for (int box = sp; box < a.nboxes; box += a.split) {
         const bool has_next = (box + a.split) < a.nboxes;
-#ifdef DRAM_WZY_STAMPS
-        unsigned long long tp_ = __builtin_readcyclecounter();
-        st_acc[4] += 1;
-#endif
         if (has_next) load_box(box + a.split);
         __builtin_amdgcn_sched_barrier(0);
-        WG_STAMP(0)
         if (DOUBLE) {
             // a wave writes the next box into the idle stage as soon as ITS MFMAs are done -- while slower waves still
-            // compute -- and a box costs one barrier.  What the stamps (-DDRAM_WZY_STAMPS, scripts/diag_wgrad_wz_stamps.py)
-            // show: every wave issues its 288 MFMAs in 9,400 cycles -- the pipe's full rate -- so the two waves of a SIMD
+            // compute -- and a box costs one barrier.  What cycle-counter stamps in a (since retired) diagnostic build
+            // showed: every wave issues its 288 MFMAs in 9,400 cycles -- the pipe's full rate -- so the two waves of a SIMD
             // run their MFMA loops one after the other (the older first; the younger makes no progress meanwhile, not even
             // through its load phase), and a box takes 21,700 cycles = both loops (18,700) + the first wave's load phase +
             // the second wave's store phase + the barrier.  Letting the partners take turns on purpose (waves 0-3 compute
@@ -2351,12 +2283,9 @@ __global__ __launch_bounds__(64 * COS * CIT, 2) void conv3d_k3_wgrad_wz_kernel(W
             // fetch only starts when the older one's loop is over, and its latency is then exposed.
             compute(lds + cur * STAGE);
             __builtin_amdgcn_sched_barrier(0);
-            WG_STAMP(1)
             if (has_next) store_box(lds + (cur ^ 1) * STAGE);
             __builtin_amdgcn_sched_barrier(0);
-            WG_STAMP(2)
             __syncthreads();
-            WG_STAMP(3)
             cur ^= 1;
         } else {
             compute(lds);
@@ -2369,11 +2298,6 @@ __global__ __launch_bounds__(64 * COS * CIT, 2) void conv3d_k3_wgrad_wz_kernel(W
         }
     }
 
-#ifdef DRAM_WZY_STAMPS
-    if (lane == 0)
-        for (int q = 0; q < 5; ++q) atomicAdd(&g_wgrad_stamps[q], st_acc[q]);
-#endif
-#undef WG_STAMP
     // G^T p per accumulator element -> the three z taps of each (ky,kx) column
     const int ci = ci0 + wci * 16 + i;
     if (ci < a.Cin) {
@@ -2683,11 +2607,7 @@ static int launch_fwd(ConvArgs& a, hipStream_t st) {
 
 // Box shape (all 256 / 64 voxels): the one that pads the volume least; ties go to the first listed.  The reference trains and infers on 80^3 chunks (RESAMPLE_SIZE), whose
 // pyramid 80/40/20/10 is covered exactly by 16-, 8-wide boxes but only to 83 % / 62 % by 32-wide ones.
-static int pick_box(int D, int H, int W, const int (*boxes)[3], int nboxes, const char* env) {
-    if (const char* f = getenv(env)) {          // experiments only
-        for (int i = 0; i < nboxes; ++i)
-            if (atoi(f) == boxes[i][0]) return i;
-    }
+static int pick_box(int D, int H, int W, const int (*boxes)[3], int nboxes) {
     int best = 0;
     int64_t best_vol = -1;
     for (int i = 0; i < nboxes; ++i) {
@@ -2702,11 +2622,16 @@ static int pick_box(int D, int H, int W, const int (*boxes)[3], int nboxes, cons
 static const int kFwdWzBoxes[4][2] = {{32, 4}, {16, 8}, {8, 16}, {10, 10}};
 static const int kFwdBoxes[3][3] = {{32, 4, 2}, {16, 4, 4}, {8, 8, 4}};
 
-// The Winograd-z kernel serves every layer with enough input channels to amortise its filter tile; the first
-// layer (Cin = 1) and DRAM_CONV_DIRECT=1 (experiments, A/B tests) use the direct kernel.
-static bool use_wz(const ConvArgs& a) {
+// DRAM_CONV_DIRECT=1 (A/B tests): every forward and backward-weights launch takes the direct kernel (read once)
+static bool conv_direct() {
     static const bool direct = getenv("DRAM_CONV_DIRECT") != nullptr;
-    return !direct && a.Cin >= 8 && a.D >= 2;
+    return direct;
+}
+
+// The Winograd-z kernel serves every layer with enough input channels to amortise its filter tile; the first
+// layer (Cin = 1) and DRAM_CONV_DIRECT=1 use the direct kernel.
+static bool use_wz(const ConvArgs& a) {
+    return !conv_direct() && a.Cin >= 8 && a.D >= 2;
 }
 
 // Which forward kernel / box shape a shape gets (shared by the launch and by dram_conv3d_k3_stats_parts).
@@ -2729,11 +2654,6 @@ static int wzy_box(const ConvArgs& a) {       // what the SHAPE allows (dram_con
     const double vol = (double)a.W * a.H * a.D;
     const double pad32 = (double)cdiv(a.W, 32) * 32 * cdiv(a.H, 4) * 4 * cdiv(a.D, 2) * 2 / vol;
     const double pad16 = (double)cdiv(a.W, 16) * 16 * cdiv(a.H, 4) * 4 * cdiv(a.D, 4) * 4 / vol;
-    if (const char* f = getenv("DRAM_WZY_BX")) {                                // experiments / A-B tests only (read per call)
-        const int bx = atoi(f);
-        if (bx == 32) return pad32 <= 1.2 ? 32 : 0;
-        if (bx == 16) return 16;
-    }
     if (pad32 <= 1.2 && pad32 <= pad16) return 32;
     if (pad16 <= 1.2 || pad16 <= 1.3 * wz_padding(a.D, a.H, a.W)) return 16;
     return 0;
@@ -2780,9 +2700,8 @@ static FwdChoice fwd_choice(const ConvArgs& a) {
     c.wzy = shape_bx != 0 && wzy_source_ok(a);
     c.wzy_bx = c.wzy ? shape_bx : 0;
     c.parts_per_box = 4;
-    static const bool direct = getenv("DRAM_CONV_DIRECT") != nullptr;
-    c.c1 = !direct && a.Cin == 1 && a.src.p2 == nullptr && a.dst.p2 == nullptr && a.coef1 == nullptr;
-    c.c1w = c.c1 && a.W % 4 == 0 && a.W >= 96 && getenv("DRAM_C1_NARROW") == nullptr;
+    c.c1 = !conv_direct() && a.Cin == 1 && a.src.p2 == nullptr && a.dst.p2 == nullptr && a.coef1 == nullptr;
+    c.c1w = c.c1 && a.W % 4 == 0 && a.W >= 96;
     if (c.c1w) {
         c.box = 0;
         c.parts_per_box = 16;           // (wave, row)
@@ -2799,16 +2718,13 @@ static FwdChoice fwd_choice(const ConvArgs& a) {
         // 20^3 and 10^3 levels of the reference's 80^3 chunks fit it exactly)
         const int (*boxes2)[2] = kFwdWzBoxes;
         int best = wz_best_box(a.H, a.W);
-        if (const char* f = getenv("DRAM_FWD_BX"))
-            for (int i = 0; i < 4; ++i)
-                if (atoi(f) == boxes2[i][0]) best = i;
         if (shape_bx == 32) best = 0;           // the (z,y) kernel's shape, refused for its source only (wzy_source_ok)
         if (shape_bx == 16) best = 1;
         c.box = best;
         c.nbx = cdiv(a.W, boxes2[best][0]); c.nby = cdiv(a.H, boxes2[best][1]); c.nbz = cdiv(a.D, 2);
     } else {
         const int (*boxes)[3] = kFwdBoxes;
-        c.box = pick_box(a.D, a.H, a.W, boxes, 3, "DRAM_FWD_BX");
+        c.box = pick_box(a.D, a.H, a.W, boxes, 3);
         c.nbx = cdiv(a.W, boxes[c.box][0]); c.nby = cdiv(a.H, boxes[c.box][1]); c.nbz = cdiv(a.D, boxes[c.box][2]);
     }
     const int64_t produced = (int64_t)c.nbx * c.nby * c.nbz * c.parts_per_box;
@@ -2932,14 +2848,13 @@ static WgradPlan wgrad_plan(int N, int Cin, int Cout, int D, int H, int W, int C
     p.wzy = 0;
     p.cit = 1;
     {   // Winograd-(z,y): full 16-wide boxes along x, whole y and z pairs, a ci tile inside one source tensor
-        static const bool direct = getenv("DRAM_CONV_DIRECT") != nullptr;
         const bool off = getenv("DRAM_WGRAD_NO_WZY") != nullptr;      // (read per call: A/B tests toggle it inside one process)
         const int cit = 1;
         // 16-wide boxes along x, the last one of a row ragged where W % 16 != 0 (16-byte pieces: W % 4 == 0) as long as it pads at
         // most 1.6x (measured at the reference's 40^3 level, 1.2x padding: 233 TFLOP/s direct-equivalent against 186 for the
         // z-only kernel on exact boxes; the 20^3 level pads 1.6x: ~175 against the z-only kernel's 151 there)
         const bool wide_ok = W % 4 == 0 && cdiv(W, 16) * 16 * 10 <= W * 16;
-        if (!direct && !off && wide_ok && H % 2 == 0 && D % 2 == 0 && D >= 4 && (C1 == 0 || C1 % (16 * cit) == 0)) {   // (D >= 4: two boxes per z column, the raw plane ring counts on it)
+        if (!conv_direct() && !off && wide_ok && H % 2 == 0 && D % 2 == 0 && D >= 4 && (C1 == 0 || C1 % (16 * cit) == 0)) {   // (D >= 4: two boxes per z column, the raw plane ring counts on it)
             p.wzy = 1;
             p.cit = cit;
             p.bx = 16; p.by = 2; p.bz = 2;
@@ -2955,16 +2870,11 @@ static WgradPlan wgrad_plan(int N, int Cin, int Cout, int D, int H, int W, int C
         // 32 ci tile (two LDS stages, one barrier per box) serves wide layers too: measured 197-200 TFLOP/s direct-equivalent
         // against 186-190 for the 128 co x 16 ci tile at 384->128, 256->256, 768->256; the latter remains for a concat
         // boundary that is a multiple of 16 only.
-        static const bool direct = getenv("DRAM_CONV_DIRECT") != nullptr;
         const int bx = (W % 16 == 0) ? 16 : ((W % 8 == 0) ? 8 : ((W % 4 == 0) ? 4 : 0));
         int variant = -1;
         if (C1 == 0 || C1 % 32 == 0) variant = 0;
         else if (Cout > 64 && C1 % 16 == 0) variant = 1;
-        if (const char* f = getenv("DRAM_WGRAD_VARIANT")) {                              // experiments only
-            const int v = atoi(f) ? 1 : 0;
-            if (C1 == 0 || C1 % (v == 1 ? 16 : 32) == 0) variant = v;
-        }
-        if (!direct && bx && D >= 2 && variant >= 0) {
+        if (!conv_direct() && bx && D >= 2 && variant >= 0) {
             p.wz = 1;
             p.variant = variant;
             p.bx = bx; p.by = 32 / bx; p.bz = 2;
@@ -2974,7 +2884,7 @@ static WgradPlan wgrad_plan(int N, int Cin, int Cout, int D, int H, int W, int C
     // ties go to the 16-wide box: its X halo (18x4x4 = 288 elements per 64 voxels, against 408 for 34x4x3)
     // needs the fewest staging loads (measured +2.6 % at 128^3 / 64^3 / 32^3)
     static const int boxes[3][3] = {{16, 2, 2}, {32, 2, 1}, {8, 4, 2}};
-    const int bi = pick_box(D, H, W, boxes, 3, "DRAM_WGRAD_BX");
+    const int bi = pick_box(D, H, W, boxes, 3);
     p.bx = boxes[bi][0]; p.by = boxes[bi][1]; p.bz = boxes[bi][2];
     }
     p.nbx = cdiv(W, p.bx); p.nby = cdiv(H, p.by); p.nbz = cdiv(D, p.bz);
@@ -3079,7 +2989,7 @@ static WgradKernel wgrad_kernel(const WgradPlan& p, int C1, bool has_x2, int W, 
     }
     // 16-byte staging needs full boxes along x and a channel tile that lies inside one source tensor
     const int ci_b = 16 * k.cit;
-    const bool vec = (W % p.bx == 0) && (!has_x2 || C1 % ci_b == 0) && getenv("DRAM_WGRAD_NOVEC") == nullptr;
+    const bool vec = (W % p.bx == 0) && (!has_x2 || C1 % ci_b == 0);
     k.kind = vec ? DRAM_K3_WGRAD_VEC : DRAM_K3_WGRAD_DIRECT;
     return k;
 }
@@ -3113,19 +3023,6 @@ static int check_cat(const char* who, const CatView& v, int D, int H, int W) {
 }  // namespace dram
 
 using namespace dram;
-
-#ifdef DRAM_WZY_STAMPS
-extern "C" int dram_debug_wzy_stamps(unsigned long long* out, int reset) {
-    unsigned long long z[32] = {};
-    if (reset) return (int)hipMemcpyToSymbol(HIP_SYMBOL(g_wzy_stamps), z, sizeof(z));
-    return (int)hipMemcpyFromSymbol(out, HIP_SYMBOL(g_wzy_stamps), sizeof(z));
-}
-extern "C" int dram_debug_wgrad_stamps(unsigned long long* out, int reset) {
-    unsigned long long z[8] = {};
-    if (reset) return (int)hipMemcpyToSymbol(HIP_SYMBOL(g_wgrad_stamps), z, sizeof(z));
-    return (int)hipMemcpyFromSymbol(out, HIP_SYMBOL(g_wgrad_stamps), sizeof(z));
-}
-#endif
 
 extern "C" size_t dram_conv3d_k3_packed_floats(int Cout, int Cin) {
     if (Cout <= 0 || Cin <= 0) return 0;
@@ -3365,7 +3262,7 @@ static int wgrad_run(const float* x1, int C1, const float* coef1, int relu1, con
     g_launches[wk.kind].fetch_add(1, std::memory_order_relaxed);
     const bool vec = wk.kind == DRAM_K3_WGRAD_VEC;
     const int64_t E = (int64_t)Cout * a.Cin * 27;
-    if (p.wzy && x2 && (a.coef1 != nullptr) != (a.coef2 != nullptr) && getenv("DRAM_WGRAD_ONE_LAUNCH") == nullptr) {
+    if (p.wzy && x2 && (a.coef1 != nullptr) != (a.coef2 != nullptr)) {
         // A virtual concat with exactly ONE lazy source (the first conv of an UpsampleConvBlock5d in the fused engine: the
         // upsampled part plain, the skip part lazy): one launch per source, each on its own instantiation and with its own
         // split.  In one launch the lazy tiles' blocks run ~9 % longer per box than the plain tiles', the blocks of a split

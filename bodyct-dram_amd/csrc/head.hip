@@ -459,9 +459,9 @@ static int conv1x1_bwd_run(const float* dy, const float* x, const float* coef, i
         float* part = (float*)ws;
         static_assert(WG_VPB == 2048, "conv1x1_wgrad_vec_kernel: two float4 per thread");
         static_assert(WM_VPB % WG_VPB == 0, "the multi-output kernel's partials fit the workspace sized for WG_VPB");
-        const bool vec = (S % 4) == 0 && ((((uintptr_t)dy) | ((uintptr_t)x)) & 15) == 0 && getenv("DRAM_K1_WGRAD_SCALAR") == nullptr;
+        const bool vec = (S % 4) == 0 && ((((uintptr_t)dy) | ((uintptr_t)x)) & 15) == 0;
         const int ci_tiles = cdiv(Cin, WM_CT), co_tiles = cdiv(Cout, WM_CO);
-        if (vec && Cout > 1 && ci_tiles * co_tiles <= 65535 && getenv("DRAM_K1_WGRAD_NOMULTI") == nullptr) {
+        if (vec && Cout > 1 && ci_tiles * co_tiles <= 65535) {
             nblk = (int)cdiv64(S, WM_VPB);
             hipLaunchKernelGGL(conv1x1_wgrad_multi_kernel, dim3(nblk, N, ci_tiles * co_tiles), dim3(256), 0, st, dy, x, part, Cin, Cout,
                                S, nblk, ci_tiles, coef, relu);

@@ -24,17 +24,13 @@
 
 namespace dram {
 
-#ifndef DRAM_NORM_Q
-#define DRAM_NORM_Q 4
-#endif
-constexpr int NQ = DRAM_NORM_Q;       // float4 per thread and tensor, all in flight together
+constexpr int NQ = 4;                 // float4 per thread and tensor, all in flight together
 constexpr int CHUNK = 256 * 4 * NQ;   // floats per (row, chunk) work item: 256 threads x NQ float4
 
 // Streaming 16-byte accesses of the row kernels: non-temporal (every tensor here is far larger than the caches and is touched once
 // per pass), four per thread and tensor in flight.  Measured on [16,64,128^3] (scripts/bench_norm.py, same-box A/B of builds):
 // dram_norm_bwd 7.48 ms with default-policy accesses and eight per thread, 7.26 non-temporal, 7.11 non-temporal with four (7.22
-// with two); dram_row_affine_act 3.22 / 3.04 / 2.91 / 2.87 ms.  -DDRAM_NORM_TEMPORAL restores the default cache policy.
-#ifndef DRAM_NORM_TEMPORAL
+// with two); dram_row_affine_act 3.22 / 3.04 / 2.91 / 2.87 ms.
 typedef float norm_f32x4 __attribute__((ext_vector_type(4)));
 __device__ __forceinline__ float4 ld4(const float* p) {
     const norm_f32x4 v = __builtin_nontemporal_load(reinterpret_cast<const norm_f32x4*>(p));
@@ -44,10 +40,6 @@ __device__ __forceinline__ void st4(float* p, float4 v) {
     const norm_f32x4 w = {v.x, v.y, v.z, v.w};
     __builtin_nontemporal_store(w, reinterpret_cast<norm_f32x4*>(p));
 }
-#else
-__device__ __forceinline__ float4 ld4(const float* p) { return *reinterpret_cast<const float4*>(p); }
-__device__ __forceinline__ void st4(float* p, float4 v) { *reinterpret_cast<float4*>(p) = v; }
-#endif
 
 // grid: (nchunks, rows).  part[(row*nchunks + chunk)*2] = {mean, M2} of that chunk.
 template <bool VEC>

@@ -747,8 +747,7 @@ static bool tri_fwd_x4_ok(const float* y, const Axis& ax) {
 static int tri_fwd_launch(const float* x, float* y, const Axis& az, const Axis& ay, const Axis& ax, int planes, const float* coef,
                           int relu, hipStream_t st) {
     const bool tiled = tri_fwd_x4_ok(y, ax) && az.half == 0 && ay.half == 0 && az.scale <= 0.5f && ay.scale <= 0.5f &&
-                       (ax.in % 4) == 0 && ax.in <= TT_MAXW && (((uintptr_t)x) & 15) == 0 && cdiv(planes, TT_CPT) <= 65535 &&
-                       getenv("DRAM_TRI_NO_TILE") == nullptr;
+                       (ax.in % 4) == 0 && ax.in <= TT_MAXW && (((uintptr_t)x) & 15) == 0 && cdiv(planes, TT_CPT) <= 65535;
     if (tiled) {
         const int ntz = cdiv(az.out, TT_Z), nty = cdiv(ay.out, TT_Y);
         const size_t lds = (size_t)TT_CPT * TT_RZ * TT_RY * ax.in * sizeof(float);      // <= 48 KB

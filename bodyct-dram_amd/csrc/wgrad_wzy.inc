@@ -186,11 +186,7 @@ __global__ __launch_bounds__(512, 1) void conv3d_k3_wgrad_wzy_kernel(WgradArgs a
                     col_xoff = 4u * (unsigned)(c_y0 * Ws + c_x0);
                 }
                 const __amdgpu_buffer_rsrc_t srd = make_rsrc(col_dy, (unsigned)a.Cout * S4);
-#ifdef WZY_DIAG_DYSAME
-                const unsigned off = 0;
-#else
                 const unsigned off = col_off + (unsigned)c_z0 * dplane4;
-#endif
 #pragma unroll
                 for (int m = 0; m < 4; ++m)
                     __builtin_amdgcn_raw_ptr_buffer_load_lds(srd, (lds_ptr_t)(lds + dy_float + (4 * fw + m) * DYG), 16, (int)dvoff[m], (int)off, 0, 0);
@@ -202,11 +198,7 @@ __global__ __launch_bounds__(512, 1) void conv3d_k3_wgrad_wzy_kernel(WgradArgs a
             const int gz = c_z0 - 1 + rz;
             const unsigned bytes = (unsigned)gz < (unsigned)D ? (unsigned)Cs * Ss4 + xmargin : 0u;      // a plane outside the volume: zeros
             const __amdgpu_buffer_rsrc_t xsrd = make_rsrc(col_xb, bytes);
-#ifdef WZY_DIAG_XSAME       // (timing only: every box reads the same X planes -- what the X traffic costs)
-            const unsigned soff = (unsigned)rz * plane4 + 4u * (unsigned)(Ws + 4);
-#else
             const unsigned soff = col_xoff + (unsigned)(c_z0 + rz) * plane4;
-#endif
             const int slot_float = NDY * DYF + 2 * XF + (ring % NSLOT) * RAWP;      // (ring counts planes: non-negative)
             ++ring;
 #pragma unroll
@@ -457,40 +449,21 @@ __global__ __launch_bounds__(512, 1) void conv3d_k3_wgrad_wzy_kernel(WgradArgs a
             asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
             __syncthreads();
 
-#ifdef DRAM_WZY_STAMPS
-            unsigned long long st_acc[8] = {};
-#define WZ_STAMP(i_) { const unsigned long long tn_ = __builtin_readcyclecounter(); st_acc[i_] += tn_ - tp_; tp_ = tn_; }
-#else
-#define WZ_STAMP(i_)
-#endif
             int dy_cur = 0, dy_ld = 2 * DYF;            // dY stage of box j / of box j + 2
             for (int j = 0; j < nbox; ++j) {
-#ifdef DRAM_WZY_STAMPS
-                unsigned long long tp_ = __builtin_readcyclecounter();
-                st_acc[3] += 1;
-#endif
                 const bool has1 = (j + 1) < nbox, has3 = (j + 2) < nbox;      // (has3: a box to fetch)
                 const int v_cur = NDY * DYF + (j & 1) * XF, v_nx = NDY * DYF + ((j + 1) & 1) * XF;
                 if (has1) transform_begin(IS_FETCHER);        // (box j + 1: its fetch was waited for at the previous barrier)
                 compute_box(dy_cur, v_cur, [&](int slot) {
-#ifndef WZY_DBG_NOLOAD
                     if (has3 && slot >= FSLOT0 && slot < FSLOT0 + 2 * NFP && (slot - FSLOT0) % 2 == 0) fetch_piece(IS_FETCHER, dy_ld, (slot - FSLOT0) / 2);
-#endif
-#ifndef WZY_DBG_NOFINISH
                     if (has1 && slot >= TSLOT0 && slot < TSLOT0 + TSTEP * 8 && (slot - TSLOT0) % TSTEP == 0) transform_piece(IS_FETCHER, v_nx, (slot - TSLOT0) / TSTEP);
-#endif
-#ifdef DRAM_WZY_STAMPS
-                    if (slot == 47) WZ_STAMP(0)             // the box's MFMAs with everything that rides
-#endif
                 });
                 dy_cur = dy_cur + DYF == NDY * DYF ? 0 : dy_cur + DYF;
                 dy_ld = dy_ld + DYF == NDY * DYF ? 0 : dy_ld + DYF;
                 if (has1) {
                     if (has3) fetch_done(true);
                     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-                    WZ_STAMP(1)                             // the wait for the fetches
                     __syncthreads();
-                    WZ_STAMP(2)                             // the barrier
                 }
             }
             if (pending) {
@@ -504,11 +477,6 @@ __global__ __launch_bounds__(512, 1) void conv3d_k3_wgrad_wzy_kernel(WgradArgs a
             for (int ct = 0; ct < 3; ++ct)
 #pragma unroll
                 for (int g = 0; g < 12; ++g) fin[ct][g] = ct < NCT ? acc[ct < NCT ? ct : 0][g] : f32x4{0.f, 0.f, 0.f, 0.f};
-#ifdef DRAM_WZY_STAMPS
-            if (lane == 0)
-                for (int t = 0; t < 4; ++t) atomicAdd(&g_wgrad_stamps[4 * cohalf + t], st_acc[t]);
-#endif
-#undef WZ_STAMP
         };
         switch (wave) {
             case 0: run(std::integral_constant<int, 0>{}); break;

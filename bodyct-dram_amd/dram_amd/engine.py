@@ -61,7 +61,7 @@ class Lazy:
 # resolution in us_modules.2: 22 % of everything the per-op path saves).  Backward needs it once, as the x operand
 # of the first conv's backward-weights.  It is kept when small, and produced again from the low-resolution lazy
 # tensor (one bandwidth pass, ~0.3 % of a step) when it is larger than this fraction of the device memory.
-KEEP_UPSAMPLED_BELOW = float(_os.environ.get("DRAM_KEEP_UPSAMPLED_FRAC", "0.08"))
+KEEP_UPSAMPLED_BELOW = 0.08
 
 
 # Lazy tensors trade time for memory: applying the norm on load costs the consumer kernels 3-6 % (forward conv) and
@@ -70,7 +70,7 @@ KEEP_UPSAMPLED_BELOW = float(_os.environ.get("DRAM_KEEP_UPSAMPLED_FRAC", "0.08")
 # small (below this fraction of the device memory) and stays lazy when it is large: with the 64 x 128^3 benchmark at
 # micro-batch 16 everything is written (8.6 GB per full-resolution tensor = 3 %), at micro-batch 32 the
 # full-resolution stages stay lazy and the step fits 288 GB.
-MATERIALISE_BELOW = float(_os.environ.get("DRAM_MATERIALISE_FRAC", "0.04"))
+MATERIALISE_BELOW = 0.04
 
 
 class Upsampled:
@@ -202,7 +202,7 @@ def _sync_forward_stats(norm, group, parts, nparts, ws, mean, rstd, coef, count,
 # backward, its gradient) would exceed this fraction of the device memory: every kernel of the stage is independent
 # per sample, only the norm statistics span the batch -- and they are finalised once, over all slices' partials.
 # That is what lets 64 x 128^3 chunks go through as ONE batch (whole-batch BatchNorm statistics, like the reference).
-SLICE_UPSAMPLED_ABOVE = float(_os.environ.get("DRAM_SLICE_UPSAMPLED_FRAC", "0.08"))
+SLICE_UPSAMPLED_ABOVE = 0.08
 
 
 def _rows(coef, lo, hi, C):
@@ -520,26 +520,22 @@ def backward(model, record, gout, need_dx, sink=None):
             dgamma = torch.empty(Co, dtype=torch.float32, device=g.device) if gamma is not None else None
             dbeta = torch.empty(Co, dtype=torch.float32, device=g.device) if s.norm.bias is not None else None
             ws = _ws(_lib.lib.dram_norm_ws_bytes(N, Co, S), g.device)
-            g_in = g
-            if _os.environ.get("DRAM_ENGINE_NO_INPLACE"):
-                g = torch.empty_like(g_in)
             if s.sync is not None:      # "sbn": the two backward sums span the ranks; the parameter gradients stay local sums
                 import torch.distributed as dist
                 group, total = s.sync
                 sums = torch.empty(2 * Co, dtype=torch.float64, device=g.device)
-                call("dram_bn_bwd_sums", _p(g_in), _p(s.y), _p(s.mean), _p(s.rstd), _p(s.coef), _p(sums), 1, N, Co, S,
+                call("dram_bn_bwd_sums", _p(g), _p(s.y), _p(s.mean), _p(s.rstd), _p(s.coef), _p(sums), 1, N, Co, S,
                      _p(ws), ws.numel(), st)
                 if dbeta is not None:
                     dbeta.copy_(sums[0::2])
                 if dgamma is not None:
                     dgamma.copy_(sums[1::2])
                 dist.all_reduce(sums, op=dist.ReduceOp.SUM, group=group)
-                call("dram_bn_bwd_apply_sums", _p(g_in), _p(s.y), _p(gamma), _p(s.mean), _p(s.rstd), _p(s.coef), _p(sums),
+                call("dram_bn_bwd_apply_sums", _p(g), _p(s.y), _p(gamma), _p(s.mean), _p(s.rstd), _p(s.coef), _p(sums),
                      float(total), _p(g), 1, N, Co, S, _p(ws), ws.numel(), st)
             else:
-                call("dram_norm_bwd", _p(g_in), _p(s.y), _p(gamma), _p(s.mean), _p(s.rstd), _p(s.coef), _p(g), _p(dgamma), _p(dbeta),
+                call("dram_norm_bwd", _p(g), _p(s.y), _p(gamma), _p(s.mean), _p(s.rstd), _p(s.coef), _p(g), _p(dgamma), _p(dbeta),
                      s.kind, s.groups, 1, int(s.batch_stats), N, Co, S, _p(ws), ws.numel(), st)
-            del g_in
             if dgamma is not None:
                 grads[gamma] = dgamma
             if dbeta is not None:
@@ -550,7 +546,7 @@ def backward(model, record, gout, need_dx, sink=None):
             need_dgrad = skip is not None or not is_root or need_dx
             ranges = s.ranges                  # as forward ran the stage (decided once, kept on the tape)
             whole = len(ranges) == 1
-            lazy_ok = bool(_lib.lib.dram_conv3d_k3_wgrad_lazy_ok(N, C1, C2, Co, D, H, W)) and not _os.environ.get("DRAM_ENGINE_NO_LAZY_WGRAD")
+            lazy_ok = bool(_lib.lib.dram_conv3d_k3_wgrad_lazy_ok(N, C1, C2, Co, D, H, W))
             dw = None
             wt = HF._pack(w, 1) if need_dgrad else None
             dx2 = None

@@ -7,7 +7,6 @@ There is no fallback: CPU tensors raise.
 """
 import ctypes
 import math
-import os
 
 import torch
 from torch.autograd import Function
@@ -563,7 +562,7 @@ def max_pool3d_2(x):
 
 # --------------------------------------------------------------------------- trilinear resize
 # workspace cap of the two-stage trilinear backward (the z-reduced intermediate of a group of planes)
-TRI_BWD_WS_CAP = int(os.environ.get("DRAM_TRI_WS_MB", "1024")) << 20
+TRI_BWD_WS_CAP = 1 << 30
 
 
 class TrilinearACFn(Function):

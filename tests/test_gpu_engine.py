@@ -69,7 +69,7 @@ def test_fused_engine_equals_per_op_path(norm, N, shape, need_dx):
     # cancel to ~1/sqrt(n) of their terms, and a single ReLU-mask flip (an element whose pre-activation is within
     # rounding of zero lands on the other side because the two paths' statistics differ in the last bit) moves them
     # by percents -- measured: ONE flip of 24576 elements in us_modules.2 -> 3.4e-2 on that bias gradient, with
-    # the fp64 oracle on the per-op side and torch's own GPU ops on the fused side (scripts/debug_engine4.py)
+    # the fp64 oracle on the per-op side and torch's own GPU ops on the fused side (a one-off diagnostic, since retired)
     gout = ((0.5 + torch.rand((N, 1) + shape, generator=g)) / x.numel()).to(DEV)
     ref = _run(model, x, gout, False, need_dx)
     model.load_state_dict(sd0)
