@@ -793,7 +793,12 @@ PCM_MERGE_MODES = {
 }
 
 
+PCM_MAX_OFFSETS = 128      # the kernels' neighbour-offset table (PCM_MAXE, csrc/pcm.hip)
+
+
 def _offsets_arg(offsets):
+    if not 0 < len(offsets) <= PCM_MAX_OFFSETS:
+        raise ValueError(f"PCM: {len(offsets)} neighbour offsets; the device kernels take 1..{PCM_MAX_OFFSETS}")
     flat = [int(v) for o in offsets for v in o]
     return (ctypes.c_int * len(flat))(*flat), len(flat) // 3
 

@@ -11,8 +11,8 @@ All compute runs on libdram_hip.so.
 `models.PCM` / `models.DC3DATGeneric` (what process_pipeline.py loads) are
 provided with the reference's constructor signatures and state-dict keys; the DGL neighbour graph of
 the reference (networkx + dgl, absent here) is replaced by the equivalent voxel-grid stencil kernels
-(csrc/pcm.hip).  Parity of the attention itself is unpinned (no DGL to run the reference against): see
-oracle/dram_oracle.py.
+(csrc/pcm.hip).  The attention is pinned to the reference's own PCM.forward and DC3DATGeneric.forward, run
+with a stand-in for its two DGL calls (tests/golden/pcm_core.npz, tests/golden/dc3dat_att.npz).
 
 Reference citations are to /root/reference/dram/models.py.
 """
@@ -239,7 +239,11 @@ class PCM(nn.Module):
     (models.py:262-264) literally, which is 0 / 0 = NaN for a node all of whose edges underflow (|theta - phi| > ~4.2 in fp32).
     Here the same ratio is computed as a softmax over the edges of 10 theta phi_e - 5 phi_e^2 (the common -5 theta^2 cancels,
     the maximum is subtracted): algebraically identical, finite for saturated inputs
-    (tests/test_gpu_pcm.py::test_pcm_l2_merge_saturated_inputs_stay_finite).  Like all of PCM: parity unpinned (DGL absent)."""
+    (tests/test_gpu_pcm.py::test_pcm_l2_merge_saturated_inputs_stay_finite).  Unsaturated inputs match the reference
+(tests/golden/pcm_core.npz, case 'l2').
+
+    k_size > 5 (more than the kernels' 128 neighbour offsets) raises ValueError before anything is launched.  A node without
+    any edge (a 1x1x1 grid without self loop) gets a zero attention row, hence r's bias (or 0) as its refined value."""
 
     def __init__(self, pool_size, in_ch, g_ch, f_dim, geo_f_dim, g_dim, non_local_iter, k_size,
                  merge_type='l2', self_loop=True, connectivity=2, residual=False, p_enc_dim=32):
@@ -324,6 +328,9 @@ class PCM(nn.Module):
         if self.graph is None:
             self.graph = self.init_graph(self.pool_size, self.k_size)
         offsets = self.graph
+        if len(offsets) > HF.PCM_MAX_OFFSETS:     # the reference accepts any k_size; refuse before anything is launched
+            raise ValueError(f"PCM: k_size {self.k_size} with connectivity {self.connectivity} gives {len(offsets)} neighbour "
+                             f"offsets; the device kernels take at most {HF.PCM_MAX_OFFSETS} (k_size <= 5)")
         theta = _channel_linear(self.theta, f)
         phi = _channel_linear(self.phi, f)
         geo_theta = geo_phi = None

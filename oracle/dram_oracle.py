@@ -588,10 +588,10 @@ def dice(predict, target, smooth):
 # --------------------------------------------------------------------------
 # PCM local attention + DC3DATGeneric (reference dram/models.py:150-597)
 #
-# PARITY UNPINNED at the PCM boundary: PCM.forward needs the real DGL (dgl.DGLGraph / update_all,
-# models.py:256-258,340), a third-party package that is absent from /root/reference and from this
-# image ("install 0.6.x", README.md:12; the Dockerfile builds git master).  The reference holds no
-# test or fixture for it.  What follows restates models.py:221-411 from reading it; `pcm_forward`
+# PCM.forward needs DGL (dgl.DGLGraph / update_all, models.py:256-258,340), a third-party package the
+# reference does not ship.  oracle/make_golden.py runs the reference's PCM with oracle/dgl_emulation.py in
+# its place (tests/golden/pcm_core.npz, dc3dat_att.npz; tests/test_oracle_golden.py pins what follows to
+# them).  What follows restates models.py:221-411 from reading it; `pcm_forward`
 # (dense, shifted views) and `pcm_forward_literal` (node by node, mailbox by mailbox, written to
 # mirror reduce_func / compute_cross_x line by line) are two independent restatements that are checked
 # against each other.  Everything of DC3DATGeneric around the PCM call *is* pinned by a golden vector

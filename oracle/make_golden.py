@@ -10,7 +10,8 @@ dram/metrics.py import dgl / SimpleITK / cv2 / skimage at module level (never
 touched by DC3D or IntRegRefineLoss); those packages are not installed, so this
 process -- and only this process -- pre-seeds sys.modules with empty stand-in
 modules for them.  metrics.py hard-codes `.cuda()`; inside this process only,
-torch.Tensor.cuda is replaced by a no-op so the loss runs on CPU.
+torch.Tensor.cuda is replaced by a no-op so the loss runs on CPU.  The PCM generators
+(`pcm`, `att_pcm`) run the reference's PCM itself: for them `dgl` is oracle/dgl_emulation.py.
 """
 import os
 import sys
@@ -395,6 +396,188 @@ def gen_att(models):
     _save("dc3dat_slim", **arrs)
 
 
+def _use_dgl_emulation(models):
+    """The PCM generators run the reference's PCM as is; its two DGL calls go to oracle/dgl_emulation.py."""
+    sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+    import dgl_emulation
+    sys.modules["dgl"] = dgl_emulation
+    models.dgl = dgl_emulation          # (models.py bound the name at import time)
+
+
+# (name, merge, in_ch, g_ch, f_dim, g_dim, k_size, connectivity, self_loop, iters, residual, p_enc_dim, geo_f_dim, grid, B)
+PCM_CASES = (
+    [("shipped", "scaled_dot_product_relu", 17, 1, 8, 8, 3, 2, False, 1, False, 0, 0, (12, 10, 14), 2)]
+    + [(m, m, 9, 2, 4, 3, 3, 2, i % 2 == 1, 1, False, 0, 0, (5, 4, 7), 2)
+       for i, m in enumerate(("sm", "scaled_dot_product", "smrelu", "smscaled", "l2sm", "l2smrelu"))]
+    + [(m, m, 9, 2, 4, 3, 3, 2, False, 1, False, 0, 0, (5, 4, 7), 2) for m in ("cosine", "heu1", "heu2")]
+    + [(m, m, 9, 2, 4, 3, 3, 2, False, 1, False, 6, 4 if m == "att_is_all" else 5, (4, 5, 6), 2)
+       for m in ("scaled_dot_product_geo", "scaled_dot_product_geo_relu", "att_is_all")]
+    + [("l2", "l2", 9, 2, 1, 3, 3, 2, True, 1, False, 0, 0, (5, 4, 7), 2),
+       ("wide_stencil", "scaled_dot_product", 9, 2, 4, 3, 5, 3, True, 1, False, 0, 0, (6, 7, 9), 1),
+       ("stencil_gt_grid", "scaled_dot_product_relu", 9, 2, 4, 3, 5, 1, False, 1, False, 0, 0, (2, 3, 4), 3),
+       ("identity_proj", "sm", 5, 2, 0, 0, 3, 1, True, 1, False, 0, 0, (4, 5, 6), 2),
+       ("iterate", "scaled_dot_product_relu", 9, 2, 4, 3, 3, 2, False, 2, True, 0, 0, (8, 8, 8), 2),
+       ("penc_unused", "scaled_dot_product", 9, 2, 4, 3, 3, 2, False, 1, False, 6, 5, (4, 5, 6), 2)])
+PCM_CFG_KEYS = ("merge", "in_ch", "g_ch", "f_dim", "g_dim", "k_size", "connectivity", "self_loop", "iters", "residual",
+                "p_enc_dim", "geo_f_dim", "grid", "B")
+# margins (fp64) kept by the inputs at the discontinuities an fp32 run could otherwise cross the other way
+PCM_RELU_MARGIN = 1e-4       # |theta . phi| of every edge whose dot product goes into a ReLU
+PCM_HEU1_MARGIN = 1e-3       # |u - 0.03| of every heu1 similarity (its mask)
+
+
+def _pcm_discontinuities(merge, th, ph, src, dst):
+    """Per-edge distance (fp64) from the discontinuity the merge puts on that edge's score, or None.
+    th, ph: [B, N, F] projected features; an edge src -> dst pairs theta of dst with phi of src."""
+    dot = (th[:, dst] * ph[:, src]).sum(-1)                                  # [B, E]
+    if merge in ("scaled_dot_product_relu", "smrelu", "l2smrelu", "scaled_dot_product_geo_relu"):
+        return dot.abs(), PCM_RELU_MARGIN
+    if merge in ("heu1", "heu2"):
+        u = dot / (1.0 + (th[:, dst] - ph[:, src]).abs().sum(-1))
+        return ((u - 0.03).abs(), PCM_HEU1_MARGIN) if merge == "heu1" else (u.abs(), PCM_RELU_MARGIN)
+    return None, None
+
+
+def gen_pcm(models):
+    """The reference's PCM (models.py:150-411) in float64, run as is through the DGL emulation: for every case of
+    PCM_CASES the configuration, state dict, inputs, output and the gradients of cam, f and every parameter (absent
+    gradients listed under <case>/nograd); and the edge lists of its own init_graph on a 3x4x5 grid."""
+    import json
+    _use_dgl_emulation(models)
+    arrs = {"cases": np.array([c[0] for c in PCM_CASES])}
+    for ci, case in enumerate(PCM_CASES):
+        name, cfg = case[0], dict(zip(PCM_CFG_KEYS, case[1:]))
+        merge, grid, B = cfg["merge"], tuple(cfg["grid"]), cfg["B"]
+        torch.manual_seed(100 + ci)
+        m = models.PCM(grid, cfg["in_ch"], cfg["g_ch"], cfg["f_dim"], cfg["geo_f_dim"], cfg["g_dim"], cfg["iters"],
+                       cfg["k_size"], merge_type=merge, self_loop=cfg["self_loop"], connectivity=cfg["connectivity"],
+                       residual=cfg["residual"], p_enc_dim=cfg["p_enc_dim"]).double()
+        g = torch.Generator().manual_seed(200 + ci)
+        sums = merge in ("cosine", "heu1", "heu2")
+        with torch.no_grad():
+            for k, p in m.named_parameters():
+                if sums and k.startswith(("theta", "phi")):
+                    p.abs_()                    # positive features: positive similarities, sums away from zero
+                    if merge == "heu1":
+                        p.mul_(0.5)             # similarities on both sides of the 0.03 mask
+                elif not sums:
+                    p.mul_(3.0)                 # spread the logits: the softmax far from uniform
+                p.copy_(p.float().double())     # every input is exactly an fp32 value: the device gets the same problem
+
+        def draw(shape, uniform=False, scale=1.0, q=2.0 ** -4):     # on a grid of q: exact in fp32, and they compress
+            t = torch.rand(shape, generator=g, dtype=torch.float64) if uniform else \
+                torch.randn(shape, generator=g, dtype=torch.float64)
+            return torch.round(t * scale / q) * q
+
+        def draw_f(n):                          # smscaled: logits / 0.01, keep the softmax out of saturation
+            return draw((n, cfg["in_ch"]), sums, *((0.03, 2.0 ** -9) if merge == "smscaled" else ()))
+        N = int(np.prod(grid))
+        f_rows = draw_f(B * N).view(B, N, -1)                   # [B, N, C] node rows, ravelled like the reference
+        graph = m.init_graph(grid, cfg["k_size"])
+        src, dst = graph.src, graph.dst
+        for it in range(200):                                   # re-draw the features of nodes on a too-close edge
+            with torch.no_grad():
+                th = m.theta(f_rows) if cfg["f_dim"] > 0 else f_rows
+                ph = m.phi(f_rows) if cfg["f_dim"] > 0 else f_rows
+                dist, margin = _pcm_discontinuities(merge, th, ph, src, dst)
+            if dist is None:
+                break
+            bad = (dist < margin).nonzero()
+            if len(bad) == 0:
+                break
+            for b, e in bad.tolist():
+                for node in (int(src[e]), int(dst[e])):
+                    f_rows[b, node] = draw_f(1)[0]
+        else:
+            raise AssertionError(f"pcm case {name}: no inputs with the margin found")
+        assert dist is None or dist.min().item() >= margin, name
+        m.graph = None
+        f = f_rows.permute(0, 2, 1).reshape((B, cfg["in_ch"]) + grid).contiguous().requires_grad_(True)
+        cam = draw((B, cfg["g_ch"]) + grid).requires_grad_(True)
+        gout = draw((B, cfg["g_ch"]) + grid)
+        tag = f"pcm/{name}"
+        arrs[f"{tag}/cfg"] = np.array(json.dumps(cfg))
+        for k, v in m.state_dict().items():                     # inputs: exact fp32 values
+            arrs[f"{tag}/sd/{k}"] = _np(v.float())
+        arrs[f"{tag}/cam"], arrs[f"{tag}/f"], arrs[f"{tag}/gout"] = _np(cam.float()), _np(f.float()), _np(gout.float())
+        out = m(cam, f)
+        assert torch.isfinite(out).all(), name
+        (out * gout).sum().backward()
+        # results: the fp64 values rounded to fp32 (fp64 would not fit the size budget of a committed file)
+        arrs[f"{tag}/out"] = _np(out.float())
+        nograd = []
+        for k, t in [("cam", cam), ("f", f)] + [(k, p) for k, p in m.named_parameters()]:
+            if t.grad is None:
+                nograd.append(k)
+            else:
+                arrs[f"{tag}/grad/{k}"] = _np(t.grad.float())
+        arrs[f"{tag}/nograd"] = np.array(nograd, dtype="U64")
+        print(f"pcm {name}: {len(src)} edges, |out| {out.abs().max().item():.3g}, no gradient: {nograd}")
+    # the reference's own graphs on a 3x4x5 grid: every (src, dst) edge, in edge-id order
+    for conn in range(5):
+        for k in (3, 4, 5):
+            for sl in (False, True):
+                m = models.PCM((3, 4, 5), 2, 1, 2, 0, 2, 1, k, merge_type="sm", self_loop=sl, connectivity=conn, p_enc_dim=0)
+                gr = m.init_graph((3, 4, 5), k)
+                arrs[f"graph/c{conn}_k{k}_sl{int(sl)}"] = torch.stack([gr.src, gr.dst], 1).numpy().astype(np.int32)
+    _save("pcm_core", **arrs)
+
+
+GRAD_Q = 32767       # gradients of dc3dat_att.npz: int16 codes of g / max|g| (fp32 or fp64 would not fit a committed file)
+
+
+def gen_att_pcm(models):
+    """DC3DATGeneric(**SLIM_ATT) of the reference in float64 with its real PCM (through the DGL emulation): the init,
+    seed and input of gen_att, one training step's outputs, the gradient of every parameter for
+    sum(d0 * g0) + sum(d1 * g1), the BatchNorm buffers after it, then an eval() forward (what process_pipeline.py
+    runs).  The initial state dict is the one dc3dat_slim.npz holds (slim_att/sd/*): only its checksums are stored.
+    Each gradient g is stored as round(g / max|g| * GRAD_Q) (int16, resolution 1.5e-5 of max|g|) with max|g| and
+    |g|_2 in fp64.  Also the reference's own fp32 run of the same step, gradient by gradient (max-abs error /
+    max|fp64|): the fp32 noise of this network, for the record."""
+    import copy
+    _use_dgl_emulation(models)
+    tag = "slim_att_pcm"
+    arrs = {}
+    torch.manual_seed(0)
+    model32 = models.DC3DATGeneric(**SLIM_ATT)
+    model32.init(models.HeNorm(mode="fan_in"))
+    model = copy.deepcopy(model32).double()
+    for k, v in model32.state_dict().items():
+        vf = v.double()
+        arrs[f"{tag}/sdsum/{k}"] = np.array([vf.sum().item(), (vf * vf).sum().item()])
+    x = torch.rand((2, 1, 16, 16, 16), generator=torch.Generator().manual_seed(1))
+    arrs[f"{tag}/x"] = _np(x)
+    g = torch.Generator().manual_seed(2)
+    g0 = torch.randn((2, 1, 16, 16, 16), generator=g) / x.numel()
+    g1 = torch.randn((2, 1, 16, 16, 16), generator=g) / x.numel()
+    arrs[f"{tag}/gout0"], arrs[f"{tag}/gout1"] = _np(g0), _np(g1)
+    res = {}
+    for prec, m in (("fp64", model), ("fp32", model32)):
+        m.train()
+        xx = x.to(torch.float64 if prec == "fp64" else torch.float32)
+        d0, d1 = m(xx, None)
+        ((d0 * g0.to(xx.dtype)).sum() + (d1 * g1.to(xx.dtype)).sum()).backward()
+        res[prec] = {k: p.grad for k, p in m.named_parameters()}
+        if prec == "fp64":
+            arrs[f"{tag}/dense"], arrs[f"{tag}/refined"] = _np(d0.float()), _np(d1.float())
+            for k, gr in res[prec].items():
+                mx = gr.abs().max().item()
+                arrs[f"{tag}/grad/{k}/q"] = _np(torch.round(gr / mx * GRAD_Q).to(torch.int16))
+                arrs[f"{tag}/grad/{k}/max"] = np.array(mx)
+                arrs[f"{tag}/grad/{k}/norm"] = np.array(gr.norm().item())
+            for k, v in m.state_dict().items():
+                if "running" in k or "num_batches" in k:
+                    arrs[f"{tag}/sd_after/{k}"] = _np(v.float() if v.is_floating_point() else v)
+            m.eval()
+            with torch.no_grad():
+                e0, e1 = m(xx)
+            arrs[f"{tag}/eval_dense"], arrs[f"{tag}/eval_refined"] = _np(e0.float()), _np(e1.float())
+    for k, g64 in res["fp64"].items():
+        err = ((res["fp32"][k].double() - g64).abs().max() / g64.abs().max().clamp_min(1e-300)).item()
+        arrs[f"{tag}/ref_fp32_vs_fp64/{k}"] = np.array(err)
+        print(f"att_pcm: reference fp32 vs fp64 gradient {k}: {err:.2e}")
+    _save("dc3dat_att", **arrs)
+
+
 def gen_loss2():
     """IntRegRefineLoss for a model whose two outputs differ (DC3DATGeneric)."""
     torch.Tensor.cuda = lambda self, *a, **k: self     # generator process only (metrics.py:136,173)
@@ -619,3 +802,7 @@ if __name__ == "__main__":
         gen_affloss()
     if not only or "infer_tail" in only:
         gen_infer_tail()
+    if not only or "pcm" in only:
+        gen_pcm(models)
+    if not only or "att_pcm" in only:
+        gen_att_pcm(models)

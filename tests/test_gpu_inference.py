@@ -182,7 +182,7 @@ def test_full_width_eval_inference_5_lobes_at_80(kind):
     the fused engine in EVAL mode (BatchNorm from running statistics: dram_bn_eval_coef; levels 80 / 40 / 20 / 10) for
     DC3D(st_dram_ref) and for DC3DATGeneric(st_dram_ref_att) -- the model process_pipeline.py:11 loads; its refined second
     output is what evaluate_scan pastes, job_runner.py:764 -- against the oracle's evaluate_scan on the host (one lobe at a
-    time, torch CPU).  Match: job_runner.py:729-770, models.py:543-597.  (The PCM itself stays parity-unpinned: DGL absent.)"""
+    time, torch CPU).  Match: job_runner.py:729-770, models.py:543-597.  (The PCM itself is pinned in tests/test_gpu_pcm.py.)"""
     import time
     from dram_amd import engine
     from dram_amd import functional as HF

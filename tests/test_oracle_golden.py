@@ -174,7 +174,7 @@ def test_dc3dat_wiring_matches_reference_golden(golden_dir):
 @pytest.mark.parametrize("merge", O.PCM_DOT_MERGES)
 @pytest.mark.parametrize("self_loop", [False, True])
 def test_pcm_dense_restatement_equals_literal_one(merge, self_loop):
-    """PARITY UNPINNED (DGL absent): two independent restatements of PCM agree with each other."""
+    """Two independent restatements of PCM agree with each other (the reference: test_pcm_oracle_matches_reference_golden)."""
     g = torch.Generator().manual_seed(5)
     r = lambda *s: torch.randn(*s, generator=g, dtype=torch.float64)
     p = {"theta.weight": r(4, 5), "theta.bias": r(4), "phi.weight": r(4, 5), "phi.bias": r(4),
@@ -189,7 +189,7 @@ def test_pcm_dense_restatement_equals_literal_one(merge, self_loop):
 
 @pytest.mark.parametrize("merge", O.PCM_SUM_MERGES)
 def test_pcm_sum_merges_dense_restatement_equals_literal_one(merge):
-    """PARITY UNPINNED (DGL absent): cosine / heu1 / heu2 (models.py:300-302, 307-320) in the two restatements."""
+    """cosine / heu1 / heu2 (models.py:300-302, 307-320) in the two restatements."""
     g = torch.Generator().manual_seed(8)
     r = lambda *s: torch.rand(*s, generator=g, dtype=torch.float64) + 0.1        # positive features: sums away from zero
     p = {"theta.weight": r(4, 5), "theta.bias": r(4), "phi.weight": r(4, 5), "phi.bias": r(4),
@@ -202,7 +202,7 @@ def test_pcm_sum_merges_dense_restatement_equals_literal_one(merge):
 
 
 def test_pcm_l2_and_heu1_gradient_semantics():
-    """PARITY UNPINNED (DGL absent).  'l2' (models.py:262-264, f_dim = 1): the dense restatement equals the literal one, which
+    """'l2' (models.py:262-264, f_dim = 1): the dense restatement equals the literal one, which
     spells the reference's expression out.  'heu1' (models.py:307-314): the masked similarities are formed under no_grad, so the
     attention is a constant of the graph -- theta / phi receive no gradient in either restatement."""
     g = torch.Generator().manual_seed(9)
@@ -228,7 +228,7 @@ def test_pcm_l2_and_heu1_gradient_semantics():
 @pytest.mark.parametrize("merge", O.PCM_GEO_MERGES)
 @pytest.mark.parametrize("geo_f", [4, 0])
 def test_pcm_geo_dense_restatement_equals_literal_one(merge, geo_f):
-    """PARITY UNPINNED (DGL absent): the geo family of merge_func (models.py:287-299) in the two restatements; the
+    """The geo family of merge_func (models.py:287-299) in the two restatements; the
     positional encoding against the reference's formula evaluated by hand at one voxel."""
     g = torch.Generator().manual_seed(7)
     r = lambda *s: torch.randn(*s, generator=g, dtype=torch.float64)
@@ -329,3 +329,149 @@ def test_resample_itk_restatement_properties():
     size = (16, 7, 10)
     req = tuple(1.0 * n / m for n, m in zip(f.shape, size))
     assert np.abs(O.resample_itk(f, (1.0, 1.0, 1.0), req, size, "linear") - O.resample_itk_linear(f, size)).max() <= 1e-6
+
+
+# ---------------------------------------------------------------- PCM against the reference's own PCM.forward
+# tests/golden/pcm_core.npz / dc3dat_att.npz: the reference's models.PCM / DC3DATGeneric run in float64
+# (oracle/make_golden.py:gen_pcm, gen_att_pcm).  Inputs are stored as the exact fp32 values they were run with.
+PCM_CASES = [str(c) for c in np.load(os.path.join(os.path.dirname(__file__), "golden", "pcm_core.npz"))["cases"]]
+FP32_ROUNDING = 2.0 ** -24
+
+
+def _close_to_fp32_golden(got, stored, tol=1e-10, scale=None):
+    """`stored` is a float64 result rounded to fp32: `got` (float64) must equal the float64 result to `tol` of `scale`
+    (default: its largest element), i.e. lie within that plus the half-ulp of fp32 rounding of every stored element."""
+    got = got.detach().double().numpy()
+    stored = np.asarray(stored, dtype=np.float64)
+    assert got.shape == stored.shape
+    scale = np.abs(stored).max() if scale is None else scale
+    bound = FP32_ROUNDING * np.abs(stored) * (1 + 1e-6) + tol * scale
+    excess = np.abs(got - stored) - bound
+    assert excess.max() <= 0.0, (float(np.abs(got - stored).max()), float(np.abs(stored).max()))
+
+
+def _pcm_case(z, case):
+    import json
+    tag = f"pcm/{case}/"
+    cfg = json.loads(str(z[tag + "cfg"]))
+    sd = {k: _t(v).double() for k, v in _sub(z, tag + "sd/").items()}
+    return tag, cfg, sd, _t(z[tag + "cam"]).double(), _t(z[tag + "f"]).double(), _t(z[tag + "gout"]).double()
+
+
+@pytest.mark.parametrize("case", PCM_CASES)
+def test_pcm_oracle_matches_reference_golden(golden_dir, case):
+    """`O.pcm_forward` reproduces the reference's PCM.forward (float64) case by case: the output and the gradients of cam, f
+    and every parameter; gradients the reference does not produce (heu1's theta / phi and f, unused geo projections) are
+    absent here too."""
+    z = _load(golden_dir, "pcm_core")
+    tag, cfg, sd, cam, f, gout = _pcm_case(z, case)
+    p = {k: v.requires_grad_(True) for k, v in sd.items()}
+    cam, f = cam.requires_grad_(True), f.requires_grad_(True)
+    out = O.pcm_forward(p, cam, f, cfg["k_size"], cfg["connectivity"], cfg["self_loop"], cfg["merge"], cfg["iters"],
+                        cfg["residual"], p_enc_dim=cfg["p_enc_dim"])
+    (out * gout).sum().backward()
+    _close_to_fp32_golden(out, z[tag + "out"])
+    grads, nograd = _sub(z, tag + "grad/"), set(z[tag + "nograd"].tolist())
+    tensors = {"cam": cam, "f": f, **p}
+    assert set(grads) | nograd == set(tensors) and not set(grads) & nograd
+    # phi.bias shifts all logits of a node equally: its exact gradient is 0 under a softmax, so parameter gradients are
+    # held to the scale of the largest one
+    pscale = max([float(np.abs(v).max()) for k, v in grads.items() if k not in ("cam", "f")], default=0.0)
+    for k, t in tensors.items():
+        if k in nograd:
+            assert t.grad is None, k
+        else:
+            _close_to_fp32_golden(t.grad, grads[k], scale=None if k in ("cam", "f") else pscale)
+
+
+def _stencil_edges(offsets, shape):
+    """The (src, dst) node pairs of a stencil on the grid: node i receives from i + o for every offset o inside the grid."""
+    D, H, W = shape
+    z, y, x = (a.ravel() for a in np.meshgrid(np.arange(D), np.arange(H), np.arange(W), indexing="ij"))
+    dst = np.arange(D * H * W)
+    edges = set()
+    for dz, dy, dx in offsets:
+        ok = (0 <= z + dz) & (z + dz < D) & (0 <= y + dy) & (y + dy < H) & (0 <= x + dx) & (x + dx < W)
+        src = ((z + dz) * H + (y + dy)) * W + (x + dx)
+        edges |= set(zip(src[ok].tolist(), dst[ok].tolist()))
+    return edges
+
+
+def test_pcm_stencil_equals_reference_graph(golden_dir):
+    """The repo's models.PCM.init_graph() offsets, expanded on a 3x4x5 grid and clipped at its border, give exactly the edge
+    set of the reference's init_graph (its interior / side-node construction, models.py:223-259) for connectivity 0-4,
+    k_size 3 / 4 / 5, with and without self loops."""
+    import models
+    z = _load(golden_dir, "pcm_core")
+    shape = (3, 4, 5)
+    for conn in range(5):
+        for k in (3, 4, 5):
+            for sl in (False, True):
+                ref = z[f"graph/c{conn}_k{k}_sl{int(sl)}"]
+                m = models.PCM(shape, 2, 1, 2, 0, 2, 1, k, merge_type="sm", self_loop=sl, connectivity=conn, p_enc_dim=0)
+                offs = m.init_graph()
+                assert len(set(offs)) == len(offs)
+                ref_edges = set(map(tuple, ref.tolist()))
+                assert len(ref_edges) == len(ref), (conn, k, sl)        # no repeated edge in the reference graph
+                assert _stencil_edges(offs, shape) == ref_edges, (conn, k, sl)
+
+
+def test_pcm_structuring_element_is_scipys():
+    """The structuring element models.PCM.init_graph builds by hand equals ndimage.generate_binary_structure(3, c), which
+    the reference calls (models.py:232), for c = 0..4 (scipy treats c < 1 as 1 and c > 3 as 3)."""
+    import models
+    from scipy import ndimage
+    for c in range(5):
+        m = models.PCM((4, 4, 4), 2, 1, 2, 0, 2, 1, 3, merge_type="sm", self_loop=True, connectivity=c, p_enc_dim=0)
+        got = np.zeros((3, 3, 3), dtype=bool)
+        for o in m.init_graph():
+            got[o[0] + 1, o[1] + 1, o[2] + 1] = True
+        assert np.array_equal(got, ndimage.generate_binary_structure(3, c)), c
+
+
+ATT_TAG = "slim_att_pcm"
+ATT_GRAD_Q = 32767          # oracle/make_golden.py:GRAD_Q
+
+
+def load_att_pcm_golden(golden_dir):
+    """dc3dat_att.npz plus the initial state dict it was generated from (dc3dat_slim.npz, checked against the stored
+    checksums); gradients decoded to float64 {name: (values, max|g|, |g|_2)}."""
+    z = _load(golden_dir, "dc3dat_att")
+    sd = {k: _t(v) for k, v in _sub(_load(golden_dir, "dc3dat_slim"), "slim_att/sd/").items()}
+    sums = _sub(z, ATT_TAG + "/sdsum/")
+    assert set(sums) == set(sd)
+    for k, v in sd.items():
+        vf = v.double()
+        assert np.allclose([vf.sum().item(), (vf * vf).sum().item()], sums[k], rtol=1e-12, atol=1e-12), k
+    grads = {}
+    for k in z.files:
+        if k.startswith(ATT_TAG + "/grad/") and k.endswith("/q"):
+            name = k[len(ATT_TAG + "/grad/"):-2]
+            mx = float(z[f"{ATT_TAG}/grad/{name}/max"])
+            grads[name] = (z[k].astype(np.float64) * (mx / ATT_GRAD_Q), mx, float(z[f"{ATT_TAG}/grad/{name}/norm"]))
+    return z, sd, grads
+
+
+def test_dc3dat_attention_oracle_matches_reference_golden(golden_dir):
+    """`O.dc3dat_forward(attention=True)` reproduces the reference's DC3DATGeneric(SLIM_ATT) step with its real PCM: both
+    outputs, and every parameter gradient (elementwise to the int16 resolution of the stored codes, max|g| and |g|_2 to
+    1e-10).  The conv biases in front of BatchNorm have an exact gradient of 0: both sides hold rounding noise only."""
+    from oracle.make_golden import SLIM_ATT
+    z, sd, grads = load_att_pcm_golden(golden_dir)
+    params, buffers = O.split_state_dict({k: v.double() if v.is_floating_point() else v.clone() for k, v in sd.items()})
+    for p in params.values():
+        p.requires_grad_(True)
+    x = _t(z[ATT_TAG + "/x"]).double()
+    d0, d1, _ = O.dc3dat_forward(SLIM_ATT, params, buffers, x, training=True, attention=True)
+    ((d0 * _t(z[ATT_TAG + "/gout0"]).double()).sum() + (d1 * _t(z[ATT_TAG + "/gout1"]).double()).sum()).backward()
+    _close_to_fp32_golden(d0, z[ATT_TAG + "/dense"])
+    _close_to_fp32_golden(d1, z[ATT_TAG + "/refined"])
+    assert set(grads) == set(params)
+    gmax = max(mx for _, mx, _ in grads.values())
+    for k, (ref, mx, nrm) in grads.items():
+        got = params[k].grad.double().numpy()
+        if k.startswith("reshape.") and k.endswith(".0.bias"):
+            assert np.abs(got).max() <= 1e-12 * gmax and mx <= 1e-12 * gmax, k
+            continue
+        assert np.abs(got - ref).max() <= (0.5 / ATT_GRAD_Q + 1e-10) * mx, k
+        assert abs(np.abs(got).max() - mx) <= 1e-10 * mx and abs(np.linalg.norm(got) - nrm) <= 1e-10 * nrm, k
