@@ -31,6 +31,11 @@ SIGNATURES = {
     "dram_conv3d_k3_wgrad_ws_bytes": (Z, [I, I, I, I, I, I]),
     "dram_conv3d_k3_wgrad": (I, [P, P, P, P, Z, I, I, I, I, I, I, P]),
     "dram_conv3d_k3_wgrad_ex": (I, [P, I, P, I, I, I, I, I, I, I, P, P, P, Z, I, I, I, I, I, P]),
+    "dram_conv3d_fwd": (I, [P, P, P, P] + [I] * 15 + [P]),
+    "dram_conv3d_bwd_data": (I, [P, P, P] + [I] * 15 + [P]),
+    "dram_conv3d_wgrad_ws_bytes": (Z, [I] * 15),
+    "dram_conv3d_wgrad": (I, [P, P, P, P, Z] + [I] * 15 + [P]),
+    "dram_conv3d_gen_launch_counts": (I, [P, I]),
     "dram_channel_sum_ws_bytes": (Z, [I, I, L]),
     "dram_channel_sum": (I, [P, P, P, Z, I, I, L, P]),
     "dram_norm_ws_bytes": (Z, [I, I, L]),

@@ -307,6 +307,94 @@ def conv3d_k1(x, w, bias=None):
     return Conv3dK1Fn.apply(x, w, bias)
 
 
+# --------------------------------------------------------------------------- general conv
+# kernel families of the general conv (include/dram_hip.h DRAM_CONV_GEN_*)
+GEN_FWD, GEN_BWD_DATA, GEN_WGRAD, GEN_KINDS = range(4)
+
+
+def conv_gen_launch_counts():
+    """Launches per general-conv kernel family (index = GEN_*) since the library was loaded."""
+    arr = (ctypes.c_ulonglong * GEN_KINDS)()
+    call("dram_conv3d_gen_launch_counts", ctypes.cast(arr, ctypes.c_void_p), GEN_KINDS)
+    return list(arr)
+
+
+def _triple(v, name):
+    t = tuple(int(e) for e in v) if isinstance(v, (tuple, list)) else (int(v),) * 3
+    if len(t) != 3:
+        raise ValueError(f"conv3d: {name} needs 1 or 3 values, got {v}")
+    return t
+
+
+def conv_out_size(size, kernel, stride, padding):
+    """Output size of nn.Conv3d per axis (dilation 1): (I + 2p - k) // s + 1; ValueError if below 1."""
+    out = tuple((i + 2 * p - k) // s + 1 if i + 2 * p >= k else 0 for i, k, s, p in zip(size, kernel, stride, padding))
+    if min(out) < 1:
+        raise ValueError(f"conv3d: input {tuple(size)} with kernel {tuple(kernel)}, stride {tuple(stride)} and padding "
+                         f"{tuple(padding)} gives output size {out}")
+    return out
+
+
+class Conv3dGenFn(Function):
+    """y = conv3d(x, w, bias, stride, padding) for kernels 1..7, padding 0..max(k-1, 1) and stride 1 or 2 per axis
+    (nn.Conv3d of reference parts.py:66-196 / models.py:54-112 built with other kernel_sizes / padding_list /
+    conv_strides than the standard 3x3x3 pad 1 and 1x1x1 pad 0)."""
+
+    @staticmethod
+    def forward(ctx, x, w, bias, stride, padding):
+        x = _chk(x, "conv3d input", 5)
+        w = _chk(w, "conv3d weight", 5)
+        N, Ci, D, H, W = x.shape
+        Co = w.shape[0]
+        k = tuple(w.shape[2:])
+        if w.shape[1] != Ci:
+            raise ValueError(f"conv3d: input has {Ci} channels, weight expects {w.shape[1]}")
+        out = conv_out_size((D, H, W), k, stride, padding)
+        if bias is not None:
+            bias = _chk(bias, "conv3d bias", 1)
+        y = torch.empty((N, Co) + out, dtype=torch.float32, device=x.device)
+        geom = (N, Ci, Co, D, H, W) + k + tuple(stride) + tuple(padding)
+        vox = N * out[0] * out[1] * out[2]
+        flops = 2.0 * Ci * Co * k[0] * k[1] * k[2] * vox
+        _timed_call("conv3d_gen_fwd_kernel", flops, 4.0 * (Ci * D * H * W * N + Co * vox), "dram_conv3d_fwd",
+                    _p(x), _p(w), _p(bias), _p(y), *geom, _stream())
+        ctx.save_for_backward(x, w)
+        ctx.has_bias = bias is not None
+        ctx.geom = geom
+        ctx.flops = flops
+        return y
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, dy):
+        x, w = ctx.saved_tensors
+        dy = _chk(dy, "conv3d grad_output", 5)
+        geom = ctx.geom
+        N, Co = geom[0], geom[2]
+        st = _stream()
+        dx = dw = db = None
+        nbytes = 4.0 * (x.numel() + dy.numel())
+        if ctx.needs_input_grad[0]:
+            dx = torch.empty_like(x)
+            _timed_call("conv3d_gen_bwd_data", ctx.flops, nbytes, "dram_conv3d_bwd_data", _p(dy), _p(w), _p(dx), *geom, st)
+        if ctx.needs_input_grad[1]:
+            dw = torch.empty_like(w)
+            ws = _ws(_lib.lib.dram_conv3d_wgrad_ws_bytes(*geom), dy.device)
+            _timed_call("conv3d_gen_wgrad_kernel", ctx.flops, nbytes, "dram_conv3d_wgrad", _p(x), _p(dy), _p(dw), _p(ws),
+                        ws.numel(), *geom, st)
+        if ctx.has_bias and ctx.needs_input_grad[2]:
+            S = dy.shape[2] * dy.shape[3] * dy.shape[4]
+            db = torch.empty(Co, dtype=torch.float32, device=dy.device)
+            ws = _ws(_lib.lib.dram_channel_sum_ws_bytes(N, Co, S), dy.device)
+            call("dram_channel_sum", _p(dy), _p(db), _p(ws), ws.numel(), N, Co, S, st)
+        return dx, dw, db, None, None
+
+
+def conv3d_gen(x, w, bias=None, stride=1, padding=0):
+    """General 3-D convolution (zero padding, dilation 1, groups 1); see Conv3dGenFn."""
+    return Conv3dGenFn.apply(x, w, bias, _triple(stride, "stride"), _triple(padding, "padding"))
+
+
 # --------------------------------------------------------------------------- norm (+ReLU)
 class NormActFn(Function):
     """BatchNorm3d / GroupNorm with optional fused ReLU (normal_wrapper + act_wrapper,

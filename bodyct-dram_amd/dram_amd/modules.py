@@ -12,24 +12,41 @@ from . import functional as HF
 
 
 class HipConv3d(nn.Conv3d):
-    """nn.Conv3d restricted to what the reference instantiates: 3x3x3/pad 1 (parts.py:95..185)
-    and 1x1x1/pad 0 (models.py:109), stride 1, no dilation/groups."""
+    """nn.Conv3d with zero padding, dilation 1 and groups 1.  Three kinds (`_kind`):
+      3      3x3x3 / pad 1 / stride 1 (parts.py:95..185 with the default knobs): conv3d_k3, which also reads a
+             virtual crop_concat `skip` input;
+      1      1x1x1 / pad 0 / stride 1 (models.py:109): conv3d_k1;
+      "gen"  any other kernel 1..7, padding 0..max(k-1, 1) and stride 1 or 2 per axis (kernel_sizes, padding_list and
+             conv_strides of parts.py:66-196 / models.py:54-112): conv3d_gen.
+    Anything else raises NotImplementedError at the first forward."""
+
+    LIMITS = "kernel 1..7, padding 0..max(k-1, 1) and stride 1 or 2 per axis, dilation 1, groups 1, padding_mode 'zeros'"
 
     def _kind(self):
-        if self.stride != (1, 1, 1) or self.dilation != (1, 1, 1) or self.groups != 1 or self.padding_mode != "zeros":
-            raise NotImplementedError("HipConv3d: only stride 1, dilation 1, groups 1, zero padding is implemented")
-        if self.kernel_size == (3, 3, 3) and self.padding == (1, 1, 1):
-            return 3
-        if self.kernel_size == (1, 1, 1) and self.padding == (0, 0, 0):
-            return 1
-        raise NotImplementedError(f"HipConv3d: kernel {self.kernel_size} / padding {self.padding} is not implemented "
-                                  f"(the DRAM models use 3x3x3 pad 1 and 1x1x1 pad 0)")
+        if self.dilation != (1, 1, 1) or self.groups != 1 or self.padding_mode != "zeros" or isinstance(self.padding, str):
+            raise NotImplementedError(f"HipConv3d: dilation {self.dilation}, groups {self.groups}, padding "
+                                      f"{self.padding!r} ({self.padding_mode}) is not implemented; supported: {self.LIMITS}")
+        if self.stride == (1, 1, 1):
+            if self.kernel_size == (3, 3, 3) and self.padding == (1, 1, 1):
+                return 3
+            if self.kernel_size == (1, 1, 1) and self.padding == (0, 0, 0):
+                return 1
+        if all(1 <= k <= 7 and s in (1, 2) and 0 <= p <= max(k - 1, 1)
+               for k, s, p in zip(self.kernel_size, self.stride, self.padding)):
+            return "gen"
+        raise NotImplementedError(f"HipConv3d: kernel {self.kernel_size} / stride {self.stride} / padding {self.padding} "
+                                  f"is not implemented; supported: {self.LIMITS}")
 
     def forward(self, x, skip=None):
-        if self._kind() == 3:
+        kind = self._kind()
+        if kind == 3:
             return HF.conv3d_k3(x, self.weight, self.bias, skip)
+        if kind == "gen":
+            if skip is not None:            # (not the benchmark's geometry: the concatenation is materialised)
+                x = HF.crop_concat(x, skip)
+            return HF.conv3d_gen(x, self.weight, self.bias, self.stride, self.padding)
         if skip is not None:
-            raise ValueError("HipConv3d: a skip input is only supported by the 3x3x3 kernel")
+            raise ValueError("HipConv3d: a skip input is only supported by the 3x3x3 and general kernels")
         return HF.conv3d_k1(x, self.weight, self.bias)
 
 

@@ -138,7 +138,8 @@ class UpsampleConvBlock5d(nn.Module):
         assert (up_inputs.dim() == cats.dim() == 5)
         assert (up_inputs.shape[-1] <= cats.shape[-1])
         first = self.conv_blocks[0][0]
-        if isinstance(first, HipConv3d) and first.kernel_size == (3, 3, 3):
+        if isinstance(first, HipConv3d) and first.kernel_size == (3, 3, 3) and first.padding == (1, 1, 1) \
+                and first.stride == (1, 1, 1):
             return run_conv_stack(self.conv_blocks, up_inputs, skip=cats)
         return run_conv_stack(self.conv_blocks, crop_concat_5d(up_inputs, cats))
 

@@ -95,6 +95,31 @@ int dram_conv3d_k3_wgrad_ex(const float* x1, int C1, const float* x2, int C2, in
 size_t dram_channel_sum_ws_bytes(int N, int C, int64_t S);
 int dram_channel_sum(const float* dy, float* dbias, void* ws, size_t ws_bytes, int N, int C, int64_t S, void* stream);
 
+/* ---- general 3-D convolution: kernel 1..7, zero padding 0..max(k-1, 1), stride 1 or 2 per axis; dilation 1, groups 1
+ * (nn.Conv3d of parts.py:66-196 / models.py:54-112 with kernel_sizes, padding_list, conv_strides other than 3x3x3/pad 1
+ * and 1x1x1/pad 0) ----
+ * Shapes: x[N,Cin,D,H,W], w[Cout,Cin,kz,ky,kx] (the parameter's own layout), y[N,Cout,OD,OH,OW] with
+ * O = (I + 2p - k) / s + 1 per axis (>= 1, else DRAM_EINVAL).  Geometry outside the limits above is DRAM_EINVAL, checked
+ * before anything is launched. */
+int dram_conv3d_fwd(const float* x, const float* w, const float* bias, float* y, int N, int Cin, int Cout, int D, int H,
+                    int W, int kz, int ky, int kx, int sz, int sy, int sx, int pz, int py, int px, void* stream);
+/* dx[N,Cin,D,H,W] from dy[N,Cout,OD,OH,OW]; D,H,W are the sizes of x (they fix OD,OH,OW as above). */
+int dram_conv3d_bwd_data(const float* dy, const float* w, float* dx, int N, int Cin, int Cout, int D, int H, int W,
+                         int kz, int ky, int kx, int sz, int sy, int sx, int pz, int py, int px, void* stream);
+/* dw[Cout,Cin,kz,ky,kx] = sum over (n, output voxel) of dy * x at the tap; deterministic (per-block partial slabs in
+ * `ws`, summed in a fixed order).  _ws_bytes returns 0 for an unsupported geometry. */
+size_t dram_conv3d_wgrad_ws_bytes(int N, int Cin, int Cout, int D, int H, int W, int kz, int ky, int kx, int sz, int sy,
+                                  int sx, int pz, int py, int px);
+int dram_conv3d_wgrad(const float* x, const float* dy, float* dw, void* ws, size_t ws_bytes, int N, int Cin, int Cout,
+                      int D, int H, int W, int kz, int ky, int kx, int sz, int sy, int sx, int pz, int py, int px,
+                      void* stream);
+/* launches per kernel family (index = DRAM_CONV_GEN_*) since the library was loaded, into counts[0..n) */
+#define DRAM_CONV_GEN_FWD 0       /* conv3d_gen_fwd_kernel, forward */
+#define DRAM_CONV_GEN_BWD_DATA 1  /* conv3d_gen_fwd_kernel, one launch per backward-data output phase */
+#define DRAM_CONV_GEN_WGRAD 2     /* conv3d_gen_wgrad_kernel (+ slab reduce) */
+#define DRAM_CONV_GEN_KINDS 3
+int dram_conv3d_gen_launch_counts(unsigned long long* counts, int n);
+
 /* ---- normalisation (+ fused ReLU) (normal_wrapper parts.py:17-35, act_wrapper parts.py:48-54) ----
  *
  * Training-mode forward: computes statistics of x (two-level Chan/Welford
