@@ -121,6 +121,12 @@ SIGNATURES = {
     # measured ceilings (bench.py)
     "dram_calibrate_hbm_copy": (I, [P, P, Z, P]),
     "dram_calibrate_mfma_f32": (I, [P, I, I, P, P]),
+    # training-time augmentation pool
+    "dram_aug_minmax": (I, [P, P, P, I, L, P]),
+    "dram_aug_gaussian_blur": (I, [P, P, P, P, I, I, I, I, I, I, P]),
+    "dram_aug_mask_out": (I, [P, P, P, P, P, P, I, I, I, I, I, I, P]),
+    "dram_aug_gaussian_noise": (I, [P, P, P, P, P, P, I, P, I, L, P]),
+    "dram_aug_permute_flip": (I, [P, P, I, P, P, P, I, I, I, I, I, I, P]),
 }
 
 

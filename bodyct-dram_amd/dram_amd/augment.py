@@ -1,0 +1,469 @@
+"""The reference's training-time augmentation pool on a whole device batch.
+
+`LesionSegChunkTrain.ensemble_scan_augmentation` (dram/job_runner.py:548-581) draws, for every chunk, a random order of
+`GaussianBlur`, `RandomMaskOut`, `RandomFlip`, `RandomRotate90` and `GaussianAddictive` (dram/data_transforms.py) and applies a
+random subset with numpy / scipy on the host.  The classes here keep those names, constructor signatures and defaults, and use
+the sample-dict protocol of `transforms.py`: entries whose key contains "#" hold device tensors [N, D, H, W] or [N, 1, D, H, W];
+the intensity transforms touch keys with both "#" and "image", flip and rotate touch every "#" key, everything else passes
+through.  The work runs in per-batch launches of csrc/augment.hip over per-sample parameter tables: no host synchronisation.
+
+Drawing.  `draw(n, shape)` returns one parameter dict per sample, in sample order, from the same `random` / `numpy.random`
+calls in the same order as the reference's `__call__` makes for one chunk, so a seeded run picks what the reference would pick
+for that chunk.  (The reference draws an intensity transform's parameters once per "#image" entry; here one set per sample
+serves every image entry, which is the same thing for the single-image samples of training.)  `apply(sample, params)` runs with
+given parameters; an entry of `params` that is None leaves that sample untouched (bit-identical).
+"""
+import itertools
+import random
+
+import numpy as np
+import torch
+
+from . import functional as HF
+from ._lib import call
+
+MAX_RADIUS = 4     # DRAM_AUG_MAX_RADIUS
+MAX_BOXES = 16     # DRAM_AUG_MAX_BOXES
+TRANSFORM, PASS, SKIP = 1, 0, -1   # per-sample flags of the C entries
+
+
+# ---------------------------------------------------------------------------------------------------------------- tables
+def blur_radius(sigma, truncate=4.0):
+    return int(truncate * float(sigma) + 0.5)
+
+
+def blur_weights(sigma, truncate=4.0):
+    """The normalised 1-D kernel scipy.ndimage.gaussian_filter1d uses for `sigma` (fp64, length 2 * radius + 1)."""
+    sigma = float(sigma)
+    radius = blur_radius(sigma, truncate)
+    x = np.arange(-radius, radius + 1)
+    phi = np.exp(-0.5 / (sigma * sigma) * x ** 2)
+    return phi / phi.sum()
+
+
+def mask_boxes(centers, sizes, shape):
+    """RandomMaskOut._mask_out's slices as rows (z0, z1, y0, y1, x0, x1), half-open; an empty box has z1 <= z0 etc."""
+    rows = []
+    for center, size in zip(centers, sizes):
+        row = []
+        for c, s, dim in zip(center, size, shape):
+            row += [max(0, c - s // 2), min(c + (s - s // 2), dim)]
+        rows.append(row)
+    return rows
+
+
+def flip_table(axis):
+    """np.flip(data, axis) for a negative spatial axis as (perm, flip) of dram_aug_permute_flip."""
+    return HF.signed_permutation([("flip", (axis % 5,))])
+
+
+def rotate_table(axis, times, shape):
+    """np.rot90(data, k=times, axes=axis) for negative spatial axes as (perm, flip).  A quarter turn by an odd count between
+    axes of different extents changes the sample's shape, which a batch tensor cannot hold."""
+    a, b = (v % 5 for v in axis)
+    if times % 2 and shape[a - 2] != shape[b - 2]:
+        raise ValueError(f"a rotation by {times} quarter turns in a plane of unequal extents {shape[a - 2]} x {shape[b - 2]} "
+                         f"changes the sample's shape and cannot live in a batch tensor (cubic chunks only)")
+    return HF.signed_permutation(HF.rot90_ops(times, (a, b)))
+
+
+def _dev(values, dtype, device):
+    """A small parameter table on the device.  From pinned memory, so that the copy neither waits for the stream nor outlives its
+    source: the pinned block is recycled only after the copy has run."""
+    t = torch.tensor(values, dtype=dtype)
+    if torch.device(device).type != "cuda":
+        return t.to(device)
+    return t.pin_memory().to(device, non_blocking=True)
+
+
+def _flags(params, device):
+    return _dev([TRANSFORM if p is not None else PASS for p in params], torch.int32, device)
+
+
+def _as_batch(t, name, dtypes=(torch.float32,)):
+    """[N, D, H, W] or [N, C, D, H, W] device tensor -> (contiguous 5-d view, original shape)."""
+    if not isinstance(t, torch.Tensor):
+        raise TypeError(f"{name}: expected a tensor")
+    if not t.is_cuda:
+        raise RuntimeError(f"{name}: tensor is on {t.device}; the augmentation kernels only run on a ROCm device "
+                           f"(there is no CPU fallback)")
+    if t.dtype not in dtypes:
+        raise TypeError(f"{name}: expected {' or '.join(str(d) for d in dtypes)}, got {t.dtype}")
+    if t.dim() not in (4, 5):
+        raise ValueError(f"{name}: expected [N, D, H, W] or [N, C, D, H, W], got shape {tuple(t.shape)}")
+    shape = tuple(t.shape)
+    t = t.contiguous()
+    return (t.unsqueeze(1) if t.dim() == 4 else t), shape
+
+
+def _as_image(t, name):
+    v, shape = _as_batch(t, name)
+    if v.shape[1] != 1:
+        raise ValueError(f"{name}: the intensity transforms work on single-channel samples, got shape {shape}")
+    return v, shape
+
+
+# --------------------------------------------------------------------------------------------- batched device primitives
+# Each takes the 5-d view, per-sample DEVICE tables and an int32 flag tensor (TRANSFORM / PASS / SKIP), and an optional `out`.
+def sample_minmax(x, flags=None, out=None):
+    """[N, 2] fp32 {min, max} of every sample (deterministic).  Rows whose flag is not TRANSFORM are left untouched."""
+    x, _ = _as_batch(x, "minmax input")
+    N = x.shape[0]
+    mm = out if out is not None else torch.empty((N, 2), dtype=torch.float32, device=x.device)
+    call("dram_aug_minmax", HF._p(x), HF._p(mm), HF._p(flags), N, x[0].numel(), HF._stream())
+    return mm
+
+
+def _blur(x, weights, flags, radius, out=None):
+    N, _, D, H, W = x.shape
+    y = torch.empty_like(x) if out is None else out
+    call("dram_aug_gaussian_blur", HF._p(x), HF._p(y), HF._p(weights), HF._p(flags), flags.numel(), int(radius), N, D, H, W,
+         HF._stream())
+    return y
+
+
+def _mask_out(x, minmax, boxes, u, flags, out=None):
+    N, _, D, H, W = x.shape
+    y = torch.empty_like(x) if out is None else out
+    call("dram_aug_mask_out", HF._p(x), HF._p(y), HF._p(minmax), HF._p(boxes), HF._p(u), HF._p(flags), flags.numel(),
+         boxes.shape[1], N, D, H, W, HF._stream())
+    return y
+
+
+def _noise(x, minmax, sigma, seeds, flags, noise=None, out=None):
+    N = x.shape[0]
+    y = torch.empty_like(x) if out is None else out
+    call("dram_aug_gaussian_noise", HF._p(x), HF._p(y), HF._p(minmax), HF._p(sigma), HF._p(seeds), HF._p(flags), flags.numel(),
+         HF._p(noise), N, x[0].numel(), HF._stream())
+    return y
+
+
+def _permute_flip(x, perm, flip, flags, out=None):
+    N, C, D, H, W = x.shape
+    y = torch.empty_like(x) if out is None else out
+    call("dram_aug_permute_flip", HF._p(x), HF._p(y), x.element_size(), HF._p(perm), HF._p(flip), HF._p(flags), flags.numel(),
+         N, C, D, H, W, HF._stream())
+    return y
+
+
+def gaussian_noise(x, minmax, sigma, seeds, noise=None):
+    """The noise kernel with explicit tables (every sample active): x [N, ...] fp32, minmax [N, 2] device tensor, sigma and
+    seeds sequences of N.  `noise`: optional [N, ...] float64 device tensor used instead of the in-kernel generator."""
+    v, shape = _as_image(x, "noise input")
+    N = v.shape[0]
+    if len(sigma) != N or len(seeds) != N:
+        raise ValueError("gaussian_noise: one sigma and one seed per sample")
+    if noise is not None and (noise.dtype != torch.float64 or noise.numel() != v.numel() or not noise.is_cuda):
+        raise ValueError("gaussian_noise: the explicit noise is a float64 device tensor of the input's shape")
+    y = _noise(v, minmax.contiguous(), _dev([float(s) for s in sigma], torch.float32, v.device),
+               _dev([int(s) for s in seeds], torch.int64, v.device), _dev([TRANSFORM] * N, torch.int32, v.device),
+               None if noise is None else noise.contiguous())
+    return y.view(shape)
+
+
+# ------------------------------------------------------------------------------------------------------------ transforms
+def _first_tensor(sample):
+    for key, value in sample.items():
+        if "#" in key:
+            return value
+    raise ValueError("the sample holds no '#' entry")
+
+
+class _Augmentation:
+    """draw / apply / __call__ shared by the five pool elements."""
+    intensity = True      # True: touches '#...image...' entries only; False: every '#' entry
+
+    def draw_one(self, shape):   # pragma: no cover - overridden
+        raise NotImplementedError
+
+    def draw(self, n, shape):
+        """One parameter dict per sample, in sample order; `shape` = the spatial extents (D, H, W)."""
+        return [self.draw_one(tuple(shape)) for _ in range(n)]
+
+    def _touches(self, key):
+        return "#" in key and ("image" in key or not self.intensity)
+
+    def _tables(self, params, shape, device):   # pragma: no cover - overridden
+        raise NotImplementedError
+
+    def _launch(self, x, tables, flags, out=None):   # pragma: no cover - overridden
+        raise NotImplementedError
+
+    def apply(self, sample, params):
+        """`params`: one entry per sample (a dict as `draw` returns it, or None = leave the sample untouched)."""
+        out, tables = {}, None
+        for key, value in sample.items():
+            if not self._touches(key):
+                out[key] = value
+                continue
+            dtypes = (torch.float32,) if self.intensity else (torch.float32, torch.uint8)
+            v, shape = (_as_image(value, key) if self.intensity else _as_batch(value, key, dtypes))
+            if len(params) != v.shape[0]:
+                raise ValueError(f"{type(self).__name__}: {len(params)} parameter sets for a batch of {v.shape[0]}")
+            if tables is None:
+                tables = self._tables(params, tuple(v.shape[2:]), v.device)
+                flags = _flags(params, v.device)
+            out[key] = self._launch(v, tables, flags).view(shape)
+        return out
+
+    def __call__(self, sample):
+        first = _first_tensor(sample)
+        return self.apply(sample, self.draw(first.shape[0], tuple(first.shape[-3:])))
+
+
+class GaussianBlur(_Augmentation):
+    """scipy.ndimage.gaussian_filter(chunk, sigma) per sample: sigma[0] when mode == 'fixed', otherwise one
+    np.random.uniform(sigma[0], sigma[1]) draw.  Radius int(4 * sigma + 0.5), at most 4 (sigma < 1.125)."""
+
+    def __init__(self, sigma, mode='fixed'):
+        self.sigma = sigma
+        self.mode = mode
+
+    def draw_one(self, shape):
+        return {"sigma": self.sigma[0] if self.mode == 'fixed' else np.random.uniform(self.sigma[0], self.sigma[1])}
+
+    def _tables(self, params, shape, device):
+        rows, radius = [], 0
+        for p in params:
+            row = [0.0] * (MAX_RADIUS + 1)
+            if p is not None:
+                r = blur_radius(p["sigma"])
+                if r > MAX_RADIUS:
+                    raise ValueError(f"GaussianBlur: sigma {p['sigma']} needs radius {r}; the kernel supports at most {MAX_RADIUS}")
+                w = blur_weights(p["sigma"])
+                row[:r + 1] = [float(v) for v in w[r:]]
+                radius = max(radius, r)
+            rows.append(row)
+        return _dev(rows, torch.float32, device), radius
+
+    def _launch(self, x, tables, flags, out=None):
+        return _blur(x, tables[0], flags, tables[1], out)
+
+
+class RandomMaskOut(_Augmentation):
+    """`times` boxes per sample, centre int(dim * U(region_range)) and size int(U(region_size) * dim) per axis, each filled with
+    one value min + (max - min) * u of the sample's own range (taken before any box is written).  `assign_value` is unused, as in
+    the reference."""
+
+    def __init__(self, times=5, region_range=((0.2, 0.8), (0.2, 0.8), (0.2, 0.8)),
+                 region_size=((0.01, 0.06), (0.01, 0.06), (0.01, 0.06)), spatial_dim=3, assign_value=0):
+        self.region_range = region_range
+        self.region_size = region_size
+        self.spatial_dim = spatial_dim
+        self.assign_value = assign_value
+        self.times = times
+        assert (len(region_range) == spatial_dim == len(region_size))
+        if spatial_dim != 3 or not 1 <= times <= MAX_BOXES:
+            raise NotImplementedError(f"RandomMaskOut: supported: spatial_dim 3, times 1..{MAX_BOXES}")
+
+    def draw_one(self, shape):
+        centers = [tuple(int(ds * np.random.uniform(r[0], r[1])) for ds, r in zip(shape, self.region_range))
+                   for _ in range(self.times)]
+        sizes = [tuple(int(np.random.uniform(rs[0], rs[1]) * ds) for rs, ds in zip(self.region_size, shape))
+                 for _ in range(self.times)]
+        # np.random.uniform(min, max) per box in the reference: min + (max - min) * random_sample()
+        u = [float(np.random.random_sample()) for _ in range(self.times)]
+        return {"mask_centers": centers, "mask_sizes": sizes, "u": u}
+
+    def _tables(self, params, shape, device):
+        boxes, u = [], []
+        for p in params:
+            if p is None:
+                boxes.append([[0] * 6] * self.times)
+                u.append([0.0] * self.times)
+                continue
+            if len(p["u"]) != self.times or len(p["mask_centers"]) != self.times or len(p["mask_sizes"]) != self.times:
+                raise ValueError(f"RandomMaskOut: {self.times} boxes per sample expected")
+            boxes.append(mask_boxes(p["mask_centers"], p["mask_sizes"], shape))
+            u.append([float(v) for v in p["u"]])
+        return _dev(boxes, torch.int32, device), _dev(u, torch.float64, device)
+
+    def _launch(self, x, tables, flags, out=None, minmax=None):
+        minmax = sample_minmax(x, flags) if minmax is None else minmax
+        return _mask_out(x, minmax, tables[0], tables[1], flags, out)
+
+
+class RandomFlip(_Augmentation):
+    """np.flip along one spatial axis drawn from (-1, ..., -spatial_dim), the same axis for every '#' entry of a sample."""
+    intensity = False
+
+    def __init__(self, spatial_dim):
+        self.spatial_dim = spatial_dim
+        if spatial_dim not in (1, 2, 3):
+            raise NotImplementedError("RandomFlip: supported: spatial_dim 1..3")
+
+    def draw_one(self, shape):
+        return {"flip_axis": random.sample([-n for n in range(1, self.spatial_dim + 1)], 1)[0]}
+
+    def _table_one(self, p, shape):
+        return flip_table(p["flip_axis"])
+
+    def _tables(self, params, shape, device):
+        perm, flip = [], []
+        for p in params:
+            pf = ((0, 1, 2), (0, 0, 0)) if p is None else self._table_one(p, shape)
+            perm.append(list(pf[0]))
+            flip.append(list(pf[1]))
+        return _dev(perm, torch.int32, device), _dev(flip, torch.int32, device)
+
+    def _launch(self, x, tables, flags, out=None):
+        return _permute_flip(x, tables[0], tables[1], flags, out)
+
+
+class RandomRotate90(RandomFlip):
+    """np.rot90 by 0..3 quarter turns in one of the three spatial planes; an odd count needs equal extents in that plane
+    (ValueError otherwise: the sample's shape would change)."""
+
+    def __init__(self, spatial_dim):
+        self.spatial_dim = spatial_dim
+        if spatial_dim not in (2, 3):
+            raise NotImplementedError("RandomRotate90: supported: spatial_dim 2 or 3")
+
+    def draw_one(self, shape):
+        rotate_times = random.sample(range(4), 1)[0]
+        all_combs = list(itertools.combinations([-n for n in range(1, self.spatial_dim + 1)], 2))
+        rotate_axis = tuple(random.sample(list(all_combs), 1)[0])
+        return {"rotate_axis": rotate_axis, "rotate_times": rotate_times}
+
+    def _table_one(self, p, shape):
+        return rotate_table(p["rotate_axis"], p["rotate_times"], shape)
+
+
+class GaussianAddictive(_Augmentation):
+    """Additive Gaussian noise on the sample rescaled to [0, 1]: ((x - min) / (range + 1e-7) + N(0, s)) clamped to [0, 1] and
+    rescaled back, s = one np.random.uniform(sigma[0], sigma[1]) draw per sample.
+
+    Deviation from the reference: its `np.random.normal(size=data.shape)` is replaced by a generator inside the kernel
+    (Philox4x32-10 keyed by a per-sample seed and the element index, then Box-Muller).  That consumes ONE host draw
+    (np.random.randint for the seed) instead of one per voxel, so `numpy.random` draws made after a GaussianAddictive differ
+    from the reference's, and the noise values are not numpy's.  A parameter dict may carry "noise" (a float64 device tensor of
+    the sample's shape) to run the reference's arithmetic on given noise instead.  Only channel_dim 0 / None (the whole sample
+    as one array) is supported."""
+
+    def __init__(self, sigma, channel_dim=0):
+        self.sigma = sigma
+        self.channel_dim = channel_dim
+        self.epsilon = 1e-7
+        if channel_dim:
+            raise NotImplementedError("GaussianAddictive: per-channel noise (channel_dim != 0 / None) is not supported")
+
+    def draw_one(self, shape):
+        sigma = np.random.uniform(self.sigma[0], self.sigma[1])
+        seed = int(np.random.randint(0, 2 ** 63 - 1, dtype=np.int64))
+        return {"sigma": sigma, "seed": seed}
+
+    def _tables(self, params, shape, device):
+        sigma = _dev([0.0 if p is None else float(p["sigma"]) for p in params], torch.float32, device)
+        seeds = _dev([0 if p is None else int(p["seed"]) for p in params], torch.int64, device)
+        given = [p is not None and p.get("noise") is not None for p in params]
+        noise = None
+        if any(given):
+            if not all(g or p is None for g, p in zip(given, params)):
+                raise ValueError("GaussianAddictive: explicit noise for every active sample of the batch, or for none")
+            n_el = int(np.prod(shape))
+            noise = torch.zeros((len(params), n_el), dtype=torch.float64, device=device)
+            for i, p in enumerate(params):
+                if p is not None:
+                    noise[i] = p["noise"].to(device=device, dtype=torch.float64).reshape(-1)
+        return sigma, seeds, noise
+
+    def _launch(self, x, tables, flags, out=None, minmax=None):
+        minmax = sample_minmax(x, flags) if minmax is None else minmax
+        return _noise(x, minmax, tables[0], tables[1], flags, tables[2], out)
+
+
+# -------------------------------------------------------------------------------------------------------------- ensemble
+class EnsembleScanAugmentation:
+    """The reference's `_T` (job_runner.py:556-579) on a batch: per sample one of the 120 orders of the pool
+    (`random.sample`), each element kept iff `np.random.randint(0, 10) < 10 * aug_ratio`, then that chain applied.  All draws of
+    a sample (order, keep decisions, then each kept element's parameters in chain order) are made before the next sample's, as
+    the reference's chunk-by-chunk loop makes them.
+
+    Execution: for each chain position and each pool element, one launch over the samples that have that element at that position
+    (others are skipped, not copied).  Every sample lives in the input or in one of two work buffers; a launch reads the samples
+    of one buffer and writes them to another, the two point-wise transforms work in place once a sample has left the input.
+    What is not in the result buffer at the end is copied there.  The result equals applying each sample's chain to that sample
+    alone.  `aug_ratio` 0 (the shipped settings' value) returns the sample dict's tensors untouched and launches nothing."""
+
+    def __init__(self, aug_ratio, pool=None):
+        self.aug_ratio = aug_ratio
+        self.transform_pool = pool if pool is not None else [
+            GaussianBlur((0.3, 0.5), "random"),
+            RandomMaskOut(region_range=((0.2, 0.8), (0.2, 0.8), (0.2, 0.8)),
+                          region_size=((0.01, 0.05), (0.01, 0.05), (0.01, 0.05))),
+            RandomFlip(3),
+            RandomRotate90(3),
+            GaussianAddictive((0.01, 0.02), None),
+        ]
+
+    def aug_sampling(self, aug_list):
+        return [x for x in aug_list if np.random.randint(0, 10) < (10 * self.aug_ratio)]
+
+    def draw(self, n, shape):
+        """Per sample a list of (pool element, parameters), in application order."""
+        chains = []
+        for _ in range(n):
+            all_p = list(itertools.permutations(self.transform_pool, len(self.transform_pool)))
+            p = list(random.sample(all_p, 1)[0])
+            p = self.aug_sampling(p)
+            chains.append([(t, t.draw_one(tuple(shape))) for t in p])
+        return chains
+
+    @staticmethod
+    def chain_names(chains):
+        return [[type(t).__name__ for t, _ in chain] for chain in chains]
+
+    def apply(self, sample, chains):
+        if not any(chains):
+            return dict(sample)
+        out = {}
+        for key, value in sample.items():
+            out[key] = self._run(key, value, chains) if "#" in key else value
+        return out
+
+    def _run(self, key, value, chains):
+        steps = [[(t, p) for t, p in chain if t._touches(key)] for chain in chains]
+        if not any(steps):
+            return value
+        image = "image" in key
+        src, shape = (_as_image(value, key) if image and any(t.intensity for c in steps for t, _ in c)
+                      else _as_batch(value, key, (torch.float32, torch.uint8)))
+        N, device, spatial = src.shape[0], src.device, tuple(src.shape[2:])
+        if len(chains) != N:
+            raise ValueError(f"EnsembleScanAugmentation: {len(chains)} chains for a batch of {N}")
+        bufs = [src, torch.empty_like(src), None]     # 0: the input (never written), 1: the result, 2: second work buffer
+        where = [0] * N
+        minmax = torch.empty((N, 2), dtype=torch.float32, device=device)
+        for pos in range(max(len(c) for c in steps)):
+            for t in self.transform_pool:
+                members = [i for i in range(N) if pos < len(steps[i]) and steps[i][pos][0] is t]
+                if not members:
+                    continue
+                params = [steps[i][pos][1] if i in members else None for i in range(N)]
+                tables = t._tables(params, spatial, device)
+                inplace = isinstance(t, (RandomMaskOut, GaussianAddictive))
+                groups = {s: [i for i in members if where[i] == s] for s in sorted({where[i] for i in members})}
+                for s, group in groups.items():
+                    d = s if (inplace and s != 0) else (2 if s == 1 else 1)
+                    if bufs[d] is None:
+                        bufs[d] = torch.empty_like(src)
+                    flags = _dev([TRANSFORM if i in group else SKIP for i in range(N)], torch.int32, device)
+                    if inplace:
+                        sample_minmax(bufs[s], flags, out=minmax)
+                        t._launch(bufs[s], tables, flags, out=bufs[d], minmax=minmax)
+                    else:
+                        t._launch(bufs[s], tables, flags, out=bufs[d])
+                    for i in group:
+                        where[i] = d
+        ident = (_dev([[0, 1, 2]] * N, torch.int32, device), _dev([[0, 0, 0]] * N, torch.int32, device))
+        for s in (0, 2):      # gather what did not end in the result buffer
+            group = [i for i in range(N) if where[i] == s]
+            if group:
+                flags = _dev([TRANSFORM if where[i] == s else SKIP for i in range(N)], torch.int32, device)
+                _permute_flip(bufs[s], ident[0], ident[1], flags, out=bufs[1])
+        return bufs[1].view(shape)
+
+    def __call__(self, sample):
+        first = _first_tensor(sample)
+        chains = self.draw(first.shape[0], tuple(first.shape[-3:]))     # (the reference draws at aug_ratio 0 as well)
+        return self.apply(sample, chains) if any(chains) else sample

@@ -62,6 +62,16 @@ class Batch:
         b.ctss, b.targets, b.weight, b.keep = self.ctss[lo:hi], self.targets[lo:hi], self.weight[lo:hi], self.keep[lo:hi]
         return b
 
+    def augmented(self, aug):
+        """This batch after `aug` (an element of dram_amd/augment.py or its EnsembleScanAugmentation): the images go through it as
+        "#image", the two masks as "#..._reference", so flips and quarter turns move all three alike while the intensity
+        transforms touch the images only.  The regression targets are sums over the chunk, which those moves keep."""
+        out = aug({"#image": self.images, "#lobes_reference": self.lobes, "#lesions_reference": self.lesions, "meta": {}})
+        b = object.__new__(Batch)
+        b.images, b.lobes, b.lesions = out["#image"], out["#lobes_reference"], out["#lesions_reference"]
+        b.ctss, b.targets, b.weight, b.keep = self.ctss, self.targets, self.weight, self.keep
+        return b
+
     def __len__(self):
         return self.images.shape[0]
 

@@ -500,6 +500,39 @@ int dram_affine_sample_bwd(const float* dy, float* dx, const float* theta12, int
 int dram_calibrate_hbm_copy(const void* src, void* dst, size_t nbytes, void* stream);
 int dram_calibrate_mfma_f32(float* sink, int blocks, int iters, double* flops, void* stream);
 
+/* ---- training-time augmentation pool on a device batch: LesionSegChunkTrain.ensemble_scan_augmentation,
+ *      dram/job_runner.py:548-581, over GaussianBlur / RandomMaskOut / RandomFlip / RandomRotate90 / GaussianAddictive of
+ *      dram/data_transforms.py:365-406, 507-535, 756-800, 935-992 ----
+ * x, y: [N, D, H, W] (S = D*H*W; permute_flip: [N, C, D, H, W]).  One launch serves the whole batch; each sample's parameters
+ * come from DEVICE tables of n_table entries (n_table must equal N).  flag[N] (device ints): 1 = transform the sample,
+ * 0 = pass it through unchanged (copied when y != x), < 0 = skip it (y is not written for that sample).
+ *
+ * dram_aug_minmax: minmax[n] = {min, max} of row n, fp32, exact and independent of the launch geometry; flag may be NULL
+ *   (every row); rows whose flag is not 1 are left as they are.  Three launches, no workspace.
+ * dram_aug_gaussian_blur: scipy.ndimage.gaussian_filter(x[n], sigma_n): separable z, y, x, mode 'reflect', intermediates rounded
+ *   to fp32.  weights[n][DRAM_AUG_MAX_RADIUS + 1]: weights[n][j] multiplies the taps at distance j, zero beyond the sample's own
+ *   radius; radius = the largest radius of the batch, 0..DRAM_AUG_MAX_RADIUS.  Not in place.
+ * dram_aug_mask_out: RandomMaskOut._mask_out: `times` (1..DRAM_AUG_MAX_BOXES) boxes per sample, boxes[n][k] = {z0, z1, y0, y1,
+ *   x0, x1} half-open (empty boxes allowed), each filled with fp32(min + (max - min) * u[n][k]) evaluated in fp64, min / max read
+ *   from minmax[n] (dram_aug_minmax of x); later boxes overwrite earlier ones.  y may be x.
+ * dram_aug_gaussian_noise: GaussianAddictive._gaussian_addictive: ((x - min) / (range + 1e-7) + noise) clamped to [0, 1],
+ *   times range, plus min, every step rounded to fp32.  noise == NULL: N(0, sigma[n]) from Philox4x32-10 keyed by seeds[n] with the
+ *   element index as counter, then Box-Muller (a function of seed and element only).  noise != NULL: [N][S] fp64 values added in
+ *   fp64 as numpy does (sigma, seeds unused).  y may be x.
+ * dram_aug_permute_flip: out[o] = in[i], i[perm[n][k]] = flip[n][k] ? n_k-1-o[k] : o[k] per sample; the permutation must keep
+ *   the shape (D, H, W).  elem_size 4 (float32) or 1 (uint8).  Not in place. */
+#define DRAM_AUG_MAX_RADIUS 4
+#define DRAM_AUG_MAX_BOXES 16
+int dram_aug_minmax(const float* x, float* minmax, const int* flag, int N, int64_t S, void* stream);
+int dram_aug_gaussian_blur(const float* x, float* y, const float* weights, const int* flag, int n_table, int radius, int N, int D,
+                           int H, int W, void* stream);
+int dram_aug_mask_out(const float* x, float* y, const float* minmax, const int* boxes, const double* u, const int* flag,
+                      int n_table, int times, int N, int D, int H, int W, void* stream);
+int dram_aug_gaussian_noise(const float* x, float* y, const float* minmax, const float* sigma, const unsigned long long* seeds,
+                            const int* flag, int n_table, const double* noise, int N, int64_t S, void* stream);
+int dram_aug_permute_flip(const void* x, void* y, int elem_size, const int* perm, const int* flip, const int* flag, int n_table,
+                          int N, int C, int D, int H, int W, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
