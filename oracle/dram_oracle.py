@@ -368,9 +368,9 @@ def get_labels(ctsses, lesion_ps, band_width):
 def reg_loss_with_probs(probs, lobes, lesions, ctsses, freq_map, band_width):
     """IntRegLoss.compute_reg_loss_with_probs (metrics.py:158-177)."""
     B = probs.shape[0]
-    ratio_ub = (lesions * lobes).view(B, 1, -1).sum(-1) / lobes.view(B, 1, -1).sum(-1)
+    ratio_ub = (lesions * lobes).reshape(B, 1, -1).sum(-1) / lobes.reshape(B, 1, -1).sum(-1)
     m = (lobes > 0).to(probs.dtype)
-    pred_ratio = (probs * m).view(B, -1).sum(-1) / m.view(B, -1).sum(-1)   # == mean of probs[lobes>0] per sample
+    pred_ratio = (probs * m).reshape(B, -1).sum(-1) / m.reshape(B, -1).sum(-1)   # == mean of probs[lobes>0] per sample
     tgt = get_labels(ctsses, ratio_ub.view(-1), band_width).to(probs.device)
     K = (0.5 * (tgt[:, 1] - tgt[:, 0])) ** 2
     unh = (pred_ratio - (tgt[:, 1] + tgt[:, 0]) / 2.0) ** 2 - K
@@ -898,3 +898,54 @@ def fused_loss_math(dense, batch, refined=None, smoothing=0.1, eps=1e-7):
     boot = -(torch.log(ph) * inside).sum() / n_in
     seg_loss = bceo + (1.0 - smoothing) * bce + smoothing * boot
     return reg_loss, seg_loss
+
+
+# --------------------------------------------------------------------------
+# affine-consistency loss (reference dram/metrics.py:376-462, dram/data_transforms.py:1140-1239)
+# --------------------------------------------------------------------------
+def oneshot_chain(chain, key, x):
+    """The OneShot transforms of data_transforms.py:1140-1239 applied in order to one "#..." entry `key` of a sample
+    dict.  `chain` is a list of ("flip", axes) -> torch.flip, ("rot90", times, (a, b)) -> torch.rot90 and
+    ("rescale", size) -> F.interpolate(size=size) with mode 'trilinear' for "#image..." keys and 'nearest' for
+    "#reference..." keys (both with F.interpolate's defaults, i.e. align_corners=False); axes in 5-D numbering."""
+    for op in chain:
+        if op[0] == "flip":
+            x = torch.flip(x, tuple(op[1]))
+        elif op[0] == "rot90":
+            x = torch.rot90(x, int(op[1]), tuple(op[2]))
+        elif op[0] == "rescale":
+            if "image" in key:
+                mode = "trilinear"
+            elif "reference" in key:
+                mode = "nearest"
+            else:
+                raise NotImplementedError(key)
+            size = tuple(int(v) for v in op[1])
+            if mode == "nearest":   # label maps: ATen picks the source index with an fp32 scale for fp32 tensors, which is what
+                x = F.interpolate(x.float(), size=size, mode=mode).to(x.dtype)      # the reference runs; keep that for fp64 callers
+            else:
+                x = F.interpolate(x, size=size, mode=mode)
+        else:
+            raise ValueError(f"unknown OneShot op {op!r}")
+    return x
+
+
+def int_reg_aff_refine_loss(model, chain, images, lobes, lesions, ctsses, freq_map, band_width=5e-2, smoothing=0.05):
+    """IntRegAffRefineLoss.__call__ (metrics.py:417-462) for a GIVEN transform chain (see `oneshot_chain`) instead of
+    one drawn by get_affine_transform; statement for statement what dram_amd.train_step.DeviceIntRegAffRefineLoss
+    runs on the kernels.  `model(images, lobes)` returns (dense, refined, cls).  Returns (reg, aff, seg)."""
+    T = lambda key, x: oneshot_chain(chain, key, x)
+    aff_images = T("#image", images)
+    aff_lobes = T("#reference", lobes).contiguous()
+    aff_lesions = T("#reference", lesions).contiguous()
+    dense, refined, cls = model(images, lobes)
+    reg, seg = int_reg_refine_loss2(dense, refined, lobes, lesions, ctsses, freq_map, band_width, smoothing)
+    probs_T = T("#image", torch.sigmoid(dense))
+    cls_T = T("#image", cls)
+    a_dense, a_refined, a_cls = model(aff_images.detach(), aff_lobes)
+    a_reg, a_seg = int_reg_refine_loss2(a_dense, a_refined, aff_lobes, aff_lesions, ctsses, freq_map, band_width, smoothing)
+    m = aff_lobes.expand_as(probs_T) > 0
+    aff_loss = F.smooth_l1_loss(probs_T[m], torch.sigmoid(a_dense)[m])
+    mc = aff_lobes.expand_as(cls_T) > 0
+    aff_loss_cls = F.smooth_l1_loss(cls_T[mc], a_cls[mc])
+    return (reg + a_reg) / 2.0, (aff_loss + aff_loss_cls) / 2.0, (seg + a_seg) / 2.0

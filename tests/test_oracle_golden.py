@@ -475,3 +475,72 @@ def test_dc3dat_attention_oracle_matches_reference_golden(golden_dir):
             continue
         assert np.abs(got - ref).max() <= (0.5 / ATT_GRAD_Q + 1e-10) * mx, k
         assert abs(np.abs(got).max() - mx) <= 1e-10 * mx and abs(np.linalg.norm(got) - nrm) <= 1e-10 * nrm, k
+
+
+def parse_oneshot_descriptor(desc):
+    """tests/golden/affloss.npz `<case>/T` ("Class:attr=value,...|Class:...", oracle/make_golden.py:gen_affloss) ->
+    the chain format of O.oneshot_chain."""
+    import re
+    ints = lambda s: tuple(int(v) for v in re.findall(r"\((\d+)\)|(?<![\w(])(\d+)(?![\w(])", s) for v in v if v != "")
+    chain = []
+    for d in (d for d in str(desc).split("|") if d):
+        name, attrs = d.split(":", 1)
+        if name == "Flip3DOneShot":
+            chain.append(("flip", ints(re.search(r"flip_axis=\(([^)]*)\)", attrs).group(1))))
+        elif name == "Rotate903DOneShot":
+            axes = ints(re.search(r"rotate_axis=\(([^)]*)\)", attrs).group(1))
+            chain.append(("rot90", int(re.search(r"rotate_times=(\d+)", attrs).group(1)), axes))
+        elif name == "Rescale3DOneShot":
+            assert "mode=size" in attrs, attrs
+            size = tuple(int(v) for v in re.findall(r"int64\((\d+)\)", attrs)) or ints(re.search(r"scale_factor=\((.*)\)", attrs).group(1))
+            assert len(size) == 3, attrs
+            chain.append(("rescale", size))
+        else:
+            raise AssertionError(f"unknown transform {name!r} in {desc!r}")
+    return chain
+
+
+def affloss_standin(theta):
+    """The closed-form 3-output stand-in model of oracle/make_golden.py:gen_affloss (dense / refined / 2-channel cls as
+    smooth, position-dependent functions of the input and three scalar parameters)."""
+    def model(imgs, lbs):
+        a, b, c = theta[0], theta[1], theta[2]
+        D, H, W = imgs.shape[-3:]
+        rz = torch.linspace(0.0, 1.0, D, dtype=imgs.dtype, device=imgs.device).view(1, 1, D, 1, 1)
+        rx = torch.linspace(0.0, 1.0, W, dtype=imgs.dtype, device=imgs.device).view(1, 1, 1, 1, W)
+        dense = a * (imgs - 0.5) * 4.0 + b + 0.6 * c * rx - 0.4 * rz
+        refined = 0.7 * dense - c * imgs
+        cls = torch.cat([a * imgs + rz, imgs * imgs + b * c * rx], dim=1)
+        return dense, refined, cls
+    return model
+
+
+def test_parse_oneshot_descriptor():
+    assert parse_oneshot_descriptor("") == []
+    got = parse_oneshot_descriptor("Rotate903DOneShot:rotate_axis=(4, 3),rotate_times=3,spatial_dim=2|Flip3DOneShot:flip_axis=(2,),spatial_dim=2|"
+                                   "Rescale3DOneShot:mode=size,scale_factor=(np.int64(8), np.int64(14), np.int64(10))")
+    assert got == [("rot90", 3, (4, 3)), ("flip", (2,)), ("rescale", (8, 14, 10))]
+    assert parse_oneshot_descriptor("Rescale3DOneShot:mode=size,scale_factor=(8, 14, 10)") == [("rescale", (8, 14, 10))]
+
+
+@pytest.mark.parametrize("case", ["all3", "all3b", "fliprot", "rescale", "none"])
+def test_affine_consistency_oracle_matches_reference_golden(golden_dir, case):
+    """O.int_reg_aff_refine_loss (fp64) with the transform chain the reference drew (`<case>/T`) against the reference's
+    IntRegAffRefineLoss (tests/golden/affloss.npz): the three loss values and the gradient of the stand-in model's
+    parameters, at the tolerances tests/test_gpu_train_step.py holds the device loss to against the same file."""
+    z = _load(golden_dir, "affloss")
+    chain = parse_oneshot_descriptor(z[f"{case}/T"])
+    assert [op[0] for op in chain] == [{"Flip3DOneShot": "flip", "Rotate903DOneShot": "rot90", "Rescale3DOneShot": "rescale"}[d.split(":")[0]]
+                                       for d in str(z[f"{case}/T"]).split("|") if d]
+    theta = _t(z["theta"]).double().requires_grad_(True)
+    freq = {k: 1.0 / 6 for k in range(6)}
+    t = lambda k: _t(z[k]).double()
+    reg, aff, seg = O.int_reg_aff_refine_loss(affloss_standin(theta), chain, t("images"), t("lobes"), t("lesions"), list(z["ctss"]),
+                                              freq, band_width=5e-2, smoothing=0.05)
+    ref = z[f"{case}/out"]
+    for name, g_, r_ in zip(("reg", "aff", "seg"), (reg, aff, seg), ref):
+        assert abs(g_.item() - float(r_)) <= 2e-5 * max(1.0, abs(float(r_))), (case, name, g_.item(), float(r_))
+    (2.0 * reg + 0.5 * aff + 1.0 * seg).backward()
+    gref = z[f"{case}/gtheta"]
+    err = np.abs(theta.grad.numpy() - gref).max() / np.abs(gref).max()
+    assert err <= 1e-4, (case, err, theta.grad.tolist(), gref.tolist())
