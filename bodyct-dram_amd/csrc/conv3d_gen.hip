@@ -26,15 +26,12 @@
 //       M = Cout (32 per block), N = (channel, tap) columns (<= 16 tiles of 32 per block, 4 per wave), K = voxels in
 //       boxes of 32 x 4 x 2.  Each block sums a contiguous range of boxes into a partial slab; the slabs are added in
 //       a fixed order (deterministic, no float atomics).
-#include "common.h"
+#include "conv_device.h"
 #include <atomic>
 
 namespace dram {
 namespace gen {
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-
-constexpr unsigned OOB = 0x80000000u;   // > any plane / filter size in bytes (checked on the host)
 constexpr int KC = 4;                   // input channels per K step (two MFMA k-pairs)
 constexpr int NQ = 6;                   // input halo elements per thread and channel: (BY-1)*is+Ty x (BX-1)*is+Tx <= 1536
 constexpr int TYX_MAX = 49;             // y x x taps per step
@@ -42,19 +39,6 @@ constexpr int WG_BOX_X = 32, WG_BOX_Y = 4, WG_BOX_Z = 2;   // backward-weights v
 constexpr int WG_PA = 257;              // LDS row stride of the dY tile (odd: conflict-free A reads)
 constexpr int WG_NT = 4;                // 32-column tiles per wave (backward-weights)
 constexpr int WG_HALO_MAX = 12288;      // floats of input halo per backward-weights block
-
-__device__ __forceinline__ __amdgpu_buffer_rsrc_t make_rsrc(const void* base, unsigned bytes) {
-    return __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(base), 0, (int)bytes, 0x00020000);
-}
-__device__ __forceinline__ float buf_load(__amdgpu_buffer_rsrc_t r, unsigned voff) {
-    return __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(r, (int)voff, 0, 0));
-}
-__device__ __forceinline__ const float* uniform_ptr(const float* p) {
-    const unsigned long long v = (unsigned long long)p;
-    const unsigned lo = __builtin_amdgcn_readfirstlane((unsigned)v);
-    const unsigned hi = __builtin_amdgcn_readfirstlane((unsigned)(v >> 32));
-    return (const float*)(((unsigned long long)hi << 32) | lo);
-}
 
 // One launch of the forward-shaped kernel: output grid q in [0,Q) per axis, written at q*os + oo of the output tensor;
 // tap t of the grid point q reads the input at q*is + ib + t and the filter at kb + ks*t (per axis).
@@ -158,12 +142,12 @@ __global__ __launch_bounds__(256, 2) void conv3d_gen_fwd_kernel(GenArgs a) {
             const float* plane = xs + ((size_t)min(c, a.C - 1) * a.ID + gz) * a.IH * a.IW;
             const __amdgpu_buffer_rsrc_t srd = make_rsrc(uniform_ptr(plane), c < a.C ? plane_bytes : 0u);
 #pragma unroll
-            for (int q = 0; q < NQ; ++q) rin[kc][q] = buf_load(srd, xoff[q]);
+            for (int q = 0; q < NQ; ++q) rin[kc][q] = buf_load(srd, xoff[q], 0);
         }
         const bool wc_ok = c0 + wc < a.C;
         const unsigned wstep = 4u * (unsigned)(c0 * a.wsk + (a.kbz + a.ksz * tz) * KyKx);
 #pragma unroll
-        for (int q = 0; q < WQ; ++q) rw[q] = buf_load(wsrd, (wc_ok && woff[q] != OOB) ? woff[q] + wstep : OOB);
+        for (int q = 0; q < WQ; ++q) rw[q] = buf_load(wsrd, (wc_ok && woff[q] != OOB) ? woff[q] + wstep : OOB, 0);
     };
     auto store_step = [&](float* stage) {
         float* lin = stage;
@@ -312,7 +296,7 @@ __global__ __launch_bounds__(256, 2) void conv3d_gen_wgrad_kernel(WgradArgs a) {
                     const bool ok = co0 + co < a.Cout && oz < a.OD && oy < a.OH && ox < a.OW;
                     const __amdgpu_buffer_rsrc_t srd =
                         make_rsrc(uniform_ptr(dyn + (size_t)min(co0 + co, a.Cout - 1) * a.OD * a.OH * a.OW), oplane);
-                    r[u] = buf_load(srd, ok ? 4u * (unsigned)((oz * a.OH + oy) * a.OW + ox) : OOB);
+                    r[u] = buf_load(srd, ok ? 4u * (unsigned)((oz * a.OH + oy) * a.OW + ox) : OOB, 0);
                 }
 #pragma unroll
                 for (int u = 0; u < 8; ++u) {
@@ -334,7 +318,7 @@ __global__ __launch_bounds__(256, 2) void conv3d_gen_wgrad_kernel(WgradArgs a) {
                     const int hz = h / (HX * HY), hy = (h / HX) % HY, hx = h % HX;
                     const int gz = gz0 + hz, gy = gy0 + hy, gx = gx0 + hx;
                     const bool ok = e < nx && gz >= 0 && gz < a.D && gy >= 0 && gy < a.H && gx >= 0 && gx < a.W;
-                    r[u] = buf_load(srd, ok ? (unsigned)cl * xplane + 4u * (unsigned)((gz * a.H + gy) * a.W + gx) : OOB);
+                    r[u] = buf_load(srd, ok ? (unsigned)cl * xplane + 4u * (unsigned)((gz * a.H + gy) * a.W + gx) : OOB, 0);
                 }
 #pragma unroll
                 for (int u = 0; u < 8; ++u) {

@@ -11,14 +11,18 @@
 // (rows along x are contiguous -> coalesced), zero padding is materialised in
 // the LDS halo, and the taps become compile-time LDS offsets.
 //
-// Two families (the library picks per layer, conv_fwd_dispatch / wgrad_plan):
-//   * Winograd F(2,3) along z -- conv3d_k3_fwd_wz_kernel (forward / backward-data) and
-//     conv3d_k3_wgrad_wz_kernel (backward-weights, the transposed algorithm): a pair of
-//     output planes costs 4 instead of 6 products per (ci, ky, kx) column, i.e. 2/3 of
-//     the MFMAs, with exact fp32 arithmetic.  Default for Cin >= 8 / W % 4 == 0.
-//   * direct 27-tap kernels -- conv3d_k3_fwd_kernel, conv3d_k3_wgrad(_vec)_kernel,
-//     conv3d_k3_wgrad_c1_kernel: the first layer (Cin = 1), widths the Winograd wgrad
-//     does not cover, and the A/B baseline (DRAM_CONV_DIRECT=1).
+// Three families (the library picks per layer, fwd_choice / wgrad_plan):
+//   * Winograd F(2x2,3x3) over (z,y) -- conv3d_k3_fwd_wzy(16)_kernel (forward / backward-data, persistent) and
+//     conv3d_k3_wgrad_wzy_kernel (backward-weights, the transposed algorithm): 16 instead of 36 products per
+//     (ci, kx) and 2x2 outputs, i.e. 4/9 of the direct MFMAs, with exact fp32 arithmetic.  These do most of the
+//     convolution time of a training step: whole 64-channel output tiles, Cin >= 8, W % 4 == 0, volumes their boxes
+//     cover with little padding.
+//   * Winograd F(2,3) along z -- conv3d_k3_fwd_wz_kernel and conv3d_k3_wgrad_wz_kernel: a pair of output planes costs
+//     4 instead of 6 products per (ci, ky, kx) column, i.e. 2/3 of the MFMAs.  Cin >= 8 / W % 4 == 0 where the (z,y)
+//     kernels do not serve the shape or the source.
+//   * direct 27-tap kernels -- conv3d_k3_fwd_kernel, conv3d_k3_wgrad(_vec)_kernel, and the first-layer kernels
+//     conv3d_k3_fwd_c1(w)_kernel / conv3d_k3_wgrad_c1_kernel (Cin = 1): widths the Winograd wgrad does not cover,
+//     and the A/B baseline (DRAM_CONV_DIRECT=1).
 //
 //   forward / backward-data  D[co][voxel] += W[co][ci] * X[ci][voxel+tap]
 //       block = 256 voxels x 32*COT output channels, 4 waves of 32x32 accumulator
@@ -32,67 +36,18 @@
 //
 // The input of forward and the output of backward-data may be a *virtual*
 // channel concatenation of two tensors (crop_concat_5d fused away).
-#include "common.h"
+//
+// This file holds every 3x3x3 kernel but the (z,y) backward-weights one (conv3d_k3_wgrad_wzy.hip), the table rows that name
+// and launch one instantiation each (conv_args.h: KernelRow), the choice of a row per shape (fwd_choice, wgrad_plan), filter
+// packing, the launch counters and every C entry point.
+#include "conv_args.h"
+#include "conv_device.h"
 #include "lane_reduce.h"
 #include <type_traits>
 #include <stdlib.h>
 #include <atomic>
 
 namespace dram {
-
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef float f32x2 __attribute__((ext_vector_type(2)));
-
-// channels [0,C1) live in p1 (spatial D,H,W); channels [C1,C1+C2) in p2 (spatial
-// D2,H2,W2) seen through a crop window starting at (oz,oy,ox).
-struct CatView {
-    float* p1;
-    float* p2;
-    int C1, C2;
-    int D2, H2, W2;
-    int oz, oy, ox;
-};
-
-struct ConvArgs {
-    CatView src;
-    CatView dst;
-    const float* wt;    // [27][Cin][Cout]
-    const float* bias;  // [Cout] or null
-    int N, Cin, Cout, D, H, W;
-    int nbx, nby, nbz, co_tiles;
-    // "normalise + ReLU on load": source tensor k is the RAW output y of the producing conv and the operand of
-    // this conv is act_k(coefk[row][0] * y + coefk[row][1]) per (n, c) row, ReLU if reluk (coefk null: the tensor
-    // is used as it is).  The activated tensor of the norm -> ReLU between two convs is then never written.
-    const float* coef1;
-    const float* coef2;
-    int relu1, relu2;
-    // BatchNorm / GroupNorm statistics of the OUTPUT in the epilogue: per (row, box, wave) {mean, M2, count} of the
-    // wave's 64 outputs of that channel -> stats[(row * nparts + part) * 3]; null: not wanted.
-    float* stats;
-    int nparts;
-    // division by co_tiles / nbx / nby / nbz as a multiply + shift (the persistent (z,y) kernel decodes three item cursors per
-    // item: 17 runtime integer divisions, each a v_rcp_iflag sequence with a VALU -> SALU round trip, ~2,000 cycles per item).
-    // One 48-byte record {divisor, multiplier, shift} x 4, so that a decode reads it with three wide scalar loads.
-    alignas(16) unsigned dv_d[4];
-    alignas(16) unsigned dv_m[4];
-    alignas(16) unsigned dv_s[4];
-};
-
-// x / d for x < 2^31 by a host-prepared multiply + shift (Granlund-Montgomery, branch-free): l = ceil(log2 d),
-// m = floor(2^32 (2^l - d) / d) + 1, x / d = (mulhi(x, m) + x) >> l (d == 1: l = 0, m = 1: mulhi = 0).
-static inline void fast_div_prepare(unsigned d, unsigned& m, unsigned& sh) {
-    if (d == 0) d = 1;
-    unsigned l = 0;
-    while ((1ull << l) < d) ++l;
-    m = (unsigned)(((((unsigned long long)1 << l) - d) << 32) / d + 1);
-    sh = l;
-}
-__device__ __forceinline__ unsigned fast_div(unsigned x, unsigned m, unsigned sh) {
-    return (__umulhi(x, m) + x) >> sh;
-}
-
-constexpr int KC = 4;  // input channels per LDS stage
 
 template <int BX, int BY, int BZ, int COT>
 struct FwdGeom {
@@ -107,41 +62,6 @@ struct FwdGeom {
     static constexpr int STAGE = KC * PS + WROWS * COB;  // floats per LDS stage
     static constexpr size_t LDS_BYTES = 2 * (size_t)STAGE * sizeof(float);
 };
-
-// Buffer (SRD) loads: 32-bit per-lane byte offset against a wave-uniform descriptor.  Offsets at or
-// beyond num_records return 0, so zero padding (volume border, channel tails) needs neither a
-// branch nor a select -- and a branch around a load would make hipcc wait vmcnt(0) per element.
-constexpr unsigned OOB = 0x80000000u;   // > any plane size in bytes (check_conv_shape)
-
-__device__ __forceinline__ __amdgpu_buffer_rsrc_t make_rsrc(const void* base, unsigned bytes) {
-    return __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(base), 0, (int)bytes, 0x00020000);
-}
-__device__ __forceinline__ float buf_load(__amdgpu_buffer_rsrc_t r, unsigned voff, unsigned soff) {
-    return __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(r, (int)voff, (int)soff, 0));
-}
-__device__ __forceinline__ f32x4 buf_load4(__amdgpu_buffer_rsrc_t r, unsigned voff, unsigned soff) {
-    typedef unsigned u32x4_t __attribute__((ext_vector_type(4)));
-    const u32x4_t v = __builtin_amdgcn_raw_buffer_load_b128(r, (int)voff, (int)soff, 0);
-    return __builtin_bit_cast(f32x4, v);
-}
-__device__ __forceinline__ const float* uniform_ptr(const float* p) {
-    const unsigned long long v = (unsigned long long)p;
-    const unsigned lo = __builtin_amdgcn_readfirstlane((unsigned)v);
-    const unsigned hi = __builtin_amdgcn_readfirstlane((unsigned)(v >> 32));
-    return (const float*)(((unsigned long long)hi << 32) | lo);
-}
-
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-
-// Workgroups are dealt round-robin over the 8 XCDs (each with a private 4 MiB L2): hardware block b
-// runs on XCD b % 8.  Map it to a logical work item so that every XCD walks a contiguous range of
-// items: neighbouring boxes (shared halos) and the tiles that share a box then hit the same L2.
-// Bijective for any n; placement is a speed matter only.
-__device__ __forceinline__ int xcd_remap(int b, int n) {
-    const int q = n / 8, r = n % 8;
-    const int xcd = b % 8, idx = b / 8;
-    return (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + idx;
-}
 
 // Statistics of a conv output tile in the epilogue (BatchNorm / GroupNorm moments without a pass over the tensor).
 // A lane holds, for each of its NREG = 16*COT accumulator registers i (channel ch(i) below) two outputs Y(0,i),
@@ -1065,8 +985,6 @@ struct FwdWzyGeomT {
 };
 using FwdWzyGeom = FwdWzyGeomT<32>;
 
-typedef __attribute__((address_space(3))) void* lds_ptr_t;
-
 // v_mov_b32 with a DPP lane pattern (quad_perm 0x00-0xFF, row_ror:n 0x120 + n, row_mirror 0x140), every lane enabled
 template <int CTRL>
 __device__ __forceinline__ float dpp_mov(float v) {
@@ -1575,21 +1493,6 @@ __device__ __forceinline__ void fwd_wzy_body(const ConvArgs& a, int total_items)
 
 __global__ __launch_bounds__(512, 1) void conv3d_k3_fwd_wzy_kernel(ConvArgs a, int total_items) { fwd_wzy_body<32>(a, total_items); }
 __global__ __launch_bounds__(512, 1) void conv3d_k3_fwd_wzy16_kernel(ConvArgs a, int total_items) { fwd_wzy_body<16>(a, total_items); }
-
-// ---------------------------------------------------------------------------------------------
-struct WgradArgs {
-    CatView src;      // x (possibly a virtual concatenation)
-    const float* dy;  // [N][Cout][D][H][W]
-    float* slabs;     // [SPLIT][Cout][Cin][27]
-    int N, Cin, Cout, D, H, W;
-    int nbx, nby, nbz, nboxes, split, ci_tiles, co_tiles;
-    int ci_tile0;     // first 16-channel ci tile of this launch ((z,y) kernel: a launch may cover the tiles of ONE source only)
-    // normalise + ReLU on load of x (see ConvArgs::coef1): source k holds the RAW conv output, the operand is
-    // act(coefk[row][0] * x + coefk[row][1]); Winograd kernel only (the host materialises for the others)
-    const float* coef1;
-    const float* coef2;
-    int relu1, relu2;
-};
 
 template <int HVv>
 struct PadTo2Mod32 {
@@ -2327,14 +2230,6 @@ __global__ __launch_bounds__(64 * COS * CIT, 2) void conv3d_k3_wgrad_wz_kernel(W
 // on v_mfma_f32_32x32x2_f32 (A[co][k] = dY[co][v+k], B[k][tap] = X[v+k+off(tap)], both from LDS).
 // HBM-bound (reads dY once: 4*Cout B/voxel).  Block = 256 voxels (32x4x2 box) x 32 co, 4 waves x 64
 // voxels; per-wave partial slabs, reduced in a fixed order by slab_reduce_kernel.
-struct WgradC1Args {
-    const float* x;   // [N][1][D][H][W]
-    const float* dy;  // [N][Cout][D][H][W]
-    float* slabs;     // [4*gridDim.x][Cout][27]
-    int N, Cout, D, H, W;
-    int nbx, nby, nbz, nboxes;
-};
-
 __global__ __launch_bounds__(256, 2) void conv3d_k3_wgrad_c1_kernel(WgradC1Args a) {
     constexpr int BX = 32, BY = 4, BZ = 2, VOX = 256;
     constexpr int HX = BX + 2, HY = BY + 2, HZ = BZ + 2, HV = HX * HY * HZ;   // 816
@@ -2408,8 +2303,6 @@ __global__ __launch_bounds__(256, 2) void conv3d_k3_wgrad_c1_kernel(WgradC1Args 
         }
     }
 }
-
-#include "wgrad_wzy.inc"
 
 static inline int wgrad_c1_blocks(int nboxes) { return nboxes < 1024 ? nboxes : 1024; }
 
@@ -2508,102 +2401,111 @@ static int persistent_blocks() {       // one block per CU of the current device
     return cus[dev];
 }
 
-template <int BX>
-static int launch_fwd_wzy_f(ConvArgs& a, unsigned nblk, hipStream_t st) {
-    using G = FwdWzyGeomT<BX>;
-    const auto kern = BX == 32 ? conv3d_k3_fwd_wzy_kernel : conv3d_k3_fwd_wzy16_kernel;
-    static LdsAttrOnce lds_once;
-    if (const int rc = ensure_dynamic_lds((const void*)kern, G::LDS_BYTES, lds_once, "conv3d_k3_fwd(wzy)")) return rc;
-    a.co_tiles = a.Cout / 64;
-    const int64_t total = (int64_t)nblk * a.co_tiles;
-    if (total > 0x7fffffffLL) {
-        set_error("conv3d_k3_fwd: grid too large");
-        return DRAM_EINVAL;
-    }
-    a.dv_d[0] = (unsigned)a.co_tiles; a.dv_d[1] = (unsigned)a.nbx; a.dv_d[2] = (unsigned)a.nby; a.dv_d[3] = (unsigned)a.nbz;
-    for (int i = 0; i < 4; ++i) fast_div_prepare(a.dv_d[i], a.dv_m[i], a.dv_s[i]);
-    const int64_t cus = persistent_blocks();
-    const unsigned grid = (unsigned)(total < cus ? total : cus);
-    hipLaunchKernelGGL(kern, dim3(grid), dim3(512), G::LDS_BYTES, st, a, (int)total);
-    return check_launch("conv3d_k3_fwd(wzy)");
-}
-
-template <int BX>
-static int launch_fwd_wzy(ConvArgs& a, hipStream_t st) {
-    a.nbx = cdiv(a.W, BX);
-    a.nby = cdiv(a.H, 4);
-    a.nbz = cdiv(a.D, FwdWzyGeomT<BX>::BZ);
-    const int64_t nblk = (int64_t)a.N * a.nbx * a.nby * a.nbz;
-    if (nblk > 0x7fffffffLL) {
-        set_error("conv3d_k3_fwd: grid too large");
-        return DRAM_EINVAL;
-    }
-    return launch_fwd_wzy_f<BX>(a, (unsigned)nblk, st);
-}
-
 // ---------------------------------------------------------------------------------------------
-template <int BX, int BY, int COT, bool FUSED>
-static int launch_fwd_wz_cot(ConvArgs& a, unsigned nblk, hipStream_t st) {
-    using G = FwdWzGeom<BX, BY, COT>;
-    static LdsAttrOnce lds_once;
-    if (const int rc = ensure_dynamic_lds((const void*)conv3d_k3_fwd_wz_kernel<BX, BY, COT, FUSED>, G::LDS_BYTES, lds_once, "conv3d_k3_fwd(wz)")) return rc;
-    a.co_tiles = cdiv(a.Cout, 32 * COT);
-    const int64_t total = (int64_t)nblk * a.co_tiles;
-    if (total > 0x7fffffffLL) {
-        set_error("conv3d_k3_fwd: grid too large");
-        return DRAM_EINVAL;
-    }
-    hipLaunchKernelGGL((conv3d_k3_fwd_wz_kernel<BX, BY, COT, FUSED>), dim3((unsigned)total), dim3(256), G::LDS_BYTES, st, a);
-    return check_launch("conv3d_k3_fwd(wz)");
-}
-
-template <int BX, int BY>
-static int launch_fwd_wz(ConvArgs& a, hipStream_t st) {
-    a.nbx = cdiv(a.W, BX);
-    a.nby = cdiv(a.H, BY);
-    a.nbz = cdiv(a.D, 2);
-    const int64_t nblk = (int64_t)a.N * a.nbx * a.nby * a.nbz;
-    if (nblk > 0x7fffffffLL) {
-        set_error("conv3d_k3_fwd: grid too large");
-        return DRAM_EINVAL;
-    }
-    // the fused variant (operand transform on load / statistics epilogue) is a separate instantiation: the plain
-    // kernel keeps its registers and schedule
-    const bool fused = a.coef1 || a.coef2 || a.stats;
-    if (a.Cout <= 32) return fused ? launch_fwd_wz_cot<BX, BY, 1, true>(a, (unsigned)nblk, st) : launch_fwd_wz_cot<BX, BY, 1, false>(a, (unsigned)nblk, st);
-    return fused ? launch_fwd_wz_cot<BX, BY, 2, true>(a, (unsigned)nblk, st) : launch_fwd_wz_cot<BX, BY, 2, false>(a, (unsigned)nblk, st);
-}
-
-// ---------------------------------------------------------------------------------------------
+// Table rows.  The fused variants (operand transform on load / statistics epilogue) are separate instantiations: the
+// plain kernels keep their registers and schedule.
 template <int BX, int BY, int BZ, int COT, bool FUSED>
-static int launch_fwd_cot(ConvArgs& a, unsigned nblk, hipStream_t st) {
-    using G = FwdGeom<BX, BY, BZ, COT>;
-    static LdsAttrOnce lds_once;
-    if (const int rc = ensure_dynamic_lds((const void*)conv3d_k3_fwd_kernel<BX, BY, BZ, COT, FUSED>, G::LDS_BYTES, lds_once, "conv3d_k3_fwd")) return rc;
-    a.co_tiles = cdiv(a.Cout, 32 * COT);
-    const int64_t total = (int64_t)nblk * a.co_tiles;
-    if (total > 0x7fffffffLL) {
-        set_error("conv3d_k3_fwd: grid too large");
-        return DRAM_EINVAL;
-    }
-    hipLaunchKernelGGL((conv3d_k3_fwd_kernel<BX, BY, BZ, COT, FUSED>), dim3((unsigned)total), dim3(256), G::LDS_BYTES, st, a);
-    return check_launch("conv3d_k3_fwd");
+static FwdRow fwd_row() {
+    return {{DRAM_K3_FWD_DIRECT, "conv3d_k3_fwd_kernel", 4, {BX, BY, BZ, COT}, FUSED}, [](ConvArgs& a, hipStream_t st) {
+                unsigned items;
+                if (const int rc = conv_fwd_items(a, BX, BY, BZ, 32 * COT, items)) return rc;
+                return launch_kernel<conv3d_k3_fwd_kernel<BX, BY, BZ, COT, FUSED>, FwdGeom<BX, BY, BZ, COT>::LDS_BYTES, 256>(
+                    "conv3d_k3_fwd", dim3(items), st, a);
+            }};
 }
+template <int BX, int BY, int COT, bool FUSED>
+static FwdRow fwd_wz_row() {
+    return {{DRAM_K3_FWD_WZ, "conv3d_k3_fwd_wz_kernel", 3, {BX, BY, COT}, FUSED}, [](ConvArgs& a, hipStream_t st) {
+                unsigned items;
+                if (const int rc = conv_fwd_items(a, BX, BY, 2, 32 * COT, items)) return rc;
+                return launch_kernel<conv3d_k3_fwd_wz_kernel<BX, BY, COT, FUSED>, FwdWzGeom<BX, BY, COT>::LDS_BYTES, 256>(
+                    "conv3d_k3_fwd(wz)", dim3(items), st, a);
+            }};
+}
+template <typename G, auto KERN>
+static FwdRow fwd_c1_row(const char* base) {
+    return {{DRAM_K3_FWD_C1, base, 0, {G::BX, G::BY, G::BZ}, -1}, [](ConvArgs& a, hipStream_t st) {
+                unsigned items;
+                if (const int rc = conv_fwd_items(a, G::BX, G::BY, G::BZ, 32, items)) return rc;
+                return launch_kernel<KERN, 0, 256>("conv3d_k3_fwd(c1)", dim3(items), st, a);
+            }};
+}
+// every box with 32 / 64 output channels per block (Cout <= 32 / wider), plain and fused
+#define DRAM_FWD_BOX(row, ...) row<__VA_ARGS__, 1, false>(), row<__VA_ARGS__, 1, true>(), row<__VA_ARGS__, 2, false>(), row<__VA_ARGS__, 2, true>()
+static const FwdRow kFwdRowList[] = {DRAM_FWD_BOX(fwd_row, 32, 4, 2), DRAM_FWD_BOX(fwd_row, 16, 4, 4), DRAM_FWD_BOX(fwd_row, 8, 8, 4)};
+static const FwdRow kFwdWzRowList[] = {DRAM_FWD_BOX(fwd_wz_row, 32, 4), DRAM_FWD_BOX(fwd_wz_row, 16, 8), DRAM_FWD_BOX(fwd_wz_row, 8, 16),
+                                           DRAM_FWD_BOX(fwd_wz_row, 10, 10)};
+#undef DRAM_FWD_BOX
+static const FwdRow kFwdC1RowList[] = {fwd_c1_row<FwdC1Geom, conv3d_k3_fwd_c1_kernel>("conv3d_k3_fwd_c1_kernel"),
+                                           fwd_c1_row<FwdC1WGeom, conv3d_k3_fwd_c1w_kernel>("conv3d_k3_fwd_c1w_kernel")};
+static const KernelTable<ConvArgs> kFwdRows = kernel_table(kFwdRowList);
+static const KernelTable<ConvArgs> kFwdWzRows = kernel_table(kFwdWzRowList);
+static const KernelTable<ConvArgs> kFwdC1Rows = kernel_table(kFwdC1RowList);
 
-template <int BX, int BY, int BZ>
-static int launch_fwd(ConvArgs& a, hipStream_t st) {
-    a.nbx = cdiv(a.W, BX);
-    a.nby = cdiv(a.H, BY);
-    a.nbz = cdiv(a.D, BZ);
-    const int64_t nblk = (int64_t)a.N * a.nbx * a.nby * a.nbz;
-    if (nblk > 0x7fffffffLL) {
-        set_error("conv3d_k3_fwd: grid too large");
-        return DRAM_EINVAL;
-    }
-    const bool fused = a.coef1 || a.coef2 || a.stats;
-    if (a.Cout <= 32) return fused ? launch_fwd_cot<BX, BY, BZ, 1, true>(a, (unsigned)nblk, st) : launch_fwd_cot<BX, BY, BZ, 1, false>(a, (unsigned)nblk, st);
-    return fused ? launch_fwd_cot<BX, BY, BZ, 2, true>(a, (unsigned)nblk, st) : launch_fwd_cot<BX, BY, BZ, 2, false>(a, (unsigned)nblk, st);
+template <int BX, auto KERN>
+static FwdRow fwd_wzy_row(const char* base) {
+    using G = FwdWzyGeomT<BX>;
+    return {{DRAM_K3_FWD_WZY, base, 0, {BX, G::BY, G::BZ}, -1}, [](ConvArgs& a, hipStream_t st) {
+                unsigned items;
+                if (const int rc = conv_fwd_items(a, BX, G::BY, G::BZ, 64, items)) return rc;
+                a.dv_d[0] = (unsigned)a.co_tiles; a.dv_d[1] = (unsigned)a.nbx; a.dv_d[2] = (unsigned)a.nby; a.dv_d[3] = (unsigned)a.nbz;
+                for (int i = 0; i < 4; ++i) fast_div_prepare(a.dv_d[i], a.dv_m[i], a.dv_s[i]);
+                const unsigned cus = (unsigned)persistent_blocks();
+                return launch_kernel<KERN, G::LDS_BYTES, 512>("conv3d_k3_fwd(wzy)", dim3(items < cus ? items : cus), st, a, (int)items);
+            }};
 }
+static const FwdRow kFwdWzyRowList[] = {fwd_wzy_row<32, conv3d_k3_fwd_wzy_kernel>("conv3d_k3_fwd_wzy_kernel"),
+                                            fwd_wzy_row<16, conv3d_k3_fwd_wzy16_kernel>("conv3d_k3_fwd_wzy16_kernel")};
+static const KernelTable<ConvArgs> kFwdWzyRows = kernel_table(kFwdWzyRowList);
+
+// ---------------------------------------------------------------------------------------------
+// Table rows.  The lazy-operand variant of the Winograd kernel is a separate instantiation: the plain kernel keeps its
+// registers and schedule.
+template <int BX, int BY, int BZ, int COS, int CIT>
+static WgradRow wgrad_row() {
+    return {{DRAM_K3_WGRAD_DIRECT, "conv3d_k3_wgrad_kernel", 5, {BX, BY, BZ, COS, CIT}, -1}, [](WgradArgs& a, hipStream_t st) {
+                return launch_kernel<conv3d_k3_wgrad_kernel<BX, BY, BZ, COS, CIT>, WgradGeom<BX, BY, BZ, COS, CIT>::LDS_BYTES, 512>(
+                    "conv3d_k3_wgrad", wgrad_grid(a), st, a);
+            }};
+}
+template <int BX, int BY, int BZ, int COS, int CIT>
+static WgradRow wgrad_vec_row() {
+    return {{DRAM_K3_WGRAD_VEC, "conv3d_k3_wgrad_vec_kernel", 5, {BX, BY, BZ, COS, CIT}, -1}, [](WgradArgs& a, hipStream_t st) {
+                return launch_kernel<conv3d_k3_wgrad_vec_kernel<BX, BY, BZ, COS, CIT>, WgradVecGeom<BX, BY, BZ, COS, CIT>::LDS_BYTES, 512>(
+                    "conv3d_k3_wgrad(vec)", wgrad_grid(a), st, a);
+            }};
+}
+template <int BX, int BY, int COS, int CIT, bool LAZY>
+static WgradRow wgrad_wz_row() {
+    using G = WgradWzGeom<BX, BY, COS, CIT>;
+    return {{LAZY ? DRAM_K3_WGRAD_WZ_LAZY : DRAM_K3_WGRAD_WZ, "conv3d_k3_wgrad_wz_kernel", 4, {BX, BY, COS, CIT}, LAZY},
+            [](WgradArgs& a, hipStream_t st) {
+                return launch_kernel<conv3d_k3_wgrad_wz_kernel<BX, BY, COS, CIT, LAZY>, G::LDS_BYTES, G::T>("conv3d_k3_wgrad(wz)",
+                                                                                                          wgrad_grid(a), st, a);
+            }};
+}
+// every box with the 128 co x 16 ci and the 64 co x 32 ci block tile
+#define DRAM_WGRAD_BOX(row, ...) row<__VA_ARGS__, 8, 1>(), row<__VA_ARGS__, 4, 2>()
+#define DRAM_WGRAD_WZ_BOX(...) wgrad_wz_row<__VA_ARGS__, 8, 1, false>(), wgrad_wz_row<__VA_ARGS__, 8, 1, true>(), \
+                               wgrad_wz_row<__VA_ARGS__, 4, 2, false>(), wgrad_wz_row<__VA_ARGS__, 4, 2, true>()
+static const WgradRow kWgradRowList[] = {DRAM_WGRAD_BOX(wgrad_row, 32, 2, 1), DRAM_WGRAD_BOX(wgrad_row, 16, 2, 2),
+                                             DRAM_WGRAD_BOX(wgrad_row, 8, 4, 2)};
+static const WgradRow kWgradVecRowList[] = {DRAM_WGRAD_BOX(wgrad_vec_row, 32, 2, 1), DRAM_WGRAD_BOX(wgrad_vec_row, 16, 2, 2),
+                                                DRAM_WGRAD_BOX(wgrad_vec_row, 8, 4, 2)};
+static const WgradRow kWgradWzRowList[] = {DRAM_WGRAD_WZ_BOX(16, 2), DRAM_WGRAD_WZ_BOX(8, 4), DRAM_WGRAD_WZ_BOX(4, 8)};
+#undef DRAM_WGRAD_BOX
+#undef DRAM_WGRAD_WZ_BOX
+// first layer: one block per (box range, 32-channel co tile), the box range as a grid-stride loop over gridDim.x blocks
+static KernelRow<WgradC1Args> wgrad_c1_row() {
+    return {{DRAM_K3_WGRAD_C1, "conv3d_k3_wgrad_c1_kernel", 0, {32, 4, 2}, -1}, [](WgradC1Args& a, hipStream_t st) {
+                return launch_kernel<conv3d_k3_wgrad_c1_kernel, 0, 256>("conv3d_k3_wgrad(c1)", dim3(wgrad_c1_blocks(a.nboxes), cdiv(a.Cout, 32)), st, a);
+            }};
+}
+static const KernelRow<WgradC1Args> kWgradC1RowList[] = {wgrad_c1_row()};
+static const KernelTable<WgradArgs> kWgradRows = kernel_table(kWgradRowList);
+static const KernelTable<WgradArgs> kWgradVecRows = kernel_table(kWgradVecRowList);
+static const KernelTable<WgradArgs> kWgradWzRows = kernel_table(kWgradWzRowList);
+static const KernelTable<WgradC1Args> kWgradC1Rows = kernel_table(kWgradC1RowList);
 
 // Box shape (all 256 / 64 voxels): the one that pads the volume least; ties go to the first listed.  The reference trains and infers on 80^3 chunks (RESAMPLE_SIZE), whose
 // pyramid 80/40/20/10 is covered exactly by 16-, 8-wide boxes but only to 83 % / 62 % by 32-wide ones.
@@ -2618,7 +2520,8 @@ static int pick_box(int D, int H, int W, const int (*boxes)[3], int nboxes) {
     return best;
 }
 
-// box tables of the z-only Winograd kernel ((x, y) positions of a plane pair) and of the direct kernel
+// boxes the choice weighs, in its order of preference: the z-only Winograd kernel's ((x, y) positions of a plane pair) and the
+// direct kernel's.  The chosen box is looked up in the kernels' row tables by its values.
 static const int kFwdWzBoxes[4][2] = {{32, 4}, {16, 8}, {8, 16}, {10, 10}};
 static const int kFwdBoxes[3][3] = {{32, 4, 2}, {16, 4, 4}, {8, 8, 4}};
 
@@ -2669,12 +2572,7 @@ static bool wzy_source_ok(const ConvArgs& a) {
 }
 
 struct FwdChoice {
-    bool c1;            // first-layer kernel (Cin = 1, plain source and destination)
-    bool c1w;           // ... its wide form (a lane owns four consecutive x: W % 4 == 0, W >= 96)
-    bool wz;
-    bool wzy;
-    int wzy_bx;         // box width of the (z,y) kernel (32 / 16)
-    int box;            // index into the kernel family's box table
+    const FwdRow* row;  // the instantiation to launch (null: the library has none for this shape -- cannot occur)
     int nbx, nby, nbz;  // boxes per sample
     int parts_per_box;  // statistics partials a box writes per row
     int parts_cap;      // partial slots per row the caller provides for this SHAPE (>= what any launch of it writes)
@@ -2695,41 +2593,38 @@ static double wz_padding(int D, int H, int W) {
 }
 static FwdChoice fwd_choice(const ConvArgs& a) {
     FwdChoice c;
-    c.wz = use_wz(a);
     const int shape_bx = wzy_box(a);
-    c.wzy = shape_bx != 0 && wzy_source_ok(a);
-    c.wzy_bx = c.wzy ? shape_bx : 0;
+    // the fused variant (operand transform on load / statistics epilogue) and the block's output channels (32 / 64)
+    const int fused = (a.coef1 || a.coef2 || a.stats) ? 1 : 0, cot = a.Cout <= 32 ? 1 : 2;
+    // first-layer kernel (Cin = 1, plain source and destination); its wide form: a lane owns four consecutive x (W % 4 == 0, W >= 96)
+    const bool c1 = !conv_direct() && a.Cin == 1 && a.src.p2 == nullptr && a.dst.p2 == nullptr && a.coef1 == nullptr;
+    int bx, by, bz;
     c.parts_per_box = 4;
-    c.c1 = !conv_direct() && a.Cin == 1 && a.src.p2 == nullptr && a.dst.p2 == nullptr && a.coef1 == nullptr;
-    c.c1w = c.c1 && a.W % 4 == 0 && a.W >= 96;
-    if (c.c1w) {
-        c.box = 0;
-        c.parts_per_box = 16;           // (wave, row)
-        c.nbx = cdiv(a.W, FwdC1WGeom::BX); c.nby = cdiv(a.H, FwdC1WGeom::BY); c.nbz = cdiv(a.D, FwdC1WGeom::BZ);
-    } else if (c.c1) {
-        c.box = 0;
-        c.parts_per_box = 8;            // (wave, row group)
-        c.nbx = cdiv(a.W, FwdC1Geom::BX); c.nby = cdiv(a.H, FwdC1Geom::BY); c.nbz = cdiv(a.D, FwdC1Geom::BZ);
-    } else if (c.wzy) {
-        c.box = 0;
-        c.nbx = cdiv(a.W, c.wzy_bx); c.nby = cdiv(a.H, 4); c.nbz = cdiv(a.D, c.wzy_bx == 32 ? 2 : 4);
-    } else if (c.wz) {
+    if (c1) {
+        const bool wide = a.W % 4 == 0 && a.W >= 96;
+        c.parts_per_box = wide ? 16 : 8;        // (wave, row) / (wave, row group)
+        bx = wide ? FwdC1WGeom::BX : FwdC1Geom::BX; by = wide ? FwdC1WGeom::BY : FwdC1Geom::BY; bz = wide ? FwdC1WGeom::BZ : FwdC1Geom::BZ;
+        c.row = kFwdC1Rows.find({bx, by, bz});
+    } else if (shape_bx != 0 && wzy_source_ok(a)) {
+        bx = shape_bx; by = 4; bz = shape_bx == 32 ? 2 : 4;
+        c.row = kFwdWzyRows.find({bx, by, bz});
+    } else if (use_wz(a)) {
         // position boxes: the padded plane area, weighted by the lanes a box leaves idle (10x10 uses 100 of 128: the
         // 20^3 and 10^3 levels of the reference's 80^3 chunks fit it exactly)
-        const int (*boxes2)[2] = kFwdWzBoxes;
         int best = wz_best_box(a.H, a.W);
         if (shape_bx == 32) best = 0;           // the (z,y) kernel's shape, refused for its source only (wzy_source_ok)
         if (shape_bx == 16) best = 1;
-        c.box = best;
-        c.nbx = cdiv(a.W, boxes2[best][0]); c.nby = cdiv(a.H, boxes2[best][1]); c.nbz = cdiv(a.D, 2);
+        bx = kFwdWzBoxes[best][0]; by = kFwdWzBoxes[best][1]; bz = 2;
+        c.row = kFwdWzRows.find({bx, by, cot}, fused);
     } else {
-        const int (*boxes)[3] = kFwdBoxes;
-        c.box = pick_box(a.D, a.H, a.W, boxes, 3);
-        c.nbx = cdiv(a.W, boxes[c.box][0]); c.nby = cdiv(a.H, boxes[c.box][1]); c.nbz = cdiv(a.D, boxes[c.box][2]);
+        const int best = pick_box(a.D, a.H, a.W, kFwdBoxes, 3);
+        bx = kFwdBoxes[best][0]; by = kFwdBoxes[best][1]; bz = kFwdBoxes[best][2];
+        c.row = kFwdRows.find({bx, by, bz, cot}, fused);
     }
+    c.nbx = cdiv(a.W, bx); c.nby = cdiv(a.H, by); c.nbz = cdiv(a.D, bz);
     const int64_t produced = (int64_t)c.nbx * c.nby * c.nbz * c.parts_per_box;
     int64_t cap = produced;
-    if (shape_bx == 16 && !c.c1) {               // either kernel of a 16-wide (z,y) shape: (z,y) on 16x4x4, z-only on 16x8x2 boxes
+    if (shape_bx == 16 && !c1) {               // either kernel of a 16-wide (z,y) shape: (z,y) on 16x4x4, z-only on 16x8x2 boxes
         const int64_t zy = (int64_t)cdiv(a.W, 16) * cdiv(a.H, 4) * cdiv(a.D, 4) * 4, z = (int64_t)cdiv(a.W, 16) * cdiv(a.H, 8) * cdiv(a.D, 2) * 4;
         cap = zy > z ? zy : z;
     }
@@ -2741,35 +2636,10 @@ static FwdChoice fwd_choice(const ConvArgs& a) {
 // benchmarked shapes assert on these, so that "the (z,y) kernel was verified" means the (z,y) kernel was launched.
 static std::atomic<unsigned long long> g_launches[DRAM_K3_KINDS];
 
-// kind + instantiation name (as rocprofv3 prints it, without namespace and argument list) of the forward /
-// backward-data kernel that conv_fwd_dispatch launches for `a`
-static int fwd_kernel_id(const ConvArgs& a, const FwdChoice& c, char* name, size_t cap) {
-    const bool fused = a.coef1 || a.coef2 || a.stats;
-    const int cot = a.Cout <= 32 ? 1 : 2;
-    int kind;
-    char buf[96];
-    if (c.c1) {
-        kind = DRAM_K3_FWD_C1;
-        snprintf(buf, sizeof(buf), c.c1w ? "conv3d_k3_fwd_c1w_kernel" : "conv3d_k3_fwd_c1_kernel");
-    } else if (c.wzy) {
-        kind = DRAM_K3_FWD_WZY;
-        snprintf(buf, sizeof(buf), c.wzy_bx == 32 ? "conv3d_k3_fwd_wzy_kernel" : "conv3d_k3_fwd_wzy16_kernel");
-    } else if (c.wz) {
-        kind = DRAM_K3_FWD_WZ;
-        snprintf(buf, sizeof(buf), "conv3d_k3_fwd_wz_kernel<%d, %d, %d, %s>", kFwdWzBoxes[c.box][0], kFwdWzBoxes[c.box][1], cot,
-                 fused ? "true" : "false");
-    } else {
-        kind = DRAM_K3_FWD_DIRECT;
-        snprintf(buf, sizeof(buf), "conv3d_k3_fwd_kernel<%d, %d, %d, %d, %s>", kFwdBoxes[c.box][0], kFwdBoxes[c.box][1],
-                 kFwdBoxes[c.box][2], cot, fused ? "true" : "false");
-    }
-    if (name && cap) snprintf(name, cap, "%s", buf);
-    return kind;
-}
-
 static int conv_fwd_dispatch(ConvArgs& a, hipStream_t st) {
     const FwdChoice c = fwd_choice(a);
-    g_launches[fwd_kernel_id(a, c, nullptr, 0)].fetch_add(1, std::memory_order_relaxed);
+    DRAM_REQUIRE(c.row != nullptr, "conv3d_k3_fwd: no kernel instantiation for [%d -> %d, %d x %d x %d]", a.Cin, a.Cout, a.D, a.H, a.W);
+    g_launches[c.row->id.kind].fetch_add(1, std::memory_order_relaxed);
     if (a.stats) {
         // the caller's slots per row (dram_conv3d_k3_stats_parts) must hold what this launch writes; slots it leaves unused
         // (a 16-wide (z,y) shape whose two kernels box the volume differently) are zero-filled: count 0, ignored by the combine
@@ -2779,40 +2649,16 @@ static int conv_fwd_dispatch(ConvArgs& a, hipStream_t st) {
         if (a.nparts > produced)
             (void)hipMemsetAsync(a.stats, 0, (size_t)a.N * a.Cout * a.nparts * 3 * sizeof(float), st);
     }
-    if (c.c1) {
-        a.nbx = c.nbx; a.nby = c.nby; a.nbz = c.nbz;
-        a.co_tiles = cdiv(a.Cout, 32);
-        const int64_t total = (int64_t)a.N * c.nbx * c.nby * c.nbz * a.co_tiles;
-        if (total > 0x7fffffffLL) {
-            set_error("conv3d_k3_fwd: grid too large");
-            return DRAM_EINVAL;
-        }
-        if (c.c1w) hipLaunchKernelGGL(conv3d_k3_fwd_c1w_kernel, dim3((unsigned)total), dim3(256), 0, st, a);
-        else hipLaunchKernelGGL(conv3d_k3_fwd_c1_kernel, dim3((unsigned)total), dim3(256), 0, st, a);
-        return check_launch("conv3d_k3_fwd(c1)");
-    }
-    if (c.wzy) {
-        a.wt += (size_t)63 * a.Cin * a.Cout;      // ... and the (z,y)-transformed ones follow those
-        return c.wzy_bx == 32 ? launch_fwd_wzy<32>(a, st) : launch_fwd_wzy<16>(a, st);
-    }
-    if (c.wz) {
-        a.wt += (size_t)27 * a.Cin * a.Cout;      // the transformed filters follow the direct ones in the packed buffer
-        switch (c.box) {
-            case 0: return launch_fwd_wz<32, 4>(a, st);
-            case 1: return launch_fwd_wz<16, 8>(a, st);
-            case 2: return launch_fwd_wz<8, 16>(a, st);
-            default: return launch_fwd_wz<10, 10>(a, st);
-        }
-    }
-    switch (c.box) {
-        case 0: return launch_fwd<32, 4, 2>(a, st);
-        case 1: return launch_fwd<16, 4, 4>(a, st);
-        default: return launch_fwd<8, 8, 4>(a, st);
-    }
+    // the packed buffer: direct filters, then the z-transformed ones, then the (z,y)-transformed ones
+    if (c.row->id.kind == DRAM_K3_FWD_WZ) a.wt += (size_t)27 * a.Cin * a.Cout;
+    if (c.row->id.kind == DRAM_K3_FWD_WZY) a.wt += (size_t)63 * a.Cin * a.Cout;
+    return c.row->launch(a, st);
 }
 
-// Split of the (z,y) backward-weights kernel's box range over blocks: one 512-thread block per CU; contiguous box ranges, so the
-// split only has to fill the device evenly (`tiles` = (ci tile, co tile) pairs of the launch, `slab` = bytes of one partial dW)
+// Split of a backward-weights kernel's box range over blocks: one 512-thread block resident per CU (256 at a time); `tiles` =
+// (ci tile, co tile) pairs of the launch, `slab` = bytes of one partial dW.  A last round that is nearly empty costs a whole
+// block duration (measured: 1032 blocks on 512 slots ran 1.5x longer than 1020), so pick the split with the best slot
+// utilisation, preferring >= 2 rounds.
 static int wzy_split(int tiles, int nboxes, size_t slab, size_t ws_cap = (size_t)1 << 30) {
     const int resident = 256;
     int best = 1;
@@ -2823,7 +2669,7 @@ static int wzy_split(int tiles, int nboxes, size_t slab, size_t ws_cap = (size_t
         if ((size_t)sp * slab > ws_cap && sp > 1) break;
         const int64_t rounds = (blocks + resident - 1) / resident;
         double util = (double)blocks / (double)(rounds * resident);
-        const int64_t per = (nboxes + sp - 1) / sp;
+        const int64_t per = (nboxes + sp - 1) / sp;     // uneven box counts per block also idle slots
         util *= (double)nboxes / (double)(per * sp);
         const double score = util + 1e-3 * (blocks >= 2LL * resident ? 1.0 : (double)blocks / (2.0 * resident));
         if (score > best_score) { best_score = score; best = sp; }
@@ -2834,174 +2680,67 @@ static int wzy_split(int tiles, int nboxes, size_t slab, size_t ws_cap = (size_t
 constexpr size_t kWgradSubWsCap = (size_t)256 << 20;      // partial slabs of a per-source launch of a virtual concat
 
 struct WgradPlan {
-    int variant;  // 0: block = 64 co x 32 ci (Cout <= 64);  1: block = 128 co x 16 ci
-    int wz;       // 1: Winograd-z kernel (boxes = bx x by positions of a plane pair)
-    int wzy;      // 1: Winograd-(z,y) kernel (boxes = 16 x positions of a y pair and z pair); cit = 16-channel ci tiles per block
-    int cit;
-    int bx, by, bz, nbx, nby, nbz, nboxes, ci_tiles, co_tiles, split;
+    const WgradRow* row;    // the instantiation to launch (null: the library has none for this shape -- cannot occur)
+    int nbx, nby, nbz, nboxes, ci_tiles, co_tiles, split;
+    bool wzy() const { return row && row->id.kind == DRAM_K3_WGRAD_WZY; }
+    // a Winograd kernel: the ones that take their x operand lazily
+    bool winograd() const { return row && (wzy() || row->id.kind == DRAM_K3_WGRAD_WZ || row->id.kind == DRAM_K3_WGRAD_WZ_LAZY); }
 };
 
-static WgradPlan wgrad_plan(int N, int Cin, int Cout, int D, int H, int W, int C1 = 0) {
-    WgradPlan p;
-    p.variant = Cout > 64 ? 1 : 0;
-    p.wz = 0;
-    p.wzy = 0;
-    p.cit = 1;
+// C1: the first source's channels of a virtual concat (0: one tensor); lazy: x normalised + rectified on load where the kernel can
+static WgradPlan wgrad_plan(int N, int Cin, int Cout, int D, int H, int W, int C1 = 0, bool lazy = false) {
+    WgradPlan p = {};
+    const size_t slab = (size_t)Cout * Cin * 27 * sizeof(float);
     {   // Winograd-(z,y): full 16-wide boxes along x, whole y and z pairs, a ci tile inside one source tensor
         const bool off = getenv("DRAM_WGRAD_NO_WZY") != nullptr;      // (read per call: A/B tests toggle it inside one process)
-        const int cit = 1;
         // 16-wide boxes along x, the last one of a row ragged where W % 16 != 0 (16-byte pieces: W % 4 == 0) as long as it pads at
         // most 1.6x (measured at the reference's 40^3 level, 1.2x padding: 233 TFLOP/s direct-equivalent against 186 for the
         // z-only kernel on exact boxes; the 20^3 level pads 1.6x: ~175 against the z-only kernel's 151 there)
         const bool wide_ok = W % 4 == 0 && cdiv(W, 16) * 16 * 10 <= W * 16;
-        if (!conv_direct() && !off && wide_ok && H % 2 == 0 && D % 2 == 0 && D >= 4 && (C1 == 0 || C1 % (16 * cit) == 0)) {   // (D >= 4: two boxes per z column, the raw plane ring counts on it)
-            p.wzy = 1;
-            p.cit = cit;
-            p.bx = 16; p.by = 2; p.bz = 2;
-            p.nbx = cdiv(W, 16); p.nby = H / 2; p.nbz = D / 2;
+        if (!conv_direct() && !off && wide_ok && H % 2 == 0 && D % 2 == 0 && D >= 4 && C1 % 16 == 0) {   // (D >= 4: two boxes per z column, the raw plane ring counts on it)
+            p.row = kWgradWzyRows.find({}, lazy);
+            p.nbx = cdiv(W, 16); p.nby = H / 2; p.nbz = D / 2;      // boxes = 16 x positions of a y pair and z pair
             p.nboxes = (int)((int64_t)N * p.nbx * p.nby * p.nbz);
-            p.ci_tiles = cdiv(Cin, 16 * cit);
+            p.ci_tiles = cdiv(Cin, 16);
             p.co_tiles = cdiv(Cout, 64);
-            p.split = wzy_split(p.ci_tiles * p.co_tiles, p.nboxes, (size_t)Cout * Cin * 27 * sizeof(float));
+            p.split = wzy_split(p.ci_tiles * p.co_tiles, p.nboxes, slab);
             return p;
         }
     }
+    // block tile: 64 co x 32 ci (Cout <= 64) or 128 co x 16 ci, as (COS, CIT) 16-channel sub-tiles
+    int cos = Cout > 64 ? 8 : 4;
+    int bx = 0, by = 0, bz = 0;
     {   // Winograd-z: rows must be full boxes along x and a channel tile must lie inside one source tensor.  Its 64 co x
         // 32 ci tile (two LDS stages, one barrier per box) serves wide layers too: measured 197-200 TFLOP/s direct-equivalent
         // against 186-190 for the 128 co x 16 ci tile at 384->128, 256->256, 768->256; the latter remains for a concat
         // boundary that is a multiple of 16 only.
-        const int bx = (W % 16 == 0) ? 16 : ((W % 8 == 0) ? 8 : ((W % 4 == 0) ? 4 : 0));
-        int variant = -1;
-        if (C1 == 0 || C1 % 32 == 0) variant = 0;
-        else if (Cout > 64 && C1 % 16 == 0) variant = 1;
-        if (!conv_direct() && bx && D >= 2 && variant >= 0) {
-            p.wz = 1;
-            p.variant = variant;
-            p.bx = bx; p.by = 32 / bx; p.bz = 2;
+        const int wbx = (W % 16 == 0) ? 16 : ((W % 8 == 0) ? 8 : ((W % 4 == 0) ? 4 : 0));
+        int wcos = 0;
+        if (C1 % 32 == 0) wcos = 4;
+        else if (Cout > 64 && C1 % 16 == 0) wcos = 8;
+        if (!conv_direct() && wbx && D >= 2 && wcos) {
+            cos = wcos;
+            bx = wbx; by = 32 / wbx; bz = 2;         // boxes = bx x by positions of a plane pair
+            p.row = kWgradWzRows.find({bx, by, cos, 8 / cos}, lazy);
         }
     }
-    if (!p.wz) {
-    // ties go to the 16-wide box: its X halo (18x4x4 = 288 elements per 64 voxels, against 408 for 34x4x3)
-    // needs the fewest staging loads (measured +2.6 % at 128^3 / 64^3 / 32^3)
-    static const int boxes[3][3] = {{16, 2, 2}, {32, 2, 1}, {8, 4, 2}};
-    const int bi = pick_box(D, H, W, boxes, 3);
-    p.bx = boxes[bi][0]; p.by = boxes[bi][1]; p.bz = boxes[bi][2];
+    const int cit = 8 / cos;
+    if (bx == 0) {
+        // ties go to the 16-wide box: its X halo (18x4x4 = 288 elements per 64 voxels, against 408 for 34x4x3)
+        // needs the fewest staging loads (measured +2.6 % at 128^3 / 64^3 / 32^3)
+        static const int boxes[3][3] = {{16, 2, 2}, {32, 2, 1}, {8, 4, 2}};
+        const int bi = pick_box(D, H, W, boxes, 3);
+        bx = boxes[bi][0]; by = boxes[bi][1]; bz = boxes[bi][2];
+        // 16-byte staging needs full boxes along x and a channel tile that lies inside one source tensor
+        const bool vec = W % bx == 0 && C1 % (16 * cit) == 0;
+        p.row = (vec ? kWgradVecRows : kWgradRows).find({bx, by, bz, cos, cit});
     }
-    p.nbx = cdiv(W, p.bx); p.nby = cdiv(H, p.by); p.nbz = cdiv(D, p.bz);
-    const int64_t nb = (int64_t)N * p.nbx * p.nby * p.nbz;
-    p.nboxes = (int)nb;
-    p.ci_tiles = cdiv(Cin, p.variant == 0 ? 32 : 16);
-    p.co_tiles = cdiv(Cout, p.variant == 1 ? 128 : 64);
-    // Blocks = tiles x split, one 512-thread block resident per CU (256 at a time).  A last round
-    // that is nearly empty costs a whole block duration (measured: 1032 blocks on 512 slots ran 1.5x
-    // longer than 1020), so pick the split with the best slot utilisation, preferring >= 2 rounds.
-    const int tiles = p.ci_tiles * p.co_tiles;
-    const int resident = 256;
-    const size_t slab = (size_t)Cout * Cin * 27 * sizeof(float);
-    int best = 1;
-    double best_score = -1.0;
-    for (int sp = 1; sp <= p.nboxes && sp <= 4096; ++sp) {
-        const int64_t blocks = (int64_t)tiles * sp;
-        if (blocks > 4LL * resident && sp > 1) break;
-        if ((size_t)sp * slab > ((size_t)1 << 30) && sp > 1) break;
-        const int64_t rounds = (blocks + resident - 1) / resident;
-        double util = (double)blocks / (double)(rounds * resident);
-        const int64_t per = (p.nboxes + sp - 1) / sp;   // uneven box counts per block also idle slots
-        util *= (double)p.nboxes / (double)(per * sp);
-        const double score = util + 1e-3 * (blocks >= 2LL * resident ? 1.0 : (double)blocks / (2.0 * resident));
-        if (score > best_score) { best_score = score; best = sp; }
-    }
-    p.split = best;
+    p.nbx = cdiv(W, bx); p.nby = cdiv(H, by); p.nbz = cdiv(D, bz);
+    p.nboxes = (int)((int64_t)N * p.nbx * p.nby * p.nbz);
+    p.ci_tiles = cdiv(Cin, 16 * cit);
+    p.co_tiles = cdiv(Cout, 16 * cos);
+    p.split = wzy_split(p.ci_tiles * p.co_tiles, p.nboxes, slab);
     return p;
-}
-
-template <int BX, int BY, int BZ, int COS, int CIT>
-static int launch_wgrad_vec(WgradArgs& a, hipStream_t st) {
-    using G = WgradVecGeom<BX, BY, BZ, COS, CIT>;
-    static LdsAttrOnce lds_once;
-    if (const int rc = ensure_dynamic_lds((const void*)conv3d_k3_wgrad_vec_kernel<BX, BY, BZ, COS, CIT>, G::LDS_BYTES, lds_once, "conv3d_k3_wgrad")) return rc;
-    const unsigned grid = (unsigned)(a.split * a.ci_tiles * a.co_tiles);
-    hipLaunchKernelGGL((conv3d_k3_wgrad_vec_kernel<BX, BY, BZ, COS, CIT>), dim3(grid), dim3(512), G::LDS_BYTES, st, a);
-    return check_launch("conv3d_k3_wgrad(vec)");
-}
-
-template <int BX, int BY, int COS, int CIT, bool LAZY>
-static int launch_wgrad_wz_l(WgradArgs& a, hipStream_t st) {
-    using G = WgradWzGeom<BX, BY, COS, CIT>;
-    static LdsAttrOnce lds_once;
-    if (const int rc = ensure_dynamic_lds((const void*)conv3d_k3_wgrad_wz_kernel<BX, BY, COS, CIT, LAZY>, G::LDS_BYTES, lds_once, "conv3d_k3_wgrad")) return rc;
-    const unsigned grid = (unsigned)(a.split * a.ci_tiles * a.co_tiles);
-    hipLaunchKernelGGL((conv3d_k3_wgrad_wz_kernel<BX, BY, COS, CIT, LAZY>), dim3(grid), dim3(G::T), G::LDS_BYTES, st, a);
-    return check_launch("conv3d_k3_wgrad(wz)");
-}
-template <int BX, int BY, int COS, int CIT>
-static int launch_wgrad_wz(WgradArgs& a, hipStream_t st) {
-    // the lazy-operand variant is a separate instantiation: the plain kernel keeps its registers and schedule
-    return (a.coef1 || a.coef2) ? launch_wgrad_wz_l<BX, BY, COS, CIT, true>(a, st) : launch_wgrad_wz_l<BX, BY, COS, CIT, false>(a, st);
-}
-
-template <bool LAZY>
-static int launch_wgrad_wzy_l(WgradArgs& a, hipStream_t st) {
-    using G = WgradWzyGeom;
-    static LdsAttrOnce lds_once;
-    if (const int rc = ensure_dynamic_lds((const void*)conv3d_k3_wgrad_wzy_kernel<LAZY>, G::LDS_BYTES, lds_once, "conv3d_k3_wgrad(wzy)")) return rc;
-    const unsigned grid = (unsigned)(a.split * a.ci_tiles * a.co_tiles);
-    const int per = cdiv(a.nboxes, a.split);
-    hipLaunchKernelGGL((conv3d_k3_wgrad_wzy_kernel<LAZY>), dim3(grid), dim3(512), G::LDS_BYTES, st, a, per);
-    return check_launch("conv3d_k3_wgrad(wzy)");
-}
-static int launch_wgrad_wzy(WgradArgs& a, hipStream_t st) {
-    return (a.coef1 || a.coef2) ? launch_wgrad_wzy_l<true>(a, st) : launch_wgrad_wzy_l<false>(a, st);
-}
-
-template <int BX, int BY, int BZ, int COS, int CIT>
-static int launch_wgrad(WgradArgs& a, hipStream_t st) {
-    using G = WgradGeom<BX, BY, BZ, COS, CIT>;
-    static LdsAttrOnce lds_once;
-    if (const int rc = ensure_dynamic_lds((const void*)conv3d_k3_wgrad_kernel<BX, BY, BZ, COS, CIT>, G::LDS_BYTES, lds_once, "conv3d_k3_wgrad")) return rc;
-    const unsigned grid = (unsigned)(a.split * a.ci_tiles * a.co_tiles);
-    hipLaunchKernelGGL((conv3d_k3_wgrad_kernel<BX, BY, BZ, COS, CIT>), dim3(grid), dim3(512), G::LDS_BYTES, st, a);
-    return check_launch("conv3d_k3_wgrad");
-}
-
-// The backward-weights kernel wgrad_run launches for a plan: kind + the instantiation's template arguments.
-struct WgradKernel {
-    int kind;               // DRAM_K3_WGRAD_*
-    int bx, by, bz, cos, cit;
-    bool lazy;
-};
-static WgradKernel wgrad_kernel(const WgradPlan& p, int C1, bool has_x2, int W, bool lazy) {
-    WgradKernel k;
-    k.bx = p.bx; k.by = p.by; k.bz = p.bz;
-    k.cos = p.variant == 1 ? 8 : 4;
-    k.cit = p.variant == 1 ? 1 : 2;
-    k.lazy = false;
-    if (p.wzy) {
-        k.kind = DRAM_K3_WGRAD_WZY;
-        k.cit = p.cit;
-        k.lazy = lazy;
-        return k;
-    }
-    if (p.wz) {
-        k.kind = lazy ? DRAM_K3_WGRAD_WZ_LAZY : DRAM_K3_WGRAD_WZ;
-        k.lazy = lazy;
-        return k;
-    }
-    // 16-byte staging needs full boxes along x and a channel tile that lies inside one source tensor
-    const int ci_b = 16 * k.cit;
-    const bool vec = (W % p.bx == 0) && (!has_x2 || C1 % ci_b == 0);
-    k.kind = vec ? DRAM_K3_WGRAD_VEC : DRAM_K3_WGRAD_DIRECT;
-    return k;
-}
-static void wgrad_kernel_name(const WgradKernel& k, char* name, size_t cap) {
-    if (!name || !cap) return;
-    if (k.kind == DRAM_K3_WGRAD_C1) snprintf(name, cap, "conv3d_k3_wgrad_c1_kernel");
-    else if (k.kind == DRAM_K3_WGRAD_WZY) snprintf(name, cap, "conv3d_k3_wgrad_wzy_kernel<%s>", k.lazy ? "true" : "false");
-    else if (k.kind == DRAM_K3_WGRAD_WZ || k.kind == DRAM_K3_WGRAD_WZ_LAZY)
-        snprintf(name, cap, "conv3d_k3_wgrad_wz_kernel<%d, %d, %d, %d, %s>", k.bx, k.by, k.cos, k.cit, k.lazy ? "true" : "false");
-    else
-        snprintf(name, cap, "conv3d_k3_%s_kernel<%d, %d, %d, %d, %d>", k.kind == DRAM_K3_WGRAD_VEC ? "wgrad_vec" : "wgrad", k.bx, k.by,
-                 k.bz, k.cos, k.cit);
 }
 
 static int check_conv_shape(const char* who, int N, int Cin, int Cout, int D, int H, int W) {
@@ -3052,10 +2791,8 @@ static int conv_fwd_fill(ConvArgs& a, const float* x1, int C1, const float* x2, 
     DRAM_REQUIRE(C1 > 0 && Co1 > 0 && (x2 == nullptr || C2 > 0) && (y2 == nullptr || Co2 > 0),
                  "conv3d_k3_fwd: bad channel counts");
     a = ConvArgs{};
-    a.src = CatView{const_cast<float*>(x1), const_cast<float*>(x2), C1, x2 ? C2 : 0, x2 ? D2 : 1, x2 ? H2 : 1,
-                    x2 ? W2 : 1, x2 ? oz : 0, x2 ? oy : 0, x2 ? ox : 0};
-    a.dst = CatView{y1, y2, Co1, y2 ? Co2 : 0, y2 ? yD2 : 1, y2 ? yH2 : 1, y2 ? yW2 : 1, y2 ? yoz : 0, y2 ? yoy : 0,
-                    y2 ? yox : 0};
+    a.src = cat_view(x1, C1, x2, C2, D2, H2, W2, oz, oy, ox);
+    a.dst = cat_view(y1, Co1, y2, Co2, yD2, yH2, yW2, yoz, yoy, yox);
     a.wt = wt;
     a.bias = bias;
     a.N = N;
@@ -3112,26 +2849,28 @@ extern "C" int dram_conv3d_k3_fwd_choice_src(int Cin, int Cout, int D, int H, in
         a.src.p2 = const_cast<float*>(al);
         a.src.C2 = srcC2; a.src.D2 = srcD2; a.src.H2 = srcH2; a.src.W2 = srcW2; a.src.ox = srcox;
     }
-    if (fused) a.stats = const_cast<float*>(dummy);          // (only tested for null-ness by fwd_kernel_id)
-    return fwd_kernel_id(a, fwd_choice(a), name, cap);
+    if (fused) a.stats = const_cast<float*>(dummy);          // (only tested for null-ness by fwd_choice)
+    const FwdChoice c = fwd_choice(a);
+    DRAM_REQUIRE(c.row != nullptr, "conv3d_k3_fwd_choice: no kernel instantiation for [%d -> %d, %d x %d x %d]", Cin, Cout, D, H, W);
+    kernel_name(c.row->id, name, cap);
+    return c.row->id.kind;
 }
 extern "C" int dram_conv3d_k3_fwd_choice(int Cin, int Cout, int D, int H, int W, int dstC1, int dstC2, int dstD2, int dstH2,
                                          int dstW2, int fused, char* name, size_t cap) {
     return dram_conv3d_k3_fwd_choice_src(Cin, Cout, D, H, W, dstC1, dstC2, dstD2, dstH2, dstW2, fused, 0, 0, 0, 0, 0, 0, name, cap);
 }
 
-// Which kernel a backward-weights call of this shape launches (the same wgrad_plan / wgrad_kernel the launch uses).
+// Which kernel a backward-weights call of this shape launches (the same wgrad_plan the launch uses).
 extern "C" int dram_conv3d_k3_wgrad_choice(int N, int C1, int C2, int Cout, int D, int H, int W, int lazy, char* name, size_t cap) {
     DRAM_REQUIRE(N > 0 && C1 > 0 && C2 >= 0 && Cout > 0 && D > 0 && H > 0 && W > 0, "conv3d_k3_wgrad_choice: bad dimension");
-    WgradKernel k = {};
-    if (C1 + C2 == 1) {
-        k.kind = DRAM_K3_WGRAD_C1;
-    } else {
-        const WgradPlan p = wgrad_plan(N, C1 + C2, Cout, D, H, W, C2 > 0 ? C1 : 0);
-        k = wgrad_kernel(p, C1, C2 > 0, W, lazy != 0 && (p.wz || p.wzy));
+    const KernelId* id = C1 + C2 == 1 ? &kWgradC1Rows.rows[0].id : nullptr;
+    if (!id) {
+        const WgradPlan p = wgrad_plan(N, C1 + C2, Cout, D, H, W, C2 > 0 ? C1 : 0, lazy != 0);
+        DRAM_REQUIRE(p.row != nullptr, "conv3d_k3_wgrad_choice: no kernel instantiation for [%d -> %d, %d x %d x %d]", C1 + C2, Cout, D, H, W);
+        id = &p.row->id;
     }
-    wgrad_kernel_name(k, name, cap);
-    return k.kind;
+    kernel_name(*id, name, cap);
+    return id->kind;
 }
 
 extern "C" int dram_conv3d_k3_launch_counts(unsigned long long* counts, int n) {
@@ -3185,7 +2924,7 @@ extern "C" size_t dram_conv3d_k3_wgrad_ws_bytes(int N, int Cin, int Cout, int D,
     const WgradPlan p = wgrad_plan(N, Cin, Cout, D, H, W, 0), q = wgrad_plan(N, Cin, Cout, D, H, W, 1);
     const size_t slab = (size_t)Cout * Cin * 27 * sizeof(float);
     int split = p.split > q.split ? p.split : q.split;
-    if (p.wzy && Cin > 16) {
+    if (p.wzy() && Cin > 16) {
         const int sub = wzy_split(p.co_tiles, p.nboxes, slab, kWgradSubWsCap);
         split = sub > split ? sub : split;
     }
@@ -3197,8 +2936,7 @@ extern "C" size_t dram_conv3d_k3_wgrad_ws_bytes(int N, int Cin, int Cout, int D,
 extern "C" int dram_conv3d_k3_wgrad_lazy_ok(int N, int C1, int C2, int Cout, int D, int H, int W) {
     if (N <= 0 || C1 <= 0 || C2 < 0 || Cout <= 0 || D <= 0 || H <= 0 || W <= 0) return 0;
     if (C1 + C2 == 1) return 0;
-    const WgradPlan p = wgrad_plan(N, C1 + C2, Cout, D, H, W, C2 > 0 ? C1 : 0);
-    return p.wz | p.wzy;
+    return wgrad_plan(N, C1 + C2, Cout, D, H, W, C2 > 0 ? C1 : 0).winograd() ? 1 : 0;
 }
 
 static int wgrad_run(const float* x1, int C1, const float* coef1, int relu1, const float* x2, int C2, const float* coef2,
@@ -3208,8 +2946,7 @@ static int wgrad_run(const float* x1, int C1, const float* coef1, int relu1, con
     WgradArgs a = {};
     a.coef1 = coef1; a.coef2 = x2 ? coef2 : nullptr;
     a.relu1 = relu1; a.relu2 = relu2;
-    a.src = CatView{const_cast<float*>(x1), const_cast<float*>(x2), C1, x2 ? C2 : 0, x2 ? D2 : 1, x2 ? H2 : 1,
-                    x2 ? W2 : 1, x2 ? oz : 0, x2 ? oy : 0, x2 ? ox : 0};
+    a.src = cat_view(x1, C1, x2, C2, D2, H2, W2, oz, oy, ox);
     a.dy = dy;
     a.slabs = (float*)ws;
     a.N = N;
@@ -3219,6 +2956,7 @@ static int wgrad_run(const float* x1, int C1, const float* coef1, int relu1, con
     int rc = check_conv_shape("conv3d_k3_wgrad", N, a.Cin, Cout, D, H, W);
     if (rc) return rc;
     if ((rc = check_cat("conv3d_k3_wgrad(src)", a.src, D, H, W))) return rc;
+    hipStream_t st = (hipStream_t)stream;
     if (a.Cin == 1 && x2 == nullptr) {   // first layer: dedicated kernel
         DRAM_REQUIRE(a.coef1 == nullptr, "conv3d_k3_wgrad_fused: the first-layer kernel (Cin = 1) takes a plain input");
         DRAM_REQUIRE(((int64_t)Cout + 32) * (int64_t)D * H * W < 0x3fffffffLL,
@@ -3236,18 +2974,18 @@ static int wgrad_run(const float* x1, int C1, const float* coef1, int relu1, con
             set_error("conv3d_k3_wgrad: workspace %zu < %zu bytes", ws_bytes, need1);
             return DRAM_EWS;
         }
-        hipStream_t st1 = (hipStream_t)stream;
         g_launches[DRAM_K3_WGRAD_C1].fetch_add(1, std::memory_order_relaxed);
-        hipLaunchKernelGGL(conv3d_k3_wgrad_c1_kernel, dim3(blocks, cdiv(Cout, 32)), dim3(256), 0, st1, c);
+        if ((rc = kWgradC1Rows.rows[0].launch(c, st))) return rc;
         const int64_t E1 = (int64_t)Cout * 27;
-        hipLaunchKernelGGL(slab_reduce_kernel, dim3((unsigned)cdiv64(E1, 256)), dim3(256), 0, st1, c.slabs, dw, E1, 4 * blocks, 0, 0, 0);
+        hipLaunchKernelGGL(slab_reduce_kernel, dim3((unsigned)cdiv64(E1, 256)), dim3(256), 0, st, c.slabs, dw, E1, 4 * blocks, 0, 0, 0);
         return check_launch("conv3d_k3_wgrad(c1)");
     }
     // running 32-bit offsets walk up to 128 channel planes past the last one: they must not wrap
     DRAM_REQUIRE(((int64_t)(a.Cin > Cout ? a.Cin : Cout) + 128) * (int64_t)D * H * W < 0x3fffffffLL,
                  "conv3d_k3_wgrad: (channels + 128) * voxels per sample exceeds 2^30 (32-bit buffer offsets)");
-    const WgradPlan p = wgrad_plan(N, a.Cin, Cout, D, H, W, x2 ? C1 : 0);
-    DRAM_REQUIRE(p.wz || p.wzy || (a.coef1 == nullptr && a.coef2 == nullptr),
+    const WgradPlan p = wgrad_plan(N, a.Cin, Cout, D, H, W, x2 ? C1 : 0, a.coef1 || a.coef2);
+    DRAM_REQUIRE(p.row != nullptr, "conv3d_k3_wgrad: no kernel instantiation for [%d -> %d, %d x %d x %d]", a.Cin, Cout, D, H, W);
+    DRAM_REQUIRE(p.winograd() || (a.coef1 == nullptr && a.coef2 == nullptr),
                  "conv3d_k3_wgrad_fused: this shape runs a kernel without the lazy-operand path "
                  "(dram_conv3d_k3_wgrad_lazy_ok): materialise x first");
     const size_t need = (size_t)p.split * Cout * a.Cin * 27 * sizeof(float);
@@ -3257,12 +2995,9 @@ static int wgrad_run(const float* x1, int C1, const float* coef1, int relu1, con
     }
     a.nbx = p.nbx; a.nby = p.nby; a.nbz = p.nbz; a.nboxes = p.nboxes;
     a.split = p.split; a.ci_tiles = p.ci_tiles; a.co_tiles = p.co_tiles;
-    hipStream_t st = (hipStream_t)stream;
-    const WgradKernel wk = wgrad_kernel(p, C1, x2 != nullptr, W, a.coef1 || a.coef2);
-    g_launches[wk.kind].fetch_add(1, std::memory_order_relaxed);
-    const bool vec = wk.kind == DRAM_K3_WGRAD_VEC;
+    g_launches[p.row->id.kind].fetch_add(1, std::memory_order_relaxed);
     const int64_t E = (int64_t)Cout * a.Cin * 27;
-    if (p.wzy && x2 && (a.coef1 != nullptr) != (a.coef2 != nullptr)) {
+    if (p.wzy() && x2 && (a.coef1 != nullptr) != (a.coef2 != nullptr)) {
         // A virtual concat with exactly ONE lazy source (the first conv of an UpsampleConvBlock5d in the fused engine: the
         // upsampled part plain, the skip part lazy): one launch per source, each on its own instantiation and with its own
         // split.  In one launch the lazy tiles' blocks run ~9 % longer per box than the plain tiles', the blocks of a split
@@ -3275,41 +3010,16 @@ static int wgrad_run(const float* x1, int C1, const float* coef1, int relu1, con
         WgradArgs b = a;
         a.ci_tile0 = 0; a.ci_tiles = t1; a.split = s1; a.coef2 = nullptr;
         b.ci_tile0 = t1; b.ci_tiles = t2; b.split = s2; b.coef1 = nullptr;
-        g_launches[wk.kind].fetch_add(1, std::memory_order_relaxed);
-        rc = launch_wgrad_wzy(a, st);
-        if (rc) return rc;
-        rc = launch_wgrad_wzy(b, st);
-        if (rc) return rc;
+        const WgradRow* ra = kWgradWzyRows.find({}, a.coef1 != nullptr);
+        const WgradRow* rb = kWgradWzyRows.find({}, b.coef2 != nullptr);
+        DRAM_REQUIRE(ra && rb, "conv3d_k3_wgrad: no (z,y) kernel instantiation for a per-source launch");
+        g_launches[p.row->id.kind].fetch_add(1, std::memory_order_relaxed);
+        if ((rc = ra->launch(a, st))) return rc;
+        if ((rc = rb->launch(b, st))) return rc;
         hipLaunchKernelGGL(slab_reduce_kernel, dim3((unsigned)cdiv64(E, 256)), dim3(256), 0, st, a.slabs, dw, E, s1, a.Cin, a.src.C1, s2);
         return check_launch("conv3d_k3_wgrad(reduce)");
     }
-    if (p.wzy) {
-        rc = launch_wgrad_wzy(a, st);
-    } else if (p.wz) {
-        if (p.variant == 1)
-            rc = p.bx == 16 ? launch_wgrad_wz<16, 2, 8, 1>(a, st) : p.bx == 8 ? launch_wgrad_wz<8, 4, 8, 1>(a, st) : launch_wgrad_wz<4, 8, 8, 1>(a, st);
-        else
-            rc = p.bx == 16 ? launch_wgrad_wz<16, 2, 4, 2>(a, st) : p.bx == 8 ? launch_wgrad_wz<8, 4, 4, 2>(a, st) : launch_wgrad_wz<4, 8, 4, 2>(a, st);
-    } else if (vec) {
-        if (p.variant == 1) {
-            if (p.bx == 32) rc = launch_wgrad_vec<32, 2, 1, 8, 1>(a, st);
-            else if (p.bx == 16) rc = launch_wgrad_vec<16, 2, 2, 8, 1>(a, st);
-            else rc = launch_wgrad_vec<8, 4, 2, 8, 1>(a, st);
-        } else {
-            if (p.bx == 32) rc = launch_wgrad_vec<32, 2, 1, 4, 2>(a, st);
-            else if (p.bx == 16) rc = launch_wgrad_vec<16, 2, 2, 4, 2>(a, st);
-            else rc = launch_wgrad_vec<8, 4, 2, 4, 2>(a, st);
-        }
-    } else if (p.variant == 1) {
-        if (p.bx == 32) rc = launch_wgrad<32, 2, 1, 8, 1>(a, st);
-        else if (p.bx == 16) rc = launch_wgrad<16, 2, 2, 8, 1>(a, st);
-        else rc = launch_wgrad<8, 4, 2, 8, 1>(a, st);
-    } else {
-        if (p.bx == 32) rc = launch_wgrad<32, 2, 1, 4, 2>(a, st);
-        else if (p.bx == 16) rc = launch_wgrad<16, 2, 2, 4, 2>(a, st);
-        else rc = launch_wgrad<8, 4, 2, 4, 2>(a, st);
-    }
-    if (rc) return rc;
+    if ((rc = p.row->launch(a, st))) return rc;
     hipLaunchKernelGGL(slab_reduce_kernel, dim3((unsigned)cdiv64(E, 256)), dim3(256), 0, st, a.slabs, dw, E, p.split, 0, 0, 0);
     return check_launch("conv3d_k3_wgrad(reduce)");
 }

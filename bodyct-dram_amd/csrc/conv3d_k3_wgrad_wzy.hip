@@ -1,6 +1,13 @@
+// 3x3x3 convolution, backward-weights with the transpose of Winograd F(2x2,3x3) over (z,y): the kernel and its table
+// rows.  The other 3x3x3 kernels and the design common to all of them: conv3d_k3.hip.
+#include "conv_args.h"
+#include "conv_device.h"
+
+namespace dram {
+
 // ---------------------------------------------------------------------------------------------
 // backward-weights with the transpose of Winograd F(2x2, 3x3) over (z, y) -- exact fp32 arithmetic, 4/9 of the direct
-// MFMAs (2/3 of the z-only kernel's).  (Included by conv3d_k3.hip inside namespace dram.)
+// MFMAs (2/3 of the z-only kernel's).
 //
 // For a 2x2 (z,y) tile e of output gradients and the 4x4 input patch d around it (per x, co, ci; the x taps stay direct)
 //     E' = A e A^T,   V = B^T d B,   P[xi] += E'[xi] * V[xi](x + kx),   dg[:, :, kx] = G^T P G
@@ -543,3 +550,17 @@ __global__ __launch_bounds__(512, 1) void conv3d_k3_wgrad_wzy_kernel(WgradArgs a
         }
     }
 }
+
+// ---------------------------------------------------------------------------------------------
+// Table rows: a block walks a contiguous range of cdiv(nboxes, split) boxes
+template <bool LAZY>
+static WgradRow wgrad_wzy_row() {
+    return {{DRAM_K3_WGRAD_WZY, "conv3d_k3_wgrad_wzy_kernel", 0, {}, LAZY}, [](WgradArgs& a, hipStream_t st) {
+                return launch_kernel<conv3d_k3_wgrad_wzy_kernel<LAZY>, WgradWzyGeom::LDS_BYTES, 512>("conv3d_k3_wgrad(wzy)", wgrad_grid(a), st, a,
+                                                                                                  cdiv(a.nboxes, a.split));
+            }};
+}
+static const WgradRow kWgradWzyRowList[] = {wgrad_wzy_row<false>(), wgrad_wzy_row<true>()};
+const KernelTable<WgradArgs> kWgradWzyRows = kernel_table(kWgradWzyRowList);
+
+}  // namespace dram

@@ -14,7 +14,7 @@ namespace dram {
 constexpr int MAXCO = 8;  // output channels handled per pass
 
 // `coef` (optional): x holds a RAW conv output and the operand is act(a*x + b) per (n,c) row, ReLU if `relu`
-// ("normalise + ReLU on load", see csrc/conv3d_k3.hip ConvArgs::coef1; same fmaf / fmaxf as everywhere)
+// ("normalise + ReLU on load", see csrc/conv_args.h ConvArgs::coef1; same fmaf / fmaxf as everywhere)
 template <bool VEC>
 __global__ __launch_bounds__(256) void conv1x1_fwd_kernel(const float* __restrict__ x, const float* __restrict__ w,
                                                           const float* __restrict__ bias, float* __restrict__ y,

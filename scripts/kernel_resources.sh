@@ -1,6 +1,6 @@
 #!/bin/bash
 # Register / LDS / spill report of the kernels of one source file (hipcc -Rpass-analysis=kernel-resource-usage):
-#   scripts/kernel_resources.sh conv3d_k3.hip [name filter]
+#   scripts/kernel_resources.sh conv3d_k3.hip [name filter]      (the (z,y) backward-weights kernel: conv3d_k3_wgrad_wzy.hip)
 set -eo pipefail
 SRC=${1:-conv3d_k3.hip}
 FILT=${2:-.}

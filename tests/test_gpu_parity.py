@@ -373,7 +373,7 @@ def test_conv3d_k3_wgrad_wzy_fused(case):
     coefficients, a concat boundary at 16 channels, D = 4 (two boxes per z column: the shortest the raw-plane ring serves),
     W = 16 (one box per row), N = 3; a cropped second source whose window starts at x % 4 != 0 and whose rows are 19 floats (its
     16-byte LDS-DMA pieces are then only dword aligned in global memory -- the kernel drops border pieces by explicit
-    out-of-range offsets, not by alignment, unlike the forward kernel's descriptor-range padding: wgrad_wzy.inc); base
+    out-of-range offsets, not by alignment, unlike the forward kernel's descriptor-range padding: conv3d_k3_wgrad_wzy.hip); base
     pointers 4 bytes off 16-byte alignment.  This pins that dword-aligned 16-byte LDS-DMA is something the kernel may rely on."""
     from dram_amd import functional as HF
     from dram_amd import _lib

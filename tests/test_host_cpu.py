@@ -281,3 +281,87 @@ def test_isa_has_no_store_data_hazard():
     mod = importlib.util.module_from_spec(spec)
     spec.loader.exec_module(mod)
     assert mod.main(os.path.join(ROOT, "bodyct-dram_amd", "libdram_hip.so")) == 0
+
+
+def _library_kernel_names():
+    """Demangled kernel symbols of every gfx950 code object of libdram_hip.so, spelled as the choice queries spell names:
+    without return type, `dram::` prefix and argument list."""
+    import importlib.util
+    import subprocess
+    import tempfile
+    spec = importlib.util.spec_from_file_location("isa_hazards", os.path.join(ROOT, "scripts", "isa_hazards.py"))
+    mod = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(mod)
+    names = set()
+    with tempfile.TemporaryDirectory() as tmp:
+        cos = mod.code_objects(os.path.join(ROOT, "bodyct-dram_amd", "libdram_hip.so"), tmp)
+        assert cos, "no gfx950 code object in libdram_hip.so"
+        for co in cos:
+            out = subprocess.run([f"{mod.LLVM}/llvm-objdump", "-t", "-C", co], capture_output=True, text=True, check=True).stdout
+            for line in out.splitlines():
+                m = re.match(r"^[0-9a-f]+\s+\S+\s+F\s+\.text\s+[0-9a-f]+\s+(?:\.\w+\s+)?(.*\))$", line)
+                if not m:
+                    continue
+                sym = m.group(1)
+                depth, cut = 0, None                     # the argument list: the parenthesis that closes the symbol
+                for i in range(len(sym) - 1, -1, -1):
+                    depth += sym[i] == ")"
+                    depth -= sym[i] == "("
+                    if depth == 0:
+                        cut = i
+                        break
+                sym = sym[:cut]
+                if sym.startswith("void "):
+                    sym = sym[len("void "):]
+                if sym.startswith("dram::"):
+                    sym = sym[len("dram::"):]
+                names.add(sym)
+    return names
+
+
+def test_every_chosen_kernel_name_is_a_kernel_of_the_library():
+    """The name a choice query returns is what the tests and the per-kernel benchmark lines key on; it must be the symbol of
+    an instantiation that exists in the built library (a typo in a format string would otherwise pass the whole suite).
+    Sweep: the shapes of the two choice tests above, widths 11 / 12 / 20 / 24 / 40, Cout 16 / 32 / 64 / 128, concat boundaries
+    16 / 32 / 48, each with lazy and fused on and off.  Every returned name is checked."""
+    from dram_amd import functional as HF
+    from dram_amd import _lib
+    kernels = _library_kernel_names()
+    assert "conv3d_k3_fwd_wzy_kernel" in kernels and len(kernels) > 100, sorted(kernels)[:20]
+
+    shapes = [(128, 128, 128), (8, 8, 32), (80, 80, 80), (16, 16, 16), (40, 40, 40), (20, 20, 20), (10, 10, 10), (5, 7, 32),
+              (5, 7, 11), (56, 32, 56)]
+    shapes += [(8, 8, w) for w in (11, 12, 20, 24, 40)] + [(1, 6, 12), (3, 5, 24)]
+    channels = [(64, 32), (64, 192), (192, 64), (32, 64), (32, 1), (256, 512), (128, 384), (256, 768), (128, 64), (16, 8), (64, 64)]
+    channels += [(co, ci) for co in (16, 32, 64, 128) for ci in (8, 64)]
+    returned = set()
+
+    def fwd_src(dhw, co, ci, fused, **src):
+        buf = ctypes.create_string_buffer(96)
+        kind = _lib.lib.dram_conv3d_k3_fwd_choice_src(ci, co, *dhw, co, 0, 0, 0, 0, int(fused), src.get("c2", 0), src.get("d2", 0),
+                                                      src.get("h2", 0), src.get("w2", 0), src.get("ox", 0), src.get("mis", 0),
+                                                      buf, len(buf))
+        assert kind >= 0, (dhw, co, ci, src)
+        return buf.value.decode()
+
+    for dhw in shapes:
+        d, h, w = dhw
+        for co, ci in channels:
+            for fused in (False, True):
+                returned.add(HF.conv_fwd_kernel_name(dhw, co, ci, fused=fused))
+                for c1 in (32, 112):            # backward-data into two tensors
+                    if c1 < co:
+                        returned.add(HF.conv_fwd_kernel_name(dhw, co, ci, fused=fused, dst_split=(c1, co - c1, d, h + 1, w + 4)))
+                if ci >= 2:                      # the source variants of the test above
+                    for src in (dict(mis=1), dict(c2=ci // 2, d2=d, h2=h, w2=w, ox=0), dict(c2=ci // 2, d2=d + 2, h2=h + 3, w2=w + 6, ox=3),
+                                dict(c2=ci // 2, d2=d, h2=h, w2=w + 2, ox=0)):
+                        returned.add(fwd_src(dhw, co, ci, fused, **src))
+            for n in (2, 64):
+                for lazy in (False, True):
+                    returned.add(HF.conv_wgrad_kernel_name(n, dhw, co, ci, lazy=lazy))
+                    for c1 in (16, 32, 48):
+                        if c1 < ci:
+                            returned.add(HF.conv_wgrad_kernel_name(n, dhw, co, c1, ci - c1, lazy=lazy))
+    assert len(returned) >= 20, sorted(returned)          # the sweep reaches every family
+    missing = sorted(returned - kernels)
+    assert not missing, f"names the choice queries return that are no kernel of libdram_hip.so: {missing}"
