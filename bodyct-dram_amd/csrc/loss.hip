@@ -1,4 +1,5 @@
-// IntRegRefineLoss on the device, fused, gfx950.
+// IntRegRefineLoss on the device, fused, gfx950; further down the pieces of the
+// affine-consistency losses and IntRegLoss (the hinge with an entropy term instead of the pseudo-label term).
 //
 // Replaces the ~30 element-wise / reduction ATen dispatches -- and the per-sample host round trips --
 // of the reference's training loss, dram/metrics.py: IntRegLoss.compute_reg_loss_with_probs (158-177),
@@ -249,6 +250,179 @@ __global__ void masked_smooth_l1_bwd_kernel(const float* __restrict__ a, const f
 
 static inline int loss_chunks(int64_t S) { return (int)cdiv64(S, LCHUNK); }
 
+
+// ---- IntRegLoss / IntRegAffLoss (dram/metrics.py:75-308): the interval hinge with an entropy term --------------------
+//   p   = sigmoid(dense)
+//   reg = sum_n max((r_n - c_n)^2 - K_n, 0) / w_n,  r_n = sum_v p m / sum_v m       (compute_reg_loss_with_probs, 158-177)
+//   enc = mean over all N*S elements of  -p log(p + 1e-7) + (p - 1) log(1 - p + 1e-7)        (compute_enc_loss, 154-156)
+// The entropy is evaluated as the reference's fp32 expression evaluates it: 1 - p is formed from the ROUNDED p (it is
+// exactly 0 once p rounds to 1) and the 1e-7 is added after, so every logarithm sees at least 1e-7 and no finite logit
+// gives a non-finite value.  The lesion mask does not enter: it reaches the loss through the regression band `targets`
+// only (get_labels, 122-138), which the caller computes with the batch.
+// Forward: one pass over dense and lobes (8 B/voxel), every lane with four 16-byte loads per tensor in flight per step;
+// a block walks its sample with a grid stride, keeps its three sums in fp64 across steps and writes one fp64 partial
+// triple; one block then adds the partials in a fixed order.  No atomics: the same input gives the same bits.
+// Backward: one pass, 8 B/voxel read and 4 B/voxel written.
+constexpr int ENC_NSUM = 3;            // per (sample, block): sum of p inside the lobe, lobe voxels, sum of the entropy terms
+constexpr int ENC_UNROLL = 4;          // loads of each tensor a lane has in flight
+constexpr int ENC_MAX_BLOCKS = 2048;   // blocks of one launch (about 8 per CU), shared between the samples
+
+__device__ __forceinline__ float enc_term(float p) {
+    const float q = 1.f - p;
+    return -p * logf(p + LEPS) + (p - 1.f) * logf(q + LEPS);
+}
+// d enc_term / dp
+__device__ __forceinline__ float enc_term_dp(float p) {
+    const float q = 1.f - p;
+    return -logf(p + LEPS) - p / (p + LEPS) + logf(q + LEPS) + q / (q + LEPS);
+}
+
+template <int V> struct EncPack;
+template <> struct EncPack<4> { using type = float4; };
+template <> struct EncPack<1> { using type = float; };
+__device__ __forceinline__ float enc_lane(const float4& v, int i) { return i == 0 ? v.x : i == 1 ? v.y : i == 2 ? v.z : v.w; }
+__device__ __forceinline__ float enc_lane(const float& v, int) { return v; }
+__device__ __forceinline__ void enc_set(float4& v, int i, float x) { (i == 0 ? v.x : i == 1 ? v.y : i == 2 ? v.z : v.w) = x; }
+__device__ __forceinline__ void enc_set(float& v, int, float x) { v = x; }
+
+// V = 4: S is a multiple of 4 and both bases are 16-byte aligned, so every sample starts on a 16-byte boundary and a
+// pack is inside [0, S) whenever its first element is.  V = 1: any S, any alignment.
+template <int V>
+__global__ __launch_bounds__(256) void enc_partial_kernel(const float* __restrict__ dense, const float* __restrict__ lobes,
+                                                          double* __restrict__ part, int64_t S, int nblk) {
+    using T = typename EncPack<V>::type;
+    __shared__ double red[ENC_NSUM][4];
+    const int n = blockIdx.y;
+    const T* pd = reinterpret_cast<const T*>(dense + (int64_t)n * S);
+    const T* pm = reinterpret_cast<const T*>(lobes + (int64_t)n * S);
+    const int64_t packs = S / V;                             // packs of this sample
+    const int64_t step = (int64_t)nblk * 256 * ENC_UNROLL;   // packs all blocks of the sample cover per step
+    double acc[ENC_NSUM] = {0.0, 0.0, 0.0};
+    for (int64_t base = (int64_t)blockIdx.x * 256 * ENC_UNROLL; base < packs; base += step) {
+        T d[ENC_UNROLL], m[ENC_UNROLL];
+        bool ok[ENC_UNROLL];
+#pragma unroll
+        for (int u = 0; u < ENC_UNROLL; ++u) {
+            const int64_t i = base + u * 256 + threadIdx.x;
+            ok[u] = i < packs;
+            if (ok[u]) { d[u] = pd[i]; m[u] = pm[i]; }
+        }
+        float sp = 0.f, nm = 0.f, ent = 0.f;
+#pragma unroll
+        for (int u = 0; u < ENC_UNROLL; ++u) {
+            if (!ok[u]) continue;
+#pragma unroll
+            for (int k = 0; k < V; ++k) {
+                float p, q;
+                sigmoid_pq(enc_lane(d[u], k), p, q);
+                if (enc_lane(m[u], k) > 0.f) { sp += p; nm += 1.f; }
+                ent += enc_term(p);
+            }
+        }
+        acc[0] += sp; acc[1] += nm; acc[2] += ent;
+    }
+#pragma unroll
+    for (int q = 0; q < ENC_NSUM; ++q) {
+        const double s = wave_sum_d(acc[q]);
+        if ((threadIdx.x & 63) == 0) red[q][threadIdx.x >> 6] = s;
+    }
+    __syncthreads();
+    if (threadIdx.x < ENC_NSUM)
+        part[((size_t)n * nblk + blockIdx.x) * ENC_NSUM + threadIdx.x] =
+            red[threadIdx.x][0] + red[threadIdx.x][1] + red[threadIdx.x][2] + red[threadIdx.x][3];
+}
+
+// state: per sample {r_n, nm_n}.  One wave per sample adds that sample's partials (lanes stride over the blocks, then a
+// butterfly: a fixed order), thread 0 combines the samples in index order.
+__global__ __launch_bounds__(256) void enc_finalize_kernel(const double* __restrict__ part, double* __restrict__ ssum,
+                                                           const float* __restrict__ targets, const float* __restrict__ weight,
+                                                           int N, int64_t S, int nblk, float* __restrict__ out,
+                                                           float* __restrict__ state) {
+    const int lane = threadIdx.x & 63;
+    for (int n = threadIdx.x >> 6; n < N; n += 4) {
+        double s[ENC_NSUM] = {0.0, 0.0, 0.0};
+        for (int b = lane; b < nblk; b += 64)
+            for (int q = 0; q < ENC_NSUM; ++q) s[q] += part[((size_t)n * nblk + b) * ENC_NSUM + q];
+        for (int q = 0; q < ENC_NSUM; ++q) {
+            const double t = wave_sum_d(s[q]);
+            if (lane == 0) ssum[(size_t)n * ENC_NSUM + q] = t;
+        }
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        double regs = 0.0, ent = 0.0;
+        for (int n = 0; n < N; ++n) {
+            const double* s = ssum + (size_t)n * ENC_NSUM;
+            const double r = s[0] / s[1];
+            state[2 * n] = (float)r;
+            state[2 * n + 1] = (float)s[1];
+            const double lo = targets[2 * n], hi = targets[2 * n + 1];
+            const double K = 0.25 * (hi - lo) * (hi - lo);
+            const double h = (r - 0.5 * (hi + lo)) * (r - 0.5 * (hi + lo)) - K;
+            regs += (h > 0.0 ? h : 0.0) / (double)weight[n];
+            ent += s[2];
+        }
+        out[0] = (float)regs;
+        out[1] = (float)(ent / ((double)N * (double)S));
+    }
+}
+
+// d(g0*reg + g1*enc)/d dense; d p / d dense = p (1 - p) with the rounded p, as autograd's sigmoid backward forms it
+template <int V>
+__global__ __launch_bounds__(256) void enc_bwd_kernel(const float* __restrict__ dense, const float* __restrict__ lobes,
+                                                      const float* __restrict__ targets, const float* __restrict__ weight,
+                                                      const float* __restrict__ state, const float* __restrict__ gout,
+                                                      float* __restrict__ ddense, int N, int64_t S) {
+    using T = typename EncPack<V>::type;
+    const int n = blockIdx.y;
+    const float g0 = gout[0], g1 = gout[1];
+    const float r = state[2 * n], nm = state[2 * n + 1];
+    const float lo = targets[2 * n], hi = targets[2 * n + 1];
+    const float c = 0.5f * (hi + lo), K = 0.25f * (hi - lo) * (hi - lo);
+    const float hinge = ((r - c) * (r - c) - K) > 0.f ? 1.f : 0.f;
+    const float greg = g0 * hinge * 2.f * (r - c) / (weight[n] * nm);       // d reg / d p_v for m_v = 1
+    const float genc = (float)((double)g1 / ((double)N * (double)S));
+    const bool with_enc = g1 != 0.f;                         // the transformed batch of IntRegAffLoss takes reg alone
+    const T* pd = reinterpret_cast<const T*>(dense + (int64_t)n * S);
+    const T* pm = reinterpret_cast<const T*>(lobes + (int64_t)n * S);
+    T* po = reinterpret_cast<T*>(ddense + (int64_t)n * S);
+    const int64_t packs = S / V;
+    const int64_t step = (int64_t)gridDim.x * 256 * ENC_UNROLL;
+    for (int64_t base = (int64_t)blockIdx.x * 256 * ENC_UNROLL; base < packs; base += step) {
+        T d[ENC_UNROLL], m[ENC_UNROLL];
+        bool ok[ENC_UNROLL];
+#pragma unroll
+        for (int u = 0; u < ENC_UNROLL; ++u) {
+            const int64_t i = base + u * 256 + threadIdx.x;
+            ok[u] = i < packs;
+            if (ok[u]) { d[u] = pd[i]; m[u] = pm[i]; }
+        }
+#pragma unroll
+        for (int u = 0; u < ENC_UNROLL; ++u) {
+            if (!ok[u]) continue;
+            T g;
+#pragma unroll
+            for (int k = 0; k < V; ++k) {
+                float p, q;
+                sigmoid_pq(enc_lane(d[u], k), p, q);
+                float gp = enc_lane(m[u], k) > 0.f ? greg : 0.f;
+                if (with_enc) gp += genc * enc_term_dp(p);
+                enc_set(g, k, gp * p * (1.f - p));
+            }
+            po[base + u * 256 + threadIdx.x] = g;
+        }
+    }
+}
+
+static inline int enc_blocks(int N, int64_t S, int V) {      // blocks per sample: a function of (N, S, V) alone
+    const int64_t want = cdiv64(S / V, 256 * ENC_UNROLL), cap = cdiv64(ENC_MAX_BLOCKS, N);
+    return (int)(want < cap ? want : cap);
+}
+static inline int enc_blocks_max(int N, int64_t S) { return enc_blocks(N, S, 1); }
+static inline bool enc_vec4(const void* a, const void* b, const void* c, int64_t S) {
+    return S % 4 == 0 && (((uintptr_t)a | (uintptr_t)b | (uintptr_t)c) & 15) == 0;
+}
+
 }  // namespace dram
 
 using namespace dram;
@@ -290,6 +464,49 @@ extern "C" int dram_intreg_loss_bwd(const float* dense, const float* refined, co
     hipLaunchKernelGGL(loss_bwd_kernel, dim3(gx ? gx : 1, N), dim3(256), 0, (hipStream_t)stream, dense, refined, lobes, lesions,
                        keep, targets, weight, state, gout, smoothing, ddense, drefined, S);
     return check_launch("intreg_loss_bwd");
+}
+
+extern "C" size_t dram_intreg_enc_loss_ws_bytes(int N, int64_t S) {
+    if (N <= 0 || S <= 0) return 0;
+    return ((size_t)N * enc_blocks_max(N, S) + (size_t)N) * ENC_NSUM * sizeof(double);
+}
+
+extern "C" int dram_intreg_enc_loss_state_floats(int N) { return 2 * (N > 0 ? N : 0); }
+
+extern "C" int dram_intreg_enc_loss_fwd(const float* dense, const float* lobes, const float* targets, const float* weight,
+                                        float* out, float* state, void* ws, size_t ws_bytes, int N, int64_t S,
+                                        void* stream) {
+    DRAM_REQUIRE(dense && lobes && targets && weight && out && state && ws, "intreg_enc_loss_fwd: null pointer");
+    DRAM_REQUIRE(N > 0 && N <= 65535 && S > 0, "intreg_enc_loss_fwd: bad dimensions");
+    DRAM_REQUIRE(((uintptr_t)ws & 7) == 0, "intreg_enc_loss_fwd: workspace must be 8-byte aligned");
+    if (ws_bytes < dram_intreg_enc_loss_ws_bytes(N, S)) {
+        set_error("intreg_enc_loss_fwd: workspace too small");
+        return DRAM_EWS;
+    }
+    hipStream_t st = (hipStream_t)stream;
+    const bool v4 = enc_vec4(dense, lobes, nullptr, S);
+    const int nblk = enc_blocks(N, S, v4 ? 4 : 1);
+    double* part = (double*)ws;
+    double* ssum = part + (size_t)N * nblk * ENC_NSUM;
+    if (v4) hipLaunchKernelGGL(enc_partial_kernel<4>, dim3(nblk, N), dim3(256), 0, st, dense, lobes, part, S, nblk);
+    else hipLaunchKernelGGL(enc_partial_kernel<1>, dim3(nblk, N), dim3(256), 0, st, dense, lobes, part, S, nblk);
+    hipLaunchKernelGGL(enc_finalize_kernel, dim3(1), dim3(256), 0, st, (const double*)part, ssum, targets, weight, N, S, nblk,
+                       out, state);
+    return check_launch("intreg_enc_loss_fwd");
+}
+
+extern "C" int dram_intreg_enc_loss_bwd(const float* dense, const float* lobes, const float* targets, const float* weight,
+                                        const float* state, const float* gout, float* ddense, int N, int64_t S,
+                                        void* stream) {
+    DRAM_REQUIRE(dense && lobes && targets && weight && state && gout && ddense, "intreg_enc_loss_bwd: null pointer");
+    DRAM_REQUIRE(N > 0 && N <= 65535 && S > 0, "intreg_enc_loss_bwd: bad dimensions");
+    const bool v4 = enc_vec4(dense, lobes, ddense, S);
+    const int nblk = enc_blocks(N, S, v4 ? 4 : 1);
+    if (v4) hipLaunchKernelGGL(enc_bwd_kernel<4>, dim3(nblk, N), dim3(256), 0, (hipStream_t)stream, dense, lobes, targets, weight,
+                               state, gout, ddense, N, S);
+    else hipLaunchKernelGGL(enc_bwd_kernel<1>, dim3(nblk, N), dim3(256), 0, (hipStream_t)stream, dense, lobes, targets, weight,
+                            state, gout, ddense, N, S);
+    return check_launch("intreg_enc_loss_bwd");
 }
 
 extern "C" int dram_sigmoid_fwd(const float* x, float* y, int64_t n, void* stream) {

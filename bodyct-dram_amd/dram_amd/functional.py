@@ -811,6 +811,51 @@ def intreg_refine_loss(dense, lobes, lesions, keep, targets, weight, smoothing=0
     return IntRegRefineLossFn.apply(dense, refined, lobes, lesions, keep, targets, weight, smoothing)
 
 
+class IntRegEncLossFn(Function):
+    """(reg_loss, enc_loss) of IntRegLoss.__call__ (reference dram/metrics.py:204-210): the interval hinge of
+    compute_reg_loss_with_probs (158-177) and the entropy term of compute_enc_loss (154-156) on one logit tensor, one
+    streaming pass for the sums and one for the gradient.  `lesions` is part of the call because the loss is a function of
+    it, but it acts through `targets` alone (the band Batch derives from the lesion ratio): the kernels read dense and lobes."""
+
+    @staticmethod
+    def forward(ctx, dense, lobes, lesions, targets, weight):
+        dense = _chk(dense, "loss dense", 5)
+        lobes = _chk(lobes, "loss lobes", 5)
+        lesions = _chk(lesions, "loss lesions", 5)
+        N = dense.shape[0]
+        S = dense.numel() // N
+        if dense.shape[1] != 1 or lobes.shape != dense.shape or lesions.shape != dense.shape:
+            raise ValueError("IntRegEncLossFn: dense / lobes / lesions must all be [N,1,D,H,W]")
+        targets, weight = _chk(targets, "loss targets"), _chk(weight, "loss weight")
+        if targets.numel() != 2 * N or weight.numel() != N:
+            raise ValueError("IntRegEncLossFn: targets[N,2], weight[N] expected")
+        dev = dense.device
+        out = torch.empty(2, dtype=torch.float32, device=dev)
+        state = torch.empty(_lib.lib.dram_intreg_enc_loss_state_floats(N), dtype=torch.float32, device=dev)
+        ws = _ws(_lib.lib.dram_intreg_enc_loss_ws_bytes(N, S), dev)
+        call("dram_intreg_enc_loss_fwd", _p(dense), _p(lobes), _p(targets), _p(weight), _p(out), _p(state), _p(ws), ws.numel(),
+             N, S, _stream())
+        ctx.save_for_backward(dense, lobes, targets, weight, state)
+        return out
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, gout):
+        dense, lobes, targets, weight, state = ctx.saved_tensors
+        gout = _chk(gout, "loss grad_output", 1)
+        N = dense.shape[0]
+        S = dense.numel() // N
+        ddense = torch.empty_like(dense)
+        call("dram_intreg_enc_loss_bwd", _p(dense), _p(lobes), _p(targets), _p(weight), _p(state), _p(gout), _p(ddense), N, S,
+             _stream())
+        return ddense, None, None, None, None
+
+
+def intreg_enc_loss(dense, lobes, lesions, targets, weight):
+    """Returns a [2] tensor: (reg_loss, enc_loss)."""
+    return IntRegEncLossFn.apply(dense, lobes, lesions, targets, weight)
+
+
 class SigmoidFn(Function):
     """F.sigmoid as a differentiable device op (the affine-consistency term compares probabilities,
     reference dram/metrics.py:434,445)."""

@@ -11,6 +11,10 @@ round-trips every sample through numpy (metrics.py:338-352) -- never synchronise
 against the reference's golden vectors).  The regression targets depend only on the data (lesion
 ratio, CT severity score), so they are computed when the batch is built, as the reference's data
 loader side would.
+
+`DeviceIntRegLoss` / `DeviceIntRegAffLoss` are the reference's two losses without the pseudo-label refinement
+(metrics.py:75-308: the same hinge plus an entropy term, one more kernel pair of csrc/loss.hip); they take the places of
+`DeviceIntRegRefineLoss` / `DeviceIntRegAffRefineLoss` unchanged.
 """
 import math
 
@@ -107,6 +111,27 @@ class DeviceIntRegRefineLoss:
         from . import functional as HF
         out = HF.intreg_refine_loss(dense, batch.lobes, batch.lesions, batch.keep, batch.targets, batch.weight,
                                     self.smoothing, refined=refined)
+        return out[0], out[1]
+
+
+class DeviceIntRegLoss:
+    """IntRegLoss.__call__ (metrics.py:204-210): the interval regression of IntRegRefineLoss without the pseudo-label
+    term, plus the entropy of the predicted probabilities (compute_enc_loss, metrics.py:154-156).  The reference takes
+    the model's SECOND output for both terms, so `refined` is used when given and `dense` otherwise (DC3D returns one
+    tensor twice).  Returns (reg_loss, enc_loss).
+
+    The call signature is DeviceIntRegRefineLoss's, so it goes into DataParallelTrainer(loss_fn=...) as it is.  `enc` is a
+    mean over the batch's elements, so the trainer's share = len(micro) / n_global weighting of the second term makes
+    micro-batches and ranks of equal chunk size add up to the whole-batch value exactly (unlike seg_loss, no statistic of
+    the micro-batch enters it)."""
+
+    def __init__(self, band_width=5e-2):
+        self.band_width = band_width
+
+    def __call__(self, dense, batch, refined=None):
+        """One fused HIP kernel each way (csrc/loss.hip); no CPU fallback (CPU tensors raise)."""
+        from . import functional as HF
+        out = HF.intreg_enc_loss(dense if refined is None else refined, batch.lobes, batch.lesions, batch.targets, batch.weight)
         return out[0], out[1]
 
 
@@ -319,3 +344,51 @@ class DeviceIntRegAffRefineLoss:
         aff_loss = HF.masked_smooth_l1(probs_T, HF.sigmoid(a_dense), aff.lobes)
         aff_loss_cls = HF.masked_smooth_l1(cls_T, a_cls, aff.lobes)
         return (reg + a_reg) / 2.0, (aff_loss + aff_loss_cls) / 2.0, (seg + a_seg) / 2.0
+
+
+class DeviceIntRegAffLoss:
+    """IntRegAffLoss.__call__ (reference dram/metrics.py:245-308) on the device: the interval regression of IntRegLoss on a
+    batch AND on an affinely transformed copy of it (compute_reg_loss, metrics.py:191-195: the model's FIRST output), the
+    consistency term smooth_l1(T(sigmoid(dense)), sigmoid(dense_T)) inside the transformed lobes, and the entropy of the
+    un-transformed probabilities.  T is drawn as get_affine_transform draws it (metrics.py:219-243: the pool and the order of
+    the `random` / `numpy.random` calls of DeviceIntRegAffRefineLoss, each transform kept with probability 0.6).  The model
+    returns three outputs.  Returns (reg, aff, enc) as the reference does; its `trace` image dumps are not restated."""
+
+    def __init__(self, rescale_jitter, band_width=5e-2, freq_map=None):
+        self.rescale_jitter, self.band_width = rescale_jitter, band_width
+        self.freq_map = freq_map or {k: 1.0 / 6 for k in range(6)}
+        self.loss = DeviceIntRegLoss(band_width)
+
+    def get_affine_transform(self):
+        """metrics.py:219-243: the three OneShot transforms in a random order, each kept with probability 0.6."""
+        import itertools
+        import random
+
+        import numpy as np
+
+        from .transforms import Flip3DOneShot, Rescale3DOneShot, Rotate903DOneShot
+        pool = [Rescale3DOneShot(self.rescale_jitter, None, mode='size'), Flip3DOneShot(), Rotate903DOneShot()]
+        order = list(random.sample(list(itertools.permutations(pool, 3)), 1)[0])
+        chosen = [t for t in order if np.random.randint(0, 10) < 6]
+
+        def apply(sample):
+            for t in chosen:
+                sample = t(sample)
+            return sample
+        apply.p = chosen
+        return apply
+
+    def __call__(self, model, batch):
+        from . import functional as HF
+        T = self.get_affine_transform()
+        aff_images = T({"#image": batch.images})["#image"]
+        aff_lobes = T({"#reference": batch.lobes})["#reference"].contiguous()
+        aff_lesions = T({"#reference": batch.lesions})["#reference"].contiguous()
+        dense = model(batch.images, batch.lobes)[0]
+        reg, enc = self.loss(dense, batch)
+        probs_T = T({"#image": HF.sigmoid(dense)})["#image"]
+        aff = Batch(aff_images.detach(), aff_lobes, aff_lesions, batch.ctss, self.freq_map, band_width=self.band_width)
+        a_dense = model(aff.images, aff.lobes)[0]
+        a_reg, _ = self.loss(a_dense, aff)
+        aff_loss = HF.masked_smooth_l1(probs_T, HF.sigmoid(a_dense), aff.lobes)
+        return (reg + a_reg) / 2.0, aff_loss, enc

@@ -324,6 +324,20 @@ int dram_intreg_loss_bwd(const float* dense, const float* refined, const float* 
                          const float* gout, float smoothing, float* ddense, float* drefined, int N, int64_t S,
                          void* stream);
 
+/* ---- IntRegLoss / IntRegAffLoss, the losses without the pseudo-label refinement: dram/metrics.py:158-177 (the same
+ *      interval hinge on the lobe-mean probability) and 154-156 (compute_enc_loss: the mean over all N*S elements of
+ *      -p log(p + 1e-7) + (p - 1) log(1 - p + 1e-7), p = sigmoid(dense), in fp32 and in that order); 204-210, 245-308 ----
+ * dense, lobes: [N,1,D,H,W] (S = D*H*W); targets[N][2], weight[N] as for dram_intreg_loss_fwd (the lesion mask enters
+ * through targets alone).  One pass reads dense and lobes once; fp64 per-block partials added in a fixed order, no atomics.
+ * out[2] = {reg_loss, enc_loss}; state (dram_intreg_enc_loss_state_floats(N) floats) feeds the backward; ws: 8-byte aligned. */
+size_t dram_intreg_enc_loss_ws_bytes(int N, int64_t S);
+int dram_intreg_enc_loss_state_floats(int N);
+int dram_intreg_enc_loss_fwd(const float* dense, const float* lobes, const float* targets, const float* weight,
+                             float* out, float* state, void* ws, size_t ws_bytes, int N, int64_t S, void* stream);
+/* d(gout[0]*reg + gout[1]*enc) / d dense -> ddense; gout is a DEVICE array of 2 floats. */
+int dram_intreg_enc_loss_bwd(const float* dense, const float* lobes, const float* targets, const float* weight,
+                             const float* state, const float* gout, float* ddense, int N, int64_t S, void* stream);
+
 /* ---- PCM local attention on the voxel grid: dram/models.py PCM.init_graph 221-258 (the
  *      neighbour graph becomes E stencil offsets), merge_func 259-331 (dot-product and geo families), compute_cross_x
  *      365-397, forward / update_all 333-363.
