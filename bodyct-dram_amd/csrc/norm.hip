@@ -607,9 +607,10 @@ __global__ __launch_bounds__(256) void norm_finalize_parts_kernel(const double* 
     const double var = bc[2] / total;  // biased
     const float rstd = (float)(1.0 / sqrt(var + (double)eps));
     const float meanf = (float)mean;
+    // a count that differs from members x spatial size means a partial went missing: poison instead of a silent bias --
+    // the statistic and the {a, b} of its rows, which is what the forward consumers read
+    const bool bad = expect_count > 0.0 && bc[0] != expect_count;
     if (threadIdx.x == 0) {
-        // a count that differs from members x spatial size means a partial went missing: poison instead of a silent bias
-        const bool bad = expect_count > 0.0 && bc[0] != expect_count;
         save_mean[stat] = bad ? NAN : meanf;
         save_rstd[stat] = bad ? NAN : rstd;
         if (kind == DRAM_NORM_BATCH && running_mean) {
@@ -624,8 +625,8 @@ __global__ __launch_bounds__(256) void norm_finalize_parts_kernel(const double* 
         const float g = gamma ? gamma[c] : 1.f;
         const float bt = beta ? beta[c] : 0.f;
         const float a = g * rstd;
-        rowcoef[2 * row] = a;
-        rowcoef[2 * row + 1] = bt - meanf * a;
+        rowcoef[2 * row] = bad ? NAN : a;
+        rowcoef[2 * row + 1] = bad ? NAN : bt - meanf * a;
     }
 }
 

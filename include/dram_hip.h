@@ -448,7 +448,8 @@ int dram_conv3d_k3_launch_counts(unsigned long long* counts, int n);
 
 /* Training-mode BatchNorm / GroupNorm statistics (parts.py:19-31) from the conv epilogue's partials: save_mean,
  * save_rstd per statistic, rowcoef[N*C][2], running statistics updated as dram_norm_fwd_train does.  Chan's
- * combine in fp64; a total count that differs from the statistic's population poisons it with NaN. */
+ * combine in fp64; a total count that differs from the statistic's population poisons it with NaN: save_mean, save_rstd
+ * and the {a, b} of every row of the statistic. */
 size_t dram_norm_parts_ws_bytes(int N, int C, int nparts);
 int dram_norm_finalize_parts(const float* parts, int nparts, const float* gamma, const float* beta,
                              float* save_mean, float* save_rstd, float* rowcoef, float* running_mean,
