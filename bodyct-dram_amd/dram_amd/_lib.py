@@ -131,6 +131,10 @@ SIGNATURES = {
     "dram_aug_mask_out": (I, [P, P, P, P, P, P, I, I, I, I, I, I, P]),
     "dram_aug_gaussian_noise": (I, [P, P, P, P, P, P, I, P, I, L, P]),
     "dram_aug_permute_flip": (I, [P, P, I, P, P, P, I, I, I, I, I, I, P]),
+    # device chunk loader
+    "dram_chunk_hist256": (I, [P, P, P, I, P, I, I, P]),
+    "dram_otsu256": (I, [P, I, ctypes.c_double, P, P]),
+    "dram_chunk_prepare": (I, [P, P, P, P, P, I, I, I, I, F, F, I, I, P, P, P, P, P]),
 }
 
 

@@ -60,6 +60,14 @@ class Batch:
         self.keep = torch.tensor([0.0 if c < 1e-7 else 1.0 for c in self.ctss],
                                  dtype=torch.float32).view(-1, 1, 1, 1, 1).to(images.device)   # metrics.py:326-327
 
+    @classmethod
+    def from_chunks(cls, chunks, ctss, freq_map, loader, band_width=1e-2):
+        """The batch of raw chunks (dicts of int16 "#image", uint8 "#lobe_reference", optional "#vessel_reference" and
+        meta["spacing"], every chunk with its own size) prepared on the device by `loader`, a dram_amd.preprocess.ChunkLoader:
+        windowing, fixed-size resample and the pseudo-lesion label of dataset.py:450-486 / job_runner.py:586-597."""
+        out = loader(loader.pack(chunks))
+        return cls(out["#image"], out["#lobe_reference"], out["#pseudo_lesion_reference"], ctss, freq_map, band_width)
+
     def micro(self, lo, hi):
         b = object.__new__(Batch)
         b.images, b.lobes, b.lesions = self.images[lo:hi], self.lobes[lo:hi], self.lesions[lo:hi]

@@ -548,6 +548,35 @@ int dram_aug_gaussian_noise(const float* x, float* y, const float* minmax, const
 int dram_aug_permute_flip(const void* x, void* y, int elem_size, const int* perm, const int* flip, const int* flag, int n_table,
                           int N, int C, int D, int H, int W, void* stream);
 
+/* ---- device chunk loader: what the reference does per chunk on the host before a training step, for a whole ragged batch.
+ *      RadboudCOVIDLobeVesselChunk.get_data (dram/dataset.py:450-486): w_scan = windowing(scan, to_span=(0, 1)) (utils.py:189-198,
+ *      default span (-1150, 350)); _, th = binary_cam(w_scan[lobe > 0], 0.75) (utils.py:226-242); pseudo lesion = (w_scan > th) &
+ *      (lobe > 0); vessel = (vessel > 0) & (lobe > 0).  LesionSegChunkTrain.preprocessing (dram/job_runner.py:586-597):
+ *      Windowing(min, max) of the image as float32 (data_transforms.py:37-54), then Resample (data_transforms.py:65-211): linear
+ *      for the image, nearest neighbour for every "...reference" key, on the grid of sitk.ResampleImageFilter as
+ *      dram_resample_volume restates it (SimpleITK absent: parity unpinned).
+ *      The N chunks lie back to back in one DEVICE buffer per kind (scans int16, lobes uint8, vessels uint8; bases 16-byte
+ *      aligned), every chunk with its own size.  table: N records of 48 bytes on the DEVICE, {int64 offset in elements; int Di,
+ *      Hi, Wi; int pad; double sz, sy, sx}, s* = required_spacing / spacing per axis (the output-to-input index step).  No entry
+ *      point reads per-sample data from the host, synchronises or allocates.
+ * dram_chunk_hist256: hist[n][256] (uint64, zeroed here) of binary_cam's 8-bit view of windowing(scan_n, (wmin, wmax), (0, 1))
+ *   over voxels with lobe_n > 0: the fp64 arithmetic of dram_scan_hist256, one launch for the batch, integer atomics.
+ * dram_otsu256: th[n] = binary_cam's threshold of hist[n] (th / 255, the value dram_amd.inference.binary_cam_threshold returns,
+ *   bit for bit): Otsu over the occupied bin range with fp64 running sums in bin order, first maximum, min(t * scaler, 255) /
+ *   255; fewer than two occupied bins: bin / 255.  An all-zero histogram (empty lobe; the reference raises IndexError there):
+ *   th = +inf, so that the sample gets no candidates.
+ * dram_chunk_prepare: outputs [N][Do][Ho][Wo] float32.  image = Windowing(wmin, wmax) in fp32 exactly as numpy evaluates it on a
+ *   float32 array, resampled linearly (lerps x, y, z in double, cast to fp32; 0 beyond size_in - 0.5).  lobe_out = the lobe
+ *   value at the nearest voxel.  lesion_out (may be NULL; needs th) = (w_scan > th[n]) & (lobe > 0) at the nearest voxel, w_scan
+ *   in fp64 from (pwmin, pwmax) as dram_lesion_post evaluates it; never materialised at source resolution.  vessel_out (may be
+ *   NULL; needs vessels) = (vessel > 0) & (lobe > 0) at the nearest voxel.  wmin / wmax are fp32 values.  Wo <= 2048. ---- */
+int dram_chunk_hist256(const int16_t* scans, const uint8_t* lobes, const void* table, int N, unsigned long long* hist, int wmin,
+                       int wmax, void* stream);
+int dram_otsu256(const unsigned long long* hist, int N, double scaler, double* th, void* stream);
+int dram_chunk_prepare(const int16_t* scans, const uint8_t* lobes, const uint8_t* vessels, const void* table, const double* th,
+                       int N, int Do, int Ho, int Wo, float wmin, float wmax, int pwmin, int pwmax, float* image,
+                       float* lobe_out, float* lesion_out, float* vessel_out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
