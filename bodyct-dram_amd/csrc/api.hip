@@ -14,4 +14,4 @@ void set_error(const char* fmt, ...) {
 }  // namespace dram
 
 extern "C" const char* dram_last_error(void) { return dram::g_err; }
-extern "C" int dram_abi_version(void) { return 1; }
+extern "C" int dram_abi_version(void) { return 2; }

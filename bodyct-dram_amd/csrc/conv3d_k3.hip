@@ -2826,9 +2826,9 @@ extern "C" int dram_conv3d_k3_stats_parts(int Cin, int Cout, int D, int H, int W
     return fwd_choice(a).parts_cap;
 }
 
-// Which kernel a forward / backward-data call of this shape launches (the same fwd_choice the launch uses).  The plain query
-// assumes a source the (z,y) kernel accepts (16-byte aligned, no cropped second tensor); dram_conv3d_k3_fwd_choice_src takes
-// the facts of the source that can send a launch to the z-only kernel instead (wzy_source_ok).
+// Which kernel a forward / backward-data call of this shape launches (the same fwd_choice the launch uses), given the facts
+// of the source that can send a launch to the z-only kernel instead (wzy_source_ok); all zero: a source the (z,y) kernel
+// accepts (16-byte aligned, no cropped second tensor).
 extern "C" int dram_conv3d_k3_fwd_choice_src(int Cin, int Cout, int D, int H, int W, int dstC1, int dstC2, int dstD2, int dstH2,
                                              int dstW2, int fused, int srcC2, int srcD2, int srcH2, int srcW2, int srcox,
                                              int src_misaligned, char* name, size_t cap) {
@@ -2854,10 +2854,6 @@ extern "C" int dram_conv3d_k3_fwd_choice_src(int Cin, int Cout, int D, int H, in
     DRAM_REQUIRE(c.row != nullptr, "conv3d_k3_fwd_choice: no kernel instantiation for [%d -> %d, %d x %d x %d]", Cin, Cout, D, H, W);
     kernel_name(c.row->id, name, cap);
     return c.row->id.kind;
-}
-extern "C" int dram_conv3d_k3_fwd_choice(int Cin, int Cout, int D, int H, int W, int dstC1, int dstC2, int dstD2, int dstH2,
-                                         int dstW2, int fused, char* name, size_t cap) {
-    return dram_conv3d_k3_fwd_choice_src(Cin, Cout, D, H, W, dstC1, dstC2, dstD2, dstH2, dstW2, fused, 0, 0, 0, 0, 0, 0, name, cap);
 }
 
 // Which kernel a backward-weights call of this shape launches (the same wgrad_plan the launch uses).
@@ -2897,20 +2893,6 @@ extern "C" int dram_conv3d_k3_fwd_fused(const float* x1, int C1, const float* co
     a.relu1 = relu1; a.relu2 = relu2;
     a.stats = stats; a.nparts = nparts;
     return conv_fwd_dispatch(a, (hipStream_t)stream);
-}
-
-extern "C" int dram_conv3d_k3_fwd(const float* x, const float* wt, const float* bias, float* y, int N, int Cin,
-                                  int Cout, int D, int H, int W, void* stream) {
-    return dram_conv3d_k3_fwd_ex(x, Cin, nullptr, 0, 0, 0, 0, 0, 0, 0, wt, bias, y, Cout, nullptr, 0, 0, 0, 0, 0, 0, 0,
-                                 N, D, H, W, stream);
-}
-
-extern "C" int dram_conv3d_k3_fwd_cat(const float* x1, int C1, const float* x2, int C2, int D2, int H2, int W2, int oz,
-                                      int oy, int ox, const float* wt, const float* bias, float* y, int N, int Cout,
-                                      int D, int H, int W, void* stream) {
-    DRAM_REQUIRE(x2 != nullptr, "conv3d_k3_fwd_cat: second tensor is null");
-    return dram_conv3d_k3_fwd_ex(x1, C1, x2, C2, D2, H2, W2, oz, oy, ox, wt, bias, y, Cout, nullptr, 0, 0, 0, 0, 0, 0,
-                                 0, N, D, H, W, stream);
 }
 
 extern "C" size_t dram_conv3d_k3_wgrad_ws_bytes(int N, int Cin, int Cout, int D, int H, int W) {
@@ -3024,24 +3006,11 @@ static int wgrad_run(const float* x1, int C1, const float* coef1, int relu1, con
     return check_launch("conv3d_k3_wgrad(reduce)");
 }
 
-extern "C" int dram_conv3d_k3_wgrad_ex(const float* x1, int C1, const float* x2, int C2, int D2, int H2, int W2,
-                                       int oz, int oy, int ox, const float* dy, float* dw, void* ws, size_t ws_bytes,
-                                       int N, int Cout, int D, int H, int W, void* stream) {
-    return wgrad_run(x1, C1, nullptr, 0, x2, C2, nullptr, 0, D2, H2, W2, oz, oy, ox, dy, dw, ws, ws_bytes, N, Cout, D, H, W,
-                     stream);
-}
-
-// Backward-weights whose x operand is act(coef * raw + ...) applied on load (see dram_conv3d_k3_fwd_fused).
+// Backward-weights whose x operand is act(coef * raw + ...) applied on load (see dram_conv3d_k3_fwd_fused; null coefK: plain).
 extern "C" int dram_conv3d_k3_wgrad_fused(const float* x1, int C1, const float* coef1, int relu1, const float* x2, int C2,
                                           const float* coef2, int relu2, int D2, int H2, int W2, int oz, int oy, int ox,
                                           const float* dy, float* dw, void* ws, size_t ws_bytes, int N, int Cout, int D,
                                           int H, int W, void* stream) {
     return wgrad_run(x1, C1, coef1, relu1, x2, C2, coef2, relu2, D2, H2, W2, oz, oy, ox, dy, dw, ws, ws_bytes, N, Cout, D, H, W,
                      stream);
-}
-
-extern "C" int dram_conv3d_k3_wgrad(const float* x, const float* dy, float* dw, void* ws, size_t ws_bytes, int N,
-                                    int Cin, int Cout, int D, int H, int W, void* stream) {
-    return dram_conv3d_k3_wgrad_ex(x, Cin, nullptr, 0, 0, 0, 0, 0, 0, 0, dy, dw, ws, ws_bytes, N, Cout, D, H, W,
-                                   stream);
 }

@@ -428,11 +428,6 @@ extern "C" int dram_pcm_attention_split_fwd(const float* theta, const float* phi
     return check_launch("pcm_attention_fwd");
 }
 
-extern "C" int dram_pcm_attention_fwd(const float* theta, const float* phi, const int* offsets, int E, int flags,
-                                      int scale_mode, float* attn, int B, int F, int D, int H, int W, void* stream) {
-    return dram_pcm_attention_split_fwd(theta, phi, offsets, E, flags, scale_mode, F, attn, B, F, D, H, W, stream);
-}
-
 extern "C" int dram_pcm_attention_split_bwd(const float* theta, const float* phi, const float* attn, const float* dattn,
                                             const int* offsets, int E, int flags, int scale_mode, int F_relu, float* ds,
                                             float* ds2, float* dtheta, float* dphi, int B, int F, int D, int H, int W,
@@ -458,13 +453,6 @@ extern "C" int dram_pcm_attention_split_bwd(const float* theta, const float* phi
         hipLaunchKernelGGL(pcm_scatter_adjoint_kernel, dim3((unsigned)cdiv64(g.S, 256), F - F1, B), dim3(256), 0, st, ds2, theta, dphi, o,
                            g, F, F1);
     return check_launch("pcm_attention_bwd");
-}
-
-extern "C" int dram_pcm_attention_bwd(const float* theta, const float* phi, const float* attn, const float* dattn,
-                                      const int* offsets, int E, int flags, int scale_mode, float* ds, float* dtheta,
-                                      float* dphi, int B, int F, int D, int H, int W, void* stream) {
-    return dram_pcm_attention_split_bwd(theta, phi, attn, dattn, offsets, E, flags, scale_mode, F, ds, nullptr, dtheta, dphi, B, F,
-                                        D, H, W, stream);
 }
 
 extern "C" int dram_pcm_attention_sum_fwd(const float* theta, const float* phi, const int* offsets, int E, int mode,

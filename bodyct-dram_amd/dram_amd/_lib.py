@@ -25,12 +25,8 @@ SIGNATURES = {
     "dram_abi_version": (I, []),
     "dram_conv3d_k3_packed_floats": (Z, [I, I]),
     "dram_conv3d_k3_pack_weights": (I, [P, P, I, I, I, P]),
-    "dram_conv3d_k3_fwd": (I, [P, P, P, P, I, I, I, I, I, I, P]),
-    "dram_conv3d_k3_fwd_cat": (I, [P, I, P, I, I, I, I, I, I, I, P, P, P, I, I, I, I, I, P]),
     "dram_conv3d_k3_fwd_ex": (I, [P, I, P, I, I, I, I, I, I, I, P, P, P, I, P, I, I, I, I, I, I, I, I, I, I, I, P]),
     "dram_conv3d_k3_wgrad_ws_bytes": (Z, [I, I, I, I, I, I]),
-    "dram_conv3d_k3_wgrad": (I, [P, P, P, P, Z, I, I, I, I, I, I, P]),
-    "dram_conv3d_k3_wgrad_ex": (I, [P, I, P, I, I, I, I, I, I, I, P, P, P, Z, I, I, I, I, I, P]),
     "dram_conv3d_fwd": (I, [P, P, P, P] + [I] * 15 + [P]),
     "dram_conv3d_bwd_data": (I, [P, P, P] + [I] * 15 + [P]),
     "dram_conv3d_wgrad_ws_bytes": (Z, [I] * 15),
@@ -87,8 +83,6 @@ SIGNATURES = {
     "dram_resize_trilinear_bwd": (I, [P, P, I, I, I, I, I, I, I, I, F, F, F, P]),
     "dram_resize_nearest": (I, [P, P, I, I, I, I, I, I, I, I, F, F, F, P]),
     "dram_spatial_permute_flip": (I, [P, P, I, I, I, I, I, P, P, P]),
-    "dram_pcm_attention_fwd": (I, [P, P, P, I, I, I, P, I, I, I, I, I, P]),
-    "dram_pcm_attention_bwd": (I, [P, P, P, P, P, I, I, I, P, P, P, I, I, I, I, I, P]),
     "dram_pcm_attention_split_fwd": (I, [P, P, P, I, I, I, I, P, I, I, I, I, I, P]),
     "dram_pcm_attention_split_bwd": (I, [P, P, P, P, P, I, I, I, I, P, P, P, P, I, I, I, I, I, P]),
     "dram_pcm_attention_sum_fwd": (I, [P, P, P, I, I, P, I, I, I, I, I, P]),
@@ -100,7 +94,6 @@ SIGNATURES = {
     "dram_conv3d_k3_fwd_fused": (I, [P, I, P, I, P, I, P, I, I, I, I, I, I, I, P, P, P, P, I, I, I, I, I, I, P]),
     "dram_conv3d_k3_wgrad_lazy_ok": (I, [I, I, I, I, I, I, I]),
     "dram_conv3d_k3_wgrad_fused": (I, [P, I, P, I, P, I, P, I, I, I, I, I, I, I, P, P, P, Z, I, I, I, I, I, P]),
-    "dram_conv3d_k3_fwd_choice": (I, [I, I, I, I, I, I, I, I, I, I, I, c_char_p, Z]),
     "dram_conv3d_k3_fwd_choice_src": (I, [I, I, I, I, I, I, I, I, I, I, I, I, I, I, I, I, I, c_char_p, Z]),
     "dram_conv3d_k3_wgrad_choice": (I, [I, I, I, I, I, I, I, I, c_char_p, Z]),
     "dram_conv3d_k3_launch_counts": (I, [P, I]),

@@ -7,7 +7,7 @@ tensors for backward.  Here the whole network (reference dram/models.py:120-147)
 forward and backward are explicit sequences of C-ABI calls over "lazy" tensors:
 
   * a conv writes its raw output y once; its epilogue leaves the BatchNorm / GroupNorm moments of y as partials
-    (`dram_conv3d_k3_fwd_fused`), `dram_norm_finalize_parts` turns them into per-row coefficients {a, b};
+    (`functional.conv3d_k3_launch_fwd`), `dram_norm_finalize_parts` turns them into per-row coefficients {a, b};
   * the activated tensor act(a*y + b) is never written: every consumer -- the next conv (forward and
     backward-weights), the max-pool, the trilinear upsample, the 1x1x1 head -- applies it while loading;
   * backward keeps the reference's arithmetic (norm backward = two reductions + one apply, in place on the
@@ -32,7 +32,7 @@ from torch.autograd.function import once_differentiable
 from . import _lib
 from . import functional as HF
 from ._lib import call
-from .functional import NORM_BATCH, NORM_GROUP, _p, _stream, _ws, crop_offsets
+from .functional import NORM_BATCH, NORM_GROUP, _p, _stream, _ws
 from .modules import HipBatchNorm3d, HipConv3d, HipGroupNorm, HipMaxPool3d, HipReLU, HipSyncBatchNorm, HipUpsample
 
 
@@ -140,7 +140,7 @@ def parameters_of(model):
 # ------------------------------------------------------------------------------------------------ forward pieces
 class _Stage:
     """What backward needs of one conv -> norm -> ReLU stage."""
-    __slots__ = ("conv", "norm", "inp", "skip", "geom", "y", "coef", "mean", "rstd", "kind", "groups", "batch_stats",
+    __slots__ = ("conv", "norm", "inp", "skip", "y", "coef", "mean", "rstd", "kind", "groups", "batch_stats",
                  "out", "need_input_grad", "ranges", "sync")
 
 
@@ -170,32 +170,15 @@ def _sync_forward_stats(norm, group, parts, nparts, ws, mean, rstd, coef, count,
     """Cross-rank combine of a stage's batch statistics (what functional.SyncBatchNormFn.forward does for the per-op
     path): this rank's per-channel {mean, M2} in fp64 straight from the conv epilogue's partials (dram_bn_parts_stats -- not
     from save_rstd, whose inversion rstd^-2 - eps cancels for channels with variance far below eps), all-gather, Chan's
-    formula in fp64, running statistics from the GLOBAL moments, then mean / rstd / per-row {a, b} written from them.
-    Returns the global element count per channel."""
-    import torch.distributed as dist
-    eps = float(norm.eps)
-    dev = mean.device
-    local = torch.empty(2 * Co + 1, dtype=torch.float64, device=dev)
+    formula in fp64, running statistics from the GLOBAL moments (functional.sync_bn_combine), then mean / rstd / per-row
+    {a, b} written from them.  Returns the global element count per channel."""
+    local = torch.empty(2 * Co + 1, dtype=torch.float64, device=mean.device)
     call("dram_bn_parts_stats", _p(parts), nparts, _p(local), N, Co, S, _p(ws), ws.numel(), st)
     local[2 * Co] = float(count)
-    world = dist.get_world_size(group)
-    allst = [torch.empty_like(local) for _ in range(world)]
-    dist.all_gather(allst, local, group=group)
-    allst = torch.stack(allst)                               # [world, 2 Co + 1]
-    cnt = allst[:, 2 * Co].view(world, 1)
-    means, m2s = allst[:, 0:2 * Co:2], allst[:, 1:2 * Co:2]
-    total = cnt.sum()
-    gmean = (means * cnt).sum(0) / total
-    m2 = (m2s + cnt * (means - gmean) ** 2).sum(0)
-    gvar = m2 / total
-    gmean_f, gvar_f = gmean.float(), gvar.float()
-    if rm is not None:
-        with torch.no_grad():
-            unb = (m2 / (total - 1.0)).float() if float(total) > 1.0 else gvar_f
-            rm.mul_(1.0 - eaf).add_(gmean_f, alpha=eaf)
-            rv.mul_(1.0 - eaf).add_(unb, alpha=eaf)
-    call("dram_bn_eval_coef", _p(norm.weight), _p(norm.bias), _p(gmean_f), _p(gvar_f), _p(mean), _p(rstd), _p(coef), eps, N, Co, st)
-    return float(total)
+    gmean_f, gvar_f, total = HF.sync_bn_combine(local, group, rm, rv, eaf)
+    call("dram_bn_eval_coef", _p(norm.weight), _p(norm.bias), _p(gmean_f), _p(gvar_f), _p(mean), _p(rstd), _p(coef),
+         float(norm.eps), N, Co, st)
+    return total
 
 
 # A stage whose first input is an Upsampled recipe runs in slices of samples when the upsampled tensor (and, in
@@ -207,6 +190,11 @@ SLICE_UPSAMPLED_ABOVE = 0.08
 
 def _rows(coef, lo, hi, C):
     return None if coef is None else coef[2 * lo * C:2 * hi * C]
+
+
+def _lazy_args(x1, sk):
+    """`lazy` of functional.conv3d_k3_launch_fwd / _wgrad for the Lazy sources x1 ++ crop(sk) (sk may be None)."""
+    return (x1.coef, x1.relu, None, 0) if sk is None else (x1.coef, x1.relu, sk.coef, sk.relu)
 
 
 def _lazy_slice(lz, lo, hi):
@@ -228,20 +216,11 @@ def _conv_stage(conv, norm, inp, skip, training, record, plan):
     """y = conv(inp ++ crop(skip)) with the moments of y from the epilogue -> Lazy(y, coef, relu).  `inp` is a Lazy or
     an Upsampled recipe (then produced here -- whole, or slice by slice -- used, and dropped unless it is small)."""
     up = isinstance(inp, Upsampled)
-    N, C1 = inp.src.raw.shape[:2] if up else inp.raw.shape[:2]
+    N = inp.src.raw.shape[0] if up else inp.raw.shape[0]
     D, H, W = inp.size if up else inp.raw.shape[2:]
     w = conv.weight
     Co, Ci = w.shape[0], w.shape[1]
     dev = w.device
-    if skip is not None:
-        C2, D2, H2, W2 = skip.raw.shape[1:]
-        if skip.raw.shape[0] != N or not (D <= D2 and H <= H2 and W <= W2):
-            raise ValueError("fused conv stage: the skip tensor must have the same batch and be at least as large")
-        oz, oy, ox = crop_offsets((D, H, W), (D2, H2, W2))
-    else:
-        C2 = D2 = H2 = W2 = oz = oy = ox = 0
-    if C1 + C2 != Ci:
-        raise ValueError(f"fused conv stage: input has {C1 + C2} channels, weight expects {Ci}")
     kind, groups, use_batch, rm, rv, eaf = _norm_plan(norm, training)
     S = D * H * W
     st = _stream()
@@ -257,20 +236,15 @@ def _conv_stage(conv, norm, inp, skip, training, record, plan):
     ranges = _slices(inp, N, plan.slice_up) if up else [(0, N)]
     plan.sliced_stages += len(ranges) > 1
     for lo, hi in ranges:
-        n = hi - lo
         if up:
             x1 = Lazy(inp.produce(lo, hi, keep_below=plan.keep_up if record is not None and len(ranges) == 1 else 0))
         else:
             x1 = inp if (lo, hi) == (0, N) else _lazy_slice(inp, lo, hi)
         sk = None if skip is None else (skip if (lo, hi) == (0, N) else _lazy_slice(skip, lo, hi))
-        vox = n * S
-        name = HF.conv_fwd_kernel_name((D, H, W), Co, Ci, fused=True, src=(x1.raw, sk.raw if sk is not None else None, ox))
-        HF._timed_call(name, 54.0 * Ci * Co * vox, 4.0 * (Ci + Co) * vox,
-                       "dram_conv3d_k3_fwd_fused", _p(x1.raw), C1, _p(x1.coef), int(x1.relu),
-                       _p(sk.raw) if sk is not None else None, C2, _p(sk.coef) if sk is not None else None,
-                       int(sk.relu) if sk is not None else 0, D2, H2, W2, oz, oy, ox, _p(wt), None, _p(y[lo:hi]),
-                       _p(parts[lo * Co * nparts * 3:]) if use_batch else None, nparts, n, Co, D, H, W, st)
-        del x1
+        src = HF.CatView(x1.raw, None if sk is None else sk.raw, (D, H, W), channels=Ci)
+        HF.conv3d_k3_launch_fwd(src, wt, None, y[lo:hi], _lazy_args(x1, sk),
+                                parts[lo * Co * nparts * 3:] if use_batch else None, nparts)
+        del x1, src
     sync, group = _sync_group(norm, training and use_batch and kind == NORM_BATCH)
     total = None
     if use_batch:
@@ -288,7 +262,6 @@ def _conv_stage(conv, norm, inp, skip, training, record, plan):
     if record is not None:
         s = _Stage()
         s.conv, s.norm, s.inp, s.skip = conv, norm, inp, skip
-        s.geom = (C1, C2, D2, H2, W2, oz, oy, ox)
         s.y, s.coef, s.mean, s.rstd = y, coef, mean, rstd
         s.kind, s.groups, s.batch_stats, s.out = kind, groups, bool(use_batch), out
         s.sync = (group, total) if sync else None
@@ -458,17 +431,6 @@ def forward(model, x, record, taps=()):
 
 
 # ------------------------------------------------------------------------------------------------ backward
-def _trilinear_bwd(dy, in_shape):
-    N, C, D, H, W = in_shape
-    Do, Ho, Wo = dy.shape[-3:]
-    dx = torch.empty(in_shape, dtype=torch.float32, device=dy.device)
-    full = _lib.lib.dram_upsample_trilinear_ac_bwd_ws_bytes(N, C, D, H, W, Do, Ho, Wo)
-    ws = _ws(min(full, HF.TRI_BWD_WS_CAP), dy.device) if full else None
-    call("dram_upsample_trilinear_ac_bwd_ws", _p(dy), _p(dx), _p(ws), ws.numel() if ws is not None else 0,
-         N, C, D, H, W, Do, Ho, Wo, _stream())
-    return dx
-
-
 def backward(model, record, gout, need_dx, sink=None):
     """Returns ({parameter: gradient}, dx or None).  `gout`: gradient w.r.t. the dense output.
     `sink(parameter, gradient) -> bool`: called as soon as a parameter's gradient is final -- the head first, then stage by
@@ -490,7 +452,7 @@ def backward(model, record, gout, need_dx, sink=None):
         if tag == "input":
             continue
         if tag == "resize":
-            g = _trilinear_bwd(g, item[1])
+            g = HF.trilinear_ac_backward(g, item[1])
         elif tag == "head":
             lz = item[1]
             top = model.top_layer
@@ -512,9 +474,9 @@ def backward(model, record, gout, need_dx, sink=None):
             g = gact.pop(id(s.out))
             N, Co, D, H, W = s.y.shape
             S = D * H * W
-            C1, C2, D2, H2, W2, oz, oy, ox = s.geom
-            Ci = C1 + C2
             w = s.conv.weight
+            C2 = 0 if s.skip is None else s.skip.raw.shape[1]
+            C1 = w.shape[1] - C2
             # norm (+ReLU) backward, in place: g <- d(raw conv output)
             gamma = s.norm.weight
             dgamma = torch.empty(Co, dtype=torch.float32, device=g.device) if gamma is not None else None
@@ -553,14 +515,12 @@ def backward(model, record, gout, need_dx, sink=None):
             if need_dgrad and skip is not None:
                 if id(skip) in gact:
                     raise RuntimeError("fused backward: a skip tensor received a gradient before its up-path consumer")
-                full = (D2, H2, W2) == (D, H, W)
-                dx2 = torch.empty_like(skip.raw) if full else torch.zeros_like(skip.raw)
+                dx2 = HF.conv3d_k3_dx2(skip.raw, (D, H, W))
             g_low = None        # gradient w.r.t. the low-resolution source of an upsampled input, filled slice by slice
             if up and need_dgrad and not whole:
                 g_low = torch.empty_like(inp.src.raw)
             for lo, hi in ranges:
                 n = hi - lo
-                vox = n * S
                 gs = g if whole else g[lo:hi]
                 # backward-weights: the x operand is the stage's lazy input(s); an upsampled input is produced again
                 if up:
@@ -571,28 +531,16 @@ def backward(model, record, gout, need_dx, sink=None):
                 if not lazy_ok:     # kernels without the on-load path (odd widths, first layer): plain operands
                     x1 = Lazy(x1.materialise())
                     sk = Lazy(sk.materialise()) if sk is not None else None
-                dws = torch.empty_like(w)
-                wsb = _ws(_lib.lib.dram_conv3d_k3_wgrad_ws_bytes(n, Ci, Co, D, H, W), g.device)
-                name = HF.conv_wgrad_kernel_name(n, (D, H, W), Co, C1, C2,
-                                                 lazy=(x1.coef is not None or (sk is not None and sk.coef is not None)))
-                HF._timed_call(name, 54.0 * Ci * Co * vox, 4.0 * (Ci + Co) * vox,
-                               "dram_conv3d_k3_wgrad_fused", _p(x1.raw), C1, _p(x1.coef), int(x1.relu),
-                               _p(sk.raw) if sk is not None else None, C2,
-                               _p(sk.coef) if sk is not None else None, int(sk.relu) if sk is not None else 0,
-                               D2, H2, W2, oz, oy, ox, _p(gs), _p(dws), _p(wsb), wsb.numel(), n, Co, D, H, W, st)
+                src = HF.CatView(x1.raw, None if sk is None else sk.raw, (D, H, W))
+                dws = HF.conv3d_k3_launch_wgrad(src, gs, w, _lazy_args(x1, sk))
                 dw = dws if dw is None else dw.add_(dws)
-                del x1, sk, dws, wsb
+                del x1, sk, src, dws
                 # backward-data: gradient w.r.t. the activated input(s)
                 if need_dgrad:
                     dx1 = torch.empty((n, C1, D, H, W), dtype=torch.float32, device=g.device)
-                    HF._timed_call(HF.conv_fwd_kernel_name((D, H, W), Ci, Co, dst_split=(C1, C2, D2, H2, W2) if dx2 is not None else None,
-                                                           src=(gs, None, 0)),
-                                   54.0 * Ci * Co * vox, 4.0 * (Ci + Co) * vox,
-                                   "dram_conv3d_k3_fwd_ex", _p(gs), Co, None, 0, 0, 0, 0, 0, 0, 0, _p(wt), None,
-                                   _p(dx1), C1, _p(dx2[lo:hi]) if dx2 is not None else None, C2, D2, H2, W2, oz, oy, ox,
-                                   n, D, H, W, st)
+                    HF.conv3d_k3_launch_bwd_data(gs, wt, dx1, None if dx2 is None else dx2[lo:hi])
                     if up and not whole:       # straight on to the low-resolution gradient: d(upsampled) is never whole
-                        g_low[lo:hi] = _trilinear_bwd(dx1, (n,) + tuple(inp.src.raw.shape[1:]))
+                        g_low[lo:hi] = HF.trilinear_ac_backward(dx1, (n,) + tuple(inp.src.raw.shape[1:]))
                     elif up:
                         gact[("up", id(inp.src))] = dx1
                     else:
@@ -615,7 +563,7 @@ def backward(model, record, gout, need_dx, sink=None):
                 _accumulate(gact, id(lz), gact.pop(("low", id(lz))))
             else:
                 gup = gact.pop(("up", id(lz)))
-                _accumulate(gact, id(lz), _trilinear_bwd(gup, tuple(lz.raw.shape)))
+                _accumulate(gact, id(lz), HF.trilinear_ac_backward(gup, tuple(lz.raw.shape)))
         elif tag == "pool":
             lz, idx, res = item[1], item[2], item[3]
             gp = gact.pop(id(res), None)

@@ -183,6 +183,96 @@ def _pack(w, mode):
     return wt
 
 
+class CatView:
+    """x1[n, C1, D, H, W] ++ centre-crop(x2[n, C2, D2, H2, W2]) along the channels, never materialised (x2 may be None): the
+    source of a 3x3x3 conv (crop_concat_5d of reference parts.py:37-46,153 fused into it), or the split destination of its
+    backward-data.  `channels`: what the filter expects of C1 + C2."""
+    __slots__ = ("x1", "x2", "C1", "C2", "dhw2", "off")
+
+    def __init__(self, x1, x2, dhw, channels=None):
+        self.x1, self.x2, self.C1 = x1, x2, x1.shape[1]
+        self.C2, self.dhw2, self.off = 0, (0, 0, 0), (0, 0, 0)
+        if x2 is not None:
+            self.C2, self.dhw2 = x2.shape[1], tuple(x2.shape[2:])
+            if x2.shape[0] != x1.shape[0]:
+                raise ValueError("conv3d: batch sizes of the two inputs differ")
+            if not all(a <= b for a, b in zip(dhw, self.dhw2)):
+                raise ValueError("conv3d: the second (skip) tensor must be at least as large as the first")
+            self.off = crop_offsets(dhw, self.dhw2)
+        if channels is not None and self.C1 + self.C2 != channels:
+            raise ValueError(f"conv3d: input has {self.C1 + self.C2} channels, weight expects {channels}")
+
+    def args(self):
+        """(p1, C1, p2, C2, D2, H2, W2, oz, oy, ox) of the C ABI."""
+        return (_p(self.x1), self.C1, _p(self.x2), self.C2, *self.dhw2, *self.off)
+
+    @property
+    def src(self):
+        """conv_fwd_kernel_name's `src`, when this view is the source of the launch."""
+        return self.x1, self.x2, self.off[2]
+
+    @property
+    def split(self):
+        """conv_fwd_kernel_name's `dst_split`, when this view is the destination of the launch."""
+        return (self.C1, self.C2, *self.dhw2) if self.x2 is not None else None
+
+
+def _k3_cost(Ci, Co, y):
+    """(flops, bytes) the KernelTimer books for a 3x3x3 conv launch over the voxels of y[n, ., D, H, W]."""
+    vox = y.shape[0] * y.shape[2] * y.shape[3] * y.shape[4]
+    return 54.0 * Ci * Co * vox, 4.0 * (Ci + Co) * vox
+
+
+def conv3d_k3_launch_fwd(src, wt, bias, y, lazy=None, parts=None, nparts=0):
+    """y[n, Co, D, H, W] = conv3d(src, w) (+ bias); `src` a CatView, `wt` = _pack(w, 0).  lazy = None: plain sources.
+    lazy = (coef1, relu1, coef2, relu2): the fused variant -- a source with a coef is normalised (+ReLU) on load, and the
+    moments of y go to parts[n * Co * nparts * 3] when given."""
+    n, Co, D, H, W = y.shape
+    Ci = src.C1 + src.C2
+    key = conv_fwd_kernel_name((D, H, W), Co, Ci, fused=lazy is not None, src=src.src) if TIMER is not None else None
+    if lazy is None:
+        _timed_call(key, *_k3_cost(Ci, Co, y), "dram_conv3d_k3_fwd_ex", *src.args(), _p(wt), _p(bias),
+                    _p(y), Co, None, 0, 0, 0, 0, 0, 0, 0, n, D, H, W, _stream())
+    else:
+        coef1, relu1, coef2, relu2 = lazy
+        _timed_call(key, *_k3_cost(Ci, Co, y), "dram_conv3d_k3_fwd_fused", _p(src.x1), src.C1, _p(coef1), int(relu1),
+                    _p(src.x2), src.C2, _p(coef2), int(relu2), *src.dhw2, *src.off, _p(wt), _p(bias), _p(y),
+                    _p(parts), nparts, n, Co, D, H, W, _stream())
+
+
+def conv3d_k3_dx2(x2, dhw):
+    """The gradient buffer of a cropped second source: backward-data writes its crop window only, so it starts as zeros
+    unless the window is the whole tensor."""
+    return torch.empty_like(x2) if tuple(x2.shape[2:]) == tuple(dhw) else torch.zeros_like(x2)
+
+
+def conv3d_k3_launch_bwd_data(dy, wt, dx1, dx2=None):
+    """Backward-data of y = conv3d(x1 ++ crop(x2), w): the transposed conv of dy (`wt` = _pack(w, 1)) into dx1 and, when
+    given, the crop window of dx2 (conv3d_k3_dx2)."""
+    n, Co, D, H, W = dy.shape
+    dst = CatView(dx1, dx2, (D, H, W))
+    Ci = dst.C1 + dst.C2
+    key = conv_fwd_kernel_name((D, H, W), Ci, Co, dst_split=dst.split, src=(dy, None, 0)) if TIMER is not None else None
+    _timed_call(key, *_k3_cost(Ci, Co, dy), "dram_conv3d_k3_fwd_ex", _p(dy), Co, None, 0, 0, 0, 0, 0, 0, 0, _p(wt), None,
+                *dst.args(), n, D, H, W, _stream())
+
+
+def conv3d_k3_launch_wgrad(src, dy, w, lazy=(None, 0, None, 0)):
+    """dw (like w) of y = conv3d(src, w) from dy[n, Co, D, H, W]; `src` a CatView, lazy = (coef1, relu1, coef2, relu2) as in
+    conv3d_k3_launch_fwd (all plain by default)."""
+    n, Co, D, H, W = dy.shape
+    Ci = src.C1 + src.C2
+    coef1, relu1, coef2, relu2 = lazy
+    dw = torch.empty_like(w)
+    ws = _ws(_lib.lib.dram_conv3d_k3_wgrad_ws_bytes(n, Ci, Co, D, H, W), dy.device)
+    key = conv_wgrad_kernel_name(n, (D, H, W), Co, src.C1, src.C2, lazy=coef1 is not None or coef2 is not None) \
+        if TIMER is not None else None
+    _timed_call(key, *_k3_cost(Ci, Co, dy), "dram_conv3d_k3_wgrad_fused", _p(src.x1), src.C1, _p(coef1), int(relu1),
+                _p(src.x2), src.C2, _p(coef2), int(relu2), *src.dhw2, *src.off, _p(dy), _p(dw), _p(ws), ws.numel(),
+                n, Co, D, H, W, _stream())
+    return dw
+
+
 class Conv3dK3Fn(Function):
     """y = conv3d(cat(x1, crop(x2)), w, bias), k=3, stride 1, zero pad 1.  x2 may be None.
     (nn.Conv3d of reference parts.py:95,105,133,142,177,185; crop_concat_5d of parts.py:153 fused.)"""
@@ -197,27 +287,13 @@ class Conv3dK3Fn(Function):
             raise ValueError(f"Conv3dK3Fn: kernel {tuple(w.shape[2:])} is not 3x3x3")
         if x2 is not None:
             x2 = _chk(x2, "conv3d second input", 5)
-            C2, D2, H2, W2 = x2.shape[1:]
-            if x2.shape[0] != N:
-                raise ValueError("conv3d: batch sizes of the two inputs differ")
-            if not (D <= D2 and H <= H2 and W <= W2):
-                raise ValueError("conv3d: the second (skip) tensor must be at least as large as the first")
-            oz, oy, ox = crop_offsets((D, H, W), (D2, H2, W2))
-        else:
-            C2 = D2 = H2 = W2 = oz = oy = ox = 0
-        if C1 + C2 != Ci:
-            raise ValueError(f"conv3d: input has {C1 + C2} channels, weight expects {Ci}")
+        src = CatView(x1, x2, (D, H, W), channels=Ci)
         if bias is not None:
             bias = _chk(bias, "conv3d bias", 1)
-        wt = _pack(w, 0)
         y = torch.empty((N, Co, D, H, W), dtype=torch.float32, device=x1.device)
-        vox = N * D * H * W
-        _timed_call(conv_fwd_kernel_name((D, H, W), Co, Ci, src=(x1, x2, ox)), 54.0 * Ci * Co * vox, 4.0 * (Ci + Co) * vox,
-                    "dram_conv3d_k3_fwd_ex", _p(x1), C1, _p(x2), C2, D2, H2, W2, oz, oy, ox, _p(wt), _p(bias),
-                    _p(y), Co, None, 0, 0, 0, 0, 0, 0, 0, N, D, H, W, _stream())
+        conv3d_k3_launch_fwd(src, _pack(w, 0), bias, y)
         ctx.save_for_backward(x1, x2, w)
         ctx.has_bias = bias is not None
-        ctx.geom = (C2, D2, H2, W2, oz, oy, ox)
         return y
 
     @staticmethod
@@ -225,41 +301,26 @@ class Conv3dK3Fn(Function):
     def backward(ctx, dy):
         x1, x2, w = ctx.saved_tensors
         dy = _chk(dy, "conv3d grad_output", 5)
-        N, C1, D, H, W = x1.shape
-        Co, Ci = w.shape[0], w.shape[1]
-        C2, D2, H2, W2, oz, oy, ox = ctx.geom
-        st = _stream()
+        N, Co, D, H, W = dy.shape
         dx1 = dx2 = dw = db = None
         need1 = ctx.needs_input_grad[0]
         need2 = x2 is not None and ctx.needs_input_grad[1]
         if need1 or need2:
-            wt = _pack(w, 1)   # filter of the transposed conv: [27][Co][Ci]
             dx1 = torch.empty_like(x1)
             if x2 is not None:
-                full = (D2, H2, W2) == (D, H, W)
-                dx2 = torch.empty_like(x2) if full else torch.zeros_like(x2)
-            vox = N * D * H * W
-            _timed_call(conv_fwd_kernel_name((D, H, W), Ci, Co, dst_split=(C1, C2, D2, H2, W2) if x2 is not None else None,
-                                             src=(dy, None, 0)), 54.0 * Ci * Co * vox, 4.0 * (Ci + Co) * vox,
-                        "dram_conv3d_k3_fwd_ex", _p(dy), Co, None, 0, 0, 0, 0, 0, 0, 0, _p(wt), None,
-                        _p(dx1), C1, _p(dx2), C2, D2, H2, W2, oz, oy, ox, N, D, H, W, st)
+                dx2 = conv3d_k3_dx2(x2, (D, H, W))
+            conv3d_k3_launch_bwd_data(dy, _pack(w, 1), dx1, dx2)   # filter of the transposed conv: [27][Co][Ci]
             if not need1:
                 dx1 = None
             if not need2:
                 dx2 = None
         if ctx.needs_input_grad[2]:
-            dw = torch.empty_like(w)
-            nbytes = _lib.lib.dram_conv3d_k3_wgrad_ws_bytes(N, Ci, Co, D, H, W)
-            ws = _ws(nbytes, dy.device)
-            vox = N * D * H * W
-            _timed_call(conv_wgrad_kernel_name(N, (D, H, W), Co, C1, C2), 54.0 * Ci * Co * vox, 4.0 * (Ci + Co) * vox,
-                        "dram_conv3d_k3_wgrad_ex", _p(x1), C1, _p(x2), C2, D2, H2, W2, oz, oy, ox, _p(dy), _p(dw),
-                        _p(ws), ws.numel(), N, Co, D, H, W, st)
+            dw = conv3d_k3_launch_wgrad(CatView(x1, x2, (D, H, W)), dy, w)
         if ctx.has_bias and ctx.needs_input_grad[3]:
             S = D * H * W
             db = torch.empty(Co, dtype=torch.float32, device=dy.device)
             ws = _ws(_lib.lib.dram_channel_sum_ws_bytes(N, Co, S), dy.device)
-            call("dram_channel_sum", _p(dy), _p(db), _p(ws), ws.numel(), N, Co, S, st)
+            call("dram_channel_sum", _p(dy), _p(db), _p(ws), ws.numel(), N, Co, S, _stream())
         return dx1, dx2, dw, db
 
 
@@ -453,6 +514,32 @@ def norm_act(x, gamma, beta, running_mean, running_var, kind, groups, use_batch_
     return NormActFn.apply(x, gamma, beta, running_mean, running_var, kind, groups, use_batch_stats, momentum, eps, relu)
 
 
+def sync_bn_combine(local, group, running_mean, running_var, momentum):
+    """Cross-rank combine of BatchNorm statistics.  `local`: this rank's fp64 [2C + 1] buffer, {mean, M2} per channel
+    (the layout of dram_bn_stats) and its element count per channel in the last slot.  All-gather over `group`, Chan's
+    parallel formula in fp64, running statistics (when given) from the GLOBAL moments.  Returns the global fp32 mean, the
+    biased fp32 variance and the total count."""
+    import torch.distributed as dist
+    C = (local.numel() - 1) // 2
+    world = dist.get_world_size(group)
+    allst = [torch.empty_like(local) for _ in range(world)]
+    dist.all_gather(allst, local, group=group)
+    allst = torch.stack(allst)                                   # [world, 2C+1]
+    cnt = allst[:, 2 * C].view(world, 1)
+    means, m2s = allst[:, 0:2 * C:2], allst[:, 1:2 * C:2]
+    total = cnt.sum()
+    mean = (means * cnt).sum(0) / total
+    m2 = (m2s + cnt * (means - mean) ** 2).sum(0)                # Chan's parallel combine
+    var = m2 / total                                             # biased
+    mean_f, var_f = mean.float(), var.float()
+    if running_mean is not None:
+        with torch.no_grad():
+            unb = (m2 / (total - 1.0)).float() if float(total) > 1.0 else var_f
+            running_mean.mul_(1.0 - momentum).add_(mean_f, alpha=momentum)
+            running_var.mul_(1.0 - momentum).add_(unb, alpha=momentum)
+    return mean_f, var_f, float(total)
+
+
 class SyncBatchNormFn(Function):
     """Training-mode BatchNorm whose statistics span all ranks of a process group (nn.SyncBatchNorm, the
     reference's normal_wrapper "sbn", parts.py:32-33, under data parallelism).  Two exchanges per layer and
@@ -462,7 +549,6 @@ class SyncBatchNormFn(Function):
 
     @staticmethod
     def forward(ctx, x, gamma, beta, running_mean, running_var, momentum, eps, relu, group):
-        import torch.distributed as dist
         x = _chk(x, "sync-bn input")
         N, C = x.shape[0], x.shape[1]
         S = x.numel() // (N * C)
@@ -472,22 +558,7 @@ class SyncBatchNormFn(Function):
         local = torch.empty(2 * C + 1, dtype=torch.float64, device=dev)
         call("dram_bn_stats", _p(x), _p(local), N, C, S, _p(ws), ws.numel(), st)
         local[2 * C] = float(N * S)
-        world = dist.get_world_size(group)
-        allst = [torch.empty_like(local) for _ in range(world)]
-        dist.all_gather(allst, local, group=group)
-        allst = torch.stack(allst)                                   # [world, 2C+1]
-        cnt = allst[:, 2 * C].view(world, 1)
-        means, m2s = allst[:, 0:2 * C:2], allst[:, 1:2 * C:2]
-        total = cnt.sum()
-        mean = (means * cnt).sum(0) / total
-        m2 = (m2s + cnt * (means - mean) ** 2).sum(0)                # Chan's parallel combine
-        var = m2 / total                                             # biased
-        mean_f, var_f = mean.float(), var.float()
-        if running_mean is not None:
-            with torch.no_grad():
-                unb = (m2 / (total - 1.0)).float() if float(total) > 1.0 else var_f
-                running_mean.mul_(1.0 - momentum).add_(mean_f, alpha=momentum)
-                running_var.mul_(1.0 - momentum).add_(unb, alpha=momentum)
+        mean_f, var_f, total = sync_bn_combine(local, group, running_mean, running_var, momentum)
         y = torch.empty_like(x)
         save_mean = torch.empty(C, dtype=torch.float32, device=dev)
         save_rstd = torch.empty(C, dtype=torch.float32, device=dev)
@@ -499,7 +570,7 @@ class SyncBatchNormFn(Function):
         call("dram_bn_fwd_eval", _p(x), _p(gamma), _p(beta), _p(mean_f), _p(var_f), _p(y), _p(save_mean), _p(save_rstd),
              _p(rowcoef), float(eps), int(relu), N, C, S, st)
         ctx.save_for_backward(x, gamma, save_mean, save_rstd, rowcoef)
-        ctx.cfg = (bool(relu), beta is not None, float(total), group)
+        ctx.cfg = (bool(relu), beta is not None, total, group)
         return y
 
     @staticmethod
@@ -653,6 +724,18 @@ def max_pool3d_2(x):
 TRI_BWD_WS_CAP = 1 << 30
 
 
+def trilinear_ac_backward(dy, in_shape):
+    """Gradient w.r.t. the [N, C, D, H, W] = `in_shape` input of the align_corners=True trilinear upsampling that gave dy."""
+    N, C, D, H, W = in_shape
+    Do, Ho, Wo = dy.shape[-3:]
+    dx = torch.empty(in_shape, dtype=torch.float32, device=dy.device)
+    full = _lib.lib.dram_upsample_trilinear_ac_bwd_ws_bytes(N, C, D, H, W, Do, Ho, Wo)
+    ws = _ws(min(full, TRI_BWD_WS_CAP), dy.device) if full else None
+    call("dram_upsample_trilinear_ac_bwd_ws", _p(dy), _p(dx), _p(ws), ws.numel() if ws is not None else 0,
+         N, C, D, H, W, Do, Ho, Wo, _stream())
+    return dx
+
+
 class TrilinearACFn(Function):
     """nn.Upsample(mode='trilinear', align_corners=True) (reference parts.py:149, models.py:146)."""
 
@@ -663,20 +746,13 @@ class TrilinearACFn(Function):
         Do, Ho, Wo = (int(s) for s in size)
         y = torch.empty((N, C, Do, Ho, Wo), dtype=torch.float32, device=x.device)
         call("dram_upsample_trilinear_ac_fwd", _p(x), _p(y), N, C, D, H, W, Do, Ho, Wo, _stream())
-        ctx.shapes = (N, C, D, H, W, Do, Ho, Wo)
+        ctx.in_shape = (N, C, D, H, W)
         return y
 
     @staticmethod
     @once_differentiable
     def backward(ctx, dy):
-        N, C, D, H, W, Do, Ho, Wo = ctx.shapes
-        dy = _chk(dy, "upsample grad_output", 5)
-        dx = torch.empty((N, C, D, H, W), dtype=torch.float32, device=dy.device)
-        full = _lib.lib.dram_upsample_trilinear_ac_bwd_ws_bytes(N, C, D, H, W, Do, Ho, Wo)
-        ws = _ws(min(full, TRI_BWD_WS_CAP), dy.device) if full else None
-        call("dram_upsample_trilinear_ac_bwd_ws", _p(dy), _p(dx), _p(ws), ws.numel() if ws is not None else 0,
-             N, C, D, H, W, Do, Ho, Wo, _stream())
-        return dx, None
+        return trilinear_ac_backward(_chk(dy, "upsample grad_output", 5), ctx.in_shape), None
 
 
 def upsample_trilinear_ac(x, size=None, scale_factor=None):

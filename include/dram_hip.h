@@ -50,28 +50,17 @@ int dram_abi_version(void);
  *   wz[9*4][Cin][Cout], the Winograd F(2,3)-along-z transformed filters ((ky,kx) column x 4 transformed taps).
  *   mode 0 (forward):  wt[t][ci][co] = w[co][ci][t]
  *   mode 1 (backward-data): wt[t][co][ci] = w[co][ci][26-t], i.e. the filter
- *          of the transposed convolution -- run dram_conv3d_k3_fwd on dy with
+ *          of the transposed convolution -- run dram_conv3d_k3_fwd_ex on dy with
  *          Cin/Cout swapped to obtain dx.
  * Which kernel runs is the library's choice (Winograd-z for Cin >= 8; exact fp32 arithmetic either way).
  */
 size_t dram_conv3d_k3_packed_floats(int Cout, int Cin);
 int dram_conv3d_k3_pack_weights(const float* w, float* wt, int Cout, int Cin, int mode, void* stream);
 
-/* y[N,Cout,D,H,W] = conv3d(x[N,Cin,D,H,W], w) (+ bias[Cout] when bias != NULL). */
-int dram_conv3d_k3_fwd(const float* x, const float* wt, const float* bias, float* y,
-                       int N, int Cin, int Cout, int D, int H, int W, void* stream);
-
-/* Same, with the input given as the channel concatenation of two tensors that
- * is never materialised: channels [0,C1) come from x1[N,C1,D,H,W]; channels
- * [C1,C1+C2) from x2[N,C2,D2,H2,W2] centre-cropped with start offsets
- * (oz,oy,ox) -- crop_concat_5d of parts.py:37-46 fused into the consumer conv
- * (parts.py:153-154). */
-int dram_conv3d_k3_fwd_cat(const float* x1, int C1, const float* x2, int C2, int D2, int H2, int W2,
-                           int oz, int oy, int ox, const float* wt, const float* bias, float* y,
-                           int N, int Cout, int D, int H, int W, void* stream);
-
-/* General form of the two calls above, also used for backward-data: the INPUT is the (virtual)
- * concatenation x1[N,C1,D,H,W] ++ crop(x2[N,C2,D2,H2,W2]) (x2 == NULL: x1 only) and the OUTPUT
+/* y = conv3d(x, w) (+ bias[Co1+Co2] when bias != NULL), forward and backward-data.  The INPUT is the channel
+ * concatenation of two tensors that is never materialised: channels [0,C1) come from x1[N,C1,D,H,W]; channels
+ * [C1,C1+C2) from x2[N,C2,D2,H2,W2] centre-cropped with start offsets (oz,oy,ox) -- crop_concat_5d of
+ * parts.py:37-46 fused into the consumer conv (parts.py:153-154); x2 == NULL: x1 only.  The OUTPUT
  * channels are split the same way over y1[N,Co1,D,H,W] and, when y2 != NULL, the crop window
  * (yoz,yoy,yox) of y2[N,Co2,yD2,yH2,yW2] (elements of y2 outside the window are not written:
  * zero them first when the window is smaller than y2).  wt is [27][C1+C2][Co1+Co2]. */
@@ -80,16 +69,9 @@ int dram_conv3d_k3_fwd_ex(const float* x1, int C1, const float* x2, int C2, int 
                           float* y1, int Co1, float* y2, int Co2, int yD2, int yH2, int yW2,
                           int yoz, int yoy, int yox, int N, int D, int H, int W, void* stream);
 
-/* dw[Cout,Cin,3,3,3] = sum over (n,z,y,x) of dy[n,co,z,y,x] * xpad[n,ci,z+dz,y+dy,x+dx].
- * Deterministic: per-block partial slabs in `ws`, summed in a fixed order. */
+/* Workspace of backward-weights (dram_conv3d_k3_wgrad_fused below): per-block partial slabs of dw, summed in a fixed
+ * order.  Cin = C1 + C2 of a virtual concatenation. */
 size_t dram_conv3d_k3_wgrad_ws_bytes(int N, int Cin, int Cout, int D, int H, int W);
-int dram_conv3d_k3_wgrad(const float* x, const float* dy, float* dw, void* ws, size_t ws_bytes,
-                         int N, int Cin, int Cout, int D, int H, int W, void* stream);
-
-/* Same with x given as a virtual concatenation (Cin = C1 + C2; size the workspace for that Cin). */
-int dram_conv3d_k3_wgrad_ex(const float* x1, int C1, const float* x2, int C2, int D2, int H2, int W2,
-                            int oz, int oy, int ox, const float* dy, float* dw, void* ws, size_t ws_bytes,
-                            int N, int Cout, int D, int H, int W, void* stream);
 
 /* dbias[Cout] = sum over (n,z,y,x) of dy (conv_bias=True when norm_method is None, models.py:78). */
 size_t dram_channel_sum_ws_bytes(int N, int C, int64_t S);
@@ -347,17 +329,12 @@ int dram_intreg_enc_loss_bwd(const float* dense, const float* lobes, const float
  * scale_mode: 0 none, 1 1/sqrt(#edges of the node), 2 1/0.01. */
 #define DRAM_PCM_RELU 1
 #define DRAM_PCM_L2NORM 2
-int dram_pcm_attention_fwd(const float* theta, const float* phi, const int* offsets, int E, int flags,
-                           int scale_mode, float* attn, int B, int F, int D, int H, int W, void* stream);
-/* ds: scratch [B,E,D,H,W] (receives d loss / d raw dot products); dtheta, dphi: [B,F,D,H,W]. */
-int dram_pcm_attention_bwd(const float* theta, const float* phi, const float* attn, const float* dattn,
-                           const int* offsets, int E, int flags, int scale_mode, float* ds, float* dtheta,
-                           float* dphi, int B, int F, int D, int H, int W, void* stream);
 /* The geo variants of merge_func (models.py:287-299: scaled_dot_product_geo, scaled_dot_product_geo_relu, att_is_all) add a
- * positional-encoding term to the appearance term.  On feature planes concatenated as [appearance ; positional] they are
- * the kernels above with the activation confined to the first F_relu planes:
+ * positional-encoding term to the appearance term.  On feature planes concatenated as [appearance ; positional] the
+ * activation is confined to the first F_relu planes:
  *     logit = act(sum_{f < F_relu} theta_f phi_f) + sum_{f >= F_relu} theta_f phi_f       (F_relu == F: the plain forms).
- * ds2: second scratch [B,E,D,H,W], needed when F_relu < F and DRAM_PCM_RELU is set (NULL otherwise). */
+ * ds: scratch [B,E,D,H,W] (receives d loss / d raw dot products); ds2: second scratch [B,E,D,H,W], needed when F_relu < F
+ * and DRAM_PCM_RELU is set (NULL otherwise); dtheta, dphi: [B,F,D,H,W]. */
 int dram_pcm_attention_split_fwd(const float* theta, const float* phi, const int* offsets, int E, int flags,
                                  int scale_mode, int F_relu, float* attn, int B, int F, int D, int H, int W, void* stream);
 int dram_pcm_attention_split_bwd(const float* theta, const float* phi, const float* attn, const float* dattn,
@@ -394,7 +371,7 @@ int dram_pcm_aggregate_bwd(const float* attn, const float* v, const float* dout,
 /* number of statistics partials per (n, c) row that dram_conv3d_k3_fwd_fused writes for this shape (0: bad shape) */
 int dram_conv3d_k3_stats_parts(int Cin, int Cout, int D, int H, int W);
 
-/* y = conv3d(act1(x1) ++ crop(act2(x2)), w) as dram_conv3d_k3_fwd_cat, each source lazily normalised (above), and --
+/* y = conv3d(act1(x1) ++ crop(act2(x2)), w) as dram_conv3d_k3_fwd_ex, each source lazily normalised (above), and --
  * when stats != NULL -- per (row of y, part) {mean, M2, count} of the outputs into stats[N*Cout][nparts][3]
  * (nparts = dram_conv3d_k3_stats_parts; two-pass moments per 64 outputs, no E[x^2]-E[x]^2).  stats and bias
  * exclude each other (a conv followed by a norm has no bias, models.py:78). */
@@ -406,7 +383,9 @@ int dram_conv3d_k3_fwd_fused(const float* x1, int C1, const float* coef1, int re
 /* 1 if backward-weights of this shape has the lazy-operand path (the Winograd kernel runs), else materialise x */
 int dram_conv3d_k3_wgrad_lazy_ok(int N, int C1, int C2, int Cout, int D, int H, int W);
 
-/* dram_conv3d_k3_wgrad_ex with lazily normalised x sources */
+/* Backward-weights: dw[Cout,C1+C2,3,3,3] = sum over (n,z,y,x) of dy[n,co,z,y,x] * xpad[n,ci,z+dz,y+dy,x+dx], x the virtual
+ * concatenation act1(x1) ++ crop(act2(x2)) of dram_conv3d_k3_fwd_fused (x2 == NULL: x1 only; coefK == NULL: a plain
+ * source).  Deterministic: per-block partial slabs in `ws` (dram_conv3d_k3_wgrad_ws_bytes), summed in a fixed order. */
 int dram_conv3d_k3_wgrad_fused(const float* x1, int C1, const float* coef1, int relu1, const float* x2, int C2,
                                const float* coef2, int relu2, int D2, int H2, int W2, int oz, int oy, int ox,
                                const float* dy, float* dw, void* ws, size_t ws_bytes, int N, int Cout, int D,
@@ -430,13 +409,11 @@ int dram_conv3d_k3_wgrad_fused(const float* x1, int C1, const float* coef1, int 
 #define DRAM_K3_KINDS 10
 
 /* forward / backward-data of [N,Cin,D,H,W] -> Cout channels; the destination may be split over two tensors as in
- * dram_conv3d_k3_fwd_ex (dstC2 = 0: one tensor); fused != 0: the dram_conv3d_k3_fwd_fused variant. */
-int dram_conv3d_k3_fwd_choice(int Cin, int Cout, int D, int H, int W, int dstC1, int dstC2, int dstD2, int dstH2,
-                              int dstW2, int fused, char* name, size_t cap);
-/* ... given what the SOURCE of the launch looks like as well: a cropped second source tensor [., srcC2, srcD2, srcH2, srcW2]
- * whose window starts at x offset srcox, and whether a source base pointer is off 16-byte alignment.  The (z,y) kernel
- * fetches rows as aligned 16-byte pieces: such a launch runs the z-only kernel on the same 32x4x2 boxes instead (the count of
- * statistics partials, dram_conv3d_k3_stats_parts, does not depend on it). */
+ * dram_conv3d_k3_fwd_ex (dstC2 = 0: one tensor); fused != 0: the dram_conv3d_k3_fwd_fused variant.  The SOURCE of the
+ * launch counts as well: a cropped second source tensor [., srcC2, srcD2, srcH2, srcW2] (srcC2 = 0: none) whose window
+ * starts at x offset srcox, and whether a source base pointer is off 16-byte alignment.  The (z,y) kernel fetches rows as
+ * aligned 16-byte pieces: such a launch runs the z-only kernel on the same 32x4x2 boxes instead (the count of statistics
+ * partials, dram_conv3d_k3_stats_parts, does not depend on it). */
 int dram_conv3d_k3_fwd_choice_src(int Cin, int Cout, int D, int H, int W, int dstC1, int dstC2, int dstD2, int dstH2,
                                   int dstW2, int fused, int srcC2, int srcD2, int srcH2, int srcW2, int srcox,
                                   int src_misaligned, char* name, size_t cap);

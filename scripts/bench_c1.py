@@ -10,8 +10,6 @@ def child():
     from dram_amd import functional as HF
     from dram_amd import _lib
     dev = torch.device("cuda:0")
-    st = torch.cuda.current_stream().cuda_stream
-    p = lambda t: None if t is None else t.data_ptr()
     for N, Co, S in ((64, 32, 128), (10, 32, 80), (16, 40, 64)):
         x = torch.rand(N, 1, S, S, S, device=dev)
         w = torch.randn(Co, 1, 3, 3, 3, device=dev) / 27 ** 0.5
@@ -22,8 +20,8 @@ def child():
         name = HF.conv_fwd_kernel_name((S, S, S), Co, 1, fused=True)
         out = []
         for stt in (None, parts):
-            fn = lambda: _lib.call("dram_conv3d_k3_fwd_fused", p(x), 1, None, 0, None, 0, None, 0, 0, 0, 0, 0, 0, 0, p(wt), None,
-                                   p(y), p(stt), nparts if stt is not None else 0, N, Co, S, S, S, st)
+            fn = lambda: HF.conv3d_k3_launch_fwd(HF.CatView(x, None, (S, S, S)), wt, None, y, (None, 0, None, 0), stt,
+                                                 nparts if stt is not None else 0)
             fn(); torch.cuda.synchronize()
             e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
             e0.record()

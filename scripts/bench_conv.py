@@ -5,7 +5,6 @@ import torch
 ROOT = os.path.abspath(os.path.join(os.path.dirname(__file__), ".."))
 sys.path[:0] = [ROOT, os.path.join(ROOT, "bodyct-dram_amd")]
 from dram_amd import functional as HF
-from dram_amd import _lib
 
 ap = argparse.ArgumentParser()
 ap.add_argument("--shapes", default="4,64,64,128;4,192,64,128;8,384,128,64;16,768,256,32;16,256,512,16")
@@ -13,7 +12,6 @@ ap.add_argument("--iters", type=int, default=5)
 ap.add_argument("--only", default="both", choices=["both", "fwd", "wgrad"])
 args = ap.parse_args()
 dev = torch.device("cuda:0")
-st = torch.cuda.current_stream().cuda_stream
 
 
 def timeit(fn, iters):
@@ -33,14 +31,11 @@ for spec in args.shapes.split(";"):
     w = torch.randn(Co, Ci, 3, 3, 3, device=dev) / (Ci * 27) ** 0.5
     wt = HF._pack(w, 0)
     y = torch.empty(N, Co, S, S, S, device=dev)
-    dw = torch.empty_like(w)
-    nb = _lib.lib.dram_conv3d_k3_wgrad_ws_bytes(N, Ci, Co, S, S, S)
-    ws = torch.empty(nb, dtype=torch.uint8, device=dev)
+    src = HF.CatView(x, None, (S, S, S))
     flops = 54.0 * Ci * Co * N * S ** 3
-    p = lambda t: t.data_ptr()
     t_f = t_w = float("nan")
     if args.only in ("both", "fwd"):
-        t_f = timeit(lambda: _lib.call("dram_conv3d_k3_fwd", p(x), p(wt), None, p(y), N, Ci, Co, S, S, S, st), args.iters)
+        t_f = timeit(lambda: HF.conv3d_k3_launch_fwd(src, wt, None, y), args.iters)
     if args.only in ("both", "wgrad"):
-        t_w = timeit(lambda: _lib.call("dram_conv3d_k3_wgrad", p(x), p(dy), p(dw), p(ws), nb, N, Ci, Co, S, S, S, st), args.iters)
+        t_w = timeit(lambda: HF.conv3d_k3_launch_wgrad(src, dy, w), args.iters)
     print(f"[{N},{Ci}->{Co},{S}^3] fwd {t_f:8.3f} ms {flops / t_f / 1e9:7.1f} TF/s | wgrad {t_w:8.3f} ms {flops / t_w / 1e9:7.1f} TF/s", flush=True)

@@ -12,8 +12,6 @@ ap.add_argument("--shapes", default="4,64,64,128;4,32,64,128;4,192,64,128;8,384,
 ap.add_argument("--iters", type=int, default=5)
 args = ap.parse_args()
 dev = torch.device("cuda:0")
-st = torch.cuda.current_stream().cuda_stream
-p = lambda t: None if t is None else t.data_ptr()
 
 
 def timeit(fn, iters):
@@ -40,16 +38,12 @@ def cat_case(spec):
     coef2 = torch.rand(N * C2 * 2, device=dev) + 0.5
     wt = HF._pack(w, 0)
     y = torch.empty(N, Co, S, S, S, device=dev)
-    dw = torch.empty_like(w)
-    nb = _lib.lib.dram_conv3d_k3_wgrad_ws_bytes(N, Ci, Co, S, S, S)
-    ws = torch.empty(nb, dtype=torch.uint8, device=dev)
     nparts = _lib.lib.dram_conv3d_k3_stats_parts(Ci, Co, S, S, S)
     parts = torch.empty(N * Co * nparts * 3, device=dev)
     flops = 54.0 * Ci * Co * N * S ** 3
-    f = lambda c2: (lambda: _lib.call("dram_conv3d_k3_fwd_fused", p(x1), C1, None, 0, p(x2), C2, p(c2), 1, S, S, S, 0, 0, 0, p(wt), None,
-                                      p(y), p(parts), nparts, N, Co, S, S, S, st))
-    g = lambda c2: (lambda: _lib.call("dram_conv3d_k3_wgrad_fused", p(x1), C1, None, 0, p(x2), C2, p(c2), 1, S, S, S, 0, 0, 0, p(dy), p(dw),
-                                      p(ws), nb, N, Co, S, S, S, st))
+    src = HF.CatView(x1, x2, (S, S, S))
+    f = lambda c2: (lambda: HF.conv3d_k3_launch_fwd(src, wt, None, y, (None, 0, c2, 1), parts, nparts))
+    g = lambda c2: (lambda: HF.conv3d_k3_launch_wgrad(src, dy, w, (None, 0, c2, 1)))
     t = {k: timeit(fn, args.iters) for k, fn in [("f", f(None)), ("fl", f(coef2)), ("g", g(None)), ("gl", g(coef2))]}
     tf = lambda ms: flops / ms / 1e9
     print(f"[{N},{C1}+{C2}->{Co},{S}^3] fwd + stats, both plain {t['f']:7.3f} ms {tf(t['f']):6.1f} | x2 lazy {t['fl']:7.3f} ({100 * (t['fl'] / t['f'] - 1):+.1f}%)"
@@ -67,20 +61,16 @@ for spec in args.shapes.split(";"):
     coef = torch.rand(N * Ci * 2, device=dev) + 0.5
     wt = HF._pack(w, 0)
     y = torch.empty(N, Co, S, S, S, device=dev)
-    dw = torch.empty_like(w)
-    nb = _lib.lib.dram_conv3d_k3_wgrad_ws_bytes(N, Ci, Co, S, S, S)
-    ws = torch.empty(nb, dtype=torch.uint8, device=dev)
     nparts = _lib.lib.dram_conv3d_k3_stats_parts(Ci, Co, S, S, S)
     parts = torch.empty(N * Co * nparts * 3, device=dev)
     flops = 54.0 * Ci * Co * N * S ** 3
+    src = HF.CatView(x, None, (S, S, S))
 
     def fwd(cf, stt):
-        return lambda: _lib.call("dram_conv3d_k3_fwd_fused", p(x), Ci, p(cf), 1, None, 0, None, 0, 0, 0, 0, 0, 0, 0, p(wt), None,
-                                 p(y), p(stt), nparts if stt is not None else 0, N, Co, S, S, S, st)
+        return lambda: HF.conv3d_k3_launch_fwd(src, wt, None, y, (cf, 1, None, 0), stt, nparts if stt is not None else 0)
 
     def wg(cf):
-        return lambda: _lib.call("dram_conv3d_k3_wgrad_fused", p(x), Ci, p(cf), 1, None, 0, None, 0, 0, 0, 0, 0, 0, 0, p(dy), p(dw),
-                                 p(ws), nb, N, Co, S, S, S, st)
+        return lambda: HF.conv3d_k3_launch_wgrad(src, dy, w, (cf, 1, None, 0))
     t = {k: timeit(f, args.iters) for k, f in [("plain", fwd(None, None)), ("stats", fwd(None, parts)), ("lazy", fwd(coef, None)),
                                                  ("both", fwd(coef, parts)), ("wg", wg(None)), ("wg_lazy", wg(coef))]}
     tf = lambda ms: flops / ms / 1e9

@@ -14,8 +14,6 @@ ap.add_argument("--relu2", type=int, default=0)
 ap.add_argument("--shapes", default="4,32,64,128;4,64,64,128;4,192,64,128;8,64,128,64;8,384,128,64;8,128,128,64;16,128,256,32;16,768,256,32;16,256,256,32")
 args = ap.parse_args()
 dev = torch.device("cuda:0")
-st = torch.cuda.current_stream().cuda_stream
-p = lambda t: None if t is None else t.data_ptr()
 
 
 def run(x, wt, Co, coef=None, stats=False, x2=None, crop=(0, 0, 0), coef2=None, bias=None, wzy=True):
@@ -31,9 +29,9 @@ def run(x, wt, Co, coef=None, stats=False, x2=None, crop=(0, 0, 0), coef2=None, 
     if stats:
         nparts = _lib.lib.dram_conv3d_k3_stats_parts(C1 + C2, Co, D, H, W)
         parts = torch.full((N * Co * nparts * 3,), float("nan"), device=dev)
-    d2 = (0, 0, 0) if x2 is None else tuple(x2.shape[2:])
-    _lib.call("dram_conv3d_k3_fwd_fused", p(x), C1, p(coef), 1, p(x2), C2, p(coef2), 1, d2[0], d2[1], d2[2], crop[0], crop[1], crop[2],
-              p(wt), p(bias), p(y), p(parts), nparts, N, Co, D, H, W, st)
+    src = HF.CatView(x, x2, (D, H, W))
+    assert src.off == tuple(crop), (src.off, crop)
+    HF.conv3d_k3_launch_fwd(src, wt, bias, y, (coef, 1, coef2, 1), parts, nparts)
     torch.cuda.synchronize()
     os.environ.pop("DRAM_CONV_NO_WZY", None)
     return y, parts, nparts
@@ -124,8 +122,8 @@ for spec in args.shapes.split(";"):
     flops = 54.0 * Ci * Co * N * S ** 3
 
     def fwd(cf, stt):
-        return lambda: _lib.call("dram_conv3d_k3_fwd_fused", p(x), Ci, p(cf), 1, None, 0, None, args.relu2, 0, 0, 0, 0, 0, 0, p(wt), None,
-                                 p(y), p(stt), nparts if stt is not None else 0, N, Co, S, S, S, st)
+        return lambda: HF.conv3d_k3_launch_fwd(HF.CatView(x, None, (S, S, S)), wt, None, y, (cf, 1, None, args.relu2), stt,
+                                               nparts if stt is not None else 0)
     out = []
     for mode in ("wzy", "wz"):
         if mode == "wz":

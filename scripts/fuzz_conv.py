@@ -18,8 +18,6 @@ ap.add_argument("--wzy", action="store_true", help="bias the shapes towards the 
 args = ap.parse_args()
 rng = np.random.default_rng(args.seed)
 dev = torch.device("cuda:0")
-st = torch.cuda.current_stream().cuda_stream
-p = lambda t: None if t is None else t.data_ptr()
 names = ["fwd_direct", "fwd_wz", "fwd_wzy", "wg_direct", "wg_vec", "wg_wz", "wg_wz_lazy", "wg_c1", "fwd_c1", "wg_wzy"]
 seen = np.zeros(len(names), dtype=np.int64)
 
@@ -64,7 +62,6 @@ for case in range(args.cases):
     x1 = torch.randn(N, C1, D, H, W, generator=g).to(dev)
     x2 = torch.randn(N, C2, D + ext[0], H + ext[1], W + ext[2], generator=g).to(dev) if C2 else None
     crop = tuple(int(np.ceil(e / 2)) for e in ext)
-    d2 = tuple(x2.shape[2:]) if C2 else (0, 0, 0)
     w = (torch.randn(Co, Ci, 3, 3, 3, generator=g) / (Ci * 27) ** 0.5).to(dev)
     dy = torch.randn(N, Co, D, H, W, generator=g).to(dev)
     cf1 = (torch.rand(N * C1 * 2, generator=g) + 0.3).to(dev) if lazy1 else None
@@ -83,8 +80,9 @@ for case in range(args.cases):
         y = torch.full((N, Co, D, H, W), float("nan"), device=dev)
         nparts = _lib.lib.dram_conv3d_k3_stats_parts(Ci, Co, D, H, W) if stats else 0
         parts = torch.full((N * Co * max(nparts, 1) * 3,), float("nan"), device=dev) if stats else None
-        _lib.call("dram_conv3d_k3_fwd_fused", p(x1), C1, p(cf1), 1, p(x2), C2, p(cf2), 1, *d2, *crop, p(wt), None, p(y), p(parts), nparts,
-                  N, Co, D, H, W, st)
+        src = HF.CatView(x1, x2, (D, H, W), channels=Ci)
+        assert src.off == crop, (src.off, crop)
+        HF.conv3d_k3_launch_fwd(src, wt, None, y, (cf1, 1, cf2, 1), parts, nparts)
         e = rel(y, yr)
         assert e <= 1e-4, ("forward", e)
         if stats:
@@ -97,8 +95,7 @@ for case in range(args.cases):
         wtb = HF._pack(w, 1)
         dx1 = torch.full((N, C1, D, H, W), float("nan"), device=dev)
         dx2 = torch.zeros_like(x2) if C2 else None
-        _lib.call("dram_conv3d_k3_fwd_ex", p(dy), Co, None, 0, 0, 0, 0, 0, 0, 0, p(wtb), None, p(dx1), C1, p(dx2), C2, *d2, *crop,
-                  N, D, H, W, st)
+        HF.conv3d_k3_launch_bwd_data(dy, wtb, dx1, dx2)
         gx = xr.grad
         if not (lazy1 or lazy2):        # d(activated input): comparable as it is only for plain sources
             assert rel(dx1, gx[:, :C1]) <= 1e-4, "backward-data (first source)"
@@ -115,10 +112,7 @@ for case in range(args.cases):
             a1 = act(x1, cf1).float(); c1_ = None
             if C2:
                 a2 = act(x2, cf2).float(); c2_ = None
-        dw = torch.full_like(w, float("nan"))
-        ws = torch.empty(max(16, _lib.lib.dram_conv3d_k3_wgrad_ws_bytes(N, Ci, Co, D, H, W)), dtype=torch.uint8, device=dev)
-        _lib.call("dram_conv3d_k3_wgrad_fused", p(a1), C1, p(c1_), 1, p(a2), C2, p(c2_), 1, *d2, *crop, p(dy), p(dw), p(ws), ws.numel(),
-                  N, Co, D, H, W, st)
+        dw = HF.conv3d_k3_launch_wgrad(HF.CatView(a1, a2, (D, H, W)), dy, w, (c1_, 1, c2_, 1))
         e = rel(dw, wr.grad)
         assert e <= 1e-4, ("backward-weights", e)
         torch.cuda.synchronize()

@@ -131,7 +131,7 @@ def test_conv3d_k3_virtual_concat(shape):
 
 def test_conv3d_k3_wzy_kernel_is_selected():
     """The shapes above that are meant for the Winograd-(z,y) kernel really launch it: the library is asked what it
-    chooses (dram_conv3d_k3_fwd_choice, the same fwd_choice the launch goes through; there is no host-side copy of the
+    chooses (dram_conv3d_k3_fwd_choice_src, the same fwd_choice the launch goes through; there is no host-side copy of the
     rule), and its launch counters are read around a real call."""
     from dram_amd import functional as HF
     assert HF.conv_fwd_kernel_name((11, 8, 32), 128, 64) == "conv3d_k3_fwd_wzy_kernel"

@@ -27,7 +27,7 @@ def test_library_exports_every_declared_symbol():
     lib = ctypes.CDLL(os.path.join(ROOT, "bodyct-dram_amd", "libdram_hip.so"))
     for name in decl:
         assert hasattr(lib, name), f"libdram_hip.so does not export {name}"
-    assert lib.dram_abi_version() == 1
+    assert lib.dram_abi_version() == 2
 
 
 def test_ctypes_signatures_match_header():
@@ -41,14 +41,15 @@ def test_ctypes_signatures_match_header():
 def test_argument_errors_are_reported_without_a_gpu():
     from dram_amd import _lib
     with pytest.raises(_lib.DramHipError, match="null pointer"):
-        _lib.call("dram_conv3d_k3_fwd", None, None, None, None, 1, 1, 1, 4, 4, 4, None)
+        _lib.call("dram_conv3d_k3_fwd_ex", None, 1, None, 0, 0, 0, 0, 0, 0, 0, None, None, None, 1, None, 0, 0, 0, 0, 0, 0, 0,
+                  1, 4, 4, 4, None)
     with pytest.raises(_lib.DramHipError, match="not divisible"):
         _lib.call("dram_norm_fwd_train", 16, None, None, 16, 16, 16, 16, None, None, 0.1, 1e-5, 1, 3, 1, 2, 4, 8, 16, 1 << 20, None)
     assert _lib.lib.dram_conv3d_k3_wgrad_ws_bytes(4, 64, 64, 128, 128, 128) > 0
 
 
 def test_kernel_choice_queries():
-    """dram_conv3d_k3_fwd_choice / dram_conv3d_k3_wgrad_choice are pure functions of the shape (no GPU needed): the
+    """dram_conv3d_k3_fwd_choice_src / dram_conv3d_k3_wgrad_choice are pure functions of the shape (no GPU needed): the
     benchmark's layers (DC3D st_dram_ref at 128^3) get the kernels DESIGN.md names, and the two rules the old host-side
     copy of use_wzy had dropped are there."""
     from dram_amd import functional as HF
