@@ -51,6 +51,10 @@ inline size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
 inline int cdiv(int a, int b) { return (a + b - 1) / b; }
 inline int64_t cdiv64(int64_t a, int64_t b) { return (a + b - 1) / b; }
 
+// Output channels that the 1x1x1 conv kernels (head.hip) handle per pass; the head policy of the norm backward (norm.hip) forms
+// that conv's input gradient itself for up to one pass of them.
+constexpr int K1_MAXCO = 8;
+
 // 64-lane wavefront reductions (gfx950: wave = 64)
 __device__ __forceinline__ float wave_sum(float v) {
 #pragma unroll

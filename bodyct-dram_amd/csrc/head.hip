@@ -11,8 +11,6 @@
 
 namespace dram {
 
-constexpr int MAXCO = 8;  // output channels handled per pass
-
 // `coef` (optional): x holds a RAW conv output and the operand is act(a*x + b) per (n,c) row, ReLU if `relu`
 // ("normalise + ReLU on load", see csrc/conv_args.h ConvArgs::coef1; same fmaf / fmaxf as everywhere)
 template <bool VEC>
@@ -24,9 +22,9 @@ __global__ __launch_bounds__(256) void conv1x1_fwd_kernel(const float* __restric
     const int64_t e = ((int64_t)blockIdx.x * 256 + threadIdx.x) * (VEC ? 4 : 1);
     if (e >= S) return;
     const float* xp = x + (int64_t)n * Cin * S + e;
-    float acc[MAXCO][4];
+    float acc[K1_MAXCO][4];
 #pragma unroll
-    for (int o = 0; o < MAXCO; ++o) {
+    for (int o = 0; o < K1_MAXCO; ++o) {
         const float b = (bias && o < nco) ? bias[co0 + o] : 0.f;
         acc[o][0] = acc[o][1] = acc[o][2] = acc[o][3] = b;
     }
@@ -45,7 +43,7 @@ __global__ __launch_bounds__(256) void conv1x1_fwd_kernel(const float* __restric
             for (int u = 0; u < 4; ++u) xv[u] = fmaxf(fmaf(ca, xv[u], cb), lo);
         }
 #pragma unroll
-        for (int o = 0; o < MAXCO; ++o) {
+        for (int o = 0; o < K1_MAXCO; ++o) {
             if (o < nco) {
                 const float wv = w[(size_t)(co0 + o) * Cin + c];
 #pragma unroll
@@ -54,7 +52,7 @@ __global__ __launch_bounds__(256) void conv1x1_fwd_kernel(const float* __restric
         }
     }
 #pragma unroll
-    for (int o = 0; o < MAXCO; ++o) {
+    for (int o = 0; o < K1_MAXCO; ++o) {
         if (o < nco) {
             float* yp = y + ((int64_t)n * Cout + co0 + o) * S + e;
             if (VEC) *reinterpret_cast<float4*>(yp) = make_float4(acc[o][0], acc[o][1], acc[o][2], acc[o][3]);
@@ -63,7 +61,7 @@ __global__ __launch_bounds__(256) void conv1x1_fwd_kernel(const float* __restric
     }
 }
 
-// dx[n,c,s] = sum_o w[o,c] * dy[n,o,s]   (Cout <= MAXCO per pass; accumulate over passes)
+// dx[n,c,s] = sum_o w[o,c] * dy[n,o,s]   (Cout <= K1_MAXCO per pass; accumulate over passes)
 template <bool VEC>
 __global__ __launch_bounds__(256) void conv1x1_dgrad_kernel(const float* __restrict__ dy, const float* __restrict__ w,
                                                             float* __restrict__ dx, int Cin, int Cout, int co0,
@@ -71,9 +69,9 @@ __global__ __launch_bounds__(256) void conv1x1_dgrad_kernel(const float* __restr
     const int n = blockIdx.y;
     const int64_t e = ((int64_t)blockIdx.x * 256 + threadIdx.x) * (VEC ? 4 : 1);
     if (e >= S) return;
-    float g[MAXCO][4];
+    float g[K1_MAXCO][4];
 #pragma unroll
-    for (int o = 0; o < MAXCO; ++o) {
+    for (int o = 0; o < K1_MAXCO; ++o) {
         g[o][0] = g[o][1] = g[o][2] = g[o][3] = 0.f;
         if (o < nco) {
             const float* p = dy + ((int64_t)n * Cout + co0 + o) * S + e;
@@ -88,7 +86,7 @@ __global__ __launch_bounds__(256) void conv1x1_dgrad_kernel(const float* __restr
     for (int c = 0; c < Cin; ++c) {
         float r[4] = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll
-        for (int o = 0; o < MAXCO; ++o) {
+        for (int o = 0; o < K1_MAXCO; ++o) {
             if (o < nco) {
                 const float wv = w[(size_t)(co0 + o) * Cin + c];
 #pragma unroll
@@ -401,8 +399,8 @@ static int conv1x1_fwd_run(const char* who, const float* x, const float* coef, i
     DRAM_REQUIRE(N > 0 && N <= 65535 && Cin > 0 && Cout > 0 && S > 0, "%s: bad dimensions", who);
     hipStream_t st = (hipStream_t)stream;
     const bool vec = vec4_ok(x, y, S);
-    for (int co0 = 0; co0 < Cout; co0 += MAXCO) {
-        const int nco = (Cout - co0) < MAXCO ? (Cout - co0) : MAXCO;
+    for (int co0 = 0; co0 < Cout; co0 += K1_MAXCO) {
+        const int nco = (Cout - co0) < K1_MAXCO ? (Cout - co0) : K1_MAXCO;
         if (vec) {
             dim3 grid((unsigned)cdiv64(S / 4, 256), N);
             hipLaunchKernelGGL(conv1x1_fwd_kernel<true>, grid, dim3(256), 0, st, x, w, bias, y, Cin, Cout, co0, nco, S, coef, relu);
@@ -438,8 +436,8 @@ static int conv1x1_bwd_run(const float* dy, const float* x, const float* coef, i
     hipStream_t st = (hipStream_t)stream;
     if (dx) {
         const bool vec = vec4_ok(dy, dx, S);
-        for (int co0 = 0; co0 < Cout; co0 += MAXCO) {
-            const int nco = (Cout - co0) < MAXCO ? (Cout - co0) : MAXCO;
+        for (int co0 = 0; co0 < Cout; co0 += K1_MAXCO) {
+            const int nco = (Cout - co0) < K1_MAXCO ? (Cout - co0) : K1_MAXCO;
             if (vec) {
                 dim3 grid((unsigned)cdiv64(S / 4, 256), N);
                 hipLaunchKernelGGL(conv1x1_dgrad_kernel<true>, grid, dim3(256), 0, st, dy, w, dx, Cin, Cout, co0, nco, S, co0 > 0);

@@ -20,7 +20,8 @@
 // Numerics: chunk statistics are computed two-pass from registers (mean, then sum of
 // squared deviations), and combined with Chan's formula in fp64 -> no E[x^2]-E[x]^2
 // cancellation even at N*S = 1.3e8 elements per channel (SURVEY "BN at scale").
-#include "common.h"
+#include "conv_args.h"
+#include "conv_device.h"
 
 namespace dram {
 
@@ -244,14 +245,160 @@ __global__ __launch_bounds__(256) void row_affine_act_kernel(const float* __rest
     }
 }
 
+// ---- where the backward row kernels take the incoming gradient d from (template parameter SRC) -------------------------------
+// A policy is a by-value kernel argument; at(dy, row, S, beg) gives the view of one (row, chunk) work item, whose quads()
+// loads the NQ float4 of a thread (all loads first, from clamped offsets `ec`, as everywhere in this file) and whose one()
+// loads a single element of the scalar kernels.  Only these loads differ between the policies: mask, sums and
+// p*d + q*x + r are the kernels' own.  Both kernels read a thread's d before the apply kernel stores its dx over it.
+
+// plain: d = dy[row][e]
+struct GradPlain {
+    struct At {
+        const float* pd;
+        __device__ __forceinline__ void quads(float4 (&dq)[NQ], const int (&ec)[NQ]) const {
+#pragma unroll
+            for (int q = 0; q < NQ; ++q) dq[q] = ld4(pd + ec[q]);
+        }
+        __device__ __forceinline__ float one(int e) const { return pd[e]; }
+    };
+    __device__ __forceinline__ At at(const float* dy, int64_t row, int64_t S, int64_t beg) const {
+        return At{dy + row * S + beg};
+    }
+};
+
+// head: the gradient of a 1x1x1 conv's input, formed from that conv's output gradient g[N][Cout][S] (passed as `dy`) and its
+// weight w[Cout][C]: d = fmaf(w[o][c], g[n][o][e], d) over o ascending from d = 0 -- conv1x1_dgrad_kernel's chain (head.hip),
+// so d has the bits of the dx that kernel would have written.  Cout <= K1_MAXCO, that kernel's single-pass group.
+// g is read by all C rows of a sample: default-policy loads, so that the cache serves the repeats.
+struct GradHead {
+    const float* w;
+    int Cout, C;
+    struct At {
+        const float* pg;    // g[n][0] + beg
+        const float* pw;    // w[0] + c
+        int64_t S;
+        int Cout, C;
+        __device__ __forceinline__ void quads(float4 (&dq)[NQ], const int (&ec)[NQ]) const {
+#pragma unroll
+            for (int q = 0; q < NQ; ++q) dq[q] = make_float4(0.f, 0.f, 0.f, 0.f);
+            for (int o = 0; o < Cout; ++o) {
+                const float wv = pw[(size_t)o * C];
+                float4 t[NQ];
+#pragma unroll
+                for (int q = 0; q < NQ; ++q) t[q] = *reinterpret_cast<const float4*>(pg + o * S + ec[q]);
+#pragma unroll
+                for (int q = 0; q < NQ; ++q) {
+                    dq[q].x = fmaf(wv, t[q].x, dq[q].x); dq[q].y = fmaf(wv, t[q].y, dq[q].y);
+                    dq[q].z = fmaf(wv, t[q].z, dq[q].z); dq[q].w = fmaf(wv, t[q].w, dq[q].w);
+                }
+            }
+        }
+        __device__ __forceinline__ float one(int e) const {
+            float d = 0.f;
+            for (int o = 0; o < Cout; ++o) d = fmaf(pw[(size_t)o * C], pg[o * S + e], d);
+            return d;
+        }
+    };
+    __device__ __forceinline__ At at(const float* g, int64_t row, int64_t S, int64_t beg) const {
+        const int64_t n = row / C;
+        return At{g + n * Cout * S + beg, w + (row - n * C), S, Cout, C};
+    }
+};
+
+// pool-add: d = dy + routed, the 2x2x2 max-pool's backward (resample.hip maxpool2_bwd*_kernel with `accumulate`) added while
+// loading: routed = gp[pooled cell] where idx[pooled cell] is the voxel's code ((z&1)<<2)|((y&1)<<1)|(x&1), else 0 -- 0 as
+// well beyond the floor-cropped extent, where the sum still runs (0 + dy, as that kernel has it).
+// An index inside the row is split into (z, y, x) by multiply + shift (conv_device.h fast_div).  Whether the row kernels are
+// the 16-byte ones is decided as for the plain policy (so the sums run in the same order as on the materialised gradient);
+// whether a float4 of dy takes its two pooled cells with one 2-byte and one 8-byte load (`quad`: W % 4 == 0 keeps it inside
+// one x row, gp / idx aligned as maxpool_bwd_run requires) or element by element is the policy's own matter.
+struct PoolGeom {
+    int H, W, Do, Ho, Wo, quad;
+    unsigned xq_m, xq_s;    // division by W/4 (quad only)
+    unsigned xe_m, xe_s;    // division by W
+    unsigned y_m, y_s;      // division by H
+};
+struct GradPoolAdd {
+    const float* gp;        // [rows][Do][Ho][Wo]
+    const uint8_t* idx;
+    PoolGeom geom;
+    struct At {
+        const float* pd;
+        const float* pg;        // this row's plane of gp / idx
+        const uint8_t* pi;
+        unsigned beg;           // first element of the chunk inside the row
+        PoolGeom s;
+        // u = t * xext + xi, t = zi * H + yi; returns the pooled-plane offset of the cell row of (zi, yi), -1: none
+        __device__ __forceinline__ int cell(unsigned u, unsigned xext, unsigned xm, unsigned xs, unsigned& xi, unsigned& yi,
+                                            unsigned& zi) const {
+            const unsigned t = fast_div(u, xm, xs);
+            xi = u - t * xext;
+            zi = fast_div(t, s.y_m, s.y_s);
+            yi = t - zi * (unsigned)s.H;
+            const int yo = (int)(yi >> 1), zo = (int)(zi >> 1);
+            return (yo < s.Ho && zo < s.Do) ? (zo * s.Ho + yo) * s.Wo : -1;
+        }
+        // the routed gradient of element e of the row
+        __device__ __forceinline__ float routed(unsigned e) const {
+            unsigned xi, yi, zi;
+            const int o = cell(e, (unsigned)s.W, s.xe_m, s.xe_s, xi, yi, zi);
+            float r = 0.f;
+            if (o >= 0 && (int)(xi >> 1) < s.Wo) {
+                const int oc = o + (int)(xi >> 1);
+                if (pi[oc] == (((zi & 1) << 2) | ((yi & 1) << 1) | (xi & 1))) r = pg[oc];
+            }
+            return r;
+        }
+        __device__ __forceinline__ void quads(float4 (&dq)[NQ], const int (&ec)[NQ]) const {
+            if (!s.quad) {      // (odd widths, unaligned gp / idx: not a path of the full-resolution stages)
+#pragma unroll
+                for (int q = 0; q < NQ; ++q) dq[q] = ld4(pd + ec[q]);
+#pragma unroll
+                for (int q = 0; q < NQ; ++q) {
+                    const unsigned e = beg + (unsigned)ec[q];
+                    dq[q].x = routed(e) + dq[q].x; dq[q].y = routed(e + 1) + dq[q].y;
+                    dq[q].z = routed(e + 2) + dq[q].z; dq[q].w = routed(e + 3) + dq[q].w;
+                }
+                return;
+            }
+            unsigned short two[NQ];
+            float2 d2[NQ];
+            int base[NQ];
+#pragma unroll
+            for (int q = 0; q < NQ; ++q) {
+                unsigned x4, yi, zi;
+                const int o = cell((beg + (unsigned)ec[q]) >> 2, (unsigned)s.W >> 2, s.xq_m, s.xq_s, x4, yi, zi);
+                base[q] = o < 0 ? -1 : (int)(((zi & 1) << 2) | ((yi & 1) << 1));
+                const int oc = o < 0 ? 0 : o + 2 * (int)x4;       // even: 2- / 8-byte aligned; 0 is always a valid cell
+                dq[q] = ld4(pd + ec[q]);
+                two[q] = *reinterpret_cast<const unsigned short*>(pi + oc);
+                d2[q] = *reinterpret_cast<const float2*>(pg + oc);
+            }
+#pragma unroll
+            for (int q = 0; q < NQ; ++q) {
+                const int i0 = two[q] & 0xff, i1 = two[q] >> 8;   // (base -1, and -1 | 1, match no code)
+                dq[q].x = (i0 == base[q] ? d2[q].x : 0.f) + dq[q].x;
+                dq[q].y = (i0 == (base[q] | 1) ? d2[q].x : 0.f) + dq[q].y;
+                dq[q].z = (i1 == base[q] ? d2[q].y : 0.f) + dq[q].z;
+                dq[q].w = (i1 == (base[q] | 1) ? d2[q].y : 0.f) + dq[q].w;
+            }
+        }
+        __device__ __forceinline__ float one(int e) const { return routed(beg + (unsigned)e) + pd[e]; }
+    };
+    __device__ __forceinline__ At at(const float* dy, int64_t row, int64_t S, int64_t beg) const {
+        const int64_t po = row * ((int64_t)geom.Do * geom.Ho * geom.Wo);
+        return At{dy + row * S + beg, gp + po, idx + po, (unsigned)beg, geom};
+    }
+};
+
 // per (row, chunk): {sum dy', sum dy' * xhat}, xhat = (x - mean)*rstd of the row's statistic
-template <bool VEC>
+template <bool VEC, class SRC>
 __global__ __launch_bounds__(256) void row_bwd_reduce_kernel(const float* __restrict__ dy, const float* __restrict__ x,
                                                              const float* __restrict__ rowcoef,
                                                              const float* __restrict__ save_mean,
                                                              const float* __restrict__ save_rstd,
                                                              float* __restrict__ part, int64_t S, int nchunks,
-                                                             int kind, int C, int G, int relu) {
+                                                             int kind, int C, int G, int relu, SRC src) {
     __shared__ float red[4];
     const int64_t row = blockIdx.y;
     const int chunk = blockIdx.x;
@@ -262,17 +409,18 @@ __global__ __launch_bounds__(256) void row_bwd_reduce_kernel(const float* __rest
     const float mean = save_mean[stat], rstd = save_rstd[stat];
     const float a = rowcoef[2 * row], b = rowcoef[2 * row + 1];
     const float* px = x + row * S + beg;
-    const float* pd = dy + row * S + beg;
+    const typename SRC::At sd = src.at(dy, row, S, beg);
     float s1 = 0.f, s2 = 0.f;
     if (VEC) {
         float4 xq[NQ], dq[NQ];    // loads first, unconditional (see row_moments_kernel)
+        int ec[NQ];
 #pragma unroll
         for (int q = 0; q < NQ; ++q) {
             const int e = (q * 256 + threadIdx.x) * 4;
-            const int ec = e < len ? e : 0;
-            xq[q] = ld4(px + ec);
-            dq[q] = ld4(pd + ec);
+            ec[q] = e < len ? e : 0;
+            xq[q] = ld4(px + ec[q]);
         }
+        sd.quads(dq, ec);
 #pragma unroll
         for (int q = 0; q < NQ; ++q) {
             const int e = (q * 256 + threadIdx.x) * 4;
@@ -289,7 +437,7 @@ __global__ __launch_bounds__(256) void row_bwd_reduce_kernel(const float* __rest
         }
     } else {
         for (int e = threadIdx.x; e < len; e += 256) {
-            float d = pd[e];
+            float d = sd.one(e);
             const float xv = px[e];
             if (relu && !(fmaf(a, xv, b) > 0.f)) d = 0.f;
             s1 += d;
@@ -387,28 +535,29 @@ __global__ void gn_bwd_finalize_params_kernel(const double* __restrict__ rowsum,
 }
 
 // dx = p*dy' + q*x + r
-template <bool VEC>
+template <bool VEC, class SRC>
 __global__ __launch_bounds__(256) void row_bwd_apply_kernel(const float* __restrict__ dy, const float* __restrict__ x,
                                                             const float* __restrict__ rowcoef,
                                                             const float* __restrict__ pqr, float* __restrict__ dx,
-                                                            int64_t S, int relu) {
+                                                            int64_t S, int relu, SRC src) {
     const int64_t row = blockIdx.y;
     const int64_t beg = (int64_t)blockIdx.x * CHUNK;
     const int len = (int)((S - beg) < CHUNK ? (S - beg) : CHUNK);
     const float a = rowcoef[2 * row], b = rowcoef[2 * row + 1];
     const float p = pqr[3 * row], qq = pqr[3 * row + 1], r = pqr[3 * row + 2];
     const float* px = x + row * S + beg;
-    const float* pd = dy + row * S + beg;
+    const typename SRC::At sd = src.at(dy, row, S, beg);
     float* o = dx + row * S + beg;
     if (VEC) {
         float4 xq[NQ], dq[NQ];    // loads first, unconditional (see row_moments_kernel)
+        int ec[NQ];
 #pragma unroll
         for (int q = 0; q < NQ; ++q) {
             const int e = (q * 256 + threadIdx.x) * 4;
-            const int ec = e < len ? e : 0;
-            xq[q] = ld4(px + ec);
-            dq[q] = ld4(pd + ec);
+            ec[q] = e < len ? e : 0;
+            xq[q] = ld4(px + ec[q]);
         }
+        sd.quads(dq, ec);
 #pragma unroll
         for (int q = 0; q < NQ; ++q) {
             const int e = (q * 256 + threadIdx.x) * 4;
@@ -423,7 +572,7 @@ __global__ __launch_bounds__(256) void row_bwd_apply_kernel(const float* __restr
         }
     } else {
         for (int e = threadIdx.x; e < len; e += 256) {
-            float d = pd[e];
+            float d = sd.one(e);
             const float xv = px[e];
             if (relu && !(fmaf(a, xv, b) > 0.f)) d = 0.f;
             o[e] = fmaf(p, d, fmaf(qq, xv, r));
@@ -726,17 +875,21 @@ extern "C" int dram_bn_fwd_eval(const float* x, const float* gamma, const float*
     return check_launch("bn_fwd_eval");
 }
 
-extern "C" int dram_norm_bwd(const float* dy, const float* x, const float* gamma, const float* save_mean,
-                             const float* save_rstd, const float* rowcoef, float* dx, float* dgamma, float* dbeta,
-                             int kind, int G, int relu, int batch_stats, int N, int C, int64_t S, void* ws,
-                             size_t ws_bytes, void* stream) {
-    DRAM_REQUIRE(dy && x && save_mean && save_rstd && rowcoef && dx && ws, "norm_bwd: null pointer");
-    int rc = check_norm("norm_bwd", kind, G, N, C, S);
+// The one launch sequence of the norm backward: reduce, row sums, finalize, apply.  `src` says where the row kernels take the
+// incoming gradient from (GradPlain / GradHead / GradPoolAdd; `dy` is what that policy's at() expects), `src_vec` whether its
+// operands allow the 16-byte kernels.
+template <class SRC>
+static int norm_bwd_run(const char* who, const SRC& src, bool src_vec, const float* dy, const float* x, const float* gamma,
+                        const float* save_mean, const float* save_rstd, const float* rowcoef, float* dx, float* dgamma,
+                        float* dbeta, int kind, int G, int relu, int batch_stats, int N, int C, int64_t S, void* ws,
+                        size_t ws_bytes, void* stream) {
+    DRAM_REQUIRE(dy && x && save_mean && save_rstd && rowcoef && dx && ws, "%s: null pointer", who);
+    int rc = check_norm(who, kind, G, N, C, S);
     if (rc) return rc;
-    DRAM_REQUIRE((int64_t)N * C <= 65535, "norm_bwd: N*C > 65535 rows not supported");
-    DRAM_REQUIRE(kind == DRAM_NORM_BATCH || batch_stats, "norm_bwd: GroupNorm always uses batch statistics");
+    DRAM_REQUIRE((int64_t)N * C <= 65535, "%s: N*C > 65535 rows not supported", who);
+    DRAM_REQUIRE(kind == DRAM_NORM_BATCH || batch_stats, "%s: GroupNorm always uses batch statistics", who);
     if (ws_bytes < dram_norm_ws_bytes(N, C, S)) {
-        set_error("norm_bwd: workspace too small");
+        set_error("%s: workspace too small", who);
         return DRAM_EWS;
     }
     hipStream_t st = (hipStream_t)stream;
@@ -749,13 +902,13 @@ extern "C" int dram_norm_bwd(const float* dy, const float* x, const float* gamma
     w += align_up((size_t)rows * 2 * sizeof(double), 256);
     float* pqr = (float*)w;
     const int Gk = kind == DRAM_NORM_BATCH ? 1 : G;
-    const bool vec = vec_ok(x, S) && vec_ok(dy, S) && vec_ok(dx, S);
+    const bool vec = src_vec && vec_ok(x, S) && vec_ok(dx, S);
     if (vec)
-        hipLaunchKernelGGL(row_bwd_reduce_kernel<true>, row_grid(nch, rows), dim3(256), 0, st, dy, x, rowcoef,
-                           save_mean, save_rstd, part, S, nch, kind, C, Gk, relu);
+        hipLaunchKernelGGL((row_bwd_reduce_kernel<true, SRC>), row_grid(nch, rows), dim3(256), 0, st, dy, x, rowcoef,
+                           save_mean, save_rstd, part, S, nch, kind, C, Gk, relu, src);
     else
-        hipLaunchKernelGGL(row_bwd_reduce_kernel<false>, row_grid(nch, rows), dim3(256), 0, st, dy, x, rowcoef,
-                           save_mean, save_rstd, part, S, nch, kind, C, Gk, relu);
+        hipLaunchKernelGGL((row_bwd_reduce_kernel<false, SRC>), row_grid(nch, rows), dim3(256), 0, st, dy, x, rowcoef,
+                           save_mean, save_rstd, part, S, nch, kind, C, Gk, relu, src);
     hipLaunchKernelGGL(row_sum_chunks_kernel, dim3((unsigned)cdiv64(rows, 256)), dim3(256), 0, st, part, rowsum,
                        (int)rows, nch);
     if (kind == DRAM_NORM_BATCH) {
@@ -769,10 +922,50 @@ extern "C" int dram_norm_bwd(const float* dy, const float* x, const float* gamma
                                dbeta, N, C);
     }
     if (vec)
-        hipLaunchKernelGGL(row_bwd_apply_kernel<true>, row_grid(nch, rows), dim3(256), 0, st, dy, x, rowcoef, pqr, dx, S, relu);
+        hipLaunchKernelGGL((row_bwd_apply_kernel<true, SRC>), row_grid(nch, rows), dim3(256), 0, st, dy, x, rowcoef, pqr, dx, S,
+                           relu, src);
     else
-        hipLaunchKernelGGL(row_bwd_apply_kernel<false>, row_grid(nch, rows), dim3(256), 0, st, dy, x, rowcoef, pqr, dx, S, relu);
-    return check_launch("norm_bwd");
+        hipLaunchKernelGGL((row_bwd_apply_kernel<false, SRC>), row_grid(nch, rows), dim3(256), 0, st, dy, x, rowcoef, pqr, dx, S,
+                           relu, src);
+    return check_launch(who);
+}
+
+extern "C" int dram_norm_bwd(const float* dy, const float* x, const float* gamma, const float* save_mean,
+                             const float* save_rstd, const float* rowcoef, float* dx, float* dgamma, float* dbeta,
+                             int kind, int G, int relu, int batch_stats, int N, int C, int64_t S, void* ws,
+                             size_t ws_bytes, void* stream) {
+    return norm_bwd_run("norm_bwd", GradPlain{}, vec_ok(dy, S), dy, x, gamma, save_mean, save_rstd, rowcoef, dx, dgamma, dbeta,
+                        kind, G, relu, batch_stats, N, C, S, ws, ws_bytes, stream);
+}
+
+extern "C" int dram_norm_bwd_head_ok(int Cout) { return Cout >= 1 && Cout <= K1_MAXCO; }
+
+extern "C" int dram_norm_bwd_head(const float* g, const float* w, int Cout, const float* x, const float* gamma,
+                                  const float* save_mean, const float* save_rstd, const float* rowcoef, float* dx,
+                                  float* dgamma, float* dbeta, int kind, int G, int relu, int batch_stats, int N, int C,
+                                  int64_t S, void* ws, size_t ws_bytes, void* stream) {
+    DRAM_REQUIRE(g && w, "norm_bwd_head: null pointer");
+    DRAM_REQUIRE(dram_norm_bwd_head_ok(Cout), "norm_bwd_head: Cout=%d outside 1..%d: materialise the gradient "
+                 "(dram_conv3d_k1_bwd) and call dram_norm_bwd", Cout, K1_MAXCO);
+    return norm_bwd_run("norm_bwd_head", GradHead{w, Cout, C}, vec_ok(g, S), g, x, gamma, save_mean, save_rstd, rowcoef, dx,
+                        dgamma, dbeta, kind, G, relu, batch_stats, N, C, S, ws, ws_bytes, stream);
+}
+
+extern "C" int dram_norm_bwd_pool_add(const float* dy, const float* gp, const uint8_t* idx, int D, int H, int W,
+                                      const float* x, const float* gamma, const float* save_mean, const float* save_rstd,
+                                      const float* rowcoef, float* dx, float* dgamma, float* dbeta, int kind, int G, int relu,
+                                      int batch_stats, int N, int C, void* ws, size_t ws_bytes, void* stream) {
+    DRAM_REQUIRE(gp && idx, "norm_bwd_pool_add: null pointer");
+    DRAM_REQUIRE(D >= 2 && H >= 2 && W >= 2, "norm_bwd_pool_add: spatial size below the 2x2x2 window");
+    const int64_t S = (int64_t)D * H * W;
+    DRAM_REQUIRE(S < (1LL << 31), "norm_bwd_pool_add: plane of 2^31 or more elements");
+    const int quad = W % 4 == 0 && vec_ok(dy, S) && ((((uintptr_t)gp) & 7) | (((uintptr_t)idx) & 1)) == 0;
+    GradPoolAdd src{gp, idx, {H, W, D / 2, H / 2, W / 2, quad, 0, 0, 0, 0, 0, 0}};
+    if (quad) fast_div_prepare((unsigned)W / 4, src.geom.xq_m, src.geom.xq_s);
+    fast_div_prepare((unsigned)W, src.geom.xe_m, src.geom.xe_s);
+    fast_div_prepare((unsigned)H, src.geom.y_m, src.geom.y_s);
+    return norm_bwd_run("norm_bwd_pool_add", src, vec_ok(dy, S), dy, x, gamma, save_mean, save_rstd, rowcoef, dx, dgamma, dbeta,
+                        kind, G, relu, batch_stats, N, C, S, ws, ws_bytes, stream);
 }
 
 extern "C" int dram_bn_stats(const float* x, double* mean_m2, int N, int C, int64_t S, void* ws, size_t ws_bytes,
@@ -812,11 +1005,11 @@ extern "C" int dram_bn_bwd_sums(const float* dy, const float* x, const float* sa
     float* part = (float*)ws;
     double* rowsum = (double*)((char*)ws + align_up((size_t)rows * nch * 2 * sizeof(float), 256));
     if (vec_ok(x, S) && vec_ok(dy, S))
-        hipLaunchKernelGGL(row_bwd_reduce_kernel<true>, row_grid(nch, rows), dim3(256), 0, st, dy, x, rowcoef, save_mean,
-                           save_rstd, part, S, nch, DRAM_NORM_BATCH, C, 1, relu);
+        hipLaunchKernelGGL((row_bwd_reduce_kernel<true, GradPlain>), row_grid(nch, rows), dim3(256), 0, st, dy, x, rowcoef, save_mean,
+                           save_rstd, part, S, nch, DRAM_NORM_BATCH, C, 1, relu, GradPlain{});
     else
-        hipLaunchKernelGGL(row_bwd_reduce_kernel<false>, row_grid(nch, rows), dim3(256), 0, st, dy, x, rowcoef, save_mean,
-                           save_rstd, part, S, nch, DRAM_NORM_BATCH, C, 1, relu);
+        hipLaunchKernelGGL((row_bwd_reduce_kernel<false, GradPlain>), row_grid(nch, rows), dim3(256), 0, st, dy, x, rowcoef, save_mean,
+                           save_rstd, part, S, nch, DRAM_NORM_BATCH, C, 1, relu, GradPlain{});
     hipLaunchKernelGGL(row_sum_chunks_kernel, dim3((unsigned)cdiv64(rows, 256)), dim3(256), 0, st, part, rowsum, (int)rows, nch);
     hipLaunchKernelGGL(bn_bwd_sums_kernel, dim3(cdiv(C, 64)), dim3(64), 0, st, rowsum, sums, N, C);
     return check_launch("bn_bwd_sums");
@@ -842,9 +1035,11 @@ extern "C" int dram_bn_bwd_apply_sums(const float* dy, const float* x, const flo
     hipLaunchKernelGGL(bn_pqr_from_sums_kernel, dim3(cdiv(C, 64)), dim3(64), 0, st, sums, count, gamma, save_mean, save_rstd,
                        pqr, N, C);
     if (vec_ok(x, S) && vec_ok(dy, S) && vec_ok(dx, S))
-        hipLaunchKernelGGL(row_bwd_apply_kernel<true>, row_grid(nch, rows), dim3(256), 0, st, dy, x, rowcoef, pqr, dx, S, relu);
+        hipLaunchKernelGGL((row_bwd_apply_kernel<true, GradPlain>), row_grid(nch, rows), dim3(256), 0, st, dy, x, rowcoef, pqr, dx, S,
+                           relu, GradPlain{});
     else
-        hipLaunchKernelGGL(row_bwd_apply_kernel<false>, row_grid(nch, rows), dim3(256), 0, st, dy, x, rowcoef, pqr, dx, S, relu);
+        hipLaunchKernelGGL((row_bwd_apply_kernel<false, GradPlain>), row_grid(nch, rows), dim3(256), 0, st, dy, x, rowcoef, pqr, dx, S,
+                           relu, GradPlain{});
     return check_launch("bn_bwd_apply_sums");
 }
 

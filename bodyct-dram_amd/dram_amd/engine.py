@@ -445,6 +445,11 @@ def backward(model, record, gout, need_dx, sink=None):
                 dict.__setitem__(self, p, g)
     grads = _Grads()
     gact = {}           # id(Lazy) -> dense gradient w.r.t. the ACTIVATED tensor (accumulated over its consumers)
+    # id(Lazy) -> a part of that gradient which is not written out: the producing stage's norm backward forms it while it
+    # loads (dram_norm_bwd_head / _pool_add), with the bits the materialising kernel would have stored.
+    #   ("head", g, w):    the 1x1x1 head's input gradient, sum_o w[o,c] * g[n,o,:] -- the whole gradient of the tensor
+    #   ("pool", gp, idx): the max-pool's routed gradient, to be added to the skip gradient in gact
+    pending = {}
     g = HF._chk(gout, "DC3D grad_output", 5)
     root = record[0][1]
     for item in reversed(record):
@@ -458,7 +463,8 @@ def backward(model, record, gout, need_dx, sink=None):
             top = model.top_layer
             N, C, D, H, W = lz.raw.shape
             Co, S = top.weight.shape[0], D * H * W
-            dxa = torch.empty_like(lz.raw)
+            from_source = bool(_lib.lib.dram_norm_bwd_head_ok(Co))      # (more output channels: written out, as before)
+            dxa = None if from_source else torch.empty_like(lz.raw)
             dw = torch.empty_like(top.weight)
             db = torch.empty(Co, dtype=torch.float32, device=g.device) if top.bias is not None else None
             ws = _ws(_lib.lib.dram_conv3d_k1_bwd_ws_bytes(N, C, Co, S), g.device)
@@ -467,11 +473,22 @@ def backward(model, record, gout, need_dx, sink=None):
             grads[top.weight] = dw
             if db is not None:
                 grads[top.bias] = db
-            gact[id(lz)] = dxa
+            if from_source:
+                pending[id(lz)] = ("head", g, top.weight)
+            else:
+                gact[id(lz)] = dxa
             g = None
         elif tag == "conv":
             s = item[1]
-            g = gact.pop(id(s.out))
+            src = pending.pop(id(s.out), None)
+            if src is not None and s.sync is not None:      # "sbn" runs its two-call backward on a gradient that is there
+                _write_pending(gact, s.out, src, st)
+                src = None
+            head = src is not None and src[0] == "head"
+            if head and id(s.out) in gact:
+                raise RuntimeError("fused backward: the head's input has a second consumer")
+            # head: dx is the first tensor of this size in backward -- it takes the place of the head's dx
+            g = torch.empty_like(s.y) if head else gact.pop(id(s.out))
             N, Co, D, H, W = s.y.shape
             S = D * H * W
             w = s.conv.weight
@@ -495,9 +512,19 @@ def backward(model, record, gout, need_dx, sink=None):
                 dist.all_reduce(sums, op=dist.ReduceOp.SUM, group=group)
                 call("dram_bn_bwd_apply_sums", _p(g), _p(s.y), _p(gamma), _p(s.mean), _p(s.rstd), _p(s.coef), _p(sums),
                      float(total), _p(g), 1, N, Co, S, _p(ws), ws.numel(), st)
-            else:
+            elif src is None:
                 call("dram_norm_bwd", _p(g), _p(s.y), _p(gamma), _p(s.mean), _p(s.rstd), _p(s.coef), _p(g), _p(dgamma), _p(dbeta),
                      s.kind, s.groups, 1, int(s.batch_stats), N, Co, S, _p(ws), ws.numel(), st)
+            elif head:
+                _, gh, wh = src
+                call("dram_norm_bwd_head", _p(gh), _p(wh), wh.shape[0], _p(s.y), _p(gamma), _p(s.mean), _p(s.rstd), _p(s.coef),
+                     _p(g), _p(dgamma), _p(dbeta), s.kind, s.groups, 1, int(s.batch_stats), N, Co, S, _p(ws), ws.numel(), st)
+            else:
+                _, gp, idx = src
+                call("dram_norm_bwd_pool_add", _p(g), _p(gp), _p(idx), D, H, W, _p(s.y), _p(gamma), _p(s.mean), _p(s.rstd),
+                     _p(s.coef), _p(g), _p(dgamma), _p(dbeta), s.kind, s.groups, 1, int(s.batch_stats), N, Co, _p(ws), ws.numel(),
+                     st)
+            src = None
             if dgamma is not None:
                 grads[gamma] = dgamma
             if dbeta is not None:
@@ -570,15 +597,31 @@ def backward(model, record, gout, need_dx, sink=None):
             if gp is None:
                 continue
             N, C, D, H, W = lz.raw.shape
-            if id(lz) in gact:      # the skip branch's gradient is already there: add the pooled branch's onto it
-                call("dram_maxpool3d_2_bwd_acc", _p(gp), _p(idx), _p(gact[id(lz)]), N, C, D, H, W, st)
+            if id(lz) in gact:      # the skip branch's gradient is already there: the stage's norm backward adds this one to it
+                pending[id(lz)] = ("pool", gp, idx)
             else:
                 dxp = torch.empty_like(lz.raw)
                 call("dram_maxpool3d_2_bwd", _p(gp), _p(idx), _p(dxp), N, C, D, H, W, st)
                 gact[id(lz)] = dxp
         else:   # pragma: no cover
             raise RuntimeError(f"fused backward: unknown tape entry {tag!r}")
+    if pending:     # pragma: no cover
+        raise RuntimeError("fused backward: a gradient source was left without the stage that consumes it")
     return grads, gact.pop(id(root), None)
+
+
+def _write_pending(gact, lz, src, st):
+    """The materialised form of a pending gradient source of `lz` (see backward), into gact."""
+    N, C, D, H, W = lz.raw.shape
+    if src[0] == "head":
+        _, g, w = src
+        dxa = torch.empty_like(lz.raw)
+        call("dram_conv3d_k1_bwd_lazy", _p(g), _p(lz.raw), _p(lz.coef), int(lz.relu), _p(w), _p(dxa), None, None, None, 0,
+             N, C, w.shape[0], D * H * W, st)
+        gact[id(lz)] = dxa
+    else:
+        _, gp, idx = src
+        call("dram_maxpool3d_2_bwd_acc", _p(gp), _p(idx), _p(gact[id(lz)]), N, C, D, H, W, st)
 
 
 def _accumulate(gact, key, t):

@@ -139,6 +139,28 @@ int dram_norm_bwd(const float* dy, const float* x, const float* gamma,
                   int kind, int G, int relu, int batch_stats, int N, int C, int64_t S,
                   void* ws, size_t ws_bytes, void* stream);
 
+/* dram_norm_bwd with the incoming gradient taken from where it comes from instead of from a tensor someone wrote first.
+ * Same workspace, same kernels but for the load of dy, same dgamma / dbeta; dx, bit for bit, what dram_norm_bwd gives on
+ * the materialised gradient (the 16-byte row kernels are chosen as dram_norm_bwd chooses them, with g resp. dy in the place of
+ * its dy, so the sums run in the same order; _head: for a g that is 16-byte aligned when dx is).
+ *   _head:     dy[n,c,e] = sum_o w[o,c] * g[n,o,e], the input gradient of a 1x1x1 conv (dram_conv3d_k1_bwd's dx, formed
+ *              with that kernel's fmaf chain) with weight w[Cout,C] and output gradient g[N,Cout,S].  dx must not alias g.
+ *              Cout within dram_norm_bwd_head_ok (one pass of the 1x1x1 kernels); otherwise DRAM_EINVAL, nothing launched.
+ *   _pool_add: dy + dram_maxpool3d_2_bwd(gp, idx), the sum dram_maxpool3d_2_bwd_acc leaves in dy; S = D*H*W,
+ *              gp / idx [N,C,D/2,H/2,W/2].  dx may alias dy. */
+int dram_norm_bwd_head_ok(int Cout);
+int dram_norm_bwd_head(const float* g, const float* w, int Cout, const float* x, const float* gamma,
+                       const float* save_mean, const float* save_rstd, const float* rowcoef,
+                       float* dx, float* dgamma, float* dbeta,
+                       int kind, int G, int relu, int batch_stats, int N, int C, int64_t S,
+                       void* ws, size_t ws_bytes, void* stream);
+int dram_norm_bwd_pool_add(const float* dy, const float* gp, const uint8_t* idx, int D, int H, int W,
+                           const float* x, const float* gamma,
+                           const float* save_mean, const float* save_rstd, const float* rowcoef,
+                           float* dx, float* dgamma, float* dbeta,
+                           int kind, int G, int relu, int batch_stats, int N, int C,
+                           void* ws, size_t ws_bytes, void* stream);
+
 /* ---- cross-rank BatchNorm (normal_wrapper "sbn" = nn.SyncBatchNorm, dram/parts.py:32-33, under data parallelism) ----
  * The statistics and the backward sums leave the device between two stages so that the host can exchange them
  * (all-gather / all-reduce over RCCL); every stage is the same row kernels as above.
