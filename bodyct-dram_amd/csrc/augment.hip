@@ -1,7 +1,8 @@
 // Training-time augmentation pool on a whole device batch (reference: LesionSegChunkTrain.ensemble_scan_augmentation,
 // dram/job_runner.py:548-581, over dram/data_transforms.py GaussianBlur / RandomMaskOut / RandomFlip / RandomRotate90 /
 // GaussianAddictive).  One launch transforms every sample of [N, D, H, W] with that sample's own parameters, read from
-// small device tables; nothing synchronises with the host.
+// small device tables; nothing synchronises with the host.  Beside the pool's five: IntensityInverse, GammaTransform,
+// ContrastStretchingTransform and ContrastJitter of the same file, point-wise over rows (a sample, or one z-slice of it).
 //
 // Every table carries a per-sample flag:  1 = transform,  0 = pass through (copied when y != x),  < 0 = skip the sample
 // (y is not written: the ensemble driver keeps samples in different buffers and moves only the ones a launch is for).
@@ -389,6 +390,148 @@ void launch_permflip(const void* x, void* y, const int* perm, const int* flip, c
                        D, H, W);
 }
 
+// ---------------------------------------------------------------- per-row mean
+// Rows of L floats (a sample, or one z-slice of it).  A block walks its row with a grid stride, every lane with four loads in
+// flight and an fp64 sum per load slot; the block's fp64 partial goes to the workspace and one thread per row adds the row's
+// partials in index order.  Which element goes to which lane depends on L alone (not on the row's alignment or on how many rows
+// the launch has), so a row gives the same bits wherever it stands.  No atomics.
+constexpr int MEAN_BLOCK_ELEMS = 4096;   // elements of a row per block and step: 16 per lane
+constexpr int MEAN_MAX_BLOCKS = 128;     // blocks per row
+
+inline int mean_blocks(int64_t L) {
+    const int64_t b = cdiv64(L, MEAN_BLOCK_ELEMS);
+    return (int)(b < 1 ? 1 : (b > MEAN_MAX_BLOCKS ? MEAN_MAX_BLOCKS : b));
+}
+
+__global__ __launch_bounds__(256) void row_sum_kernel(const float* __restrict__ x, double* __restrict__ part,
+                                                      const int* __restrict__ flag, int64_t L, int nblk) {
+    __shared__ double red[4];
+    const int r = blockIdx.y;
+    if (flag && flag[r] != 1) return;
+    const float* row = x + (int64_t)r * L;
+    const int64_t stride = (int64_t)nblk * 256;
+    double a[4] = {0.0, 0.0, 0.0, 0.0};
+    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < L; i += 4 * stride) {
+#pragma unroll
+        for (int u = 0; u < 4; ++u) {
+            const int64_t j = i + u * stride;
+            if (j < L) a[u] += (double)row[j];
+        }
+    }
+    const double s = wave_sum_d((a[0] + a[1]) + (a[2] + a[3]));
+    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = s;
+    __syncthreads();
+    if (threadIdx.x == 0) part[(size_t)r * nblk + blockIdx.x] = (red[0] + red[1]) + (red[2] + red[3]);
+}
+
+// numpy's mean of a float32 array is a float32: the fp64 quotient is rounded once.
+__global__ void row_mean_kernel(const double* __restrict__ part, float* __restrict__ mean, const int* __restrict__ flag, int R,
+                                int64_t L, int nblk) {
+    const int r = blockIdx.x * blockDim.x + threadIdx.x;
+    if (r >= R || (flag && flag[r] != 1)) return;
+    double s = 0.0;
+    for (int b = 0; b < nblk; ++b) s += part[(size_t)r * nblk + b];
+    mean[r] = (float)(s / (double)L);
+}
+
+// ---------------------------------------------------------------- point-wise intensity maps
+// IntensityInverse, GammaTransform, ContrastStretchingTransform and ContrastJitter (data_transforms.py:213-248, 279-362, 538-579)
+// with the reference's roundings: numpy keeps a float32 array float32 against Python scalars, so every step is one fp32
+// operation and the drawn factors enter rounded to fp32.  `**` is powf.
+struct MapCoef {
+    float lo, hi, range, denom, rmin, mean, a, b;
+    int keep;
+};
+
+template <int MODE>
+__device__ __forceinline__ MapCoef map_coef(const float* __restrict__ mm, const float* __restrict__ mean,
+                                            const float* __restrict__ par, int keep, int r) {
+    MapCoef c = {};
+    c.keep = keep;
+    if (mm) {
+        c.lo = mm[2 * r];
+        c.hi = mm[2 * r + 1];
+    }
+    c.range = __fsub_rn(c.hi, c.lo);
+    c.denom = __fadd_rn(c.range, 1e-7f);
+    if (MODE == DRAM_AUG_MAP_INVERSE)   // (1 - rescaled).min(): the map decreases, so it is the value at x = max
+        c.rmin = __fsub_rn(1.f, __fdiv_rn(__fsub_rn(c.hi, c.lo), c.denom));
+    if (MODE == DRAM_AUG_MAP_JITTER) c.mean = mean[r];
+    if (MODE != DRAM_AUG_MAP_INVERSE) {
+        c.a = par[2 * r];
+        c.b = par[2 * r + 1];
+    }
+    return c;
+}
+
+template <int MODE>
+__device__ __forceinline__ float map_one(float v, const MapCoef& c) {
+    if (MODE == DRAM_AUG_MAP_JITTER) {
+        float t = __fadd_rn(__fmul_rn(__fsub_rn(v, c.mean), c.a), c.mean);
+        if (c.keep) {
+            t = t < c.lo ? c.lo : t;
+            t = t > c.hi ? c.hi : t;
+        }
+        return t;
+    }
+    const float r = __fdiv_rn(__fsub_rn(v, c.lo), c.denom);
+    float d;
+    if (MODE == DRAM_AUG_MAP_INVERSE) d = __fsub_rn(__fsub_rn(1.f, r), c.rmin);
+    else if (MODE == DRAM_AUG_MAP_GAMMA) d = powf(r, c.a);
+    else d = __fdiv_rn(1.f, __fadd_rn(1.f, powf(__fdiv_rn(c.b, __fadd_rn(r, 1e-7f)), c.a)));
+    return __fadd_rn(__fmul_rn(d, c.range), c.lo);
+}
+
+// Grid (blocks, row).  VEC: both bases are 16-byte aligned, so a row that starts `r * L` floats in is 16-byte aligned after
+// `head` elements, at the same place in x and in y; lanes 0 .. nvec-1 move one float4 each and lane nvec moves the head and the
+// tail (six elements at most).  !VEC: four scalar elements per lane.  Every element is read and written by one lane: y may be x.
+template <int MODE, bool VEC>
+__global__ __launch_bounds__(256) void intensity_map_kernel(const float* x, float* y, const float* __restrict__ mm,
+                                                            const float* __restrict__ mean, const float* __restrict__ par,
+                                                            const int* __restrict__ flag, int keep, int64_t L) {
+    const int r = blockIdx.y;
+    const int f = flag[r];
+    if (f < 0 || (f == 0 && x == y)) return;
+    const int64_t off = (int64_t)r * L;
+    const float* xs = x + off;
+    float* ys = y + off;
+    int64_t head = VEC ? ((4 - (off & 3)) & 3) : 0;
+    if (head > L) head = L;
+    const int64_t nvec = VEC ? ((L - head) >> 2) : 0;
+    const int64_t g = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (VEC ? g > nvec : g * 4 >= L) return;
+    MapCoef c = {};
+    if (f == 1) c = map_coef<MODE>(mm, mean, par, keep, r);
+    if (g < nvec) {
+        float4 q = *reinterpret_cast<const float4*>(xs + head + 4 * g);
+        if (f == 1) {
+            q.x = map_one<MODE>(q.x, c);
+            q.y = map_one<MODE>(q.y, c);
+            q.z = map_one<MODE>(q.z, c);
+            q.w = map_one<MODE>(q.w, c);
+        }
+        *reinterpret_cast<float4*>(ys + head + 4 * g) = q;
+        return;
+    }
+    if (VEC) {
+        for (int64_t i = 0; i < head; ++i) ys[i] = f == 1 ? map_one<MODE>(xs[i], c) : xs[i];
+        for (int64_t i = head + 4 * nvec; i < L; ++i) ys[i] = f == 1 ? map_one<MODE>(xs[i], c) : xs[i];
+    } else {
+        const int64_t end = g * 4 + 4 < L ? g * 4 + 4 : L;
+        for (int64_t i = g * 4; i < end; ++i) ys[i] = f == 1 ? map_one<MODE>(xs[i], c) : xs[i];
+    }
+}
+
+template <int MODE>
+void launch_intensity_map(const float* x, float* y, const float* mm, const float* mean, const float* par, const int* flag,
+                          int keep, int R, int64_t L, hipStream_t st) {
+    const dim3 grid((unsigned)cdiv64(L / 4 + 1, 256), R);
+    if (aligned16(x) && aligned16(y))
+        hipLaunchKernelGGL((intensity_map_kernel<MODE, true>), grid, dim3(256), 0, st, x, y, mm, mean, par, flag, keep, L);
+    else
+        hipLaunchKernelGGL((intensity_map_kernel<MODE, false>), grid, dim3(256), 0, st, x, y, mm, mean, par, flag, keep, L);
+}
+
 int check_batch(const char* who, int n_table, int N, int64_t S) {
     DRAM_REQUIRE(N > 0 && N <= 65535 && S > 0 && S <= 0x7fffffff, "%s: bad sizes (N 1..65535, D*H*W 1..2^31-1)", who);
     DRAM_REQUIRE(n_table == N, "%s: table length %d does not match the batch of %d samples", who, n_table, N);
@@ -484,4 +627,53 @@ extern "C" int dram_aug_permute_flip(const void* x, void* y, int elem_size, cons
     if (elem_size == 4) launch_permflip<float, 32>(x, y, perm, flip, flag, N, C, D, H, W, st);
     else launch_permflip<unsigned char, 64>(x, y, perm, flip, flag, N, C, D, H, W, st);
     return check_launch("aug_permute_flip");
+}
+
+extern "C" size_t dram_aug_row_mean_ws_bytes(int R, int64_t L) {
+    if (R <= 0 || L <= 0) return 0;
+    return (size_t)R * mean_blocks(L) * sizeof(double);
+}
+
+extern "C" int dram_aug_row_mean(const float* x, float* mean, const int* flag, int R, int64_t L, void* ws, size_t ws_bytes,
+                                 void* stream) {
+    DRAM_REQUIRE(x && mean && ws, "aug_row_mean: null pointer");
+    DRAM_REQUIRE(R > 0 && R <= 65535 && L > 0 && L <= 0x7fffffff, "aug_row_mean: bad sizes (rows 1..65535, row length 1..2^31-1)");
+    DRAM_REQUIRE(((uintptr_t)ws & 7) == 0, "aug_row_mean: workspace must be 8-byte aligned");
+    if (ws_bytes < dram_aug_row_mean_ws_bytes(R, L)) {
+        set_error("aug_row_mean: workspace too small");
+        return DRAM_EWS;
+    }
+    hipStream_t st = (hipStream_t)stream;
+    const int nblk = mean_blocks(L);
+    hipLaunchKernelGGL(row_sum_kernel, dim3(nblk, R), dim3(256), 0, st, x, (double*)ws, flag, L, nblk);
+    hipLaunchKernelGGL(row_mean_kernel, dim3(cdiv(R, 256)), dim3(256), 0, st, (const double*)ws, mean, flag, R, L, nblk);
+    return check_launch("aug_row_mean");
+}
+
+extern "C" int dram_aug_intensity_map(const float* x, float* y, int mode, const float* minmax, const float* mean,
+                                      const float* params, int keep_range, const int* flag, int n_table, int R, int64_t L,
+                                      void* stream) {
+    DRAM_REQUIRE(mode >= DRAM_AUG_MAP_INVERSE && mode <= DRAM_AUG_MAP_JITTER, "aug_intensity_map: unknown mode %d", mode);
+    const bool jitter = mode == DRAM_AUG_MAP_JITTER;
+    DRAM_REQUIRE(x && y && flag && (minmax || (jitter && !keep_range)) && (mean || !jitter) &&
+                     (params || mode == DRAM_AUG_MAP_INVERSE),
+                 "aug_intensity_map: null pointer");
+    int rc = check_batch("aug_intensity_map", n_table, R, L);
+    if (rc) return rc;
+    hipStream_t st = (hipStream_t)stream;
+    switch (mode) {
+        case DRAM_AUG_MAP_INVERSE:
+            launch_intensity_map<DRAM_AUG_MAP_INVERSE>(x, y, minmax, mean, params, flag, 0, R, L, st);
+            break;
+        case DRAM_AUG_MAP_GAMMA:
+            launch_intensity_map<DRAM_AUG_MAP_GAMMA>(x, y, minmax, mean, params, flag, 0, R, L, st);
+            break;
+        case DRAM_AUG_MAP_STRETCH:
+            launch_intensity_map<DRAM_AUG_MAP_STRETCH>(x, y, minmax, mean, params, flag, 0, R, L, st);
+            break;
+        default:
+            launch_intensity_map<DRAM_AUG_MAP_JITTER>(x, y, minmax, mean, params, flag, keep_range != 0, R, L, st);
+            break;
+    }
+    return check_launch("aug_intensity_map");
 }

@@ -6,4 +6,15 @@ the reference's flat `parts.py` / `models.py` live one directory up.
 """
 from . import _lib, functional, modules  # noqa: F401
 
-__all__ = ["_lib", "functional", "modules"]
+# the augmentation transforms of `augment`, importable from here; the module is loaded on first use
+_AUGMENT = ("GaussianBlur", "RandomMaskOut", "RandomFlip", "RandomRotate90", "GaussianAddictive", "IntensityInverse",
+            "GammaTransform", "ContrastStretchingTransform", "ContrastJitter", "EnsembleScanAugmentation")
+
+__all__ = ["_lib", "functional", "modules", *_AUGMENT]
+
+
+def __getattr__(name):
+    if name in _AUGMENT:
+        from . import augment
+        return getattr(augment, name)
+    raise AttributeError(f"module {__name__!r} has no attribute {name!r}")

@@ -127,6 +127,9 @@ SIGNATURES = {
     "dram_aug_mask_out": (I, [P, P, P, P, P, P, I, I, I, I, I, I, P]),
     "dram_aug_gaussian_noise": (I, [P, P, P, P, P, P, I, P, I, L, P]),
     "dram_aug_permute_flip": (I, [P, P, I, P, P, P, I, I, I, I, I, I, P]),
+    "dram_aug_row_mean_ws_bytes": (Z, [I, L]),
+    "dram_aug_row_mean": (I, [P, P, P, I, L, P, Z, P]),
+    "dram_aug_intensity_map": (I, [P, P, I, P, P, P, I, P, I, I, L, P]),
     # device chunk loader
     "dram_chunk_hist256": (I, [P, P, P, I, P, I, I, P]),
     "dram_otsu256": (I, [P, I, ctypes.c_double, P, P]),

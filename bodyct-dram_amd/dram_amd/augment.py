@@ -7,6 +7,10 @@ the sample-dict protocol of `transforms.py`: entries whose key contains "#" hold
 the intensity transforms touch keys with both "#" and "image", flip and rotate touch every "#" key, everything else passes
 through.  The work runs in per-batch launches of csrc/augment.hip over per-sample parameter tables: no host synchronisation.
 
+Beside the pool's five, four more intensity transforms of data_transforms.py are here for pools of the user's own
+(`EnsembleScanAugmentation(aug_ratio, pool=[...])`): `IntensityInverse`, `GammaTransform`, `ContrastStretchingTransform` and
+`ContrastJitter`.
+
 Drawing.  `draw(n, shape)` returns one parameter dict per sample, in sample order, from the same `random` / `numpy.random`
 calls in the same order as the reference's `__call__` makes for one chunk, so a seeded run picks what the reference would pick
 for that chunk.  (The reference draws an intensity transform's parameters once per "#image" entry; here one set per sample
@@ -20,11 +24,13 @@ import numpy as np
 import torch
 
 from . import functional as HF
+from . import _lib
 from ._lib import call
 
 MAX_RADIUS = 4     # DRAM_AUG_MAX_RADIUS
 MAX_BOXES = 16     # DRAM_AUG_MAX_BOXES
 TRANSFORM, PASS, SKIP = 1, 0, -1   # per-sample flags of the C entries
+MAP_INVERSE, MAP_GAMMA, MAP_STRETCH, MAP_JITTER = 0, 1, 2, 3   # DRAM_AUG_MAP_*
 
 
 # ---------------------------------------------------------------------------------------------------------------- tables
@@ -114,6 +120,37 @@ def sample_minmax(x, flags=None, out=None):
     return mm
 
 
+def _rows(x, rows):
+    """(R, L) of the 5-d view split into `rows` rows per sample."""
+    return x.shape[0] * rows, x[0].numel() // rows
+
+
+def row_minmax(x, rows, flags=None):
+    """[N * rows, 2] fp32 {min, max} of every sample cut into `rows` equal rows (rows = D: its z-slices); `flags` per row."""
+    R, L = _rows(x, rows)
+    mm = torch.empty((R, 2), dtype=torch.float32, device=x.device)
+    call("dram_aug_minmax", HF._p(x), HF._p(mm), HF._p(flags), R, L, HF._stream())
+    return mm
+
+
+def row_mean(x, rows, flags=None):
+    """[N * rows] fp32 mean of every row (fp64 sums added in a fixed order: deterministic); `flags` per row."""
+    R, L = _rows(x, rows)
+    mean = torch.empty((R,), dtype=torch.float32, device=x.device)
+    nbytes = _lib.lib.dram_aug_row_mean_ws_bytes(R, L)
+    ws = HF._ws(nbytes, x.device)
+    call("dram_aug_row_mean", HF._p(x), HF._p(mean), HF._p(flags), R, L, HF._p(ws), nbytes, HF._stream())
+    return mean
+
+
+def _intensity_map(x, mode, minmax, mean, par, keep_range, flags, rows=1, out=None):
+    R, L = _rows(x, rows)
+    y = torch.empty_like(x) if out is None else out
+    call("dram_aug_intensity_map", HF._p(x), HF._p(y), mode, HF._p(minmax), HF._p(mean), HF._p(par), int(bool(keep_range)),
+         HF._p(flags), flags.numel(), R, L, HF._stream())
+    return y
+
+
 def _blur(x, weights, flags, radius, out=None):
     N, _, D, H, W = x.shape
     y = torch.empty_like(x) if out is None else out
@@ -170,8 +207,10 @@ def _first_tensor(sample):
 
 
 class _Augmentation:
-    """draw / apply / __call__ shared by the five pool elements."""
+    """draw / apply / __call__ shared by the transforms."""
     intensity = True      # True: touches '#...image...' entries only; False: every '#' entry
+    pointwise = False     # True: every element is read and written by one lane, so the ensemble driver may run it in place
+    uses_minmax = False   # True: _launch takes the samples' {min, max} (minmax=), which the ensemble driver computes for it
 
     def draw_one(self, shape):   # pragma: no cover - overridden
         raise NotImplementedError
@@ -244,6 +283,7 @@ class RandomMaskOut(_Augmentation):
     """`times` boxes per sample, centre int(dim * U(region_range)) and size int(U(region_size) * dim) per axis, each filled with
     one value min + (max - min) * u of the sample's own range (taken before any box is written).  `assign_value` is unused, as in
     the reference."""
+    pointwise = uses_minmax = True
 
     def __init__(self, times=5, region_range=((0.2, 0.8), (0.2, 0.8), (0.2, 0.8)),
                  region_size=((0.01, 0.06), (0.01, 0.06), (0.01, 0.06)), spatial_dim=3, assign_value=0):
@@ -339,6 +379,7 @@ class GaussianAddictive(_Augmentation):
     from the reference's, and the noise values are not numpy's.  A parameter dict may carry "noise" (a float64 device tensor of
     the sample's shape) to run the reference's arithmetic on given noise instead.  Only channel_dim 0 / None (the whole sample
     as one array) is supported."""
+    pointwise = uses_minmax = True
 
     def __init__(self, sigma, channel_dim=0):
         self.sigma = sigma
@@ -370,6 +411,125 @@ class GaussianAddictive(_Augmentation):
     def _launch(self, x, tables, flags, out=None, minmax=None):
         minmax = sample_minmax(x, flags) if minmax is None else minmax
         return _noise(x, minmax, tables[0], tables[1], flags, tables[2], out)
+
+
+class _RangeMap(_Augmentation):
+    """A point-wise map of the sample rescaled to [0, 1] by its own {min, max} and back, every step in fp32 as numpy computes
+    it.  These classes test `not channel_dim`: 0 and None both mean the whole chunk as one array, anything else makes the
+    reference work slice by slice along that axis with draws per slice, which is not built."""
+    pointwise = uses_minmax = True
+    mode = None
+
+    def _check_channel_dim(self):
+        if self.channel_dim:
+            raise NotImplementedError(f"{type(self).__name__}: channel_dim={self.channel_dim!r} (per-slice transforms along "
+                                      f"that axis) is not supported; supported: channel_dim 0 or None (the whole chunk)")
+
+    def _row(self, p):   # pragma: no cover - overridden
+        raise NotImplementedError
+
+    def _tables(self, params, shape, device):
+        return _dev([[0.0, 0.0] if p is None else self._row(p) for p in params], torch.float32, device)
+
+    def _launch(self, x, tables, flags, out=None, minmax=None):
+        minmax = sample_minmax(x, flags) if minmax is None else minmax
+        return _intensity_map(x, self.mode, minmax, None, tables, False, flags, 1, out)
+
+
+class IntensityInverse(_RangeMap):
+    """(1 - rescaled), shifted so that its minimum is 0, rescaled back: max <-> min.  Draws nothing."""
+    mode = MAP_INVERSE
+
+    def __init__(self, channel_dim=0):
+        self.channel_dim = channel_dim
+        self.epsilon = 1e-7
+        self._check_channel_dim()
+
+    def draw_one(self, shape):
+        return {}
+
+    def _tables(self, params, shape, device):
+        return None
+
+
+class GammaTransform(_RangeMap):
+    """rescaled ** factor, factor = one np.random.uniform(gamma_range) draw per sample."""
+    mode = MAP_GAMMA
+
+    def __init__(self, gamma_range=(0.5, 2), channel_dim=0):
+        self.gamma_range = gamma_range
+        self.epsilon = 1e-7
+        self.channel_dim = channel_dim
+        self._check_channel_dim()
+
+    def draw_one(self, shape):
+        return {"factor": np.random.uniform(self.gamma_range[0], self.gamma_range[1])}
+
+    def _row(self, p):
+        return [float(p["factor"]), 0.0]
+
+
+class ContrastStretchingTransform(_RangeMap):
+    """1 / (1 + (mp / (rescaled + 1e-7)) ** factor): two np.random.uniform draws per sample, factor (gamma_range) then mp
+    (middle_point)."""
+    mode = MAP_STRETCH
+
+    def __init__(self, gamma_range=(0.5, 2), middle_point=(0.3, 0.7), channel_dim=0):
+        self.gamma_range = gamma_range
+        self.middle_point = middle_point
+        self.epsilon = 1e-7
+        self.channel_dim = channel_dim
+        self._check_channel_dim()
+
+    def draw_one(self, shape):
+        factor = np.random.uniform(self.gamma_range[0], self.gamma_range[1])
+        mp = np.random.uniform(self.middle_point[0], self.middle_point[1])
+        return {"factor": factor, "mp": mp}
+
+    def _row(self, p):
+        return [float(p["factor"]), float(p["mp"])]
+
+
+class ContrastJitter(_Augmentation):
+    """(x - mean) * factor + mean, clamped to the data's own [min, max] when if_keep_range.
+
+    Unlike the other intensity transforms the reference tests `channel_dim is None` here, so its DEFAULT channel_dim=0 jitters
+    every z-slice of a [D, H, W] chunk on its own: mean, min, max and one np.random.uniform(jitter_range) draw per slice, D
+    draws per sample in slice order.  Only channel_dim=None treats the chunk as one array (one draw).  Both are kept as they
+    are; "factor" is the list of the sample's D factors (of its one factor for channel_dim=None).
+
+    The mean is an fp64 sum rounded to fp32; numpy adds float32 pairwise, so the two means can differ in the last bit."""
+    pointwise = True      # the slice statistics are its own: the driver's per-sample {min, max} do not serve them
+
+    def __init__(self, jitter_range=(0.75, 1.25), if_keep_range=True, channel_dim=0):
+        self.jitter_range = jitter_range
+        self.if_keep_range = if_keep_range
+        self.channel_dim = channel_dim
+        if channel_dim not in (None, 0):
+            raise NotImplementedError(f"ContrastJitter: channel_dim={channel_dim!r} is not supported; supported: channel_dim 0 "
+                                      f"(every z-slice on its own) or None (the whole chunk)")
+
+    def _rows(self, shape):
+        return 1 if self.channel_dim is None else int(shape[0])
+
+    def draw_one(self, shape):
+        return {"factor": [np.random.uniform(self.jitter_range[0], self.jitter_range[1]) for _ in range(self._rows(shape))]}
+
+    def _tables(self, params, shape, device):
+        rows, table = self._rows(shape), []
+        for p in params:
+            factors = [0.0] * rows if p is None else [float(v) for v in p["factor"]]
+            if len(factors) != rows:
+                raise ValueError(f"ContrastJitter: {rows} factors per sample expected (channel_dim={self.channel_dim!r}), "
+                                 f"got {len(factors)}")
+            table += [[v, 0.0] for v in factors]
+        return _dev(table, torch.float32, device), rows
+
+    def _launch(self, x, tables, flags, out=None):
+        par, rows = tables
+        row_flags = flags if rows == 1 else flags.repeat_interleave(rows)
+        minmax = row_minmax(x, rows, row_flags) if self.if_keep_range else None
+        return _intensity_map(x, MAP_JITTER, minmax, row_mean(x, rows, row_flags), par, self.if_keep_range, row_flags, rows, out)
 
 
 # -------------------------------------------------------------------------------------------------------------- ensemble
@@ -441,14 +601,14 @@ class EnsembleScanAugmentation:
                     continue
                 params = [steps[i][pos][1] if i in members else None for i in range(N)]
                 tables = t._tables(params, spatial, device)
-                inplace = isinstance(t, (RandomMaskOut, GaussianAddictive))
+                inplace = t.pointwise
                 groups = {s: [i for i in members if where[i] == s] for s in sorted({where[i] for i in members})}
                 for s, group in groups.items():
                     d = s if (inplace and s != 0) else (2 if s == 1 else 1)
                     if bufs[d] is None:
                         bufs[d] = torch.empty_like(src)
                     flags = _dev([TRANSFORM if i in group else SKIP for i in range(N)], torch.int32, device)
-                    if inplace:
+                    if t.uses_minmax:
                         sample_minmax(bufs[s], flags, out=minmax)
                         t._launch(bufs[s], tables, flags, out=bufs[d], minmax=minmax)
                     else:

@@ -547,6 +547,29 @@ int dram_aug_gaussian_noise(const float* x, float* y, const float* minmax, const
 int dram_aug_permute_flip(const void* x, void* y, int elem_size, const int* perm, const int* flip, const int* flag, int n_table,
                           int N, int C, int D, int H, int W, void* stream);
 
+/* Point-wise intensity transforms of dram/data_transforms.py over ROWS of L floats: x, y hold R rows back to back, a row being a
+ * sample (R = N, L = D*H*W) or one z-slice of it (R = N*D, L = H*W); flag, the tables and n_table (= R) are per row.  A row need
+ * not start on a 16-byte boundary.
+ *
+ * dram_aug_row_mean: mean[r] = fp32(sum of row r in fp64 / L), the same bits for the same row whatever R and the row's position;
+ *   flag may be NULL; rows whose flag is not 1 are left as they are.  ws: dram_aug_row_mean_ws_bytes(R, L) bytes, 8-byte aligned.
+ * dram_aug_intensity_map: with {min, max} = minmax[r] (dram_aug_minmax over the same rows), range = max - min and
+ *   t = (x - min) / (range + 1e-7), every operation rounded to fp32 as numpy rounds it, powers by powf:
+ *   DRAM_AUG_MAP_INVERSE (IntensityInverse, 213-248):  ((1 - t) - (1 - t at x = max)) * range + min; params unused
+ *   DRAM_AUG_MAP_GAMMA (GammaTransform, 279-315):      t ** params[r][0] * range + min
+ *   DRAM_AUG_MAP_STRETCH (ContrastStretchingTransform, 318-362): 1 / (1 + (params[r][1] / (t + 1e-7)) ** params[r][0]) * range + min
+ *   DRAM_AUG_MAP_JITTER (ContrastJitter, 538-579):     (x - mean[r]) * params[r][0] + mean[r], clamped to [min, max] when keep_range
+ *   params: [R][2] fp32 {factor, middle point}; mean: [R] fp32 (dram_aug_row_mean), jitter only; minmax may be NULL for a jitter
+ *   without keep_range.  y may be x. */
+#define DRAM_AUG_MAP_INVERSE 0
+#define DRAM_AUG_MAP_GAMMA 1
+#define DRAM_AUG_MAP_STRETCH 2
+#define DRAM_AUG_MAP_JITTER 3
+size_t dram_aug_row_mean_ws_bytes(int R, int64_t L);
+int dram_aug_row_mean(const float* x, float* mean, const int* flag, int R, int64_t L, void* ws, size_t ws_bytes, void* stream);
+int dram_aug_intensity_map(const float* x, float* y, int mode, const float* minmax, const float* mean, const float* params,
+                           int keep_range, const int* flag, int n_table, int R, int64_t L, void* stream);
+
 /* ---- device chunk loader: what the reference does per chunk on the host before a training step, for a whole ragged batch.
  *      RadboudCOVIDLobeVesselChunk.get_data (dram/dataset.py:450-486): w_scan = windowing(scan, to_span=(0, 1)) (utils.py:189-198,
  *      default span (-1150, 350)); _, th = binary_cam(w_scan[lobe > 0], 0.75) (utils.py:226-242); pseudo lesion = (w_scan > th) &
