@@ -2,7 +2,8 @@
 // dram/job_runner.py:548-581, over dram/data_transforms.py GaussianBlur / RandomMaskOut / RandomFlip / RandomRotate90 /
 // GaussianAddictive).  One launch transforms every sample of [N, D, H, W] with that sample's own parameters, read from
 // small device tables; nothing synchronises with the host.  Beside the pool's five: IntensityInverse, GammaTransform,
-// ContrastStretchingTransform and ContrastJitter of the same file, point-wise over rows (a sample, or one z-slice of it).
+// ContrastStretchingTransform and ContrastJitter of the same file, point-wise over rows (a sample, or one z-slice of it); the
+// three slab projections (a causal sliding min / max along one axis); DiskMaskOut and RandomCubeMask (keep a region, zero the rest).
 //
 // Every table carries a per-sample flag:  1 = transform,  0 = pass through (copied when y != x),  < 0 = skip the sample
 // (y is not written: the ensemble driver keeps samples in different buffers and moves only the ones a launch is for).
@@ -532,6 +533,256 @@ void launch_intensity_map(const float* x, float* y, const float* mm, const float
         hipLaunchKernelGGL((intensity_map_kernel<MODE, false>), grid, dim3(256), 0, st, x, y, mm, mean, par, flag, keep, L);
 }
 
+// ---------------------------------------------------------------- slab projections (causal sliding min / max along one axis)
+// MinimalIntensityProjection / MaximumIntensityProjection / MinimalIntensityAxialProjection (data_transforms.py:409-504):
+// out[.., i, ..] = min or max of in[.., max(0, i - t) .. i, ..] along the sample's axis.  A row of W floats is cut where the
+// OUTPUT address is 16-byte aligned: `head` scalars, `nvec` quads, a scalar tail; one lane per quad and one more lane per row for
+// the head and the tail.  The input is read through a 4-byte aligned quad type: window rows of a z or y walk stand W or H*W floats
+// apart, which need not be a multiple of four.
+constexpr int SLAB_MAX = DRAM_AUG_MAX_SLAB;
+constexpr int SLAB_HALO = SLAB_MAX + 4;     // LDS columns in front of a row segment: a full window left of a head element
+constexpr int SLAB_SEG_QUADS = 64;          // quads of a row per LDS pass (x walk)
+constexpr int SLAB_MAX_ROWS = 64;           // rows per block (x walk)
+
+struct __attribute__((packed, aligned(4))) quad_u { float x, y, z, w; };
+
+template <bool IS_MAX>
+__device__ __forceinline__ float slab_op(float a, float b) { return IS_MAX ? fmaxf(a, b) : fminf(a, b); }
+
+template <bool IS_MAX>
+__device__ __forceinline__ float4 slab_op4(float4 a, const quad_u& b) {
+    return make_float4(slab_op<IS_MAX>(a.x, b.x), slab_op<IS_MAX>(a.y, b.y), slab_op<IS_MAX>(a.z, b.z), slab_op<IS_MAX>(a.w, b.w));
+}
+
+__device__ __forceinline__ int slab_head(const float* yrow, int W) {
+    const int head = (int)(((16 - (reinterpret_cast<uintptr_t>(yrow) & 15)) & 15) >> 2);
+    return head < W ? head : W;
+}
+
+// x walk: quads per LDS pass, lanes per row (one per quad and one for head and tail), rows per block, LDS floats per row.
+struct SlabXGeom { int sq, slots, rows, stride; };
+__host__ __device__ constexpr SlabXGeom slab_x_geom(int W) {
+    const int sq = W / 4 < SLAB_SEG_QUADS ? W / 4 : SLAB_SEG_QUADS;
+    const int rows = 256 / (sq + 1) < SLAB_MAX_ROWS ? 256 / (sq + 1) : SLAB_MAX_ROWS;
+    return {sq, sq + 1, rows, SLAB_HALO + 4 * sq + 4};
+}
+constexpr int slab_x_lds_floats() {
+    int m = 0;
+    for (int sq = 0; sq <= SLAB_SEG_QUADS; ++sq) {
+        const SlabXGeom g = slab_x_geom(4 * sq);
+        m = g.rows * g.stride > m ? g.rows * g.stride : m;
+    }
+    return m;
+}
+constexpr int SLAB_X_LDS = slab_x_lds_floats();
+
+// z or y walk: a lane owns its quad and walks the window through rows `step` floats apart (coalesced across the lanes of a row;
+// what a neighbouring output row read a moment ago comes from the cache).  i = the row's index along the axis.
+template <bool IS_MAX>
+__device__ __forceinline__ void slab_walk_rows(const float* __restrict__ xs, float* __restrict__ ys, int t, int axis, int rows,
+                                               int H, int W) {
+    const int slots = (W + 3) / 4 + 1;
+    const int64_t g = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (g >= (int64_t)rows * slots) return;      // rows * slots < 2^32, as D*H*W < 2^31: 32-bit divisions from here on
+    const unsigned row = (unsigned)g / (unsigned)slots;
+    const int q = (int)((unsigned)g - row * (unsigned)slots);
+    const int i = axis == 0 ? (int)(row / (unsigned)H) : (int)(row % (unsigned)H);
+    const int64_t step = axis == 0 ? (int64_t)H * W : W;
+    const int m = t < i ? t : i;
+    const int64_t off = (int64_t)row * W;
+    const int head = slab_head(ys + off, W);
+    const int nvec = (W - head) >> 2;
+    if (q < nvec) {
+        const int64_t o = off + head + 4 * q;
+        const quad_u v = *reinterpret_cast<const quad_u*>(xs + o);
+        float4 acc = make_float4(v.x, v.y, v.z, v.w);
+#pragma unroll 4
+        for (int k = 1; k <= m; ++k) acc = slab_op4<IS_MAX>(acc, *reinterpret_cast<const quad_u*>(xs + o - k * step));
+        *reinterpret_cast<float4*>(ys + o) = acc;
+    } else if (q == slots - 1) {
+        for (int c = 0; c < W; ++c) {
+            if (c == head) c += 4 * nvec;
+            if (c >= W) break;
+            float acc = xs[off + c];
+            for (int k = 1; k <= m; ++k) acc = slab_op<IS_MAX>(acc, xs[off + c - k * step]);
+            ys[off + c] = acc;
+        }
+    }
+}
+
+// x walk: a block stages `rows` rows in LDS, SLAB_SEG_QUADS quads of each at a time, behind SLAB_HALO columns that hold the
+// elements to their left (the identity of the operation left of the row's start, so the window needs no clipping).  Column
+// SLAB_HALO is the segment's first aligned quad, so quads are 16-byte aligned in LDS as well.
+template <bool IS_MAX>
+__device__ __forceinline__ void slab_walk_x(const float* __restrict__ xs, float* __restrict__ ys, int t, int rows, int W,
+                                            float* smem) {
+    const SlabXGeom gm = slab_x_geom(W);
+    if ((int64_t)blockIdx.x * gm.rows >= rows) return;
+    const float ident = IS_MAX ? -INFINITY : INFINITY;
+    const int rr = threadIdx.x / gm.slots, q = threadIdx.x - rr * gm.slots;
+    const int64_t row = (int64_t)blockIdx.x * gm.rows + rr;
+    const bool active = rr < gm.rows && row < rows;
+    const int64_t off = active ? row * W : 0;
+    const int head = active ? slab_head(ys + off, W) : 0;
+    const int nvec = (W - head) >> 2;
+    float* srow = smem + (active ? rr : 0) * gm.stride;
+    const int nseg = (W / 4 + SLAB_SEG_QUADS - 1) / SLAB_SEG_QUADS > 1 ? (W / 4 + SLAB_SEG_QUADS - 1) / SLAB_SEG_QUADS : 1;
+    for (int s = 0; s < nseg; ++s) {
+        const int qs = s * SLAB_SEG_QUADS;
+        int nq = nvec - qs;
+        nq = nq < 0 ? 0 : (nq > SLAB_SEG_QUADS ? SLAB_SEG_QUADS : nq);
+        const int xlo = head + 4 * qs;                   // the row element in LDS column SLAB_HALO
+        const int tail0 = head + 4 * nvec;               // the row's scalar tail [tail0, W): staged and formed in the last pass
+        const bool last = s == nseg - 1;
+        if (active) {
+            if (q < nq) {
+                const quad_u v = *reinterpret_cast<const quad_u*>(xs + off + xlo + 4 * q);
+                *reinterpret_cast<float4*>(srow + SLAB_HALO + 4 * q) = make_float4(v.x, v.y, v.z, v.w);
+            }
+            for (int j = q; j < SLAB_HALO; j += gm.slots) {
+                const int c = xlo - SLAB_HALO + j;
+                srow[j] = c >= 0 ? xs[off + c] : ident;
+            }
+            if (last && q == gm.slots - 1)
+                for (int c = tail0; c < W; ++c) srow[c - xlo + SLAB_HALO] = xs[off + c];
+        }
+        __syncthreads();
+        if (active) {
+            if (q < nq) {
+                const float* p = srow + SLAB_HALO + 4 * q - t;
+                float o[4] = {ident, ident, ident, ident};
+                for (int i = 0; i < t + 4; ++i) {        // p[i] lies in the window of output e iff 0 <= i - e <= t
+                    const float v = p[i];
+#pragma unroll
+                    for (int e = 0; e < 4; ++e)
+                        if (i >= e && i - e <= t) o[e] = slab_op<IS_MAX>(o[e], v);
+                }
+                *reinterpret_cast<float4*>(ys + off + xlo + 4 * q) = make_float4(o[0], o[1], o[2], o[3]);
+            } else if (q == gm.slots - 1) {
+                for (int c = (s == 0 ? 0 : W); c < W; ++c) {     // the head, with the first pass
+                    if (c == head) break;
+                    const float* p = srow + c - xlo + SLAB_HALO;
+                    float acc = p[0];
+                    for (int k = 1; k <= t; ++k) acc = slab_op<IS_MAX>(acc, p[-k]);
+                    ys[off + c] = acc;
+                }
+                for (int c = (last ? tail0 : W); c < W; ++c) {
+                    const float* p = srow + c - xlo + SLAB_HALO;
+                    float acc = p[0];
+                    for (int k = 1; k <= t; ++k) acc = slab_op<IS_MAX>(acc, p[-k]);
+                    ys[off + c] = acc;
+                }
+            }
+        }
+        __syncthreads();
+    }
+}
+
+// Grid (blocks, sample).  Axis and thickness are the sample's, so a block takes one path.  A passed-through sample is a window of
+// one element; so is a table entry outside 0..2 / 0..DRAM_AUG_MAX_SLAB (the host side refuses those earlier).
+template <bool IS_MAX>
+__global__ __launch_bounds__(256) void slab_project_kernel(const float* __restrict__ x, float* __restrict__ y,
+                                                           const int* __restrict__ thickness, const int* __restrict__ axis,
+                                                           const int* __restrict__ flag, int D, int H, int W) {
+    __shared__ __attribute__((aligned(16))) float smem[SLAB_X_LDS];
+    const int n = blockIdx.y;
+    const int f = flag[n];
+    if (f < 0) return;
+    int t = 0, a = 0;
+    if (f == 1) {
+        t = thickness[n];
+        a = axis[n];
+        if (t < 0 || t > SLAB_MAX || a < 0 || a > 2) t = a = 0;
+    }
+    const int64_t S = (int64_t)D * H * W;
+    const float* xs = x + (int64_t)n * S;
+    float* ys = y + (int64_t)n * S;
+    if (a == 2 && t > 0) slab_walk_x<IS_MAX>(xs, ys, t, D * H, W, smem);
+    else slab_walk_rows<IS_MAX>(xs, ys, t, a, D * H, H, W);
+}
+
+// ---------------------------------------------------------------- keep a region, zero the rest
+// DiskMaskOut / RandomCubeMask._mask (data_transforms.py:840-870, 647-657).  Grid (blocks, channel, sample); a lane moves 16
+// bytes (VEC elements) or, beside the aligned body and when a base is unaligned, single elements, as intensity_map_kernel does.
+struct Region {
+    int z0, z1, y0, y1, x0, x1, cy, cx, r2;
+};
+
+__device__ __forceinline__ bool region_keeps(const Region& g, int z, int yy, int xx) {
+    if (z < g.z0 || z >= g.z1 || yy < g.y0 || yy >= g.y1 || xx < g.x0 || xx >= g.x1) return false;
+    if (g.r2 < 0) return true;
+    const long long dy = yy - g.cy, dx = xx - g.cx;
+    return dy * dy + dx * dx <= (long long)g.r2;
+}
+
+template <typename T, bool VEC>
+__global__ __launch_bounds__(256) void keep_region_kernel(const T* x, T* y, const int* __restrict__ boxes,
+                                                          const int* __restrict__ disk, const int* __restrict__ flag, int C,
+                                                          int D, int H, int W) {
+    constexpr int PER = 16 / (int)sizeof(T);
+    const int n = blockIdx.z;
+    const int f = flag[n];
+    if (f < 0 || (f == 0 && x == y)) return;
+    const int64_t L = (int64_t)D * H * W;
+    const int64_t off = ((int64_t)n * C + blockIdx.y) * L;
+    const T* xs = x + off;
+    T* ys = y + off;
+    int64_t head = VEC ? ((PER - (off & (PER - 1))) & (PER - 1)) : 0;
+    if (head > L) head = L;
+    const int64_t nvec = VEC ? (L - head) / PER : 0;
+    const int64_t g = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (VEC ? g > nvec : g * PER >= L) return;
+    Region rg = {};
+    if (f == 1) {
+        const int* b = boxes + 6 * n;
+        const int* d = disk + 3 * n;
+        rg = {b[0], b[1], b[2], b[3], b[4], b[5], d[0], d[1], d[2]};
+    }
+    auto range = [&](int64_t i0, int64_t i1) {      // single elements [i0, i1)
+        if (i0 >= i1) return;
+        const unsigned r0 = (unsigned)i0 / (unsigned)W;      // i0 < 2^31: 32-bit divisions
+        int xx = (int)((unsigned)i0 - r0 * (unsigned)W), yy = (int)(r0 % (unsigned)H), z = (int)(r0 / (unsigned)H);
+        for (int64_t i = i0; i < i1; ++i) {
+            ys[i] = (f == 0 || region_keeps(rg, z, yy, xx)) ? xs[i] : T(0);
+            if (++xx == W) { xx = 0; if (++yy == H) { yy = 0; ++z; } }
+        }
+    };
+    if (g < nvec) {
+        const int64_t i0 = head + g * PER;
+        union { uint4 q; T e[PER]; } v;
+        v.q = *reinterpret_cast<const uint4*>(xs + i0);
+        if (f == 1) {
+            const unsigned r0 = (unsigned)i0 / (unsigned)W;
+            int xx = (int)((unsigned)i0 - r0 * (unsigned)W), yy = (int)(r0 % (unsigned)H), z = (int)(r0 / (unsigned)H);
+#pragma unroll
+            for (int e = 0; e < PER; ++e) {
+                if (!region_keeps(rg, z, yy, xx)) v.e[e] = T(0);
+                if (++xx == W) { xx = 0; if (++yy == H) { yy = 0; ++z; } }
+            }
+        }
+        *reinterpret_cast<uint4*>(ys + i0) = v.q;
+        return;
+    }
+    if (VEC) {
+        range(0, head);
+        range(head + nvec * PER, L);
+    } else {
+        range(g * PER, g * PER + PER < L ? g * PER + PER : L);
+    }
+}
+
+template <typename T>
+void launch_keep_region(const void* x, void* y, const int* boxes, const int* disk, const int* flag, int N, int C, int D, int H,
+                        int W, hipStream_t st) {
+    constexpr int PER = 16 / (int)sizeof(T);
+    const int64_t L = (int64_t)D * H * W;
+    const dim3 grid((unsigned)cdiv64(L / PER + 1, 256), C, N);
+    if (aligned16(x) && aligned16(y))
+        hipLaunchKernelGGL((keep_region_kernel<T, true>), grid, dim3(256), 0, st, (const T*)x, (T*)y, boxes, disk, flag, C, D, H, W);
+    else
+        hipLaunchKernelGGL((keep_region_kernel<T, false>), grid, dim3(256), 0, st, (const T*)x, (T*)y, boxes, disk, flag, C, D, H, W);
+}
+
 int check_batch(const char* who, int n_table, int N, int64_t S) {
     DRAM_REQUIRE(N > 0 && N <= 65535 && S > 0 && S <= 0x7fffffff, "%s: bad sizes (N 1..65535, D*H*W 1..2^31-1)", who);
     DRAM_REQUIRE(n_table == N, "%s: table length %d does not match the batch of %d samples", who, n_table, N);
@@ -627,6 +878,36 @@ extern "C" int dram_aug_permute_flip(const void* x, void* y, int elem_size, cons
     if (elem_size == 4) launch_permflip<float, 32>(x, y, perm, flip, flag, N, C, D, H, W, st);
     else launch_permflip<unsigned char, 64>(x, y, perm, flip, flag, N, C, D, H, W, st);
     return check_launch("aug_permute_flip");
+}
+
+extern "C" int dram_aug_slab_project(const float* x, float* y, const int* thickness, const int* axis, int is_max,
+                                     const int* flag, int n_table, int N, int D, int H, int W, void* stream) {
+    DRAM_REQUIRE(x && y && thickness && axis && flag, "aug_slab_project: null pointer");
+    DRAM_REQUIRE(D > 0 && H > 0 && W > 0, "aug_slab_project: bad sizes");
+    int rc = check_batch("aug_slab_project", n_table, N, (int64_t)D * H * W);
+    if (rc) return rc;
+    DRAM_REQUIRE(x != y, "aug_slab_project: cannot run in place");
+    hipStream_t st = (hipStream_t)stream;
+    const int64_t rows = (int64_t)D * H;
+    const int64_t by_rows = cdiv64(rows * (cdiv(W, 4) + 1), 256), by_x = cdiv64(rows, slab_x_geom(W).rows);
+    const dim3 grid((unsigned)(by_rows > by_x ? by_rows : by_x), N);
+    if (is_max) hipLaunchKernelGGL(slab_project_kernel<true>, grid, dim3(256), 0, st, x, y, thickness, axis, flag, D, H, W);
+    else hipLaunchKernelGGL(slab_project_kernel<false>, grid, dim3(256), 0, st, x, y, thickness, axis, flag, D, H, W);
+    return check_launch("aug_slab_project");
+}
+
+extern "C" int dram_aug_keep_region(const void* x, void* y, int elem_size, const int* boxes, const int* disk, const int* flag,
+                                    int n_table, int N, int C, int D, int H, int W, void* stream) {
+    DRAM_REQUIRE(x && y && boxes && disk && flag, "aug_keep_region: null pointer");
+    DRAM_REQUIRE(elem_size == 1 || elem_size == 4, "aug_keep_region: element size %d (supported: 4 = float32, 1 = uint8)",
+                 elem_size);
+    DRAM_REQUIRE(D > 0 && H > 0 && W > 0 && C > 0 && C <= 65535, "aug_keep_region: bad sizes");
+    int rc = check_batch("aug_keep_region", n_table, N, (int64_t)D * H * W);
+    if (rc) return rc;
+    hipStream_t st = (hipStream_t)stream;
+    if (elem_size == 4) launch_keep_region<float>(x, y, boxes, disk, flag, N, C, D, H, W, st);
+    else launch_keep_region<unsigned char>(x, y, boxes, disk, flag, N, C, D, H, W, st);
+    return check_launch("aug_keep_region");
 }
 
 extern "C" size_t dram_aug_row_mean_ws_bytes(int R, int64_t L) {

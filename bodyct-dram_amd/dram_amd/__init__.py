@@ -8,7 +8,9 @@ from . import _lib, functional, modules  # noqa: F401
 
 # the augmentation transforms of `augment`, importable from here; the module is loaded on first use
 _AUGMENT = ("GaussianBlur", "RandomMaskOut", "RandomFlip", "RandomRotate90", "GaussianAddictive", "IntensityInverse",
-            "GammaTransform", "ContrastStretchingTransform", "ContrastJitter", "EnsembleScanAugmentation")
+            "GammaTransform", "ContrastStretchingTransform", "ContrastJitter", "MinimalIntensityProjection",
+            "MaximumIntensityProjection", "MinimalIntensityAxialProjection", "DiskMaskOut", "RandomCubeMask", "RandomMoveAxis",
+            "RandomRotateInplane90", "EnsembleScanAugmentation")
 
 __all__ = ["_lib", "functional", "modules", *_AUGMENT]
 

@@ -9,7 +9,9 @@ through.  The work runs in per-batch launches of csrc/augment.hip over per-sampl
 
 Beside the pool's five, four more intensity transforms of data_transforms.py are here for pools of the user's own
 (`EnsembleScanAugmentation(aug_ratio, pool=[...])`): `IntensityInverse`, `GammaTransform`, `ContrastStretchingTransform` and
-`ContrastJitter`.
+`ContrastJitter`; the slab projections `MinimalIntensityProjection`, `MaximumIntensityProjection` and
+`MinimalIntensityAxialProjection`; the region masks `DiskMaskOut` and `RandomCubeMask`; and the axis moves `RandomMoveAxis` and
+`RandomRotateInplane90`.
 
 Drawing.  `draw(n, shape)` returns one parameter dict per sample, in sample order, from the same `random` / `numpy.random`
 calls in the same order as the reference's `__call__` makes for one chunk, so a seeded run picks what the reference would pick
@@ -29,6 +31,7 @@ from ._lib import call
 
 MAX_RADIUS = 4     # DRAM_AUG_MAX_RADIUS
 MAX_BOXES = 16     # DRAM_AUG_MAX_BOXES
+MAX_SLAB = 16      # DRAM_AUG_MAX_SLAB
 TRANSFORM, PASS, SKIP = 1, 0, -1   # per-sample flags of the C entries
 MAP_INVERSE, MAP_GAMMA, MAP_STRETCH, MAP_JITTER = 0, 1, 2, 3   # DRAM_AUG_MAP_*
 
@@ -56,6 +59,31 @@ def mask_boxes(centers, sizes, shape):
             row += [max(0, c - s // 2), min(c + (s - s // 2), dim)]
         rows.append(row)
     return rows
+
+
+def cube_box(center, size, shape):
+    """RandomCubeMask._mask's slices as one row (z0, z1, y0, y1, x0, x1), half-open: the box of `mask_boxes` for one centre."""
+    return mask_boxes([center], [size], shape)[0]
+
+
+def disk_table(shape):
+    """DiskMaskOut's disk in every z-slice as (cy, cx, r^2): centre (H // 2, W // 2), radius min(H, W) // 2, rim included."""
+    return [shape[1] // 2, shape[2] // 2, (min(shape[1], shape[2]) // 2) ** 2]
+
+
+def moveaxis_table(comb, shape):
+    """np.moveaxis(data, comb[0], comb[1]) for negative spatial axes as (perm, flip): the moved axis changes place with its
+    neighbours one after another ((-1, -3) is a 3-cycle: two transposes).  A move that changes the sample's shape cannot live in
+    a batch tensor."""
+    a, b = (v % 5 for v in comb)
+    if min(a, b) < 2:
+        raise ValueError(f"RandomMoveAxis: axes {tuple(comb)} are not spatial axes")
+    step = 1 if b > a else -1
+    perm, _ = HF.signed_permutation([("transpose", j, j + step) for j in range(a, b, step)])
+    if tuple(shape[k] for k in perm) != tuple(shape):
+        raise ValueError(f"moving axis {comb[0]} to {comb[1]} turns extents {tuple(shape)} into "
+                         f"{tuple(shape[k] for k in perm)}: it changes the sample's shape and cannot live in a batch tensor")
+    return perm, (0, 0, 0)
 
 
 def flip_table(axis):
@@ -179,6 +207,26 @@ def _permute_flip(x, perm, flip, flags, out=None):
     N, C, D, H, W = x.shape
     y = torch.empty_like(x) if out is None else out
     call("dram_aug_permute_flip", HF._p(x), HF._p(y), x.element_size(), HF._p(perm), HF._p(flip), HF._p(flags), flags.numel(),
+         N, C, D, H, W, HF._stream())
+    return y
+
+
+def slab_project(x, thickness, axis, is_max, flags, out=None):
+    """y[.., i, ..] = min (max when is_max) of x[.., max(0, i - t) .. i, ..] along the sample's axis (0 = z, 1 = y, 2 = x);
+    thickness, axis: [N] int32 device tables.  Not in place."""
+    N, _, D, H, W = x.shape
+    y = torch.empty_like(x) if out is None else out
+    call("dram_aug_slab_project", HF._p(x), HF._p(y), HF._p(thickness), HF._p(axis), int(bool(is_max)), HF._p(flags),
+         flags.numel(), N, D, H, W, HF._stream())
+    return y
+
+
+def keep_region(x, boxes, disk, flags, out=None):
+    """x inside the sample's half-open box (and disk, when its r^2 >= 0), 0 elsewhere; boxes [N, 6], disk [N, 3] int32 device
+    tables; fp32 or uint8; `out` may be x."""
+    N, C, D, H, W = x.shape
+    y = torch.empty_like(x) if out is None else out
+    call("dram_aug_keep_region", HF._p(x), HF._p(y), x.element_size(), HF._p(boxes), HF._p(disk), HF._p(flags), flags.numel(),
          N, C, D, H, W, HF._stream())
     return y
 
@@ -530,6 +578,143 @@ class ContrastJitter(_Augmentation):
         row_flags = flags if rows == 1 else flags.repeat_interleave(rows)
         minmax = row_minmax(x, rows, row_flags) if self.if_keep_range else None
         return _intensity_map(x, MAP_JITTER, minmax, row_mean(x, rows, row_flags), par, self.if_keep_range, row_flags, rows, out)
+
+
+class MinimalIntensityProjection(_Augmentation):
+    """A causal slab projection: voxel i along axis `angle` becomes the minimum of voxels max(0, i - slab_thickness) .. i, that
+    is slab_thickness + 1 voxels.  Two np.random.randint draws per sample: the thickness from `slab_thickness`, then the axis
+    from `angle` (0 = z, 1 = y, 2 = x).  The reference stores both draws in a copy of `meta`; `meta` passes through here."""
+    is_max = False
+
+    def __init__(self, slab_thickness=(3, 10), angle=(0, 3)):
+        self.slab_thickness = slab_thickness
+        self.angle = angle
+        self.epsilon = 1e-7
+
+    def draw_one(self, shape):
+        slab_thickness = np.random.randint(self.slab_thickness[0], self.slab_thickness[1])
+        angle = np.random.randint(self.angle[0], self.angle[1])
+        return {"slab_thickness": slab_thickness, "angle": angle}
+
+    def _tables(self, params, shape, device):
+        name, thickness, axis = type(self).__name__, [], []
+        for p in params:
+            t, a = (0, 0) if p is None else (int(p["slab_thickness"]), int(p.get("angle", 0)))
+            if not 0 <= t <= MAX_SLAB:
+                raise ValueError(f"{name}: slab_thickness {t} outside the supported 0..{MAX_SLAB}")
+            if not -3 <= a < 3:
+                raise ValueError(f"{name}: angle {a} is no axis of a 3-d sample")
+            thickness.append(t)
+            axis.append(a % 3)
+        return _dev(thickness, torch.int32, device), _dev(axis, torch.int32, device)
+
+    def _launch(self, x, tables, flags, out=None):
+        return slab_project(x, tables[0], tables[1], self.is_max, flags, out)
+
+
+class MaximumIntensityProjection(MinimalIntensityProjection):
+    """MinimalIntensityProjection with the maximum.  (The reference stores nothing in `meta` for this one.)"""
+    is_max = True
+
+
+class MinimalIntensityAxialProjection(MinimalIntensityProjection):
+    """MinimalIntensityProjection along z, one np.random.randint draw per sample.  The window is slab_thickness + 1 VOXELS, as
+    in the reference, whose `axial_thickness = int(slab_thickness / spacing[0])` is computed and never used.
+
+    Deviation from the reference: it reads meta['spacing'] for that unused value and stores it as 'axial_thickness' in the
+    caller's own meta; this class neither reads nor writes `meta`."""
+
+    def __init__(self, slab_thickness=(3, 10)):
+        self.slab_thickness = slab_thickness
+        self.epsilon = 1e-7
+
+    def draw_one(self, shape):
+        return {"slab_thickness": np.random.randint(self.slab_thickness[0], self.slab_thickness[1])}
+
+
+class DiskMaskOut(_Augmentation):
+    """Every z-slice of every '#' entry (fp32 and uint8) times the disk of centre (H // 2, W // 2) and radius min(H, W) // 2,
+    rim included; zero outside.  Draws nothing.  Only select_axis=-3 (the slices along z) and spatial_dim=3 are supported."""
+    intensity = False
+    pointwise = True
+
+    def __init__(self, select_axis=-3, spatial_dim=3):
+        self.spatial_dim = spatial_dim
+        self.select_axis = select_axis
+        if spatial_dim != 3 or select_axis != -3:
+            raise NotImplementedError(f"DiskMaskOut: select_axis={select_axis!r}, spatial_dim={spatial_dim!r} is not supported; "
+                                      f"supported: select_axis -3 with spatial_dim 3 (a disk in every z-slice)")
+
+    def draw_one(self, shape):
+        return {}
+
+    def _tables(self, params, shape, device):
+        whole = [0, shape[0], 0, shape[1], 0, shape[2]]
+        return (_dev([whole] * len(params), torch.int32, device), _dev([disk_table(shape)] * len(params), torch.int32, device))
+
+    def _launch(self, x, tables, flags, out=None):
+        return keep_region(x, tables[0], tables[1], flags, out)
+
+
+class RandomCubeMask(DiskMaskOut):
+    """Every '#' entry kept inside one box per sample and zeroed outside: sizes int(np.random.uniform(ratio, 1) * dim) per axis
+    (three draws), then the centre dim // 2 + int(np.random.uniform(-c * shift, c * shift)) per axis (three draws); the box is
+    [max(0, c - s // 2), min(c + (s - s // 2), dim)).
+
+    Deviation from the reference: its `__call__` raises KeyError('crop_sizes_ratio') after the work is done (it stores a meta
+    entry that was never made); this class returns the result."""
+
+    def __init__(self, shift_from_center, crop_sizes_ratio, spatial_dim=3):
+        self.shift_from_center = shift_from_center
+        self.crop_sizes_ratio = crop_sizes_ratio
+        self.spatial_dim = spatial_dim
+        assert (len(crop_sizes_ratio) == spatial_dim == len(shift_from_center))
+        if spatial_dim != 3:
+            raise NotImplementedError("RandomCubeMask: supported: spatial_dim 3")
+
+    def draw_one(self, shape):
+        crop_sizes_ratio = tuple([np.random.uniform(ratio, 1.0) for ratio in self.crop_sizes_ratio])
+        crop_sizes = tuple([int(cs * ds) for cs, ds in zip(crop_sizes_ratio, shape)])
+        center = np.asarray(shape) // 2
+        offset = tuple([int(np.random.uniform(-c * sh, c * sh)) for c, sh in zip(center, self.shift_from_center)])
+        shifted_center = tuple([int(c + offs) for c, offs in zip(center, offset)])
+        return {"shifted_center": shifted_center, "crop_sizes": crop_sizes}
+
+    def _tables(self, params, shape, device):
+        boxes = [[0] * 6 if p is None else cube_box(p["shifted_center"], p["crop_sizes"], shape) for p in params]
+        return _dev(boxes, torch.int32, device), _dev([[0, 0, -1]] * len(params), torch.int32, device)
+
+
+class RandomMoveAxis(RandomFlip):
+    """np.moveaxis(data, a, b) with (a, b) drawn from the pairs of (-1, ..., -spatial_dim), the same pair for every '#' entry of
+    a sample.  A move between unequal extents changes the sample's shape: ValueError."""
+
+    def __init__(self, spatial_dim):
+        self.spatial_dim = spatial_dim
+        if spatial_dim not in (2, 3):
+            raise NotImplementedError("RandomMoveAxis: supported: spatial_dim 2 or 3")
+
+    def draw_one(self, shape):
+        all_combs = list(itertools.combinations([-n for n in range(1, self.spatial_dim + 1)], 2))
+        return {"sampled_comb": tuple(random.sample(all_combs, 1)[0])}
+
+    def _table_one(self, p, shape):
+        return moveaxis_table(p["sampled_comb"], shape)
+
+
+class RandomRotateInplane90(RandomFlip):
+    """np.rot90 by 0..3 quarter turns in the (x, y) plane, axes (-1, -2); an odd count needs H == W (ValueError otherwise)."""
+
+    def __init__(self, spatial_dim):
+        self.spatial_dim = spatial_dim
+        if spatial_dim not in (2, 3):
+            raise NotImplementedError("RandomRotateInplane90: supported: spatial_dim 2 or 3")
+
+    def draw_one(self, shape):
+        return {"rotate_times": random.sample(range(4), 1)[0]}
+
+    def _table_one(self, p, shape):
+        return rotate_table((-1, -2), p["rotate_times"], shape)
 
 
 # -------------------------------------------------------------------------------------------------------------- ensemble

@@ -570,6 +570,22 @@ int dram_aug_row_mean(const float* x, float* mean, const int* flag, int R, int64
 int dram_aug_intensity_map(const float* x, float* y, int mode, const float* minmax, const float* mean, const float* params,
                            int keep_range, const int* flag, int n_table, int R, int64_t L, void* stream);
 
+/* Slab projections, region masks (dram/data_transforms.py:409-504, 639-678, 840-870); tables and flags as for the pool above.
+ *
+ * dram_aug_slab_project: MinimalIntensityProjection / MaximumIntensityProjection / MinimalIntensityAxialProjection `maip`: with
+ *   t = thickness[n] (0..DRAM_AUG_MAX_SLAB) and a = axis[n] (0 = z, 1 = y, 2 = x), y[.., i, ..] = min (is_max == 0) or max of
+ *   x[.., max(0, i - t) .. i, ..] along axis a: a causal window of t + 1 elements, clipped at the start of the axis; t = 0 copies.
+ *   x, y: [N, D, H, W] fp32.  Min and max are exact, so finite inputs give numpy's bits; which operand a NaN in the window yields
+ *   is unspecified (numpy propagates it, fminf / fmaxf drop it).  Not in place.
+ * dram_aug_keep_region: DiskMaskOut / RandomCubeMask._mask: y = x where the voxel (z, y, x) lies in the half-open box boxes[n] =
+ *   {z0, z1, y0, y1, x0, x1} and, when disk[n] = {cy, cx, r2} has r2 >= 0, also (y - cy)^2 + (x - cx)^2 <= r2; 0 elsewhere (an
+ *   empty box zeroes the sample).  x, y: [N, C, D, H, W], elem_size 4 (float32) or 1 (uint8).  y may be x. */
+#define DRAM_AUG_MAX_SLAB 16
+int dram_aug_slab_project(const float* x, float* y, const int* thickness, const int* axis, int is_max, const int* flag,
+                          int n_table, int N, int D, int H, int W, void* stream);
+int dram_aug_keep_region(const void* x, void* y, int elem_size, const int* boxes, const int* disk, const int* flag, int n_table,
+                         int N, int C, int D, int H, int W, void* stream);
+
 /* ---- device chunk loader: what the reference does per chunk on the host before a training step, for a whole ragged batch.
  *      RadboudCOVIDLobeVesselChunk.get_data (dram/dataset.py:450-486): w_scan = windowing(scan, to_span=(0, 1)) (utils.py:189-198,
  *      default span (-1150, 350)); _, th = binary_cam(w_scan[lobe > 0], 0.75) (utils.py:226-242); pseudo lesion = (w_scan > th) &
