@@ -435,6 +435,63 @@ __global__ void row_mean_kernel(const double* __restrict__ part, float* __restri
     mean[r] = (float)(s / (double)L);
 }
 
+// StandarizeChannel (data_transforms.py:873-899): a = x - x.mean(); a /= a.std(), float32 arrays.  Three launches: the row sums
+// above; then every block forms the row's mean from the partials (the order row_mean_kernel adds them in, so the same fp32 mean
+// in every block) and adds d = fp32(x - mean) and d * d in fp64, element to lane as in row_sum_kernel; then one thread per row
+// adds those partials in index order: std = sqrt(sum d^2 / L - (sum d / L)^2), numpy's population form of the centred values.
+__global__ __launch_bounds__(256) void row_sqdev_kernel(const float* __restrict__ x, const double* __restrict__ part,
+                                                        double* __restrict__ part2, const int* __restrict__ flag, int64_t L,
+                                                        int nblk) {
+    __shared__ double red[8];
+    __shared__ float mean_s;
+    const int r = blockIdx.y;
+    if (flag && flag[r] != 1) return;
+    if (threadIdx.x == 0) {
+        double s = 0.0;
+        for (int b = 0; b < nblk; ++b) s += part[(size_t)r * nblk + b];
+        mean_s = (float)(s / (double)L);
+    }
+    __syncthreads();
+    const float mean = mean_s;
+    const float* row = x + (int64_t)r * L;
+    const int64_t stride = (int64_t)nblk * 256;
+    double a[4] = {0.0, 0.0, 0.0, 0.0}, q[4] = {0.0, 0.0, 0.0, 0.0};
+    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < L; i += 4 * stride) {
+#pragma unroll
+        for (int u = 0; u < 4; ++u) {
+            const int64_t j = i + u * stride;
+            if (j < L) {
+                const double d = (double)__fsub_rn(row[j], mean);
+                a[u] += d;
+                q[u] += d * d;
+            }
+        }
+    }
+    const double sa = wave_sum_d((a[0] + a[1]) + (a[2] + a[3])), sq = wave_sum_d((q[0] + q[1]) + (q[2] + q[3]));
+    if ((threadIdx.x & 63) == 0) { red[threadIdx.x >> 6] = sa; red[4 + (threadIdx.x >> 6)] = sq; }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        part2[((size_t)r * nblk + blockIdx.x) * 2] = (red[0] + red[1]) + (red[2] + red[3]);
+        part2[((size_t)r * nblk + blockIdx.x) * 2 + 1] = (red[4] + red[5]) + (red[6] + red[7]);
+    }
+}
+
+__global__ void row_mean_std_kernel(const double* __restrict__ part, const double* __restrict__ part2, float* __restrict__ ms,
+                                    const int* __restrict__ flag, int R, int64_t L, int nblk) {
+    const int r = blockIdx.x * blockDim.x + threadIdx.x;
+    if (r >= R || (flag && flag[r] != 1)) return;
+    double s = 0.0, sa = 0.0, sq = 0.0;
+    for (int b = 0; b < nblk; ++b) {
+        s += part[(size_t)r * nblk + b];
+        sa += part2[((size_t)r * nblk + b) * 2];
+        sq += part2[((size_t)r * nblk + b) * 2 + 1];
+    }
+    const double md = sa / (double)L;
+    const double var = sq / (double)L - md * md;
+    ms[2 * r] = (float)(s / (double)L);
+    ms[2 * r + 1] = (float)sqrt(var > 0.0 ? var : 0.0);
+}
+
 // ---------------------------------------------------------------- point-wise intensity maps
 // IntensityInverse, GammaTransform, ContrastStretchingTransform and ContrastJitter (data_transforms.py:213-248, 279-362, 538-579)
 // with the reference's roundings: numpy keeps a float32 array float32 against Python scalars, so every step is one fp32
@@ -467,6 +524,7 @@ __device__ __forceinline__ MapCoef map_coef(const float* __restrict__ mm, const 
 
 template <int MODE>
 __device__ __forceinline__ float map_one(float v, const MapCoef& c) {
+    if (MODE == DRAM_AUG_MAP_STANDARDIZE) return __fdiv_rn(__fsub_rn(v, c.a), c.b);     // params = {mean, std} of the row
     if (MODE == DRAM_AUG_MAP_JITTER) {
         float t = __fadd_rn(__fmul_rn(__fsub_rn(v, c.mean), c.a), c.mean);
         if (c.keep) {
@@ -931,12 +989,36 @@ extern "C" int dram_aug_row_mean(const float* x, float* mean, const int* flag, i
     return check_launch("aug_row_mean");
 }
 
+extern "C" size_t dram_aug_row_mean_std_ws_bytes(int R, int64_t L) { return 3 * dram_aug_row_mean_ws_bytes(R, L); }
+
+extern "C" int dram_aug_row_mean_std(const float* x, float* mean_std, const int* flag, int R, int64_t L, void* ws,
+                                     size_t ws_bytes, void* stream) {
+    DRAM_REQUIRE(x && mean_std && ws, "aug_row_mean_std: null pointer");
+    DRAM_REQUIRE(R > 0 && R <= 65535 && L > 0 && L <= 0x7fffffff,
+                 "aug_row_mean_std: bad sizes (rows 1..65535, row length 1..2^31-1)");
+    DRAM_REQUIRE(((uintptr_t)ws & 7) == 0, "aug_row_mean_std: workspace must be 8-byte aligned");
+    if (ws_bytes < dram_aug_row_mean_std_ws_bytes(R, L)) {
+        set_error("aug_row_mean_std: workspace too small");
+        return DRAM_EWS;
+    }
+    hipStream_t st = (hipStream_t)stream;
+    const int nblk = mean_blocks(L);
+    double* part = (double*)ws;
+    double* part2 = part + (size_t)R * nblk;
+    hipLaunchKernelGGL(row_sum_kernel, dim3(nblk, R), dim3(256), 0, st, x, part, flag, L, nblk);
+    hipLaunchKernelGGL(row_sqdev_kernel, dim3(nblk, R), dim3(256), 0, st, x, (const double*)part, part2, flag, L, nblk);
+    hipLaunchKernelGGL(row_mean_std_kernel, dim3(cdiv(R, 256)), dim3(256), 0, st, (const double*)part, (const double*)part2,
+                       mean_std, flag, R, L, nblk);
+    return check_launch("aug_row_mean_std");
+}
+
 extern "C" int dram_aug_intensity_map(const float* x, float* y, int mode, const float* minmax, const float* mean,
                                       const float* params, int keep_range, const int* flag, int n_table, int R, int64_t L,
                                       void* stream) {
-    DRAM_REQUIRE(mode >= DRAM_AUG_MAP_INVERSE && mode <= DRAM_AUG_MAP_JITTER, "aug_intensity_map: unknown mode %d", mode);
-    const bool jitter = mode == DRAM_AUG_MAP_JITTER;
-    DRAM_REQUIRE(x && y && flag && (minmax || (jitter && !keep_range)) && (mean || !jitter) &&
+    DRAM_REQUIRE((mode >= DRAM_AUG_MAP_INVERSE && mode <= DRAM_AUG_MAP_JITTER) || mode == DRAM_AUG_MAP_STANDARDIZE,
+                 "aug_intensity_map: unknown mode %d", mode);
+    const bool jitter = mode == DRAM_AUG_MAP_JITTER, stand = mode == DRAM_AUG_MAP_STANDARDIZE;
+    DRAM_REQUIRE(x && y && flag && (minmax || stand || (jitter && !keep_range)) && (mean || !jitter) &&
                      (params || mode == DRAM_AUG_MAP_INVERSE),
                  "aug_intensity_map: null pointer");
     int rc = check_batch("aug_intensity_map", n_table, R, L);
@@ -951,6 +1033,9 @@ extern "C" int dram_aug_intensity_map(const float* x, float* y, int mode, const 
             break;
         case DRAM_AUG_MAP_STRETCH:
             launch_intensity_map<DRAM_AUG_MAP_STRETCH>(x, y, minmax, mean, params, flag, 0, R, L, st);
+            break;
+        case DRAM_AUG_MAP_STANDARDIZE:
+            launch_intensity_map<DRAM_AUG_MAP_STANDARDIZE>(x, y, nullptr, nullptr, params, flag, 0, R, L, st);
             break;
         default:
             launch_intensity_map<DRAM_AUG_MAP_JITTER>(x, y, minmax, mean, params, flag, keep_range != 0, R, L, st);

@@ -130,8 +130,13 @@ SIGNATURES = {
     "dram_aug_row_mean_ws_bytes": (Z, [I, L]),
     "dram_aug_row_mean": (I, [P, P, P, I, L, P, Z, P]),
     "dram_aug_intensity_map": (I, [P, P, I, P, P, P, I, P, I, I, L, P]),
+    "dram_aug_row_mean_std_ws_bytes": (Z, [I, L]),
+    "dram_aug_row_mean_std": (I, [P, P, P, I, L, P, Z, P]),
     "dram_aug_slab_project": (I, [P, P, P, P, I, P, I, I, I, I, I, P]),
     "dram_aug_keep_region": (I, [P, P, I, P, P, P, I, I, I, I, I, I, P]),
+    "dram_aug_pad_min_ws_bytes": (Z, [I, I, I, I, I]),
+    "dram_aug_pad_min": (I, [P, I, P, I, I, I, I, P, Z, P]),
+    "dram_aug_crop_resample": (I, [P, P, I, I, P, P, Z, P, I, I, I, I, I, P]),
     # device chunk loader
     "dram_chunk_hist256": (I, [P, P, P, I, P, I, I, P]),
     "dram_otsu256": (I, [P, I, ctypes.c_double, P, P]),

@@ -11,7 +11,8 @@ Beside the pool's five, four more intensity transforms of data_transforms.py are
 (`EnsembleScanAugmentation(aug_ratio, pool=[...])`): `IntensityInverse`, `GammaTransform`, `ContrastStretchingTransform` and
 `ContrastJitter`; the slab projections `MinimalIntensityProjection`, `MaximumIntensityProjection` and
 `MinimalIntensityAxialProjection`; the region masks `DiskMaskOut` and `RandomCubeMask`; and the axis moves `RandomMoveAxis` and
-`RandomRotateInplane90`.
+`RandomRotateInplane90`; the scale-and-translate augmentation `RandomCrop` (pad, crop, resample back to the chunk's size); and
+`StandarizeChannel`.
 
 Drawing.  `draw(n, shape)` returns one parameter dict per sample, in sample order, from the same `random` / `numpy.random`
 calls in the same order as the reference's `__call__` makes for one chunk, so a seeded run picks what the reference would pick
@@ -33,7 +34,13 @@ MAX_RADIUS = 4     # DRAM_AUG_MAX_RADIUS
 MAX_BOXES = 16     # DRAM_AUG_MAX_BOXES
 MAX_SLAB = 16      # DRAM_AUG_MAX_SLAB
 TRANSFORM, PASS, SKIP = 1, 0, -1   # per-sample flags of the C entries
-MAP_INVERSE, MAP_GAMMA, MAP_STRETCH, MAP_JITTER = 0, 1, 2, 3   # DRAM_AUG_MAP_*
+MAP_INVERSE, MAP_GAMMA, MAP_STRETCH, MAP_JITTER, MAP_STANDARDIZE = 0, 1, 2, 3, 5   # DRAM_AUG_MAP_*
+PAD_MODES = {"constant": 0, "edge": 1, "minimum": 2}     # DRAM_AUG_PAD_*
+MAX_W = 2048       # csrc/crop.hip CROP_MAX_W / PAD_MAX_DIM
+# one record per sample (csrc/crop.hip: CropRec): window start (z, y, x), actual crop size, pad mode, output-to-crop index steps
+CROP_DTYPE = np.dtype([("z0", "<i4"), ("y0", "<i4"), ("x0", "<i4"), ("cd", "<i4"), ("ch", "<i4"), ("cw", "<i4"),
+                       ("mode", "<i4"), ("pad", "<i4"), ("sz", "<f8"), ("sy", "<f8"), ("sx", "<f8")])
+assert CROP_DTYPE.itemsize == 56
 
 
 # ---------------------------------------------------------------------------------------------------------------- tables
@@ -99,6 +106,28 @@ def rotate_table(axis, times, shape):
         raise ValueError(f"a rotation by {times} quarter turns in a plane of unequal extents {shape[a - 2]} x {shape[b - 2]} "
                          f"changes the sample's shape and cannot live in a batch tensor (cubic chunks only)")
     return HF.signed_permutation(HF.rot90_ops(times, (a, b)))
+
+
+def crop_window(params, shape):
+    """RandomCrop._crop's slice in chunk coordinates: (start, size) per axis.  The reference pads by `padding` and slices
+    [cc - s // 2 + p0 : cc + (s - s // 2) + p0]; the upper pad is max(0, cc + s // 2 - dim), so for an odd s that reaches the
+    top edge the slice runs one past the padded array and numpy truncates it: the crop is then one voxel shorter than
+    `crop_sizes`.  `start` is negative where the window begins in the lower pad."""
+    start, size = [], []
+    for cc, s, (p0, p1), dim in zip(params["shifted_center"], params["crop_sizes"], params["padding"], shape):
+        lo = cc - s // 2
+        hi = min(cc + (s - s // 2), dim + p1)
+        start.append(int(lo))
+        size.append(int(hi - lo))
+    return tuple(start), tuple(size)
+
+
+def pad_crop(x, params, mode="minimum"):
+    """The reference's pad and slice of one [D, H, W] array in numpy (RandomCrop._crop), for the tests and the bench."""
+    padding = [tuple(int(v) for v in p) for p in params["padding"]]
+    padded = np.pad(x, padding, mode=mode)
+    start, size = crop_window(params, x.shape)
+    return padded[tuple(slice(st + p[0], st + p[0] + sz) for st, sz, p in zip(start, size, padding))]
 
 
 def _dev(values, dtype, device):
@@ -231,6 +260,38 @@ def keep_region(x, boxes, disk, flags, out=None):
     return y
 
 
+def pad_min(x, flags):
+    """(workspace, bytes) of dram_aug_pad_min: the min projections np.pad(mode='minimum') needs, for the samples whose flag is
+    TRANSFORM; fp32 or uint8."""
+    N, _, D, H, W = x.shape
+    nbytes = _lib.lib.dram_aug_pad_min_ws_bytes(N, D, H, W, x.element_size())
+    ws = torch.empty(nbytes, dtype=torch.uint8, device=x.device)
+    call("dram_aug_pad_min", HF._p(x), x.element_size(), HF._p(flags), N, D, H, W, HF._p(ws), nbytes, HF._stream())
+    return ws, nbytes
+
+
+def crop_resample(x, table, flags, linear, pad_ws=None, out=None):
+    """The window of every sample (table: N CROP_DTYPE records as a uint8 device tensor) stretched back to (D, H, W); `pad_ws`:
+    what `pad_min` returned, for the samples that pad with 'minimum'.  Not in place."""
+    N, _, D, H, W = x.shape
+    y = torch.empty_like(x) if out is None else out
+    ws, nbytes = pad_ws if pad_ws is not None else (None, 0)
+    call("dram_aug_crop_resample", HF._p(x), HF._p(y), x.element_size(), int(bool(linear)), HF._p(table), HF._p(ws), nbytes,
+         HF._p(flags), flags.numel(), N, D, H, W, HF._stream())
+    return y
+
+
+def row_mean_std(x, rows, flags=None):
+    """[N * rows, 2] fp32 {mean, std} of every row: fp64 sums in a fixed order (deterministic), the std of the centred fp32
+    values in numpy's population form; `flags` per row."""
+    R, L = _rows(x, rows)
+    ms = torch.empty((R, 2), dtype=torch.float32, device=x.device)
+    nbytes = _lib.lib.dram_aug_row_mean_std_ws_bytes(R, L)
+    ws = HF._ws(nbytes, x.device)
+    call("dram_aug_row_mean_std", HF._p(x), HF._p(ms), HF._p(flags), R, L, HF._p(ws), nbytes, HF._stream())
+    return ms
+
+
 def gaussian_noise(x, minmax, sigma, seeds, noise=None):
     """The noise kernel with explicit tables (every sample active): x [N, ...] fp32, minmax [N, 2] device tensor, sigma and
     seeds sequences of N.  `noise`: optional [N, ...] float64 device tensor used instead of the in-kernel generator."""
@@ -276,6 +337,10 @@ class _Augmentation:
     def _launch(self, x, tables, flags, out=None):   # pragma: no cover - overridden
         raise NotImplementedError
 
+    def _launch_key(self, key, x, tables, flags, out=None, **kw):
+        """`_launch` for the entry `key` of the sample dict (for the transforms that treat keys differently)."""
+        return self._launch(x, tables, flags, out, **kw)
+
     def apply(self, sample, params):
         """`params`: one entry per sample (a dict as `draw` returns it, or None = leave the sample untouched)."""
         out, tables = {}, None
@@ -290,7 +355,7 @@ class _Augmentation:
             if tables is None:
                 tables = self._tables(params, tuple(v.shape[2:]), v.device)
                 flags = _flags(params, v.device)
-            out[key] = self._launch(v, tables, flags).view(shape)
+            out[key] = self._launch_key(key, v, tables, flags).view(shape)
         return out
 
     def __call__(self, sample):
@@ -717,6 +782,126 @@ class RandomRotateInplane90(RandomFlip):
         return rotate_table((-1, -2), p["rotate_times"], shape)
 
 
+class RandomCrop(_Augmentation):
+    """A window of every '#' entry, padded where it leaves the chunk, stretched back to the chunk's size.  Six
+    np.random.uniform draws per sample: the window's size int(U(ratio, 1) * dim) per axis, then its centre dim // 2 +
+    int(U(-c * shift, c * shift)) per axis; `padding` is what np.pad gets ((max(0, s // 2 - cc), max(0, cc + s // 2 - dim))), and
+    the window is `crop_window(params, shape)`.  keep_size=True then runs Resample('fixed_size', 1, shape) on the crop: linear for
+    the image, nearest neighbour for every key with 'reference' or 'weight_map' in its name, on the grid of `ChunkLoader`
+    (`preprocess.resample_plan`; output voxel o reads crop index o * crop / dim, and is 0 from crop - 0.5 on: an axis cropped to
+    less than half ends in zeros, as ITK leaves it).  A parameter dict may carry "spacing" (default (1.0, 1.0, 1.0)), the
+    sample's meta['spacing'], from which the steps are formed as the reference forms them.  Padding modes 'minimum', 'constant'
+    and 'edge'.  `meta` passes through: the reference's entries (the draws, 'size', 'spacing') are not written."""
+    intensity = False
+
+    def __init__(self, shift_from_center, crop_sizes_ratio, spatial_dim=3, padding_mode='minimum', keep_size=True):
+        self.shift_from_center = shift_from_center
+        self.crop_sizes_ratio = crop_sizes_ratio
+        self.spatial_dim = spatial_dim
+        self.padding_mode = padding_mode
+        self.keep_size = keep_size
+        assert (len(crop_sizes_ratio) == spatial_dim == len(shift_from_center))
+        if spatial_dim != 3:
+            raise NotImplementedError("RandomCrop: supported: spatial_dim 3")
+        if padding_mode not in PAD_MODES:
+            raise NotImplementedError(f"RandomCrop: padding_mode={padding_mode!r} is not supported; supported: "
+                                      f"{', '.join(sorted(PAD_MODES))}")
+        if not keep_size:
+            raise ValueError("RandomCrop: keep_size=False changes the sample's shape and cannot live in a batch tensor")
+
+    def draw_one(self, shape):
+        crop_sizes_ratio = tuple([float(np.random.uniform(ratio, 1.0)) for ratio in self.crop_sizes_ratio])
+        crop_sizes = tuple([int(cs * ds) for cs, ds in zip(crop_sizes_ratio, shape)])
+        center = np.asarray(shape) // 2
+        offset = tuple([int(np.random.uniform(-c * sh, c * sh)) for c, sh in zip(center, self.shift_from_center)])
+        shifted_center = tuple([int(c + offs) for c, offs in zip(center, offset)])
+        padding = [(int(max(0, si // 2 - cc)), int(max(0, cc + si // 2 - sh)))
+                   for sh, si, cc in zip(shape, crop_sizes, shifted_center)]
+        return {"crop_sizes_ratio": crop_sizes_ratio, "crop_sizes": crop_sizes, "offset": offset,
+                "shifted_center": shifted_center, "padding": padding}
+
+    def _tables(self, params, shape, device):
+        from .preprocess import resample_plan
+        if shape[2] > MAX_W or shape[1] > MAX_W:
+            raise ValueError(f"RandomCrop: rows and columns of up to {MAX_W} voxels, got {tuple(shape)}")
+        table = np.zeros(len(params), dtype=CROP_DTYPE)
+        pads = []
+        for i, p in enumerate(params):
+            if p is None:
+                table[i] = (0, 0, 0) + tuple(shape) + (0, 0, 1.0, 1.0, 1.0)
+                pads.append(False)
+                continue
+            start, size = crop_window(p, shape)
+            if min(size) <= 0:
+                raise ValueError(f"RandomCrop: sample {i}: empty crop {size}")
+            spacing = np.asarray(p.get("spacing", (1.0, 1.0, 1.0)), dtype=np.float64)
+            req, new_size = resample_plan("fixed_size", 1, list(shape), spacing, size)
+            step = [float(req[a]) / float(spacing[a]) for a in range(3)]
+            if tuple(new_size) != tuple(shape) or not all(np.isfinite(v) and v > 0 for v in step):
+                raise ValueError(f"RandomCrop: sample {i}: resampling steps {step}")
+            table[i] = start + size + (PAD_MODES[self.padding_mode], 0) + tuple(step)
+            pads.append(self.padding_mode == "minimum" and
+                        any(st < 0 or st + sz > dim for st, sz, dim in zip(start, size, shape)))
+        tab = torch.from_numpy(table.view(np.uint8).copy())
+        if torch.device(device).type == "cuda":
+            tab = tab.pin_memory().to(device, non_blocking=True)
+        return tab, pads
+
+    def _launch(self, x, tables, flags, out=None):     # pragma: no cover - the key decides the interpolation
+        raise NotImplementedError("RandomCrop works per key: _launch_key")
+
+    def _launch_key(self, key, x, tables, flags, out=None):
+        table, pads = tables
+        linear = not ("reference" in key or "weight_map" in key)
+        if x.shape[1] != 1:
+            raise NotImplementedError(f"RandomCrop: '{key}': single-channel samples only, got shape {tuple(x.shape)}")
+        if linear and x.dtype != torch.float32:
+            raise NotImplementedError(f"RandomCrop: '{key}' is {x.dtype} and would be resampled linearly; linear interpolation "
+                                      f"is built for float32 (nearest neighbour: keys with 'reference' or 'weight_map')")
+        ws = None
+        if any(pads):
+            # SKIP samples of an ensemble launch (flag < 0) take no part: their flag is not TRANSFORM
+            ws = pad_min(x, flags * _dev([1 if p else 0 for p in pads], torch.int32, x.device))
+        return crop_resample(x, table, flags, linear, ws, out)
+
+
+class StandarizeChannel(_Augmentation):
+    """a = a.astype(float32); a = a - a.mean(); a /= a.std() on every '#...image...' entry: [N, D, H, W] and [N, 1, D, H, W] per
+    sample, [N, C, D, H, W] with ch_dim == 0 per (sample, channel) -- the reference's 4-d sample [C, D, H, W] taken along its
+    first axis.  Draws nothing.  The mean and the std come from fp64 sums (numpy adds float32 pairwise): results agree with
+    the reference to a few fp32 steps, not bit for bit.  A constant sample (std 0) divides by zero, as in the reference."""
+    pointwise = True
+
+    def __init__(self, ch_dim):
+        self.ch_dim = ch_dim
+
+    def draw_one(self, shape):
+        return {}
+
+    def _tables(self, params, shape, device):
+        return None
+
+    def apply(self, sample, params):
+        out = {}
+        for key, value in sample.items():
+            if not self._touches(key):
+                out[key] = value
+                continue
+            v, shape = _as_batch(value, key)
+            if len(params) != v.shape[0]:
+                raise ValueError(f"StandarizeChannel: {len(params)} parameter sets for a batch of {v.shape[0]}")
+            C = v.shape[1]
+            if C != 1 and self.ch_dim != 0:
+                raise NotImplementedError(f"StandarizeChannel: ch_dim={self.ch_dim!r} on a multi-channel tensor {shape} is not "
+                                          f"supported; supported: ch_dim 0 (per sample and channel)")
+            flags = _dev([TRANSFORM if p is not None else PASS for p in params for _ in range(C)], torch.int32, v.device)
+            out[key] = self._launch(v, None, flags, rows=C).view(shape)
+        return out
+
+    def _launch(self, x, tables, flags, out=None, rows=1):
+        return _intensity_map(x, MAP_STANDARDIZE, None, None, row_mean_std(x, rows, flags), False, flags, rows, out)
+
+
 # -------------------------------------------------------------------------------------------------------------- ensemble
 class EnsembleScanAugmentation:
     """The reference's `_T` (job_runner.py:556-579) on a batch: per sample one of the 120 orders of the pool
@@ -795,9 +980,9 @@ class EnsembleScanAugmentation:
                     flags = _dev([TRANSFORM if i in group else SKIP for i in range(N)], torch.int32, device)
                     if t.uses_minmax:
                         sample_minmax(bufs[s], flags, out=minmax)
-                        t._launch(bufs[s], tables, flags, out=bufs[d], minmax=minmax)
+                        t._launch_key(key, bufs[s], tables, flags, out=bufs[d], minmax=minmax)
                     else:
-                        t._launch(bufs[s], tables, flags, out=bufs[d])
+                        t._launch_key(key, bufs[s], tables, flags, out=bufs[d])
                     for i in group:
                         where[i] = d
         ident = (_dev([[0, 1, 2]] * N, torch.int32, device), _dev([[0, 0, 0]] * N, torch.int32, device))

@@ -559,14 +559,24 @@ int dram_aug_permute_flip(const void* x, void* y, int elem_size, const int* perm
  *   DRAM_AUG_MAP_GAMMA (GammaTransform, 279-315):      t ** params[r][0] * range + min
  *   DRAM_AUG_MAP_STRETCH (ContrastStretchingTransform, 318-362): 1 / (1 + (params[r][1] / (t + 1e-7)) ** params[r][0]) * range + min
  *   DRAM_AUG_MAP_JITTER (ContrastJitter, 538-579):     (x - mean[r]) * params[r][0] + mean[r], clamped to [min, max] when keep_range
+ *   DRAM_AUG_MAP_STANDARDIZE (StandarizeChannel, 873-899): (x - params[r][0]) / params[r][1], params = dram_aug_row_mean_std's
+ *     output; minmax and mean unused.  (The value 4 is no mode and stays rejected.)
  *   params: [R][2] fp32 {factor, middle point}; mean: [R] fp32 (dram_aug_row_mean), jitter only; minmax may be NULL for a jitter
- *   without keep_range.  y may be x. */
+ *   without keep_range.  y may be x.
+ * dram_aug_row_mean_std: mean_std[r] = {fp32 mean as dram_aug_row_mean, fp32 std of d = fp32(x - mean): sqrt(sum d^2 / L -
+ *   (sum d / L)^2)}, fp64 sums added in a fixed order (deterministic, the same bits wherever the row stands); a constant row has
+ *   std 0.  flag may be NULL; rows whose flag is not 1 are left as they are.  ws: dram_aug_row_mean_std_ws_bytes(R, L) bytes,
+ *   8-byte aligned. */
 #define DRAM_AUG_MAP_INVERSE 0
 #define DRAM_AUG_MAP_GAMMA 1
 #define DRAM_AUG_MAP_STRETCH 2
 #define DRAM_AUG_MAP_JITTER 3
+#define DRAM_AUG_MAP_STANDARDIZE 5
 size_t dram_aug_row_mean_ws_bytes(int R, int64_t L);
 int dram_aug_row_mean(const float* x, float* mean, const int* flag, int R, int64_t L, void* ws, size_t ws_bytes, void* stream);
+size_t dram_aug_row_mean_std_ws_bytes(int R, int64_t L);
+int dram_aug_row_mean_std(const float* x, float* mean_std, const int* flag, int R, int64_t L, void* ws, size_t ws_bytes,
+                          void* stream);
 int dram_aug_intensity_map(const float* x, float* y, int mode, const float* minmax, const float* mean, const float* params,
                            int keep_range, const int* flag, int n_table, int R, int64_t L, void* stream);
 
@@ -585,6 +595,35 @@ int dram_aug_slab_project(const float* x, float* y, const int* thickness, const 
                           int n_table, int N, int D, int H, int W, void* stream);
 int dram_aug_keep_region(const void* x, void* y, int elem_size, const int* boxes, const int* disk, const int* flag, int n_table,
                          int N, int C, int D, int H, int W, void* stream);
+
+/* RandomCrop(keep_size=True) (dram/data_transforms.py:582-636): np.pad where the drawn window leaves the chunk, the window sliced
+ * out, then Resample('fixed_size', 1, data_shape) back to the chunk's size on the ITK grid of dram_chunk_prepare.  x, y:
+ * [N, D, H, W], elem_size 4 (float32) or 1 (uint8); W <= 2048, D <= 65535, D*H*W < 2^29.
+ *
+ * dram_aug_pad_min: what np.pad(mode='minimum') puts outside the chunk: the sample's minimum over every non-empty subset of its
+ *   axes, the other coordinates held fixed (np.pad pads axis by axis with the minimum along that axis of the array as padded so
+ *   far).  Per sample, in elements: Pz [H][W], Py [D][W], Px [D][H], Pzy [W], Pzx [H], Pyx [D], Pzyx [1], rounded up to a multiple
+ *   of four.  Only samples whose flag is 1 are read and written.  Exact in any order; which operand a NaN yields is unspecified.
+ *   ws: dram_aug_pad_min_ws_bytes(N, D, H, W, elem_size) bytes, 16-byte aligned; H, W <= 2048.  Three launches.
+ * dram_aug_crop_resample: table: N records of 56 bytes on the DEVICE, {int z0, y0, x0: the window's first voxel in chunk
+ *   coordinates, negative where it starts in the pad; int cd, ch, cw: the crop's actual size; int mode (DRAM_AUG_PAD_*); int pad;
+ *   double sz, sy, sx: required_spacing / spacing, the output-to-crop index step}.  Output voxel o reads crop index c = o * step
+ *   per axis; 0 where c >= size - 0.5; linear != 0: fp64 lerps along x, y, z with the upper neighbour clamped to the crop, cast
+ *   to fp32 (float32 only); otherwise the voxel at (int)(c + 0.5).  A crop voxel outside the chunk is 0 (CONSTANT), the chunk's
+ *   voxel at the clamped coordinate (EDGE) or pad_ws's projection (MINIMUM; pad_ws = dram_aug_pad_min of x).  flag as above: 0
+ *   copies the sample.  Not in place.
+ *   THE CALLER'S RESPONSIBILITY: the modes live in the device table, which the host side of this entry cannot read, so it
+ *   cannot tell whether a workspace is needed.  pad_ws may be NULL only when no MINIMUM sample's window leaves the chunk; a
+ *   MINIMUM sample that does pad without a workspace gets 0 there (wrong values, no error), and a workspace must have been
+ *   filled by dram_aug_pad_min for every such sample (flag 1 there) of this very x. */
+#define DRAM_AUG_PAD_CONSTANT 0
+#define DRAM_AUG_PAD_EDGE 1
+#define DRAM_AUG_PAD_MINIMUM 2
+size_t dram_aug_pad_min_ws_bytes(int N, int D, int H, int W, int elem_size);
+int dram_aug_pad_min(const void* x, int elem_size, const int* flag, int N, int D, int H, int W, void* ws, size_t ws_bytes,
+                     void* stream);
+int dram_aug_crop_resample(const void* x, void* y, int elem_size, int linear, const void* table, const void* pad_ws,
+                           size_t pad_ws_bytes, const int* flag, int n_table, int N, int D, int H, int W, void* stream);
 
 /* ---- device chunk loader: what the reference does per chunk on the host before a training step, for a whole ragged batch.
  *      RadboudCOVIDLobeVesselChunk.get_data (dram/dataset.py:450-486): w_scan = windowing(scan, to_span=(0, 1)) (utils.py:189-198,
