@@ -7,7 +7,7 @@
 //
 // Every table carries a per-sample flag:  1 = transform,  0 = pass through (copied when y != x),  < 0 = skip the sample
 // (y is not written: the ensemble driver keeps samples in different buffers and moves only the ones a launch is for).
-#include "common.h"
+#include "volume_math.h"
 #include <math.h>
 
 namespace dram {
@@ -16,19 +16,8 @@ namespace {
 constexpr int AUG_MAX_RADIUS = DRAM_AUG_MAX_RADIUS;
 constexpr int AUG_MAX_BOXES = DRAM_AUG_MAX_BOXES;
 
-inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
-
 // ---------------------------------------------------------------- per-sample min / max
-// Floats mapped to unsigned ints of the same order: integer atomicMin / atomicMax are exact, associative and commutative,
-// so the result does not depend on which block arrives first.
-__device__ __forceinline__ unsigned order_enc(float f) {
-    const unsigned u = __float_as_uint(f);
-    return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-}
-__device__ __forceinline__ float order_dec(unsigned e) {
-    return __uint_as_float((e & 0x80000000u) ? (e & 0x7fffffffu) : ~e);
-}
-
+// Through the order keys of volume_math.h, so that the result does not depend on which block arrives first.
 __global__ void minmax_init_kernel(unsigned* mm, const int* flag, int N) {
     const int n = blockIdx.x * blockDim.x + threadIdx.x;
     if (n >= N || (flag && flag[n] != 1)) return;
@@ -69,8 +58,8 @@ __global__ __launch_bounds__(256) void minmax_kernel(const float* __restrict__ x
     if (threadIdx.x == 0) {
         lo = fminf(fminf(red[0], red[1]), fminf(red[2], red[3]));
         hi = fmaxf(fmaxf(red[4], red[5]), fmaxf(red[6], red[7]));
-        atomicMin(&mm[2 * n], order_enc(lo));
-        atomicMax(&mm[2 * n + 1], order_enc(hi));
+        atomicMin(&mm[2 * n], Key<float>::enc(lo));
+        atomicMax(&mm[2 * n + 1], Key<float>::enc(hi));
     }
 }
 
@@ -78,7 +67,7 @@ __global__ void minmax_decode_kernel(unsigned* mm, const int* flag, int N) {
     const int n = blockIdx.x * blockDim.x + threadIdx.x;
     if (n >= N || (flag && flag[n] != 1)) return;
     float* out = reinterpret_cast<float*>(mm);
-    const float lo = order_dec(mm[2 * n]), hi = order_dec(mm[2 * n + 1]);
+    const float lo = Key<float>::dec(mm[2 * n]), hi = Key<float>::dec(mm[2 * n + 1]);
     out[2 * n] = lo;
     out[2 * n + 1] = hi;
 }

@@ -50,6 +50,7 @@ inline int ensure_dynamic_lds(const void* fn, size_t bytes, LdsAttrOnce& once, c
 inline size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
 inline int cdiv(int a, int b) { return (a + b - 1) / b; }
 inline int64_t cdiv64(int64_t a, int64_t b) { return (a + b - 1) / b; }
+inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
 
 // Output channels that the 1x1x1 conv kernels (head.hip) handle per pass; the head policy of the norm backward (norm.hip) forms
 // that conv's input gradient itself for up to one pass of them.

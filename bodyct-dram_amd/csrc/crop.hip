@@ -3,7 +3,7 @@
 // The reference (dram/data_transforms.py:582-636) pads every "#" array with np.pad(mode=padding_mode) where the drawn window
 // leaves the chunk, slices the window out and hands it to Resample('fixed_size', 1, data_shape) (data_transforms.py:170-175 ->
 // utils.resample, utils.py:414-434): linear for the image, nearest neighbour for every "reference" / "weight_map" key, on the
-// grid of sitk.ResampleImageFilter as chunk_prepare (prep.hip) restates it.  Here the crop is never materialised: an output voxel
+// grid of sitk.ResampleImageFilter (volume_math.h).  Here the crop is never materialised: an output voxel
 // maps to a crop index, the crop index plus the window's start is a chunk coordinate, and a coordinate outside the chunk takes the
 // value np.pad would have put there:
 //   'constant'  0
@@ -12,7 +12,7 @@
 //               holds the minimum of the chunk over exactly the axes in which it lies outside, the other coordinates held fixed.
 //               Those seven projections (over z, y, x, zy, zx, yx, zyx) come from a pre-pass, pad_min, into a workspace.
 // Two entry points, neither of which synchronises, allocates or reads per-sample data from the host.
-#include "common.h"
+#include "volume_math.h"
 #include <limits.h>
 #include <math.h>
 
@@ -31,24 +31,6 @@ struct CropRec {                        // 56 bytes, mirrored by dram_amd/augmen
     double sz, sy, sx;                  // output-to-crop index step per axis (required_spacing / spacing)
 };
 static_assert(sizeof(CropRec) == 56, "CropRec is part of the ABI");
-
-// Elements mapped to unsigned keys of the same order, so that one integer min serves fp32 and uint8 (and LDS atomics are exact).
-template <typename T> struct Key;
-template <> struct Key<float> {
-    static __device__ __forceinline__ unsigned enc(float f) {
-        const unsigned u = __float_as_uint(f);
-        return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-    }
-    static __device__ __forceinline__ float dec(unsigned e) {
-        return __uint_as_float((e & 0x80000000u) ? (e & 0x7fffffffu) : ~e);
-    }
-};
-template <> struct Key<unsigned char> {
-    static __device__ __forceinline__ unsigned enc(unsigned char v) { return v; }
-    static __device__ __forceinline__ unsigned char dec(unsigned e) { return (unsigned char)e; }
-};
-constexpr unsigned KEY_TOP = 0xffffffffu;
-__device__ __forceinline__ unsigned umin_(unsigned a, unsigned b) { return a < b ? a : b; }
 
 // ---------------------------------------------------------------- pad_min: the seven min projections of a sample
 // Workspace of one sample, in elements of T: Pz [H][W] (min over z), Py [D][W], Px [D][H], Pzy [W], Pzx [H], Pyx [D], Pzyx [1].
@@ -169,25 +151,19 @@ struct CropArgs {
     int D, H, W, rows;
 };
 
-// One axis of the ITK grid (prep_axis of prep.hip) in crop indices, then shifted to chunk coordinates: c = o * step with the
-// product rounded on its own; inside while c < size - 0.5; linear: base = floor(c), upper neighbour clamped to the crop's last
-// voxel, t = 0 where they coincide; nearest = (int)(c + 0.5) (Math::RoundHalfIntegerUp).  'edge' clamps the chunk coordinate
-// here, once per table entry, so that its fetches are plain reads.
+// One axis of the ITK grid (itk_axis, volume_math.h) in crop indices, c = o * step: the linear pair or, twice, the nearest voxel,
+// shifted by the window's start to chunk coordinates.  'edge' clamps the chunk coordinate here, once per table entry, so that
+// its fetches are plain reads.
 template <bool LINEAR>
 __device__ __forceinline__ void crop_axis(int o, double step, int size, int start, int dim, int mode, int& i0, int& i1, double& t) {
-#pragma clang fp contract(off)
-    const double c = (double)o * step;
-    t = 0.0;
-    if (!(c < (double)size - 0.5)) {                           // (also NaN, an empty crop and every c that would overflow an int)
+    const ItkAxis g = itk_axis(mul_rn((double)o, step), size);
+    t = LINEAR ? g.t : 0.0;
+    if (!g.inside) {                                           // (also NaN and an empty crop)
         i0 = i1 = CROP_OUT;
         return;
     }
-    int a = LINEAR ? (int)c : (int)(c + 0.5);
-    a = a > size - 1 ? size - 1 : a;
-    int b = LINEAR && a + 1 <= size - 1 ? a + 1 : a;
-    if (b != a) t = c - (double)a;
-    a += start;
-    b += start;
+    int a = (LINEAR ? g.lo : g.nearest) + start;
+    int b = (LINEAR ? g.hi : g.nearest) + start;
     if (mode == DRAM_AUG_PAD_EDGE) {
         a = a < 0 ? 0 : (a > dim - 1 ? dim - 1 : a);
         b = b < 0 ? 0 : (b > dim - 1 ? dim - 1 : b);
@@ -201,8 +177,8 @@ __device__ __forceinline__ void crop_axis(int o, double step, int size, int star
 // span in groups of 16 bytes aligned in the OUTPUT'S ADDRESS (the base's misalignment in elements is added to the element index
 // before it is cut into groups): a group inside the span is one 16-byte store, the ragged ends go element by element, so any W
 // and any base address take this one path.  Per output voxel: 8 source fetches (linear) or 1 (nearest), gathered through the
-// caches; a fetch outside the chunk reads the pad value instead (file comment).  fp64 lerps along x, then y, then z, each
-// p + (q - p) * t with no contraction, cast to the element type: the bits of oracle.resample_itk.
+// caches; a fetch outside the chunk reads the pad value instead (file comment).  fp64 lerps along x, then y, then z (lerp_rn,
+// volume_math.h), cast to the element type: the bits of oracle.resample_itk.
 template <typename T, bool LINEAR>
 __global__ __launch_bounds__(256) void crop_resample_kernel(CropArgs a) {
 #pragma clang fp contract(off)
@@ -260,16 +236,11 @@ __global__ __launch_bounds__(256) void crop_resample_kernel(CropArgs a) {
         const CropX q = xt[x];
         if (p.z0 == CROP_OUT || p.y0 == CROP_OUT || q.x0 == CROP_OUT) return (T)0;
         if (!LINEAR) return fetch(p.z0, p.y0, q.x0);
-        auto lerp = [](double u, double v, double t) {
-#pragma clang fp contract(off)
-            const double pr = (v - u) * t;
-            return u + pr;
-        };
-        const double v00 = lerp((double)fetch(p.z0, p.y0, q.x0), (double)fetch(p.z0, p.y0, q.x1), q.tx);
-        const double v01 = lerp((double)fetch(p.z0, p.y1, q.x0), (double)fetch(p.z0, p.y1, q.x1), q.tx);
-        const double v10 = lerp((double)fetch(p.z1, p.y0, q.x0), (double)fetch(p.z1, p.y0, q.x1), q.tx);
-        const double v11 = lerp((double)fetch(p.z1, p.y1, q.x0), (double)fetch(p.z1, p.y1, q.x1), q.tx);
-        return (T)lerp(lerp(v00, v01, p.ty), lerp(v10, v11, p.ty), p.tz);
+        const double v00 = lerp_rn((double)fetch(p.z0, p.y0, q.x0), (double)fetch(p.z0, p.y0, q.x1), q.tx);
+        const double v01 = lerp_rn((double)fetch(p.z0, p.y1, q.x0), (double)fetch(p.z0, p.y1, q.x1), q.tx);
+        const double v10 = lerp_rn((double)fetch(p.z1, p.y0, q.x0), (double)fetch(p.z1, p.y0, q.x1), q.tx);
+        const double v11 = lerp_rn((double)fetch(p.z1, p.y1, q.x0), (double)fetch(p.z1, p.y1, q.x1), q.tx);
+        return (T)lerp_rn(lerp_rn(v00, v01, p.ty), lerp_rn(v10, v11, p.ty), p.tz);
     };
 
     const T* same = static_cast<const T*>(a.x);                // a PASS sample: the same elements of x

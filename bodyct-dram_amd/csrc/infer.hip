@@ -12,10 +12,10 @@
 // All HBM-bound gathers/streams; one thread per output voxel.  The scan (int16) and the lobe label
 // map (uint8) stay resident in HBM; nothing goes back to the host except 5 boxes and 256 counts.
 //
-// Resampling grid: the reference resamples the crop with SimpleITK (absent here: parity unpinned); the crop -> R^3 step
-// restates the grid of that ResampleImageFilter call from ITK's published semantics (itk_index below); the way back is the
-// reference's own F.interpolate(..., align_corners=True) (job_runner.py:767).
-#include "common.h"
+// Resampling grid: the reference resamples the crop with SimpleITK; the crop -> R^3 step runs on the grid of that
+// ResampleImageFilter call (itk_axis, volume_math.h); the way back is the reference's own F.interpolate(...,
+// align_corners=True) (job_runner.py:767).
+#include "volume_math.h"
 
 namespace dram {
 
@@ -100,22 +100,13 @@ __device__ __forceinline__ void ac_index(int in, int out, int o, int& i0, int& i
     l0 = 1.f - l1;
 }
 
-// The crop -> R^3 grid of the reference: Resample('fixed_size') (data_transforms.py:170-175) -> utils.resample ->
-// sitk.ResampleImageFilter.Execute(image, new_size, identity transform, sitkLinear, the image's own origin and direction,
-// new_spacing = spacing * size_in / size_out, fill 0) (utils.py:371-381).  SimpleITK is not available here (parity unpinned);
-// the grid is restated from ITK's published semantics of that call: output voxel o lies at physical position origin +
-// o * new_spacing, i.e. at continuous input index c = o * size_in / size_out; it is inside the input buffer while
-// c < size_in - 0.5 (ImageFunction::IsInsideBuffer: [-0.5, size - 0.5)), otherwise the default value 0; linear interpolation
-// between floor(c) and floor(c) + 1, the upper neighbour clamped to the last voxel (LinearInterpolateImageFunction).
-__device__ __forceinline__ void itk_index(int in, int out, int o, int& i0, int& i1, float& l0, float& l1, bool& inside) {
-    const double c = (double)o * (double)in / (double)out;
-    inside = c < (double)in - 0.5;
-    int b = (int)c;
-    b = b > in - 1 ? in - 1 : b;
-    i0 = b;
-    i1 = b + 1 <= in - 1 ? b + 1 : b;
-    l1 = i1 == i0 ? 0.f : (float)(c - (double)b);
+// One axis of the crop -> R^3 grid: Resample('fixed_size') (data_transforms.py:170-175 -> utils.resample, utils.py:371-381:
+// sitkLinear, new_spacing = spacing * size_in / size_out), so c = o * size_in / size_out (itk_axis, volume_math.h); fp32 weights.
+__device__ __forceinline__ ItkAxis fixed_size_axis(int in, int out, int o, float& l0, float& l1) {
+    const ItkAxis a = itk_axis((double)o * (double)in / (double)out, in);
+    l1 = (float)a.t;
     l0 = 1.f - l1;
+    return a;
 }
 
 // out[l][R][R][R]: windowed, lobe-masked crop resampled to R^3
@@ -127,13 +118,9 @@ __global__ __launch_bounds__(256) void lobe_chunks_kernel(const int16_t* __restr
     const int e = blockIdx.x * 256 + threadIdx.x;
     if (e >= R * R * R) return;
     const int xo = e % R, yo = (e / R) % R, zo = e / (R * R);
-    int z0, z1, y0, y1, x0, x1;
     float a0, a1, b0, b1, c0, c1;
-    bool inz, iny, inx;
-    itk_index(c.dz, R, zo, z0, z1, a0, a1, inz);
-    itk_index(c.dy, R, yo, y0, y1, b0, b1, iny);
-    itk_index(c.dx, R, xo, x0, x1, c0, c1, inx);
-    if (!(inz && iny && inx)) {                                   // beyond the crop's buffer (a crop smaller than R): default value
+    const ItkAxis gz = fixed_size_axis(c.dz, R, zo, a0, a1), gy = fixed_size_axis(c.dy, R, yo, b0, b1), gx = fixed_size_axis(c.dx, R, xo, c0, c1);
+    if (!(gz.inside && gy.inside && gx.inside)) {                 // beyond the crop's buffer (a crop smaller than R): default value
         out[(size_t)l * R * R * R + e] = 0.f;
         return;
     }
@@ -145,6 +132,7 @@ __global__ __launch_bounds__(256) void lobe_chunks_kernel(const int16_t* __restr
         v = fminf(fmaxf(v, wmin), wmax);
         return (v - wmin) * inv;                                  // windowing(), utils.py:189-198, to_span (0,1)
     };
+    const int z0 = gz.lo, z1 = gz.hi, y0 = gy.lo, y1 = gy.hi, x0 = gx.lo, x1 = gx.hi;
     const float v = a0 * (b0 * (c0 * at(z0, y0, x0) + c1 * at(z0, y0, x1)) + b1 * (c0 * at(z0, y1, x0) + c1 * at(z0, y1, x1))) +
                     a1 * (b0 * (c0 * at(z1, y0, x0) + c1 * at(z1, y0, x1)) + b1 * (c0 * at(z1, y1, x0) + c1 * at(z1, y1, x1)));
     out[(size_t)l * R * R * R + e] = v;
@@ -205,16 +193,8 @@ __global__ void threshold_kernel(const float* __restrict__ htp, uint8_t* __restr
     for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) mask[i] = htp[i] > th ? 1 : 0;
 }
 
-// ---- the post-processing tail of LesionSegTest.run (dram/job_runner.py:1003-1012, 1033-1037)
-// w_scan = windowing(scan, from_span=(wmin, wmax), to_span=(0, 1)) (utils.py:189-198: numpy clips the int16 scan, subtracts in
-// integers and divides by float(wmax - wmin): fp64), and binary_cam's 8-bit view of it (utils.py:233: windowing(., (0, 1)) ->
-// (w / 1.0) * 255 + 0 -> astype(uint8) truncates).  The same fp64 operations in the same order, so that bin and comparison
-// are bit-identical to numpy's.
-__device__ __forceinline__ double windowed_scan(int s, int wmin, int wmax) {
-    const int c = s < wmin ? wmin : (s > wmax ? wmax : s);
-    return (double)(c - wmin) / (double)(wmax - wmin);
-}
-
+// ---- the post-processing tail of LesionSegTest.run (dram/job_runner.py:1003-1012, 1033-1037); w_scan and binary_cam's 8-bit
+// view of it are windowed_scan and scan_bin (volume_math.h)
 // hist[b] = #{v : lobe[v] > 0, uint8(w_scan[v] * 255) == b}
 __global__ __launch_bounds__(256) void scan_hist_kernel(const int16_t* __restrict__ scan, const uint8_t* __restrict__ lobe,
                                                         unsigned long long* __restrict__ hist, int wmin, int wmax, size_t n) {
@@ -224,8 +204,7 @@ __global__ __launch_bounds__(256) void scan_hist_kernel(const int16_t* __restric
     const size_t stride = (size_t)gridDim.x * 256;
     for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < n; i += stride) {
         if (lobe[i] > 0) {
-            const double w = windowed_scan((int)scan[i], wmin, wmax);
-            atomicAdd(&lh[(int)((w / 1.0) * 255.0 + 0.0)], 1u);
+            atomicAdd(&lh[scan_bin(windowed_scan((int)scan[i], wmin, wmax))], 1u);
         }
     }
     __syncthreads();
@@ -271,29 +250,13 @@ __global__ __launch_bounds__(256) void mask_overlap_kernel(const uint8_t* __rest
 // ---- utils.resample(narray, spacing, required_spacing=..., new_size=..., interpolator=...) (utils.py:414-434 -> 299-381): the
 // volumes of LesionSegTest.run going back to the scan's original grid (job_runner.py:1016-1032).  sitk.ResampleImageFilter with
 // the identity transform, the image's own origin and direction, output spacing = required_spacing, default value 0, output
-// pixel type = input pixel type.  SimpleITK 1.1.0 is not available (PARITY UNPINNED); restated from ITK's published semantics:
-// output voxel o sits at continuous input index c = o * spacing_out / spacing_in per axis; it is inside the buffer while
-// c < size_in - 0.5 (ImageFunction::IsInsideBuffer; c >= 0 always: same origin), else the default value.
-//   nearest: voxel floor(c + 0.5) (NearestNeighborInterpolateImageFunction: Math::RoundHalfIntegerUp);
-//   linear:  base = floor(c), upper neighbour clamped to the last voxel, lerps x, then y, then z in double
-//            (LinearInterpolateImageFunction::EvaluateOptimized: RealType of short / float pixels is double), then the cast of
-//            ResampleImageFilter::CastPixelWithBoundsChecking: clamp to the pixel type's range, static_cast (int16: truncation).
+// pixel type = input pixel type; c = o * spacing_out / spacing_in per axis.  The grid, the nearest voxel and the fp64 lerps
+// (x, then y, then z): itk_axis and lerp_rn (volume_math.h); then the cast of ResampleImageFilter::CastPixelWithBoundsChecking:
+// clamp to the pixel type's range, static_cast (int16: truncation).
 struct ResampleGrid {
     int Di, Hi, Wi, Do, Ho, Wo;
     double sz, sy, sx;          // spacing_out / spacing_in per axis
 };
-__device__ __forceinline__ double mul_rn(double a, double b) {       // (HIP's __dmul_rn is a plain `*`, open to contraction)
-#pragma clang fp contract(off)
-    return a * b;
-}
-__device__ __forceinline__ bool itk_axis(double c, int in, int& i0, int& i1, double& t) {
-#pragma clang fp contract(off)
-    const int b = (int)c;                                  // c >= 0
-    i0 = b > in - 1 ? in - 1 : b;
-    i1 = i0 + 1 <= in - 1 ? i0 + 1 : i0;
-    t = i1 == i0 ? 0.0 : c - (double)i0;
-    return c < (double)in - 0.5;
-}
 template <typename T> __device__ __forceinline__ T itk_cast(double v);
 template <> __device__ __forceinline__ float itk_cast<float>(double v) { return (float)v; }
 template <> __device__ __forceinline__ int16_t itk_cast<int16_t>(double v) {
@@ -307,27 +270,17 @@ __global__ __launch_bounds__(256) void resample_volume_kernel(const T* __restric
     const int x = blockIdx.x * 256 + threadIdx.x, y = blockIdx.y, z = blockIdx.z;
     if (x >= g.Wo) return;
     const size_t o = ((size_t)z * g.Ho + y) * g.Wo + x;
-    // (products rounded on their own: hipcc would otherwise contract c - base into fma(o, s, -base), which is not what ITK or the oracle compute)
-    const double cz = mul_rn((double)z, g.sz), cy = mul_rn((double)y, g.sy), cx = mul_rn((double)x, g.sx);
-    int z0, z1, y0, y1, x0, x1;
-    double tz, ty, tx;
-    const bool inz = itk_axis(cz, g.Di, z0, z1, tz), iny = itk_axis(cy, g.Hi, y0, y1, ty), inx = itk_axis(cx, g.Wi, x0, x1, tx);
-    if (!(inz && iny && inx)) { out[o] = (T)0; return; }
+    const ItkAxis gz = itk_axis(mul_rn((double)z, g.sz), g.Di), gy = itk_axis(mul_rn((double)y, g.sy), g.Hi), gx = itk_axis(mul_rn((double)x, g.sx), g.Wi);
+    if (!(gz.inside && gy.inside && gx.inside)) { out[o] = (T)0; return; }
     auto at = [&](int zz, int yy, int xx) { return in[((size_t)zz * g.Hi + yy) * g.Wi + xx]; };
     if (!LINEAR) {
-        out[o] = at((int)(cz + 0.5), (int)(cy + 0.5), (int)(cx + 0.5));       // (inside: c + 0.5 < size_in)
+        out[o] = at(gz.nearest, gy.nearest, gx.nearest);
         return;
     }
-    // (no fused multiply-add: ITK's x86 builds round the product, and so does the oracle -- it shows where an int16 result
-    //  truncates: -484 + 705 * 0.4 is -202 with a rounded product, -201.99999999999997 fused.  HIP's __dmul_rn is a plain `*`.)
-    auto lerp = [](double a, double b, double t) {
-#pragma clang fp contract(off)
-        const double p = (b - a) * t;
-        return a + p;
-    };
-    const double v00 = lerp((double)at(z0, y0, x0), (double)at(z0, y0, x1), tx), v10 = lerp((double)at(z0, y1, x0), (double)at(z0, y1, x1), tx);
-    const double v01 = lerp((double)at(z1, y0, x0), (double)at(z1, y0, x1), tx), v11 = lerp((double)at(z1, y1, x0), (double)at(z1, y1, x1), tx);
-    out[o] = itk_cast<T>(lerp(lerp(v00, v10, ty), lerp(v01, v11, ty), tz));
+    const int z0 = gz.lo, z1 = gz.hi, y0 = gy.lo, y1 = gy.hi, x0 = gx.lo, x1 = gx.hi;
+    const double v00 = lerp_rn((double)at(z0, y0, x0), (double)at(z0, y0, x1), gx.t), v10 = lerp_rn((double)at(z0, y1, x0), (double)at(z0, y1, x1), gx.t);
+    const double v01 = lerp_rn((double)at(z1, y0, x0), (double)at(z1, y0, x1), gx.t), v11 = lerp_rn((double)at(z1, y1, x0), (double)at(z1, y1, x1), gx.t);
+    out[o] = itk_cast<T>(lerp_rn(lerp_rn(v00, v10, gy.t), lerp_rn(v01, v11, gy.t), gz.t));
 }
 
 }  // namespace dram

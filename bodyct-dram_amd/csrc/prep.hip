@@ -6,8 +6,7 @@
 //       lesion_candidate = (w_scan > th) & (lobe > 0); vessel = (vessel > 0) & (lobe > 0)
 //   LesionSegChunkTrain.preprocessing (dram/job_runner.py:586-597): Windowing(min, max) of "#image" as float32
 //       (data_transforms.py:37-54), then Resample (data_transforms.py:65-211): linear for the image, nearest neighbour for every
-//       "...reference" key, through sitk.ResampleImageFilter (utils.py:299-381; restated from ITK's published semantics like
-//       resample_volume_kernel of infer.hip -- SimpleITK absent, parity unpinned).
+//       "...reference" key, through sitk.ResampleImageFilter (utils.py:299-381; its grid: volume_math.h).
 // Here the N chunks of a batch lie back to back in one buffer per kind (int16 scans, uint8 lobes, uint8 vessels), every chunk
 // with its own size, described by a device table of ChunkRec; three entry points, none of which synchronises, allocates or
 // reads per-sample data from the host:
@@ -15,7 +14,7 @@
 //   otsu256         binary_cam's threshold from those histograms, on the device (one block per sample)
 //   chunk_prepare   windowed + linearly resampled image, nearest-neighbour lobe / pseudo-lesion / vessel masks at the common
 //                   output size, one launch, the pseudo-lesion mask never written at source resolution
-#include "common.h"
+#include "volume_math.h"
 
 namespace dram {
 
@@ -26,14 +25,7 @@ struct ChunkRec {            // 48 bytes, mirrored by dram_amd/preprocess.py:TAB
 };
 static_assert(sizeof(ChunkRec) == 48, "ChunkRec is part of the ABI");
 
-// bin of binary_cam's 8-bit view of windowing(scan, (wmin, wmax), (0, 1)): the fp64 operations of scan_hist_kernel (infer.hip)
-__device__ __forceinline__ int scan_bin(int s, int wmin, int wmax) {
-#pragma clang fp contract(off)
-    const int c = s < wmin ? wmin : (s > wmax ? wmax : s);
-    const double w = (double)(c - wmin) / (double)(wmax - wmin);
-    return (int)((w / 1.0) * 255.0 + 0.0);
-}
-
+// hist[n][b] = #{v in chunk n : lobe[v] > 0, scan_bin(windowed_scan(scan[v])) == b} (volume_math.h), as scan_hist_kernel (infer.hip).
 // grid (blocks per sample, N).  The packed buffers are walked in groups of 8 elements aligned in BUFFER coordinates (the bases
 // are 16-byte aligned, a chunk's offset is not): a group inside the chunk is one 16-byte scan load and one 8-byte lobe load, the
 // two ragged groups at the chunk's ends go element by element.  One LDS histogram per wave (the lobe's values crowd a few
@@ -62,12 +54,12 @@ __global__ __launch_bounds__(256) void chunk_hist_kernel(const int16_t* __restri
 #pragma unroll
             for (int k = 0; k < 8; ++k) {
                 const unsigned l = ((k < 4 ? lb.x : lb.y) >> (8 * (k & 3))) & 0xffu;
-                if (l) atomicAdd(&mine[scan_bin((int)(int16_t)((sw[k >> 1] >> (16 * (k & 1))) & 0xffffu), wmin, wmax)], 1u);
+                if (l) atomicAdd(&mine[scan_bin(windowed_scan((int)(int16_t)((sw[k >> 1] >> (16 * (k & 1))) & 0xffffu), wmin, wmax))], 1u);
             }
         } else {
             const long long a = e0 > lo ? e0 : lo, b = e0 + 8 < hi ? e0 + 8 : hi;
             for (long long e = a; e < b; ++e)
-                if (lobes[e] > 0) atomicAdd(&mine[scan_bin((int)scans[e], wmin, wmax)], 1u);
+                if (lobes[e] > 0) atomicAdd(&mine[scan_bin(windowed_scan((int)scans[e], wmin, wmax))], 1u);
         }
     }
     __syncthreads();
@@ -158,20 +150,6 @@ struct PrepArgs {
     int pwmin, pwmax;
 };
 
-// one axis of the ITK grid (itk_axis of infer.hip, plus the nearest-neighbour voxel): c = o * step with the product rounded on
-// its own; inside while c < size_in - 0.5; base = floor(c), upper neighbour clamped, t = 0 where they coincide; nearest =
-// (int)(c + 0.5) (Math::RoundHalfIntegerUp), which is inside the buffer whenever c is.
-__device__ __forceinline__ void prep_axis(int o, double step, int in, int& i0, int& i1, int& in_, double& t) {
-#pragma clang fp contract(off)
-    const double c = (double)o * step;
-    const bool inside = c < (double)in - 0.5;                  // (false for NaN and for every c that would overflow an int)
-    const int b = inside ? (int)c : in - 1;
-    i0 = b > in - 1 ? in - 1 : b;
-    i1 = i0 + 1 <= in - 1 ? i0 + 1 : i0;
-    t = i1 == i0 ? 0.0 : c - (double)i0;
-    in_ = inside ? (int)(c + 0.5) : -1;
-}
-
 // Windowing(min, max) of the scan cast to float32 (data_transforms.py:46-54 -> utils.windowing on a float32 array): clip,
 // subtract, divide by float(max - min), * (1 - 0) + 0, every step rounded to fp32 (the last two change nothing: x * 1 = x and
 // the quotient is never -0).  `/` is IEEE-rounded: the library is built without -ffast-math and hipcc's default for HIP is the
@@ -185,11 +163,10 @@ __device__ __forceinline__ float window_f32(int16_t s, float wmin, float wmax, f
 
 // grid (row tiles, N), 256 threads.  A block owns `rows` consecutive output rows (z, y) of one sample: a contiguous span of every
 // output.  It first fills the sample's x table (index pair, weight, nearest voxel per output column), the z / y entries of its
-// rows and the pseudo-lesion cut into LDS -- per block, not per voxel --, then walks its span in quads aligned in OUTPUT
+// rows (itk_axis, volume_math.h) and the pseudo-lesion cut into LDS -- per block, not per voxel --, then walks its span in quads aligned in OUTPUT
 // coordinates: a quad inside the span is one 16-byte store per output, the ragged ends go element by element, so any Wo works.
 // Per output voxel: the 8 scan neighbours of the linear cell (the nearest voxel is one of them), 1 lobe and 1 vessel value.
-// Pseudo-lesion: (w_scan > th) with w_scan = (double)(clip(s) - pwmin) / (double)(pwmax - pwmin) as lesion_post_kernel (infer.hip)
-// evaluates it.  That predicate is monotone in the clipped integer k = clip(s) - pwmin (a correctly rounded division by a
+// Pseudo-lesion: (w_scan > th) with w_scan = windowed_scan(s, pwmin, pwmax) (volume_math.h).  That predicate is monotone in the clipped integer k = clip(s) - pwmin (a correctly rounded division by a
 // positive constant is non-decreasing), so the block finds the smallest k whose quotient exceeds th by bisection with that very
 // expression, and a voxel is a candidate iff its k reaches it: the same truth value for every voxel, one fp64 division per
 // bisection step instead of one per voxel.  th = +inf (empty lobe): no k, no candidates.
@@ -207,15 +184,15 @@ __global__ __launch_bounds__(256) void chunk_prepare_kernel(PrepArgs a) {
     const bool empty = r.Di <= 0 || r.Hi <= 0 || r.Wi <= 0;
     if (!empty) {
         for (int x = threadIdx.x; x < a.Wo; x += 256) {
-            int x0, x1, xn; double tx;
-            prep_axis(x, r.sx, r.Wi, x0, x1, xn, tx);
-            xt[x].x0 = x0; xt[x].xn = xn; xt[x].tx = tx;
+            const ItkAxis g = itk_axis(mul_rn((double)x, r.sx), r.Wi);
+            xt[x].x0 = g.lo; xt[x].xn = g.inside ? g.nearest : -1; xt[x].tx = g.t;
         }
         if ((int)threadIdx.x < nrows) {
             const int row = row0 + threadIdx.x;
             PrepRow& p = rt[threadIdx.x];
-            prep_axis(row / a.Ho, r.sz, r.Di, p.z0, p.z1, p.zn, p.tz);
-            prep_axis(row % a.Ho, r.sy, r.Hi, p.y0, p.y1, p.yn, p.ty);
+            const ItkAxis gz = itk_axis(mul_rn((double)(row / a.Ho), r.sz), r.Di), gy = itk_axis(mul_rn((double)(row % a.Ho), r.sy), r.Hi);
+            p.z0 = gz.lo; p.z1 = gz.hi; p.zn = gz.inside ? gz.nearest : -1; p.tz = gz.t;
+            p.y0 = gy.lo; p.y1 = gy.hi; p.yn = gy.inside ? gy.nearest : -1; p.ty = gy.t;
         }
         if (threadIdx.x == 255) {
             int cut = 0x7fffffff;
@@ -225,7 +202,7 @@ __global__ __launch_bounds__(256) void chunk_prepare_kernel(PrepArgs a) {
                 int lo = 0, hi = span + 1;                         // smallest k in [0, span] with k / span > th; span + 1: none
                 while (lo < hi) {
                     const int mid = lo + (hi - lo) / 2;
-                    if ((double)mid / (double)span > th) hi = mid; else lo = mid + 1;
+                    if (windowed_scan(a.pwmin + mid, a.pwmin, a.pwmax) > th) hi = mid; else lo = mid + 1;
                 }
                 cut = lo;
             }
@@ -253,15 +230,10 @@ __global__ __launch_bounds__(256) void chunk_prepare_kernel(PrepArgs a) {
         const size_t r10 = (size_t)p.z1 * HW + (size_t)p.y0 * r.Wi, r11 = (size_t)p.z1 * HW + (size_t)p.y1 * r.Wi;
         const int16_t s000 = scan[r00 + x0], s001 = scan[r00 + x1], s010 = scan[r01 + x0], s011 = scan[r01 + x1];
         const int16_t s100 = scan[r10 + x0], s101 = scan[r10 + x1], s110 = scan[r11 + x0], s111 = scan[r11 + x1];
-        auto lerp = [](double u, double v, double t) {
-#pragma clang fp contract(off)
-            const double pr = (v - u) * t;
-            return u + pr;
-        };
         auto w = [&](int16_t s) { return (double)window_f32(s, a.wmin, a.wmax, range); };
-        const double v00 = lerp(w(s000), w(s001), q.tx), v10 = lerp(w(s010), w(s011), q.tx);
-        const double v01 = lerp(w(s100), w(s101), q.tx), v11 = lerp(w(s110), w(s111), q.tx);
-        o_img = (float)lerp(lerp(v00, v10, p.ty), lerp(v01, v11, p.ty), p.tz);
+        const double v00 = lerp_rn(w(s000), w(s001), q.tx), v10 = lerp_rn(w(s010), w(s011), q.tx);
+        const double v01 = lerp_rn(w(s100), w(s101), q.tx), v11 = lerp_rn(w(s110), w(s111), q.tx);
+        o_img = (float)lerp_rn(lerp_rn(v00, v10, p.ty), lerp_rn(v01, v11, p.ty), p.tz);
         // the nearest voxel is a corner of the linear cell (c + 0.5 < size_in: base or base + 1, never past the clamp)
         const bool zu = p.zn != p.z0, yu = p.yn != p.y0, xu = q.xn != x0;
         const size_t near = (size_t)p.zn * HW + (size_t)p.yn * r.Wi + q.xn;
@@ -309,8 +281,6 @@ __global__ __launch_bounds__(256) void chunk_prepare_kernel(PrepArgs a) {
 }  // namespace dram
 
 using namespace dram;
-
-static bool aligned16(const void* p) { return (((size_t)p) & 15) == 0; }
 
 // hist: [N][256] uint64 (zeroed here).  scans / lobes: the packed buffers, 16-byte aligned bases; table: N ChunkRec on the device.
 extern "C" int dram_chunk_hist256(const int16_t* scans, const uint8_t* lobes, const void* table, int N,
