@@ -21,8 +21,8 @@
 //     4 instead of 6 products per (ci, ky, kx) column, i.e. 2/3 of the MFMAs.  Cin >= 8 / W % 4 == 0 where the (z,y)
 //     kernels do not serve the shape or the source.
 //   * direct 27-tap kernels -- conv3d_k3_fwd_kernel, conv3d_k3_wgrad(_vec)_kernel, and the first-layer kernels
-//     conv3d_k3_fwd_c1(w)_kernel / conv3d_k3_wgrad_c1_kernel (Cin = 1): widths the Winograd wgrad does not cover,
-//     and the A/B baseline (DRAM_CONV_DIRECT=1).
+//     conv3d_k3_fwd_c1(w)_kernel / conv3d_k3_wgrad_c1_kernel (Cin = 1): the shapes and sources the Winograd
+//     kernels do not cover (for backward-weights see wgrad_plan), and the A/B baseline (DRAM_CONV_DIRECT=1).
 //
 //   forward / backward-data  D[co][voxel] += W[co][ci] * X[ci][voxel+tap]
 //       block = 256 voxels x 32*COT output channels, 4 waves of 32x32 accumulator
@@ -42,6 +42,7 @@
 // packing, the launch counters and every C entry point.
 #include "conv_args.h"
 #include "conv_device.h"
+#include "wgrad_device.h"
 #include "lane_reduce.h"
 #include <type_traits>
 #include <stdlib.h>
@@ -1534,14 +1535,9 @@ __global__ __launch_bounds__(512, 2) void conv3d_k3_wgrad_kernel(WgradArgs a) {
     float* ldy = lds;             // [CO_B][PA]
     float* lx = lds + CO_B * PA;  // [CI_B][PB]
 
-    const int tid = threadIdx.x, lane = tid & 63;
-    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int wco = wave % COS, wci = wave / COS;   // this wave's (co, ci) sub-tile
-    int b = xcd_remap(blockIdx.x, gridDim.x);       // logical item = (split, co tile, ci tile), ci tile fastest
-    const int ci_t = b % a.ci_tiles; b /= a.ci_tiles;
-    const int co_t = b % a.co_tiles;
-    const int sp = b / a.co_tiles;
-    const int ci0 = ci_t * CI_B, co0 = co_t * CO_B;
+    const int tid = threadIdx.x;
+    const WgradItem it = wgrad_item<CO_B, CI_B, COS>(a);
+    const int ci0 = it.ci0, co0 = it.co0;
     const int D = a.D, H = a.H, W = a.W;
     const int S = D * H * W;
     const int S2 = a.src.D2 * a.src.H2 * a.src.W2;
@@ -1550,7 +1546,6 @@ __global__ __launch_bounds__(512, 2) void conv3d_k3_wgrad_kernel(WgradArgs a) {
 #pragma unroll
     for (int t = 0; t < 27; ++t) acc[t] = f32x4{0.f, 0.f, 0.f, 0.f};
 
-    const int i = lane & 15, k = lane >> 4;
     // dY staging role: voxel v_st of the box, channel rows co_st + RPP*q (co_st is wave-uniform)
     const int v_st = tid % VOX;
     const int co_st = __builtin_amdgcn_readfirstlane(tid / VOX);
@@ -1570,12 +1565,8 @@ __global__ __launch_bounds__(512, 2) void conv3d_k3_wgrad_kernel(WgradArgs a) {
     // which tensor(s) this block's CI_B channels come from: 0 = x1 only, 1 = x2 only, 2 = straddles both
     const int src_mode = (a.src.p2 == nullptr || ci0 + CI_B <= a.src.C1) ? 0 : (ci0 >= a.src.C1 ? 1 : 2);
     auto load_box = [&](int box) {
-        int bb = box;
-        const int bx = bb % a.nbx; bb /= a.nbx;
-        const int by = bb % a.nby; bb /= a.nby;
-        const int bz = bb % a.nbz;
-        const int n = bb / a.nbz;
-        const int x0 = bx * BX, y0 = by * BY, z0 = bz * BZ;
+        const WgradBox bb = wgrad_box(a, box, BX, BY, BZ);
+        const int n = bb.n, x0 = bb.x0, y0 = bb.y0, z0 = bb.z0;
         {   // dY[CO_B][VOX]
             const int gx = x0 + svx, gy = y0 + svy, gz = z0 + svz;
             const bool vok = gx < W && gy < H && gz < D;
@@ -1642,34 +1633,14 @@ __global__ __launch_bounds__(512, 2) void conv3d_k3_wgrad_kernel(WgradArgs a) {
                 if (tid + T * q < HV) lx[c * PB + tid + T * q] = rx[c][q];
     };
     auto compute = [&]() {
-        // VOX/4 k-steps (4 voxels along x each) x 27 taps of 16x16x4 MFMAs
-        const float* ap = ldy + (wco * 16 + i) * PA + k;
-        const float* bp = lx + (wci * 16 + i) * PB + k;
-        constexpr int NS = VOX / 4;
-        float av[2], bv[2][27];
-        // two operand sets live; one operand read of k-step s beside each MFMA of k-step s-1 (see the vec kernel)
-#pragma unroll
-        for (int s = 0; s <= NS; ++s) {
-            const int x4 = s % (BX / 4), vy = (s / (BX / 4)) % BY, vz = s / ((BX / 4) * BY);
-            const float* bq = bp + (vz * HY + vy) * HX + 4 * x4;
-            if (s < NS) av[s & 1] = ap[(vz * BY + vy) * BX + 4 * x4];
-#pragma unroll
-            for (int tap = 0; tap < 27; ++tap) {
-                const int dz = tap / 9, dy = (tap / 3) % 3, dx = tap % 3;
-                if (s < NS) bv[s & 1][tap] = bq[(dz * HY + dy) * HX + dx];
-                if (s > 0)
-                    acc[tap] = __builtin_amdgcn_mfma_f32_16x16x4f32(av[(s - 1) & 1], bv[(s - 1) & 1][tap], acc[tap], 0, 0, 0);
-                __builtin_amdgcn_sched_barrier(0);
-            }
-        }
+        wgrad_direct_mfma<BX, BY, BZ, HX, HY>(ldy + (it.wco * 16 + it.i) * PA + it.k, lx + (it.wci * 16 + it.i) * PB + it.k, acc);
     };
-
-    if (sp < a.nboxes) {
-        load_box(sp);
+    if (it.sp < a.nboxes) {
+        load_box(it.sp);
         store_box();
     }
     __syncthreads();
-    for (int box = sp; box < a.nboxes; box += a.split) {
+    for (int box = it.sp; box < a.nboxes; box += a.split) {
         const bool has_next = (box + a.split) < a.nboxes;
         if (has_next) load_box(box + a.split);      // global loads in flight during the MFMAs
         __builtin_amdgcn_sched_barrier(0);
@@ -1681,20 +1652,7 @@ __global__ __launch_bounds__(512, 2) void conv3d_k3_wgrad_kernel(WgradArgs a) {
             __syncthreads();
         }
     }
-
-    // ---- partial slab: D row = co (4*(lane>>4)+r), col = ci (lane&15) ----
-    const int ci = ci0 + wci * 16 + i;
-    if (ci < a.Cin) {
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-            const int co = co0 + wco * 16 + 4 * k + r;
-            if (co < a.Cout) {
-                float* o = a.slabs + (((size_t)sp * a.Cout + co) * a.Cin + ci) * 27;
-#pragma unroll
-                for (int tap = 0; tap < 27; ++tap) o[tap] = acc[tap][r];
-            }
-        }
-    }
+    wgrad_store_slab27(a, it, acc);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -1737,14 +1695,9 @@ __global__ __launch_bounds__(512, 2) void conv3d_k3_wgrad_vec_kernel(WgradArgs a
     float* ldy = lds;             // [CO_B][PA]
     float* lx = lds + CO_B * PA;  // [CI_B][PB], row r of channel c at c*PB + r*HXP, halo x index h at column h+3
 
-    const int tid = threadIdx.x, lane = tid & 63;
-    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int wco = wave % COS, wci = wave / COS;
-    int b = xcd_remap(blockIdx.x, gridDim.x);
-    const int ci_t = b % a.ci_tiles; b /= a.ci_tiles;
-    const int co_t = b % a.co_tiles;
-    const int sp = b / a.co_tiles;
-    const int ci0 = ci_t * CI_B, co0 = co_t * CO_B;
+    const int tid = threadIdx.x;
+    const WgradItem it = wgrad_item<CO_B, CI_B, COS>(a);
+    const int ci0 = it.ci0;
     const int D = a.D, H = a.H, W = a.W;
     const int S = D * H * W;
     // the source tensor of this block's channel tile (the host guarantees the tile does not straddle)
@@ -1760,7 +1713,6 @@ __global__ __launch_bounds__(512, 2) void conv3d_k3_wgrad_vec_kernel(WgradArgs a
     f32x4 acc[27];
 #pragma unroll
     for (int t = 0; t < 27; ++t) acc[t] = f32x4{0.f, 0.f, 0.f, 0.f};
-    const int i = lane & 15, k = lane >> 4;
 
     f32x4 rdy[DYP];
     f32x4 rxi[XIP];
@@ -1771,7 +1723,7 @@ __global__ __launch_bounds__(512, 2) void conv3d_k3_wgrad_vec_kernel(WgradArgs a
     const int d_c = tid / DY_TPC, d_v = 4 * (tid % DY_TPC);
     const int d_vx = d_v % BX, d_vy = (d_v / BX) % BY, d_vz = d_v / (BX * BY);
     const bool d_act = d_c < DY_CPP;
-    const unsigned d_rel = (unsigned)(co0 + d_c) * S4 + 4u * (unsigned)((d_vz * H + d_vy) * W + d_vx);
+    const unsigned d_rel = (unsigned)(it.co0 + d_c) * S4 + 4u * (unsigned)((d_vz * H + d_vy) * W + d_vx);
     // X interior: channel i_c + p*XI_CPP, halo row (i_hz, i_hy), columns 4*i_j..+3
     const int i_c = tid / XI_TPC, i_r = (tid % XI_TPC) / (BX / 4), i_j = tid % (BX / 4);
     const int i_hy = i_r % HY, i_hz = i_r / HY;
@@ -1784,12 +1736,8 @@ __global__ __launch_bounds__(512, 2) void conv3d_k3_wgrad_vec_kernel(WgradArgs a
     const unsigned e_rel = (unsigned)(cs0 + e_c) * Ss4 + 4u * (unsigned)((e_hz * Hs + e_hy) * Ws + (e_side ? BX : -1));
 
     auto load_box = [&](int box) {
-        int bb = box;
-        const int bx = bb % a.nbx; bb /= a.nbx;
-        const int by = bb % a.nby; bb /= a.nby;
-        const int bz = bb % a.nbz;
-        const int n = bb / a.nbz;
-        const int x0 = bx * BX, y0 = by * BY, z0 = bz * BZ;
+        const WgradBox bb = wgrad_box(a, box, BX, BY, BZ);
+        const int n = bb.n, x0 = bb.x0, y0 = bb.y0, z0 = bb.z0;
         {   // dY: rows of the box are full in x (W % BX == 0); rows beyond H / D read 0, and so do channels
             // >= Cout (their offset is beyond the descriptor's num_records)
             const __amdgpu_buffer_rsrc_t srd = make_rsrc(uniform_ptr(a.dy + (size_t)n * a.Cout * S), (unsigned)a.Cout * S4);
@@ -1829,7 +1777,6 @@ __global__ __launch_bounds__(512, 2) void conv3d_k3_wgrad_vec_kernel(WgradArgs a
         }
     };
     auto store_box = [&]() {
-        typedef float f32x2 __attribute__((ext_vector_type(2)));
 #pragma unroll
         for (int p = 0; p < DYP; ++p)
             if (d_act && (DYP * DY_CPP == CO_B || d_c + p * DY_CPP < CO_B))
@@ -1846,35 +1793,15 @@ __global__ __launch_bounds__(512, 2) void conv3d_k3_wgrad_vec_kernel(WgradArgs a
             if (e_act && (XEP * XE_CPP == CI_B || e_c + p * XE_CPP < CI_B))
                 lx[(e_c + p * XE_CPP) * PB + e_r * HXP + (e_side ? BX + 4 : 3)] = rxe[p];
     };
-    auto compute = [&]() {
-        const float* ap = ldy + (wco * 16 + i) * PA + k;
-        const float* bp = lx + (wci * 16 + i) * PB + k + 3;
-        constexpr int NS = VOX / 4;
-        float av[2], bv[2][27];
-        // one operand read of k-step s beside each MFMA of k-step s-1: the 28 LDS reads of a step are spread over
-        // its 27 MFMA slots instead of being issued as one burst that the 4-bit lgkmcnt counter throttles
-#pragma unroll
-        for (int s = 0; s <= NS; ++s) {
-            const int x4 = s % (BX / 4), vy = (s / (BX / 4)) % BY, vz = s / ((BX / 4) * BY);
-            const float* bq = bp + (vz * HY + vy) * HXP + 4 * x4;
-            if (s < NS) av[s & 1] = ap[(vz * BY + vy) * BX + 4 * x4];
-#pragma unroll
-            for (int tap = 0; tap < 27; ++tap) {
-                const int dz = tap / 9, dy = (tap / 3) % 3, dx = tap % 3;
-                if (s < NS) bv[s & 1][tap] = bq[(dz * HY + dy) * HXP + dx];
-                if (s > 0)
-                    acc[tap] = __builtin_amdgcn_mfma_f32_16x16x4f32(av[(s - 1) & 1], bv[(s - 1) & 1][tap], acc[tap], 0, 0, 0);
-                __builtin_amdgcn_sched_barrier(0);
-            }
-        }
+    auto compute = [&]() {      // (+3: halo x index h lies at column h+3)
+        wgrad_direct_mfma<BX, BY, BZ, HXP, HY>(ldy + (it.wco * 16 + it.i) * PA + it.k, lx + (it.wci * 16 + it.i) * PB + it.k + 3, acc);
     };
-
-    if (sp < a.nboxes) {
-        load_box(sp);
+    if (it.sp < a.nboxes) {
+        load_box(it.sp);
         store_box();
     }
     __syncthreads();
-    for (int box = sp; box < a.nboxes; box += a.split) {
+    for (int box = it.sp; box < a.nboxes; box += a.split) {
         const bool has_next = (box + a.split) < a.nboxes;
         if (has_next) load_box(box + a.split);
         __builtin_amdgcn_sched_barrier(0);
@@ -1886,19 +1813,7 @@ __global__ __launch_bounds__(512, 2) void conv3d_k3_wgrad_vec_kernel(WgradArgs a
             __syncthreads();
         }
     }
-
-    const int ci = ci0 + wci * 16 + i;
-    if (ci < a.Cin) {
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-            const int co = co0 + wco * 16 + 4 * k + r;
-            if (co < a.Cout) {
-                float* o = a.slabs + (((size_t)sp * a.Cout + co) * a.Cin + ci) * 27;
-#pragma unroll
-                for (int tap = 0; tap < 27; ++tap) o[tap] = acc[tap][r];
-            }
-        }
-    }
+    wgrad_store_slab27(a, it, acc);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -1941,19 +1856,13 @@ __global__ __launch_bounds__(64 * COS * CIT, 2) void conv3d_k3_wgrad_wz_kernel(W
     constexpr bool DOUBLE = G::DOUBLE;
     static_assert((COS * CIT == 8 || COS * CIT == 4) && BX % 4 == 0 && POS % 8 == 0 && PB % 2 == 0 && RA % 2 == 0 && DY_CPP >= 1 &&
                       XI_CPP >= 1 && XE_CPP >= 1, "block geometry");
-    typedef float f32x2 __attribute__((ext_vector_type(2)));
 
     extern __shared__ __attribute__((aligned(16))) float lds[];
     // stage layout: dY [CO_B][4][POS] (+2), then X [CI_B][4][HY][HXP]; halo x index h of a row at column h
 
-    const int tid = threadIdx.x, lane = tid & 63;
-    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int wco = wave % COS, wci = wave / COS;
-    int b = xcd_remap(blockIdx.x, gridDim.x);
-    const int ci_t = b % a.ci_tiles; b /= a.ci_tiles;
-    const int co_t = b % a.co_tiles;
-    const int sp = b / a.co_tiles;
-    const int ci0 = ci_t * CI_B, co0 = co_t * CO_B;
+    const int tid = threadIdx.x;
+    const WgradItem it = wgrad_item<CO_B, CI_B, COS>(a);
+    const int ci0 = it.ci0, co0 = it.co0;
     const int D = a.D, H = a.H, W = a.W;
     const int S = D * H * W;
     const bool use2 = a.src.p2 != nullptr && ci0 >= a.src.C1;
@@ -1971,7 +1880,6 @@ __global__ __launch_bounds__(64 * COS * CIT, 2) void conv3d_k3_wgrad_wz_kernel(W
     for (int t = 0; t < 9; ++t)
 #pragma unroll
         for (int q = 0; q < 4; ++q) acc[t][q] = f32x4{0.f, 0.f, 0.f, 0.f};
-    const int i = lane & 15, k = lane >> 4;
 
     f32x4 rdy[DYP][2];
     f32x4 rxi[XIP][4];
@@ -1999,12 +1907,8 @@ __global__ __launch_bounds__(64 * COS * CIT, 2) void conv3d_k3_wgrad_wz_kernel(W
     // makes hipcc split a load into two exec-masked loads of the same registers, with an s_waitcnt vmcnt(0) between
     // them -- a full memory latency inside the issue sequence, per plane and pass
     auto load_box = [&](int box) {
-        int bb = box;
-        const int bx = bb % a.nbx; bb /= a.nbx;
-        const int by = bb % a.nby; bb /= a.nby;
-        const int bz = bb % a.nbz;
-        const int n = bb / a.nbz;
-        const int x0 = bx * BX, y0 = by * BY, z0 = 2 * bz;
+        const WgradBox bb = wgrad_box(a, box, BX, BY, 2);
+        const int n = bb.n, x0 = bb.x0, y0 = bb.y0, z0 = bb.z0;
         {   // dY, planes z0 and z0+1 (full rows in x: W % BX == 0)
             const __amdgpu_buffer_rsrc_t srd = make_rsrc(uniform_ptr(a.dy + (size_t)n * a.Cout * S), (unsigned)a.Cout * S4);
             const int ok = (int)d_act & (int)((y0 + d_vy) < H);
@@ -2141,8 +2045,8 @@ __global__ __launch_bounds__(64 * COS * CIT, 2) void conv3d_k3_wgrad_wz_kernel(W
         for (int piece = 0; piece < NPIECE; ++piece) store_piece(st, piece);
     };
     auto compute = [&](const float* st) {
-        const float* ap = st + (wco * 16 + i) * RA + k;
-        const float* bp = st + CO_B * RA + (wci * 16 + i) * PB + k;
+        const float* ap = st + (it.wco * 16 + it.i) * RA + it.k;
+        const float* bp = st + CO_B * RA + (it.wci * 16 + it.i) * PB + it.k;
         constexpr int NU = POS;     // (POS/4 k-steps) x (4 planes)
         float av[2], bv[2][9];
         // one operand read of step u beside each MFMA of step u-1
@@ -2165,13 +2069,13 @@ __global__ __launch_bounds__(64 * COS * CIT, 2) void conv3d_k3_wgrad_wz_kernel(W
         }
     };
 
-    if (sp < a.nboxes) {
-        load_box(sp);
+    if (it.sp < a.nboxes) {
+        load_box(it.sp);
         store_box(lds);
     }
     __syncthreads();
     int cur = 0;
-    for (int box = sp; box < a.nboxes; box += a.split) {
+    for (int box = it.sp; box < a.nboxes; box += a.split) {
         const bool has_next = (box + a.split) < a.nboxes;
         if (has_next) load_box(box + a.split);
         __builtin_amdgcn_sched_barrier(0);
@@ -2202,13 +2106,13 @@ __global__ __launch_bounds__(64 * COS * CIT, 2) void conv3d_k3_wgrad_wz_kernel(W
     }
 
     // G^T p per accumulator element -> the three z taps of each (ky,kx) column
-    const int ci = ci0 + wci * 16 + i;
+    const int ci = ci0 + it.wci * 16 + it.i;
     if (ci < a.Cin) {
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
-            const int co = co0 + wco * 16 + 4 * k + r;
+            const int co = co0 + it.wco * 16 + 4 * it.k + r;
             if (co < a.Cout) {
-                float* o = a.slabs + (((size_t)sp * a.Cout + co) * a.Cin + ci) * 27;
+                float* o = a.slabs + (((size_t)it.sp * a.Cout + co) * a.Cin + ci) * 27;
 #pragma unroll
                 for (int tap = 0; tap < 9; ++tap) {
                     const float p0 = acc[tap][0][r], p1 = acc[tap][1][r], p2 = acc[tap][2][r], p3 = acc[tap][3][r];
@@ -2725,6 +2629,10 @@ static WgradPlan wgrad_plan(int N, int Cin, int Cout, int D, int H, int W, int C
         }
     }
     const int cit = 8 / cos;
+    // The direct kernels.  conv3d_k3_wgrad_kernel (dword staging) is the general fallback: W % 4 != 0, a concat boundary that
+    // is no multiple of 16 (the only kernel whose channel tile may straddle the two tensors), D == 1 with a ragged x box.  The
+    // 16-byte variant runs only where the Winograd-z kernel above would have served the shape but may not: D < 2, or
+    // DRAM_CONV_DIRECT is set.
     if (bx == 0) {
         // ties go to the 16-wide box: its X halo (18x4x4 = 288 elements per 64 voxels, against 408 for 34x4x3)
         // needs the fewest staging loads (measured +2.6 % at 128^3 / 64^3 / 32^3)
