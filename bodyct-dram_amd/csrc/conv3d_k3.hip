@@ -37,11 +37,13 @@
 // The input of forward and the output of backward-data may be a *virtual*
 // channel concatenation of two tensors (crop_concat_5d fused away).
 //
-// This file holds every 3x3x3 kernel but the (z,y) backward-weights one (conv3d_k3_wgrad_wzy.hip), the table rows that name
+// This file holds every 3x3x3 kernel but the (z,y) backward-weights one (conv3d_k3_wgrad_wzy.hip) -- what several of them share
+// per block is in fwd_device.h (forward / backward-data) and wgrad_device.h (backward-weights) --, the table rows that name
 // and launch one instantiation each (conv_args.h: KernelRow), the choice of a row per shape (fwd_choice, wgrad_plan), filter
 // packing, the launch counters and every C entry point.
 #include "conv_args.h"
 #include "conv_device.h"
+#include "fwd_device.h"
 #include "wgrad_device.h"
 #include "lane_reduce.h"
 #include <type_traits>
@@ -178,26 +180,6 @@ __device__ __forceinline__ void stats_epilogue_tiles4(YF Y, bool ok, int lane, f
     stats_epilogue_tiles<4>(Y, [&](int) { return ok; }, lane, stats, row0, co0, Cout, nparts, pidx);
 }
 
-// Operand transform of a lazily normalised source (ConvArgs::coef1/2): per K-chunk channel the wave-uniform
-// {a, b, lo}: v -> max(a*v + b, lo), lo = 0 with ReLU and -inf without; identity {1, 0, -inf} for a plain source,
-// {0, 0, 0} for the channel tail beyond Cin.
-struct LazyCoef {
-    float a, b, lo;
-};
-__device__ __forceinline__ LazyCoef lazy_coef(const ConvArgs& a, int n, int ci) {
-    LazyCoef c;
-    if (ci >= a.Cin) { c.a = 0.f; c.b = 0.f; c.lo = 0.f; return c; }
-    const bool first = ci < a.src.C1;
-    const float* cf = first ? a.coef1 : a.coef2;
-    const int relu = first ? a.relu1 : a.relu2;
-    if (cf == nullptr) { c.a = 1.f; c.b = 0.f; c.lo = -INFINITY; return c; }
-    const int64_t row = first ? (int64_t)n * a.src.C1 + ci : (int64_t)n * a.src.C2 + (ci - a.src.C1);
-    c.a = cf[2 * row];
-    c.b = cf[2 * row + 1];
-    c.lo = relu ? 0.f : -INFINITY;
-    return c;
-}
-
 // Software pipeline (one barrier per K chunk): while the MFMAs of chunk c run out of LDS stage
 // c&1, the global loads of chunk c+1 are in flight into registers; they are written to the other
 // stage after the MFMAs and become visible at the barrier.  Inside a chunk the LDS operand reads
@@ -215,13 +197,8 @@ __global__ __launch_bounds__(256, 2) void conv3d_k3_fwd_kernel(ConvArgs a) {
     extern __shared__ __attribute__((aligned(16))) float lds[];
 
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    int b = xcd_remap(blockIdx.x, gridDim.x);       // logical item = (box, co tile), co tile fastest
-    const int co0 = (b % a.co_tiles) * COB; b /= a.co_tiles;
-    const int bx = b % a.nbx; b /= a.nbx;
-    const int by = b % a.nby; b /= a.nby;
-    const int bz = b % a.nbz;
-    const int n = b / a.nbz;
-    const int x0 = bx * BX, y0 = by * BY, z0 = bz * BZ;
+    const FwdItem it = fwd_item<COB>(a, BX, BY, BZ);
+    const int co0 = it.co0, bx = it.bx, by = it.by, bz = it.bz, n = it.n, x0 = it.x0, y0 = it.y0, z0 = it.z0;
     const int D = a.D, H = a.H, W = a.W;
     const int S = D * H * W;
     const int S2 = a.src.D2 * a.src.H2 * a.src.W2;
@@ -431,13 +408,8 @@ __global__ __launch_bounds__(256, 3) void conv3d_k3_fwd_c1_kernel(ConvArgs a) {
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int j = lane & 31, kh = lane >> 5;
-    int b = xcd_remap(blockIdx.x, gridDim.x);       // logical item = (box, co tile), co tile fastest
-    const int co0 = (b % a.co_tiles) * 32; b /= a.co_tiles;
-    const int bx = b % a.nbx; b /= a.nbx;
-    const int by = b % a.nby; b /= a.nby;
-    const int bz = b % a.nbz;
-    const int n = b / a.nbz;
-    const int x0 = bx * G::BX, y0 = by * G::BY, z0 = bz * G::BZ;
+    const FwdItem it = fwd_item<32>(a, G::BX, G::BY, G::BZ);
+    const int co0 = it.co0, bx = it.bx, by = it.by, bz = it.bz, n = it.n, x0 = it.x0, y0 = it.y0, z0 = it.z0;
     const int D = a.D, H = a.H, W = a.W, Cout = a.Cout;
     const int S = D * H * W;
 
@@ -545,13 +517,8 @@ __global__ __launch_bounds__(256, 3) void conv3d_k3_fwd_c1w_kernel(ConvArgs a) {
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int j = lane & 31, kh = lane >> 5;
-    int b = xcd_remap(blockIdx.x, gridDim.x);       // logical item = (box, co tile), co tile fastest
-    const int co0 = (b % a.co_tiles) * 32; b /= a.co_tiles;
-    const int bx = b % a.nbx; b /= a.nbx;
-    const int by = b % a.nby; b /= a.nby;
-    const int bz = b % a.nbz;
-    const int n = b / a.nbz;
-    const int x0 = bx * G::BX, y0 = by * G::BY, z0 = bz * G::BZ;
+    const FwdItem it = fwd_item<32>(a, G::BX, G::BY, G::BZ);
+    const int co0 = it.co0, bx = it.bx, by = it.by, bz = it.bz, n = it.n, x0 = it.x0, y0 = it.y0, z0 = it.z0;
     const int D = a.D, H = a.H, W = a.W, Cout = a.Cout;
     const int S = D * H * W;
 
@@ -688,13 +655,8 @@ __global__ __launch_bounds__(256, 2) void conv3d_k3_fwd_wz_kernel(ConvArgs a) {
     float* lwt = lds + 2 * IN_STAGE;
 
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    int b = xcd_remap(blockIdx.x, gridDim.x);       // logical item = (box, co tile), co tile fastest
-    const int co0 = (b % a.co_tiles) * COB; b /= a.co_tiles;
-    const int bx = b % a.nbx; b /= a.nbx;
-    const int by = b % a.nby; b /= a.nby;
-    const int bz = b % a.nbz;
-    const int n = b / a.nbz;
-    const int x0 = bx * BX, y0 = by * BY, z0 = bz * 2;
+    const FwdItem it = fwd_item<COB>(a, BX, BY, 2);
+    const int co0 = it.co0, bx = it.bx, by = it.by, bz = it.bz, n = it.n, x0 = it.x0, y0 = it.y0, z0 = it.z0;
     const int D = a.D, H = a.H, W = a.W;
     const int S = D * H * W;
     const int S2 = a.src.D2 * a.src.H2 * a.src.W2;
