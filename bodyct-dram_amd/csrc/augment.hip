@@ -72,6 +72,30 @@ __global__ void minmax_decode_kernel(unsigned* mm, const int* flag, int N) {
     out[2 * n + 1] = hi;
 }
 
+// The same {min, max} table (fp32: every uint8 value is exact in it) for a uint8 sample, between the same two small kernels.
+__global__ __launch_bounds__(256) void minmax_u8_kernel(const unsigned char* __restrict__ x, unsigned* mm, const int* flag,
+                                                        int64_t S) {
+    const int n = blockIdx.y;
+    if (flag && flag[n] != 1) return;
+    const unsigned char* row = x + (int64_t)n * S;
+    unsigned lo = 255u, hi = 0u;
+    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < S; i += (int64_t)gridDim.x * 256) {
+        const unsigned v = row[i];
+        lo = v < lo ? v : lo;
+        hi = v > hi ? v : hi;
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+        const unsigned a = (unsigned)__shfl_xor((int)lo, o, 64), b = (unsigned)__shfl_xor((int)hi, o, 64);
+        lo = a < lo ? a : lo;
+        hi = b > hi ? b : hi;
+    }
+    if ((threadIdx.x & 63) == 0) {
+        atomicMin(&mm[2 * n], Key<float>::enc((float)lo));
+        atomicMax(&mm[2 * n + 1], Key<float>::enc((float)hi));
+    }
+}
+
 // ---------------------------------------------------------------- Gaussian blur (scipy.ndimage.gaussian_filter, mode='reflect')
 // 'reflect' (d c b a | a b c d): index into the 2n-periodic mirrored sequence; valid for any i and n >= 1.
 __device__ __forceinline__ int reflect_index(int i, int n) {
@@ -856,6 +880,20 @@ extern "C" int dram_aug_minmax(const float* x, float* minmax, const int* flag, i
     else hipLaunchKernelGGL(minmax_kernel<false>, dim3((unsigned)bps, N), dim3(256), 0, st, x, mm, flag, S);
     hipLaunchKernelGGL(minmax_decode_kernel, dim3(cdiv(N, 256)), dim3(256), 0, st, mm, flag, N);
     return check_launch("aug_minmax");
+}
+
+extern "C" int dram_aug_minmax_u8(const unsigned char* x, float* minmax, const int* flag, int N, int64_t S, void* stream) {
+    DRAM_REQUIRE(x && minmax, "aug_minmax_u8: null pointer");
+    DRAM_REQUIRE(N > 0 && N <= 65535 && S > 0, "aug_minmax_u8: bad sizes");
+    hipStream_t st = (hipStream_t)stream;
+    unsigned* mm = reinterpret_cast<unsigned*>(minmax);
+    int64_t bps = cdiv64(S, 256 * 32);
+    const int64_t cap = 8192 / N > 1 ? 8192 / N : 1;
+    if (bps > cap) bps = cap;
+    hipLaunchKernelGGL(minmax_init_kernel, dim3(cdiv(N, 256)), dim3(256), 0, st, mm, flag, N);
+    hipLaunchKernelGGL(minmax_u8_kernel, dim3((unsigned)bps, N), dim3(256), 0, st, x, mm, flag, S);
+    hipLaunchKernelGGL(minmax_decode_kernel, dim3(cdiv(N, 256)), dim3(256), 0, st, mm, flag, N);
+    return check_launch("aug_minmax_u8");
 }
 
 extern "C" int dram_aug_gaussian_blur(const float* x, float* y, const float* weights, const int* flag, int n_table, int radius,

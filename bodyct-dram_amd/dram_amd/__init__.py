@@ -10,7 +10,8 @@ from . import _lib, functional, modules  # noqa: F401
 _AUGMENT = ("GaussianBlur", "RandomMaskOut", "RandomFlip", "RandomRotate90", "GaussianAddictive", "IntensityInverse",
             "GammaTransform", "ContrastStretchingTransform", "ContrastJitter", "MinimalIntensityProjection",
             "MaximumIntensityProjection", "MinimalIntensityAxialProjection", "DiskMaskOut", "RandomCubeMask", "RandomMoveAxis",
-            "RandomRotateInplane90", "RandomCrop", "StandarizeChannel", "EnsembleScanAugmentation")
+            "RandomRotateInplane90", "RandomCrop", "StandarizeChannel", "RandomAffineTransform3D", "RandomRotate",
+            "EnsembleScanAugmentation")
 
 __all__ = ["_lib", "functional", "modules", *_AUGMENT]
 

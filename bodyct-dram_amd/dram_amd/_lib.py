@@ -137,6 +137,10 @@ SIGNATURES = {
     "dram_aug_pad_min_ws_bytes": (Z, [I, I, I, I, I]),
     "dram_aug_pad_min": (I, [P, I, P, I, I, I, I, P, Z, P]),
     "dram_aug_crop_resample": (I, [P, P, I, I, P, P, Z, P, I, I, I, I, I, P]),
+    "dram_aug_minmax_u8": (I, [P, P, P, I, L, P]),
+    "dram_aug_spline_ws_bytes": (Z, [I, I, I, I]),
+    "dram_aug_spline_prefilter": (I, [P, P, P, I, I, I, I, I, P, Z, P]),
+    "dram_aug_spline_resample": (I, [P, P, I, I, P, P, P, Z, P, I, I, I, I, I, P]),
     # device chunk loader
     "dram_chunk_hist256": (I, [P, P, P, I, P, I, I, P]),
     "dram_otsu256": (I, [P, I, ctypes.c_double, P, P]),

@@ -11,8 +11,9 @@ Beside the pool's five, four more intensity transforms of data_transforms.py are
 (`EnsembleScanAugmentation(aug_ratio, pool=[...])`): `IntensityInverse`, `GammaTransform`, `ContrastStretchingTransform` and
 `ContrastJitter`; the slab projections `MinimalIntensityProjection`, `MaximumIntensityProjection` and
 `MinimalIntensityAxialProjection`; the region masks `DiskMaskOut` and `RandomCubeMask`; and the axis moves `RandomMoveAxis` and
-`RandomRotateInplane90`; the scale-and-translate augmentation `RandomCrop` (pad, crop, resample back to the chunk's size); and
-`StandarizeChannel`.
+`RandomRotateInplane90`; the scale-and-translate augmentation `RandomCrop` (pad, crop, resample back to the chunk's size);
+`StandarizeChannel`; and the two spline-resampled geometric transforms `RandomAffineTransform3D` and `RandomRotate`
+(csrc/spline.hip: cubic B-spline for the image, nearest neighbour for every other entry).
 
 Drawing.  `draw(n, shape)` returns one parameter dict per sample, in sample order, from the same `random` / `numpy.random`
 calls in the same order as the reference's `__call__` makes for one chunk, so a seeded run picks what the reference would pick
@@ -21,6 +22,7 @@ serves every image entry, which is the same thing for the single-image samples o
 given parameters; an entry of `params` that is None leaves that sample untouched (bit-identical).
 """
 import itertools
+import math
 import random
 
 import numpy as np
@@ -41,6 +43,10 @@ MAX_W = 2048       # csrc/crop.hip CROP_MAX_W / PAD_MAX_DIM
 CROP_DTYPE = np.dtype([("z0", "<i4"), ("y0", "<i4"), ("x0", "<i4"), ("cd", "<i4"), ("ch", "<i4"), ("cw", "<i4"),
                        ("mode", "<i4"), ("pad", "<i4"), ("sz", "<f8"), ("sy", "<f8"), ("sx", "<f8")])
 assert CROP_DTYPE.itemsize == 56
+# one record per sample (csrc/spline.hip: SplineRec): source = m * (z, y, x) + off; fixed = the axis a plane transform leaves alone
+SPLINE_DTYPE = np.dtype([("m", "<f8", (9,)), ("off", "<f8", (3,)), ("fixed", "<i4"), ("pad", "<i4")])
+assert SPLINE_DTYPE.itemsize == 104
+ROTATE_PLANES = [(-1, -2), (-1, -3), (-2, -3)]     # RandomRotate's planes, in the order of itertools.combinations([-1, -2, -3], 2)
 
 
 # ---------------------------------------------------------------------------------------------------------------- tables
@@ -128,6 +134,49 @@ def pad_crop(x, params, mode="minimum"):
     padded = np.pad(x, padding, mode=mode)
     start, size = crop_window(params, x.shape)
     return padded[tuple(slice(st + p[0], st + p[0] + sz) for st, sz, p in zip(start, size, padding))]
+
+
+def _homogeneous(lin, shift=(0.0, 0.0, 0.0)):
+    h = np.eye(4)
+    h[:3, :3] = lin
+    h[:3, 3] = shift
+    return h
+
+
+def affine_matrix(scales, angles, shape):
+    """RandomAffineTransform3D._affine's output-to-input map as (3 x 3 matrix, offset), fp64: the inverse (np.linalg.inv) of
+    T1 . rotz . roty . rotx . T0, multiplied from the right as the reference multiplies them -- T0 scales and moves the centre
+    shape / 2 to the origin, rotz / roty / rotx turn about the third / second / first axis of the array, T1 moves back."""
+    half = [n / 2.0 for n in shape]
+    (ca, sa), (cb, sb), (ct, st) = [(math.cos(v), math.sin(v)) for v in angles]
+    T0 = _homogeneous(np.diag([scales[0], scales[1], scales[2]]), [-v for v in half])
+    rotz = _homogeneous([[ca, -sa, 0], [sa, ca, 0], [0, 0, 1]])
+    roty = _homogeneous([[cb, 0, sb], [0, 1, 0], [-sb, 0, cb]])
+    rotx = _homogeneous([[1, 0, 0], [0, ct, -st], [0, st, ct]])
+    T1 = _homogeneous(np.eye(3), half)
+    inv = np.linalg.inv(T1.dot(rotz.dot(roty.dot(rotx.dot(T0)))))
+    return inv[:3, :3].copy(), inv[:3, 3].copy()
+
+
+def rotate_matrix(angle, axes, shape):
+    """scipy.ndimage.rotate(reshape=False) by `angle` degrees in the plane of the (negative) spatial axes `axes`, as (3 x 3
+    matrix, offset, fixed axis): scipy sorts the two axes, turns every plane with [[c, s], [-s, c]] (cosdg / sindg: exact at
+    multiples of 90) about the centre (n - 1) / 2 of each plane axis, and leaves the third axis alone."""
+    from scipy import special
+    plane = sorted(a % 3 for a in axes)
+    if len(plane) != 2 or plane[0] == plane[1]:
+        raise ValueError(f"RandomRotate: {tuple(axes)} is no plane of a 3-d sample")
+    c, s = special.cosdg(angle), special.sindg(angle)
+    rot = np.array([[c, s], [-s, c]])
+    centre = (np.asarray([shape[a] for a in plane], dtype=np.float64) - 1) / 2
+    shift = centre - rot @ centre
+    m, off = np.eye(3), np.zeros(3)
+    for i, a in enumerate(plane):
+        off[a] = shift[i]
+        m[a, a] = 0.0
+        for j, b in enumerate(plane):
+            m[a, b] = rot[i, j]
+    return m, off, 3 - plane[0] - plane[1]
 
 
 def _dev(values, dtype, device):
@@ -278,6 +327,40 @@ def crop_resample(x, table, flags, linear, pad_ws=None, out=None):
     ws, nbytes = pad_ws if pad_ws is not None else (None, 0)
     call("dram_aug_crop_resample", HF._p(x), HF._p(y), x.element_size(), int(bool(linear)), HF._p(table), HF._p(ws), nbytes,
          HF._p(flags), flags.numel(), N, D, H, W, HF._stream())
+    return y
+
+
+def sample_min_table(x, flags=None):
+    """[N, 2] fp32 {min, max} of every fp32 or uint8 sample: what `spline_resample` fills with."""
+    if x.dtype == torch.float32:
+        return sample_minmax(x, flags)
+    N = x.shape[0]
+    mm = torch.empty((N, 2), dtype=torch.float32, device=x.device)
+    call("dram_aug_minmax_u8", HF._p(x), HF._p(mm), HF._p(flags), N, x[0].numel(), HF._stream())
+    return mm
+
+
+def spline_prefilter(x, axes, flags):
+    """(workspace, bytes): the fp64 cubic B-spline coefficients [N, D, H, W] of the fp32 samples whose flag is TRANSFORM,
+    filtered along the axes of the sample's mask (`axes`: [N] int32 device table, bit 0 = z, 1 = y, 2 = x).  The workspace is
+    allocated here on every call and is 8 bytes per voxel of the whole batch -- twice the tensor itself, 1 GiB at 64 x 128^3 --,
+    transient memory to count when sizing a batch; it goes back to torch's caching allocator once the gather has run."""
+    N, _, D, H, W = x.shape
+    nbytes = _lib.lib.dram_aug_spline_ws_bytes(N, D, H, W)
+    ws = torch.empty(max(nbytes, 16), dtype=torch.uint8, device=x.device)
+    call("dram_aug_spline_prefilter", HF._p(x), HF._p(axes), HF._p(flags), flags.numel(), N, D, H, W, HF._p(ws), nbytes,
+         HF._stream())
+    return ws, nbytes
+
+
+def spline_resample(x, table, minmax, flags, order, coef=None, out=None):
+    """Every sample resampled at source = m * index + off (table: N SPLINE_DTYPE records as a uint8 device tensor), `minmax[n, 0]`
+    where the source lies outside; order 3 (fp32, `coef` = what `spline_prefilter` returned) or order 0.  Not in place."""
+    N, _, D, H, W = x.shape
+    y = torch.empty_like(x) if out is None else out
+    ws, nbytes = coef if coef is not None else (None, 0)
+    call("dram_aug_spline_resample", HF._p(x), HF._p(y), x.element_size(), int(order), HF._p(table), HF._p(minmax), HF._p(ws),
+         nbytes, HF._p(flags), flags.numel(), N, D, H, W, HF._stream())
     return y
 
 
@@ -900,6 +983,91 @@ class StandarizeChannel(_Augmentation):
 
     def _launch(self, x, tables, flags, out=None, rows=1):
         return _intensity_map(x, MAP_STANDARDIZE, None, None, row_mean_std(x, rows, flags), False, flags, rows, out)
+
+
+class _SplineTransform(_Augmentation):
+    """Shared by the two spline-resampled transforms: every '#' entry is resampled at a per-sample affine map of the output
+    index, keys containing "image" with cubic B-splines (scipy's order 3: fp64 coefficients from a prefilter, then 64 taps per
+    voxel, 16 in a rotation plane), every other key at the nearest voxel (order 0; fp32 or uint8, dtype kept).  mode="constant":
+    a voxel whose source lies outside [0, n - 1] in any axis gets the entry's own per-sample minimum."""
+    intensity = False
+
+    def _record(self, p, shape):   # pragma: no cover - overridden
+        """(3 x 3 matrix, offset, fixed axis or -1, prefilter axes mask) of one sample."""
+        raise NotImplementedError
+
+    def _tables(self, params, shape, device):
+        table = np.zeros(len(params), dtype=SPLINE_DTYPE)
+        axes = []
+        for i, p in enumerate(params):
+            m, off, fixed, mask = (np.eye(3), np.zeros(3), -1, 0) if p is None else self._record(p, shape)
+            if not (np.all(np.isfinite(m)) and np.all(np.isfinite(off))):
+                raise ValueError(f"{type(self).__name__}: sample {i}: the transform is not finite")
+            table[i] = (np.asarray(m, dtype=np.float64).reshape(9), np.asarray(off, dtype=np.float64), fixed, 0)
+            axes.append(mask)
+        tab = torch.from_numpy(table.view(np.uint8).copy())
+        if torch.device(device).type == "cuda":
+            tab = tab.pin_memory().to(device, non_blocking=True)
+        return tab, _dev(axes, torch.int32, device)
+
+    def _launch(self, x, tables, flags, out=None):     # pragma: no cover - the key decides the interpolation
+        raise NotImplementedError(f"{type(self).__name__} works per key: _launch_key")
+
+    def _launch_key(self, key, x, tables, flags, out=None):
+        table, axes = tables
+        order = 3 if "image" in key else 0
+        if x.shape[1] != 1:
+            raise NotImplementedError(f"{type(self).__name__}: '{key}': single-channel samples only, got shape {tuple(x.shape)}")
+        if order == 3 and x.dtype != torch.float32:
+            raise NotImplementedError(f"{type(self).__name__}: '{key}' is {x.dtype} and would be resampled with cubic splines; "
+                                      f"order 3 is built for float32 (nearest neighbour: keys without 'image')")
+        minmax = sample_min_table(x, flags)
+        coef = spline_prefilter(x, axes, flags) if order == 3 else None
+        return spline_resample(x, table, minmax, flags, order, coef, out)
+
+
+class RandomAffineTransform3D(_SplineTransform):
+    """scipy.ndimage.affine_transform of every '#' entry with one scale per axis and three rotation angles per sample: six
+    np.random.uniform draws, the scales U(1 - s, 1 + s) first, then the angles U(-r, r); the matrix is `affine_matrix`, built
+    and inverted on the host in fp64.  `meta` passes through (the reference stores the draws and 'size' there)."""
+
+    def __init__(self, spatial_dim, rotations=(0.2 * math.pi, 0.2 * math.pi, 0.2 * math.pi), scales=(0.05, 0.05, 0.05)):
+        self.spatial_dim = spatial_dim
+        self.rotations = rotations
+        self.scales = scales
+        if spatial_dim != 3:
+            raise NotImplementedError("RandomAffineTransform3D: supported: spatial_dim 3")
+
+    def draw_one(self, shape):
+        draw = np.random.uniform
+        return {"scales": [float(draw(1.0 - s, 1.0 + s)) for s in self.scales],               # the scales first,
+                "rotate_angles": [float(draw(-r, r)) for r in self.rotations]}                # then the angles
+
+    def _record(self, p, shape):
+        m, off = affine_matrix(p["scales"], p["rotate_angles"], shape)
+        return m, off, -1, 7
+
+
+class RandomRotate(_SplineTransform):
+    """scipy.ndimage.rotate(reshape=False) of every '#' entry: one random.randint(*rotate_range) angle in degrees, then the
+    plane as the first of two planes sampled from ROTATE_PLANES (Python's `random`, in that order).  scipy turns a 3-d array
+    plane by plane with a 2-d transform, so the spline prefilter runs along the two plane axes only; the fill value is the
+    minimum of the whole sample.  `meta` passes through."""
+
+    def __init__(self, spatial_dim, rotate_range):
+        self.spatial_dim = spatial_dim
+        self.rotate_range = rotate_range
+        if spatial_dim != 3:
+            raise NotImplementedError("RandomRotate: supported: spatial_dim 3")
+
+    def draw_one(self, shape):
+        angle = random.randint(*self.rotate_range)
+        plane = random.sample(ROTATE_PLANES, 2)[0]       # two are sampled and the first is used: the stream moves as it does there
+        return {"rotate_axis": tuple(plane), "rotate_angle": angle}
+
+    def _record(self, p, shape):
+        m, off, fixed = rotate_matrix(p["rotate_angle"], p["rotate_axis"], shape)
+        return m, off, fixed, 7 & ~(1 << fixed)
 
 
 # -------------------------------------------------------------------------------------------------------------- ensemble

@@ -625,6 +625,30 @@ int dram_aug_pad_min(const void* x, int elem_size, const int* flag, int N, int D
 int dram_aug_crop_resample(const void* x, void* y, int elem_size, int linear, const void* table, const void* pad_ws,
                            size_t pad_ws_bytes, const int* flag, int n_table, int N, int D, int H, int W, void* stream);
 
+/* RandomAffineTransform3D and RandomRotate (dram/data_transforms.py:995-1102): scipy.ndimage.affine_transform / rotate with
+ * mode="constant", order 3 (float32) or order 0 (float32 or uint8), cval = the sample's own minimum.  x, y: [N, D, H, W];
+ * D*H*W < 2^29.  Per-sample flags as above.
+ *
+ * dram_aug_minmax_u8: dram_aug_minmax for uint8 samples; minmax[n] = {min, max} as fp32 (exact).
+ * dram_aug_spline_prefilter: the fp64 cubic B-spline coefficients of every sample whose flag is 1 into ws [N][D][H][W] doubles
+ *   (dram_aug_spline_ws_bytes(N, D, H, W) bytes, 8-byte aligned): per axis in turn, z first, the mirror-boundary filter with
+ *   the pole sqrt(3) - 2 along every line of more than one element.  axes[n]: bit 0 = filter along z, bit 1 = y, bit 2 = x (7 for
+ *   an affine transform, the two plane axes for a rotation, which scipy runs plane by plane).  Up to three launches.
+ * dram_aug_spline_resample: table: N records of 104 bytes on the DEVICE, {double m[9]: row-major 3 x 3; double off[3]; int fixed:
+ *   -1 for a 3-d transform, or the axis (0 = z, 1 = y, 2 = x) that a plane transform leaves alone, whose row of m is the unit
+ *   row and whose off is 0; int pad}.  Output voxel idx reads source coordinate x_h = off[h] + sum_l m[h][l] * idx[l] (fp64, added
+ *   left to right, products rounded on their own).  Any x_h outside [0, n_h - 1]: minmax[n][0] (dram_aug_minmax or
+ *   dram_aug_minmax_u8 of x).  order 3 (float32 only): the taps floor(x) - 1 .. floor(x) + 2 per axis (one tap on the fixed
+ *   axis) of ws = dram_aug_spline_prefilter of this x, indices mirrored with period 2n - 2, cubic B-spline weights, added in
+ *   fp64 with z slowest, cast to fp32.  order 0: the voxel of x at floor(x_h + 0.5); ws may be NULL.  Not in place. */
+int dram_aug_minmax_u8(const unsigned char* x, float* minmax, const int* flag, int N, int64_t S, void* stream);
+size_t dram_aug_spline_ws_bytes(int N, int D, int H, int W);
+int dram_aug_spline_prefilter(const float* x, const int* axes, const int* flag, int n_table, int N, int D, int H, int W, void* ws,
+                              size_t ws_bytes, void* stream);
+int dram_aug_spline_resample(const void* x, void* y, int elem_size, int order, const void* table, const float* minmax,
+                             const void* ws, size_t ws_bytes, const int* flag, int n_table, int N, int D, int H, int W,
+                             void* stream);
+
 /* ---- device chunk loader: what the reference does per chunk on the host before a training step, for a whole ragged batch.
  *      RadboudCOVIDLobeVesselChunk.get_data (dram/dataset.py:450-486): w_scan = windowing(scan, to_span=(0, 1)) (utils.py:189-198,
  *      default span (-1150, 350)); _, th = binary_cam(w_scan[lobe > 0], 0.75) (utils.py:226-242); pseudo lesion = (w_scan > th) &
