@@ -1,9 +1,11 @@
 // The less-travelled branches of the reference's factories, gfx950:
 //   * nn.PReLU(num_parameters, init)           act_wrapper "prelu", dram/parts.py:51-52
 //   * F.adaptive_max_pool3d(x, 1)              pooling_dense_features 'global_max', dram/models.py:41-42
-// Both are HBM-bound streaming passes over (n,c) rows of S = D*H*W contiguous floats; every reduction is a
-// fixed-order tree (deterministic, no atomics).
+//   * nn.Dropout(dropout)                      the trailing module of a conv stage, dram/parts.py:95-96
+// The first two are HBM-bound streaming passes over (n,c) rows of S = D*H*W contiguous floats; every reduction is a
+// fixed-order tree (deterministic, no atomics).  Dropout is a streaming pass over the flat tensor.
 #include "common.h"
+#include "philox.h"
 
 namespace dram {
 
@@ -109,6 +111,36 @@ __global__ __launch_bounds__(256) void global_max_bwd_kernel(const float* __rest
     for (int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x; e < S; e += stride) dr[e] = e == hit ? g : 0.f;
 }
 
+// ---------------------------------------------------------------- dropout
+// Element i belongs to group g = i / 4; the group's four words are philox4x32_10(counter = {g, offset}, key = seed) and
+// element i is kept iff the top 24 bits of word i % 4 are >= threshold24.  The mask depends on (seed, offset, i) alone, so the
+// backward pass recomputes it from the same two integers (dy in, dx out) and nothing is stored.  A lane makes one Philox call
+// for the group g0 + its global lane index; VEC moves the group as one 16-byte access and is launched over whole groups only.
+template <bool VEC>
+__global__ __launch_bounds__(256) void dropout_kernel(const float* x, float* y, int64_t n, int64_t g0, unsigned threshold24,
+                                                      float scale, unsigned k0, unsigned k1, unsigned o0, unsigned o1) {
+    const int64_t g = g0 + (int64_t)blockIdx.x * 256 + threadIdx.x;
+    const int64_t i = g * 4;
+    if (i >= n) return;
+    const int cnt = (n - i) < 4 ? (int)(n - i) : 4;   // VEC: always 4 (n is a multiple of 4 there)
+    float v[4] = {0.f, 0.f, 0.f, 0.f};
+    if (VEC) {
+        const float4 q = *reinterpret_cast<const float4*>(x + i);
+        v[0] = q.x; v[1] = q.y; v[2] = q.z; v[3] = q.w;
+    } else {
+        for (int e = 0; e < cnt; ++e) v[e] = x[i + e];
+    }
+    unsigned r[4];
+    philox4x32_10((unsigned)g, (unsigned)((unsigned long long)g >> 32), o0, o1, k0, k1, r);
+#pragma unroll
+    for (int e = 0; e < 4; ++e) v[e] = (r[e] >> 8) >= threshold24 ? __fmul_rn(v[e], scale) : 0.f;
+    if (VEC) {
+        *reinterpret_cast<float4*>(y + i) = make_float4(v[0], v[1], v[2], v[3]);
+    } else {
+        for (int e = 0; e < cnt; ++e) y[i + e] = v[e];
+    }
+}
+
 static inline unsigned stream_blocks(int64_t S) {
     const int64_t b = cdiv64(S, 256 * 8);
     return (unsigned)(b < 1 ? 1 : (b > 1024 ? 1024 : b));
@@ -159,4 +191,24 @@ extern "C" int dram_global_max_bwd(const float* dout, const int64_t* idx, float*
     DRAM_REQUIRE(NC > 0 && NC <= 65535 && S > 0, "global_max_bwd: bad dimensions");
     hipLaunchKernelGGL(global_max_bwd_kernel, dim3(stream_blocks(S), NC), dim3(256), 0, (hipStream_t)stream, dout, idx, dx, S);
     return check_launch("global_max_bwd");
+}
+
+extern "C" int dram_dropout(const float* x, float* y, int64_t n, unsigned threshold24, float scale, unsigned long long seed,
+                            unsigned long long offset, void* stream) {
+    DRAM_REQUIRE(n >= 0, "dropout: negative element count");
+    DRAM_REQUIRE(threshold24 <= (1u << 24), "dropout: threshold24 %u is above 1 << 24", threshold24);
+    if (n == 0) return DRAM_OK;
+    DRAM_REQUIRE(x && y, "dropout: null pointer");
+    DRAM_REQUIRE(n <= ((int64_t)1 << 40), "dropout: more than 2^40 elements");   // one block per 1024 elements, grid.x < 2^31
+    hipStream_t st = (hipStream_t)stream;
+    const unsigned k0 = (unsigned)seed, k1 = (unsigned)(seed >> 32), o0 = (unsigned)offset, o1 = (unsigned)(offset >> 32);
+    const int64_t whole = aligned16(x) && aligned16(y) ? n / 4 : 0;   // groups moved as 16-byte accesses
+    if (whole > 0)
+        hipLaunchKernelGGL(dropout_kernel<true>, dim3((unsigned)cdiv64(whole, 256)), dim3(256), 0, st, x, y, whole * 4, (int64_t)0,
+                           threshold24, scale, k0, k1, o0, o1);
+    const int64_t rest = cdiv64(n, 4) - whole;                        // the tail group, or every group of an unaligned tensor
+    if (rest > 0)
+        hipLaunchKernelGGL(dropout_kernel<false>, dim3((unsigned)cdiv64(rest, 256)), dim3(256), 0, st, x, y, n, whole,
+                           threshold24, scale, k0, k1, o0, o1);
+    return check_launch("dropout");
 }

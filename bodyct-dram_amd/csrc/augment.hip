@@ -7,6 +7,7 @@
 //
 // Every table carries a per-sample flag:  1 = transform,  0 = pass through (copied when y != x),  < 0 = skip the sample
 // (y is not written: the ensemble driver keeps samples in different buffers and moves only the ones a launch is for).
+#include "philox.h"
 #include "volume_math.h"
 #include <math.h>
 
@@ -248,18 +249,7 @@ __global__ __launch_bounds__(256) void maskout_kernel(const float* x, float* y, 
 }
 
 // ---------------------------------------------------------------- additive Gaussian noise
-// Philox4x32-10 (Salmon et al., SC'11): key = the sample's seed, counter = index of the group of four elements.
-__device__ __forceinline__ void philox4x32_10(unsigned k0, unsigned k1, unsigned c0, unsigned c1, unsigned out[4]) {
-    unsigned c2 = 0u, c3 = 0u;
-#pragma unroll
-    for (int r = 0; r < 10; ++r) {
-        const unsigned hi0 = __umulhi(0xD2511F53u, c0), lo0 = 0xD2511F53u * c0;
-        const unsigned hi1 = __umulhi(0xCD9E8D57u, c2), lo1 = 0xCD9E8D57u * c2;
-        c0 = hi1 ^ c1 ^ k0; c1 = lo1; c2 = hi0 ^ c3 ^ k1; c3 = lo0;
-        k0 += 0x9E3779B9u; k1 += 0xBB67AE85u;
-    }
-    out[0] = c0; out[1] = c1; out[2] = c2; out[3] = c3;
-}
+// Philox4x32-10 (philox.h): key = the sample's seed, counter = index of the group of four elements.
 
 // Box-Muller on 24-bit uniforms strictly inside (0, 1): two independent N(0, 1) values.
 __device__ __forceinline__ void box_muller(unsigned a, unsigned b, float& z0, float& z1) {

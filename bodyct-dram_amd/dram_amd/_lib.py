@@ -82,6 +82,7 @@ SIGNATURES = {
     "dram_prelu_bwd": (I, [P, P, P, P, P, P, Z, I, I, I, L, P]),
     "dram_global_max_fwd": (I, [P, P, P, I, L, P]),
     "dram_global_max_bwd": (I, [P, P, P, I, L, P]),
+    "dram_dropout": (I, [P, P, L, ctypes.c_uint, F, ctypes.c_ulonglong, ctypes.c_ulonglong, P]),
     "dram_resize_trilinear_fwd": (I, [P, P, I, I, I, I, I, I, I, I, F, F, F, P]),
     "dram_resize_trilinear_bwd": (I, [P, P, I, I, I, I, I, I, I, I, F, F, F, P]),
     "dram_resize_nearest": (I, [P, P, I, I, I, I, I, I, I, I, F, F, F, P]),

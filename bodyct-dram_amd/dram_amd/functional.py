@@ -8,6 +8,7 @@ There is no fallback: CPU tensors raise.
 import ctypes
 import math
 
+import numpy as np
 import torch
 from torch.autograd import Function
 from torch.autograd.function import once_differentiable
@@ -658,6 +659,49 @@ class PReLUFn(Function):
 
 def prelu(x, a):
     return PReLUFn.apply(x, a)
+
+
+def dropout_constants(p):
+    """(threshold24, scale) of dram_dropout for drop probability p: an element is kept iff its 24-bit uniform is
+    >= threshold24 = round(p * 2^24), so the kept share is exactly 1 - threshold24 / 2^24; scale is the fp64 quotient
+    1 / (1 - p) rounded once to fp32 (0 when p == 1: everything is dropped)."""
+    p = float(p)
+    if not 0.0 <= p <= 1.0:
+        raise ValueError(f"dropout probability has to be between 0 and 1, but got {p}")
+    return int(round(p * 2 ** 24)), (0.0 if p == 1.0 else float(np.float32(1.0 / (1.0 - p))))
+
+
+class DropoutFn(Function):
+    """nn.Dropout in training mode (reference parts.py:95-96).  The mask is Philox4x32-10 of (seed, offset, element index)
+    (include/dram_hip.h) and is recomputed in the backward pass: ctx keeps two integers and no tensor.  Seed and offset are
+    the device generator's, and a call advances its offset by 4 as an ATen kernel that consumes up to four values per
+    thread does, so torch.manual_seed, get_rng_state / set_rng_state and torch.utils.checkpoint's RNG preservation apply."""
+
+    @staticmethod
+    def forward(ctx, x, p):
+        x = _chk(x, "dropout input")
+        if torch.cuda.is_current_stream_capturing():
+            raise RuntimeError("dropout: the stream is capturing a graph; the generator's offset cannot be read there "
+                               "(graph capture of dropout is not supported)")
+        ctx.threshold24, ctx.scale = dropout_constants(p)
+        gen = torch.cuda.default_generators[x.device.index]
+        ctx.seed, ctx.offset = gen.initial_seed(), gen.get_offset()
+        gen.set_offset(ctx.offset + 4)
+        y = torch.empty_like(x)
+        call("dram_dropout", _p(x), _p(y), x.numel(), ctx.threshold24, ctx.scale, ctx.seed, ctx.offset, _stream())
+        return y
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, dy):
+        dy = _chk(dy, "dropout grad_output")
+        dx = torch.empty_like(dy)
+        call("dram_dropout", _p(dy), _p(dx), dy.numel(), ctx.threshold24, ctx.scale, ctx.seed, ctx.offset, _stream())
+        return dx, None
+
+
+def dropout(x, p):
+    return DropoutFn.apply(x, p)
 
 
 class GlobalMaxFn(Function):

@@ -135,6 +135,16 @@ class HipPReLU(nn.PReLU):
         return HF.prelu(x, self.weight)
 
 
+class HipDropout(nn.Dropout):
+    """nn.Dropout (the trailing module of a conv stage, parts.py:95-96).  The identity (the input object itself) in eval
+    mode or with p == 0; otherwise a new tensor, `inplace` is ignored as in HipReLU."""
+
+    def forward(self, x):
+        if not self.training or self.p == 0:
+            return x
+        return HF.dropout(x, self.p)
+
+
 class HipMaxPool3d(nn.MaxPool3d):
     """nn.MaxPool3d(2, 2, 0) (parts.py:191)."""
 

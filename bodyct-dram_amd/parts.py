@@ -19,8 +19,8 @@ import torch.nn.functional as F  # noqa: F401
 from torch.utils.checkpoint import checkpoint, checkpoint_sequential  # noqa: F401
 
 from dram_amd import functional as HF
-from dram_amd.modules import (HipBatchNorm3d, HipConv3d, HipGroupNorm, HipMaxPool3d, HipPReLU, HipReLU, HipSyncBatchNorm,
-                              HipUpsample, run_conv_stack)
+from dram_amd.modules import (HipBatchNorm3d, HipConv3d, HipDropout, HipGroupNorm, HipMaxPool3d, HipPReLU, HipReLU,
+                              HipSyncBatchNorm, HipUpsample, run_conv_stack)
 
 
 class Identity(nn.Module):
@@ -93,7 +93,7 @@ def _conv_stack(in_chs, out_chs, ksize, pad, stride, bias, norm_method, act_meth
             layers.append(normal_wrapper(norm_method, co))
         layers.append(act_wrapper(act_method))
         if dropout > 0 and not lite:
-            layers.append(nn.Dropout(dropout))
+            layers.append(HipDropout(dropout))
         stages.append(nn.Sequential(*layers))
     return nn.Sequential(*stages)
 

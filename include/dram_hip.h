@@ -290,6 +290,15 @@ int dram_prelu_bwd(const float* dy, const float* x, const float* a, float* dx, f
 int dram_global_max_fwd(const float* x, float* out, int64_t* idx, int NC, int64_t S, void* stream);
 int dram_global_max_bwd(const float* dout, const int64_t* idx, float* dx, int NC, int64_t S, void* stream);
 
+/* ---- nn.Dropout (the trailing module of a conv stage, dram/parts.py:95-96), forward and backward in one entry.
+ * For element i of the n contiguous floats: g = i / 4, r = philox4x32_10(counter = {g lo, g hi, offset lo, offset hi},
+ * key = {seed lo, seed hi}); the element is kept iff (r[i % 4] >> 8) >= threshold24, and
+ * y[i] = keep ? x[i] * scale (one fp32 rounding) : +0.  The mask is a function of (seed, offset, i) only -- not of
+ * alignment, grid or tensor shape -- so the backward is the same call with dy in and dx out and no mask is stored.
+ * threshold24 in [0, 1 << 24]: the kept share is exactly 1 - threshold24 / 2^24.  y may be x.  n == 0 is a no-op. */
+int dram_dropout(const float* x, float* y, int64_t n, unsigned threshold24, float scale, unsigned long long seed,
+                 unsigned long long offset, void* stream);
+
 /* ---- on-device OneShot transforms (dram/data_transforms.py:1140-1239, used by the affine-consistency
  *      losses dram/metrics.py:213-310 on [N,C,D,H,W] device tensors) ----
  * Rescale3DOneShot: F.interpolate(mode='trilinear') with align_corners=False on "#image" tensors (+ its adjoint, the
