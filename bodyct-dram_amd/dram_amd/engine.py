@@ -21,6 +21,12 @@ Not an oracle and not a fallback: every step is a kernel of libdram_hip.so.  Net
 (PReLU, dropout, `lite` blocks, conv kernels other than 3x3x3, checkpoint_mode="recompute") run the per-op path.
 "sbn" (cross-rank BatchNorm, parts.py:32-33) is covered: the per-rank statistics of the conv epilogue are combined over the
 process group (_sync_forward_stats), and so are the two sums of the norm's backward.
+
+The tape that forward records is a list of typed entries, and `backward` walks it in reverse, one handler per kind:
+_Input (the root tensor and the memory plan of this forward call; nothing to do), _Stage (_stage_backward: _norm_backward,
+then _conv_backward), _Pool (_pool_backward), _Up (_up_backward), _Head (_head_backward), _Resize (_resize_backward).
+What the handlers share -- the gradients under way, the pending gradient sources, the delivery of finished parameter
+gradients -- is one _Backward object; whatever else a handler allocates dies when it returns.
 """
 import os as _os
 
@@ -132,16 +138,45 @@ def supports(model):
         return False
 
 
-def parameters_of(model):
-    """The parameters the engine differentiates, in a fixed order (the autograd Function's tensor inputs)."""
-    return [p for p in model.parameters()]
-
-
 # ------------------------------------------------------------------------------------------------ forward pieces
 class _Stage:
     """What backward needs of one conv -> norm -> ReLU stage."""
     __slots__ = ("conv", "norm", "inp", "skip", "y", "coef", "mean", "rstd", "kind", "groups", "batch_stats",
                  "out", "need_input_grad", "ranges", "sync")
+
+
+class _Entry:
+    """The other tape entries: their fields, in the order of __slots__."""
+    __slots__ = ()
+
+    def __init__(self, *fields):
+        for name, value in zip(self.__slots__, fields):
+            setattr(self, name, value)
+
+
+class _Input(_Entry):
+    """The network's input (the root of backward) and the memory plan of this forward call (see _Plan)."""
+    __slots__ = ("lazy", "plan")
+
+
+class _Pool(_Entry):
+    """out = maxpool 2x2x2 of the Lazy `inp`, with the uint8 argmax `idx`."""
+    __slots__ = ("inp", "idx", "out")
+
+
+class _Up(_Entry):
+    """The Lazy `src` was upsampled (an Upsampled recipe) into the first stage of an up-block."""
+    __slots__ = ("src",)
+
+
+class _Head(_Entry):
+    """The 1x1x1 head read the Lazy `inp`."""
+    __slots__ = ("inp",)
+
+
+class _Resize(_Entry):
+    """The head's output, of `shape`, was resized to the input's size."""
+    __slots__ = ("shape",)
 
 
 def _norm_plan(norm, training):
@@ -266,7 +301,7 @@ def _conv_stage(conv, norm, inp, skip, training, record, plan):
         s.kind, s.groups, s.batch_stats, s.out = kind, groups, bool(use_batch), out
         s.sync = (group, total) if sync else None
         s.ranges = ranges
-        record.append(("conv", s))
+        record.append(s)
     return out
 
 
@@ -285,7 +320,7 @@ def _pool(lz, record):
     call("dram_maxpool3d_2_fwd_lazy", _p(lz.raw), _p(lz.coef), int(lz.relu), _p(out), _p(idx), N, C, D, H, W, _stream())
     res = Lazy(out)
     if record is not None:
-        record.append(("pool", lz, idx, res))
+        record.append(_Pool(lz, idx, res))
     return res
 
 
@@ -373,7 +408,7 @@ def forward(model, x, record, taps=()):
     us_flag = L + int(getattr(model, "us_flag_offset", 0))
     cur = Lazy(x)
     if record is not None:
-        record.append(("input", cur, plan))
+        record.append(_Input(cur, plan))
     skips = []
 
     def run_block(flag, block, fn):
@@ -409,7 +444,7 @@ def forward(model, x, record, taps=()):
                 raise AssertionError("UpsampleConvBlock5d: upsampled tensor larger than the skip tensor")
             up = Upsampled(cur, size)
             if record is not None:
-                record.append(("up", cur, size))
+                record.append(_Up(cur))
             cur = run_block(model.checkpoint_layers[us_flag + i], us, lambda: _conv_stack(us.conv_blocks, up, skip, training, record, plan))
             if L + 1 + i in taps:
                 tapped[L + 1 + i] = cur.materialise()
@@ -420,194 +455,211 @@ def forward(model, x, record, taps=()):
     call("dram_conv3d_k1_fwd_lazy", _p(cur.raw), _p(cur.coef), int(cur.relu), _p(top.weight), _p(top.bias), _p(dense),
          N, C, Co, D * H * W, _stream())
     if record is not None:
-        record.append(("head", cur))
+        record.append(_Head(cur))
     if tuple(dense.shape[-3:]) != tuple(x.shape[-3:]):
         small = dense
         dense = torch.empty((N, Co) + tuple(x.shape[-3:]), dtype=torch.float32, device=x.device)
         call("dram_upsample_trilinear_ac_fwd", _p(small), _p(dense), N, Co, D, H, W, *x.shape[-3:], _stream())
         if record is not None:
-            record.append(("resize", tuple(small.shape)))
+            record.append(_Resize(tuple(small.shape)))
     return dense, tapped
 
 
 # ------------------------------------------------------------------------------------------------ backward
+class _Backward:
+    """What the handlers of one backward walk share.  A tensor referenced from here outlives the handler that put it here:
+    only gradients that a later entry consumes belong in `g`, `gact` and `pending`."""
+    __slots__ = ("model", "root", "need_dx", "sink", "st", "g", "gact", "pending", "grads")
+
+    def __init__(self, model, root, gout, need_dx, sink):
+        self.model, self.root, self.need_dx, self.sink = model, root, need_dx, sink
+        self.st = _stream()
+        self.g = HF._chk(gout, "DC3D grad_output", 5)      # gradient w.r.t. the dense output, until the head has taken it
+        self.gact = {}      # id(Lazy) -> dense gradient w.r.t. the ACTIVATED tensor (accumulated over its consumers)
+        # id(Lazy) -> a part of that gradient which is not written out: the producing stage's norm backward forms it while it
+        # loads (dram_norm_bwd_head / _pool_add), with the bits the materialising kernel would have stored.
+        #   ("head", g, w):    the 1x1x1 head's input gradient, sum_o w[o,c] * g[n,o,:] -- the whole gradient of the tensor
+        #   ("pool", gp, idx): the max-pool's routed gradient, to be added to the skip gradient in gact
+        self.pending = {}
+        self.grads = {}     # parameter -> gradient (what the sink does not take)
+
+    def deliver(self, p, g):
+        if self.sink is None or not self.sink(p, g):
+            self.grads[p] = g
+
+
 def backward(model, record, gout, need_dx, sink=None):
     """Returns ({parameter: gradient}, dx or None).  `gout`: gradient w.r.t. the dense output.
     `sink(parameter, gradient) -> bool`: called as soon as a parameter's gradient is final -- the head first, then stage by
     stage from the last up-block to the first down-block, each right after its backward-weights launch -- so that a
     data-parallel trainer can start that gradient's all-reduce while the rest of backward still runs
     (train_step.DataParallelTrainer); a gradient the sink takes (True) is left out of the returned dict."""
-    st = _stream()
-
-    class _Grads(dict):         # parameter -> gradient (what the sink does not take)
-        def __setitem__(self, p, g):
-            if sink is None or not sink(p, g):
-                dict.__setitem__(self, p, g)
-    grads = _Grads()
-    gact = {}           # id(Lazy) -> dense gradient w.r.t. the ACTIVATED tensor (accumulated over its consumers)
-    # id(Lazy) -> a part of that gradient which is not written out: the producing stage's norm backward forms it while it
-    # loads (dram_norm_bwd_head / _pool_add), with the bits the materialising kernel would have stored.
-    #   ("head", g, w):    the 1x1x1 head's input gradient, sum_o w[o,c] * g[n,o,:] -- the whole gradient of the tensor
-    #   ("pool", gp, idx): the max-pool's routed gradient, to be added to the skip gradient in gact
-    pending = {}
-    g = HF._chk(gout, "DC3D grad_output", 5)
-    root = record[0][1]
-    for item in reversed(record):
-        tag = item[0]
-        if tag == "input":
-            continue
-        if tag == "resize":
-            g = HF.trilinear_ac_backward(g, item[1])
-        elif tag == "head":
-            lz = item[1]
-            top = model.top_layer
-            N, C, D, H, W = lz.raw.shape
-            Co, S = top.weight.shape[0], D * H * W
-            from_source = bool(_lib.lib.dram_norm_bwd_head_ok(Co))      # (more output channels: written out, as before)
-            dxa = None if from_source else torch.empty_like(lz.raw)
-            dw = torch.empty_like(top.weight)
-            db = torch.empty(Co, dtype=torch.float32, device=g.device) if top.bias is not None else None
-            ws = _ws(_lib.lib.dram_conv3d_k1_bwd_ws_bytes(N, C, Co, S), g.device)
-            call("dram_conv3d_k1_bwd_lazy", _p(g), _p(lz.raw), _p(lz.coef), int(lz.relu), _p(top.weight), _p(dxa), _p(dw),
-                 _p(db), _p(ws), ws.numel(), N, C, Co, S, st)
-            grads[top.weight] = dw
-            if db is not None:
-                grads[top.bias] = db
-            if from_source:
-                pending[id(lz)] = ("head", g, top.weight)
-            else:
-                gact[id(lz)] = dxa
-            g = None
-        elif tag == "conv":
-            s = item[1]
-            src = pending.pop(id(s.out), None)
-            if src is not None and s.sync is not None:      # "sbn" runs its two-call backward on a gradient that is there
-                _write_pending(gact, s.out, src, st)
-                src = None
-            head = src is not None and src[0] == "head"
-            if head and id(s.out) in gact:
-                raise RuntimeError("fused backward: the head's input has a second consumer")
-            # head: dx is the first tensor of this size in backward -- it takes the place of the head's dx
-            g = torch.empty_like(s.y) if head else gact.pop(id(s.out))
-            N, Co, D, H, W = s.y.shape
-            S = D * H * W
-            w = s.conv.weight
-            C2 = 0 if s.skip is None else s.skip.raw.shape[1]
-            C1 = w.shape[1] - C2
-            # norm (+ReLU) backward, in place: g <- d(raw conv output)
-            gamma = s.norm.weight
-            dgamma = torch.empty(Co, dtype=torch.float32, device=g.device) if gamma is not None else None
-            dbeta = torch.empty(Co, dtype=torch.float32, device=g.device) if s.norm.bias is not None else None
-            ws = _ws(_lib.lib.dram_norm_ws_bytes(N, Co, S), g.device)
-            if s.sync is not None:      # "sbn": the two backward sums span the ranks; the parameter gradients stay local sums
-                import torch.distributed as dist
-                group, total = s.sync
-                sums = torch.empty(2 * Co, dtype=torch.float64, device=g.device)
-                call("dram_bn_bwd_sums", _p(g), _p(s.y), _p(s.mean), _p(s.rstd), _p(s.coef), _p(sums), 1, N, Co, S,
-                     _p(ws), ws.numel(), st)
-                if dbeta is not None:
-                    dbeta.copy_(sums[0::2])
-                if dgamma is not None:
-                    dgamma.copy_(sums[1::2])
-                dist.all_reduce(sums, op=dist.ReduceOp.SUM, group=group)
-                call("dram_bn_bwd_apply_sums", _p(g), _p(s.y), _p(gamma), _p(s.mean), _p(s.rstd), _p(s.coef), _p(sums),
-                     float(total), _p(g), 1, N, Co, S, _p(ws), ws.numel(), st)
-            elif src is None:
-                call("dram_norm_bwd", _p(g), _p(s.y), _p(gamma), _p(s.mean), _p(s.rstd), _p(s.coef), _p(g), _p(dgamma), _p(dbeta),
-                     s.kind, s.groups, 1, int(s.batch_stats), N, Co, S, _p(ws), ws.numel(), st)
-            elif head:
-                _, gh, wh = src
-                call("dram_norm_bwd_head", _p(gh), _p(wh), wh.shape[0], _p(s.y), _p(gamma), _p(s.mean), _p(s.rstd), _p(s.coef),
-                     _p(g), _p(dgamma), _p(dbeta), s.kind, s.groups, 1, int(s.batch_stats), N, Co, S, _p(ws), ws.numel(), st)
-            else:
-                _, gp, idx = src
-                call("dram_norm_bwd_pool_add", _p(g), _p(gp), _p(idx), D, H, W, _p(s.y), _p(gamma), _p(s.mean), _p(s.rstd),
-                     _p(s.coef), _p(g), _p(dgamma), _p(dbeta), s.kind, s.groups, 1, int(s.batch_stats), N, Co, _p(ws), ws.numel(),
-                     st)
-            src = None
-            if dgamma is not None:
-                grads[gamma] = dgamma
-            if dbeta is not None:
-                grads[s.norm.bias] = dbeta
-            inp, skip = s.inp, s.skip
-            up = isinstance(inp, Upsampled)
-            is_root = (not up) and inp is root
-            need_dgrad = skip is not None or not is_root or need_dx
-            ranges = s.ranges                  # as forward ran the stage (decided once, kept on the tape)
-            whole = len(ranges) == 1
-            lazy_ok = bool(_lib.lib.dram_conv3d_k3_wgrad_lazy_ok(N, C1, C2, Co, D, H, W))
-            dw = None
-            wt = HF._pack(w, 1) if need_dgrad else None
-            dx2 = None
-            if need_dgrad and skip is not None:
-                if id(skip) in gact:
-                    raise RuntimeError("fused backward: a skip tensor received a gradient before its up-path consumer")
-                dx2 = HF.conv3d_k3_dx2(skip.raw, (D, H, W))
-            g_low = None        # gradient w.r.t. the low-resolution source of an upsampled input, filled slice by slice
-            if up and need_dgrad and not whole:
-                g_low = torch.empty_like(inp.src.raw)
-            for lo, hi in ranges:
-                n = hi - lo
-                gs = g if whole else g[lo:hi]
-                # backward-weights: the x operand is the stage's lazy input(s); an upsampled input is produced again
-                if up:
-                    x1 = Lazy(inp.produce(lo, hi))
-                else:
-                    x1 = inp
-                sk = None if skip is None else (skip if whole else _lazy_slice(skip, lo, hi))
-                if not lazy_ok:     # kernels without the on-load path (odd widths, first layer): plain operands
-                    x1 = Lazy(x1.materialise())
-                    sk = Lazy(sk.materialise()) if sk is not None else None
-                src = HF.CatView(x1.raw, None if sk is None else sk.raw, (D, H, W))
-                dws = HF.conv3d_k3_launch_wgrad(src, gs, w, _lazy_args(x1, sk))
-                dw = dws if dw is None else dw.add_(dws)
-                del x1, sk, src, dws
-                # backward-data: gradient w.r.t. the activated input(s)
-                if need_dgrad:
-                    dx1 = torch.empty((n, C1, D, H, W), dtype=torch.float32, device=g.device)
-                    HF.conv3d_k3_launch_bwd_data(gs, wt, dx1, None if dx2 is None else dx2[lo:hi])
-                    if up and not whole:       # straight on to the low-resolution gradient: d(upsampled) is never whole
-                        g_low[lo:hi] = HF.trilinear_ac_backward(dx1, (n,) + tuple(inp.src.raw.shape[1:]))
-                    elif up:
-                        gact[("up", id(inp.src))] = dx1
-                    else:
-                        _accumulate(gact, id(inp), dx1)
-                    del dx1
-            if up:
-                inp.kept = None                  # last use of a kept upsampled tensor
-            if g_low is not None:
-                gact[("low", id(inp.src))] = g_low
-            if dx2 is not None:
-                gact[id(skip)] = dx2
-            grads[w] = dw
-            # this stage's tensors are dead from here on (its consumers ran their backward before it did)
-            s.y = s.coef = s.mean = s.rstd = None
-            s.out.raw = s.out.coef = None
-            g = None
-        elif tag == "up":
-            lz, size = item[1], item[2]
-            if ("low", id(lz)) in gact:      # the consumer stage ran in slices and already went through the resize
-                _accumulate(gact, id(lz), gact.pop(("low", id(lz))))
-            else:
-                gup = gact.pop(("up", id(lz)))
-                _accumulate(gact, id(lz), HF.trilinear_ac_backward(gup, tuple(lz.raw.shape)))
-        elif tag == "pool":
-            lz, idx, res = item[1], item[2], item[3]
-            gp = gact.pop(id(res), None)
-            if gp is None:
-                continue
-            N, C, D, H, W = lz.raw.shape
-            if id(lz) in gact:      # the skip branch's gradient is already there: the stage's norm backward adds this one to it
-                pending[id(lz)] = ("pool", gp, idx)
-            else:
-                dxp = torch.empty_like(lz.raw)
-                call("dram_maxpool3d_2_bwd", _p(gp), _p(idx), _p(dxp), N, C, D, H, W, st)
-                gact[id(lz)] = dxp
-        else:   # pragma: no cover
-            raise RuntimeError(f"fused backward: unknown tape entry {tag!r}")
-    if pending:     # pragma: no cover
+    bw = _Backward(model, record[0].lazy, gout, need_dx, sink)
+    for entry in reversed(record[1:]):      # (record[0] is the _Input entry)
+        _BACKWARD[type(entry)](bw, entry)
+    if bw.pending:     # pragma: no cover
         raise RuntimeError("fused backward: a gradient source was left without the stage that consumes it")
-    return grads, gact.pop(id(root), None)
+    return bw.grads, bw.gact.pop(id(bw.root), None)
+
+
+def _resize_backward(bw, e):
+    bw.g = HF.trilinear_ac_backward(bw.g, e.shape)
+
+
+def _head_backward(bw, e):
+    lz, top, g = e.inp, bw.model.top_layer, bw.g
+    N, C, D, H, W = lz.raw.shape
+    Co, S = top.weight.shape[0], D * H * W
+    from_source = bool(_lib.lib.dram_norm_bwd_head_ok(Co))      # (more output channels: written out, as before)
+    dxa = None if from_source else torch.empty_like(lz.raw)
+    dw = torch.empty_like(top.weight)
+    db = torch.empty(Co, dtype=torch.float32, device=g.device) if top.bias is not None else None
+    ws = _ws(_lib.lib.dram_conv3d_k1_bwd_ws_bytes(N, C, Co, S), g.device)
+    call("dram_conv3d_k1_bwd_lazy", _p(g), _p(lz.raw), _p(lz.coef), int(lz.relu), _p(top.weight), _p(dxa), _p(dw),
+         _p(db), _p(ws), ws.numel(), N, C, Co, S, bw.st)
+    bw.deliver(top.weight, dw)
+    if db is not None:
+        bw.deliver(top.bias, db)
+    if from_source:
+        bw.pending[id(lz)] = ("head", g, top.weight)
+    else:
+        bw.gact[id(lz)] = dxa
+    bw.g = None
+
+
+def _stage_backward(bw, s):
+    src = bw.pending.pop(id(s.out), None)
+    if src is not None and s.sync is not None:      # "sbn" runs its two-call backward on a gradient that is there
+        _write_pending(bw.gact, s.out, src, bw.st)
+        src = None
+    head = src is not None and src[0] == "head"
+    if head and id(s.out) in bw.gact:
+        raise RuntimeError("fused backward: the head's input has a second consumer")
+    # head: dx is the first tensor of this size in backward -- it takes the place of the head's dx
+    g = torch.empty_like(s.y) if head else bw.gact.pop(id(s.out))
+    dgamma, dbeta = _norm_backward(bw, s, g, src)
+    del src
+    if dgamma is not None:
+        bw.deliver(s.norm.weight, dgamma)
+    if dbeta is not None:
+        bw.deliver(s.norm.bias, dbeta)
+    bw.deliver(s.conv.weight, _conv_backward(bw, s, g))
+    # this stage's tensors are dead from here on (its consumers ran their backward before it did); g dies with this frame
+    s.y = s.coef = s.mean = s.rstd = None
+    s.out.raw = s.out.coef = None
+
+
+def _norm_backward(bw, s, g, src):
+    """Norm (+ReLU) backward of stage `s`, in place: g <- d(raw conv output).  `src`: the pending source that g's content
+    comes from (see _Backward.pending), or None when g holds it.  Returns (dgamma, dbeta), None where there is no parameter."""
+    N, Co, D, H, W = s.y.shape
+    gamma = s.norm.weight
+    if s.sync is not None:      # "sbn": the two backward sums span the ranks; the parameter gradients stay local sums
+        group, total = s.sync
+        return HF.sync_bn_backward(g, s.y, gamma, s.mean, s.rstd, s.coef, total, group, True, g, s.norm.bias is not None)
+    dgamma = torch.empty(Co, dtype=torch.float32, device=g.device) if gamma is not None else None
+    dbeta = torch.empty(Co, dtype=torch.float32, device=g.device) if s.norm.bias is not None else None
+    ws = _ws(_lib.lib.dram_norm_ws_bytes(N, Co, D * H * W), g.device)
+    stage = (_p(s.y), _p(gamma), _p(s.mean), _p(s.rstd), _p(s.coef), _p(g), _p(dgamma), _p(dbeta), s.kind, s.groups, 1,
+             int(s.batch_stats), N, Co)
+    work = (_p(ws), ws.numel(), bw.st)
+    if src is None:
+        call("dram_norm_bwd", _p(g), *stage, D * H * W, *work)
+    elif src[0] == "head":
+        _, gh, wh = src
+        call("dram_norm_bwd_head", _p(gh), _p(wh), wh.shape[0], *stage, D * H * W, *work)
+    else:
+        _, gp, idx = src
+        call("dram_norm_bwd_pool_add", _p(g), _p(gp), _p(idx), D, H, W, *stage, *work)
+    return dgamma, dbeta
+
+
+def _conv_backward(bw, s, g):
+    """Backward-weights and backward-data of stage `s` over the sample ranges forward ran it in.  `g`: gradient w.r.t. the
+    raw conv output.  Returns dw; the gradients w.r.t. the stage's inputs go into bw.gact."""
+    gact = bw.gact
+    N, Co, D, H, W = s.y.shape
+    w = s.conv.weight
+    inp, skip = s.inp, s.skip
+    C2 = 0 if skip is None else skip.raw.shape[1]
+    C1 = w.shape[1] - C2
+    up = isinstance(inp, Upsampled)
+    is_root = (not up) and inp is bw.root
+    need_dgrad = skip is not None or not is_root or bw.need_dx
+    ranges = s.ranges                  # as forward ran the stage (decided once, kept on the tape)
+    whole = len(ranges) == 1
+    lazy_ok = bool(_lib.lib.dram_conv3d_k3_wgrad_lazy_ok(N, C1, C2, Co, D, H, W))
+    dw = None
+    wt = HF._pack(w, 1) if need_dgrad else None
+    dx2 = None
+    if need_dgrad and skip is not None:
+        if id(skip) in gact:
+            raise RuntimeError("fused backward: a skip tensor received a gradient before its up-path consumer")
+        dx2 = HF.conv3d_k3_dx2(skip.raw, (D, H, W))
+    g_low = None        # gradient w.r.t. the low-resolution source of an upsampled input, filled slice by slice
+    if up and need_dgrad and not whole:
+        g_low = torch.empty_like(inp.src.raw)
+    for lo, hi in ranges:
+        n = hi - lo
+        gs = g if whole else g[lo:hi]
+        # backward-weights: the x operand is the stage's lazy input(s); an upsampled input is produced again
+        if up:
+            x1 = Lazy(inp.produce(lo, hi))
+        else:
+            x1 = inp
+        sk = None if skip is None else (skip if whole else _lazy_slice(skip, lo, hi))
+        if not lazy_ok:     # kernels without the on-load path (odd widths, first layer): plain operands
+            x1 = Lazy(x1.materialise())
+            sk = Lazy(sk.materialise()) if sk is not None else None
+        src = HF.CatView(x1.raw, None if sk is None else sk.raw, (D, H, W))
+        dws = HF.conv3d_k3_launch_wgrad(src, gs, w, _lazy_args(x1, sk))
+        dw = dws if dw is None else dw.add_(dws)
+        del x1, sk, src, dws
+        # backward-data: gradient w.r.t. the activated input(s)
+        if need_dgrad:
+            dx1 = torch.empty((n, C1, D, H, W), dtype=torch.float32, device=g.device)
+            HF.conv3d_k3_launch_bwd_data(gs, wt, dx1, None if dx2 is None else dx2[lo:hi])
+            if up and not whole:       # straight on to the low-resolution gradient: d(upsampled) is never whole
+                g_low[lo:hi] = HF.trilinear_ac_backward(dx1, (n,) + tuple(inp.src.raw.shape[1:]))
+            elif up:
+                gact[("up", id(inp.src))] = dx1
+            else:
+                _accumulate(gact, id(inp), dx1)
+            del dx1
+    if up:
+        inp.kept = None                  # last use of a kept upsampled tensor
+    if g_low is not None:
+        gact[("low", id(inp.src))] = g_low
+    if dx2 is not None:
+        gact[id(skip)] = dx2
+    return dw
+
+
+def _up_backward(bw, e):
+    gact, lz = bw.gact, e.src
+    if ("low", id(lz)) in gact:      # the consumer stage ran in slices and already went through the resize
+        _accumulate(gact, id(lz), gact.pop(("low", id(lz))))
+    else:
+        gup = gact.pop(("up", id(lz)))
+        _accumulate(gact, id(lz), HF.trilinear_ac_backward(gup, tuple(lz.raw.shape)))
+
+
+def _pool_backward(bw, e):
+    gact, lz = bw.gact, e.inp
+    gp = gact.pop(id(e.out), None)
+    if gp is None:
+        return
+    N, C, D, H, W = lz.raw.shape
+    if id(lz) in gact:      # the skip branch's gradient is already there: the stage's norm backward adds this one to it
+        bw.pending[id(lz)] = ("pool", gp, e.idx)
+    else:
+        dxp = torch.empty_like(lz.raw)
+        call("dram_maxpool3d_2_bwd", _p(gp), _p(e.idx), _p(dxp), N, C, D, H, W, bw.st)
+        gact[id(lz)] = dxp
+
+
+_BACKWARD = {_Stage: _stage_backward, _Pool: _pool_backward, _Up: _up_backward, _Head: _head_backward,
+             _Resize: _resize_backward}
 
 
 def _write_pending(gact, lz, src, st):

@@ -541,6 +541,27 @@ def sync_bn_combine(local, group, running_mean, running_var, momentum):
     return mean_f, var_f, float(total)
 
 
+def sync_bn_backward(dy, x, gamma, save_mean, save_rstd, rowcoef, total, group, relu, dx, has_beta):
+    """Backward of a BatchNorm (+ReLU if `relu`) whose statistics span the `total` elements per channel of all ranks of
+    `group`: this rank's {sum dy', sum dy'*xhat} in fp64, all-reduced, applied into `dx` (which may be `dy` itself).
+    Returns (dgamma, dbeta) -- taken from the LOCAL sums, before the exchange (see SyncBatchNormFn) -- or None where the
+    norm has no such parameter."""
+    import torch.distributed as dist
+    N, C = x.shape[0], x.shape[1]
+    S = x.numel() // (N * C)
+    st = _stream()
+    ws = _ws(_lib.lib.dram_norm_ws_bytes(N, C, S), x.device)
+    sums = torch.empty(2 * C, dtype=torch.float64, device=x.device)
+    call("dram_bn_bwd_sums", _p(dy), _p(x), _p(save_mean), _p(save_rstd), _p(rowcoef), _p(sums), int(relu), N, C, S,
+         _p(ws), ws.numel(), st)
+    dbeta = sums[0::2].float() if has_beta else None
+    dgamma = sums[1::2].float() if gamma is not None else None
+    dist.all_reduce(sums, op=dist.ReduceOp.SUM, group=group)
+    call("dram_bn_bwd_apply_sums", _p(dy), _p(x), _p(gamma), _p(save_mean), _p(save_rstd), _p(rowcoef), _p(sums),
+         float(total), _p(dx), int(relu), N, C, S, _p(ws), ws.numel(), st)
+    return dgamma, dbeta
+
+
 class SyncBatchNormFn(Function):
     """Training-mode BatchNorm whose statistics span all ranks of a process group (nn.SyncBatchNorm, the
     reference's normal_wrapper "sbn", parts.py:32-33, under data parallelism).  Two exchanges per layer and
@@ -577,25 +598,11 @@ class SyncBatchNormFn(Function):
     @staticmethod
     @once_differentiable
     def backward(ctx, dy):
-        import torch.distributed as dist
         x, gamma, save_mean, save_rstd, rowcoef = ctx.saved_tensors
         relu, has_beta, total, group = ctx.cfg
         dy = _chk(dy, "sync-bn grad_output")
-        N, C = x.shape[0], x.shape[1]
-        S = x.numel() // (N * C)
-        dev = x.device
-        st = _stream()
-        ws = _ws(_lib.lib.dram_norm_ws_bytes(N, C, S), dev)
-        sums = torch.empty(2 * C, dtype=torch.float64, device=dev)
-        call("dram_bn_bwd_sums", _p(dy), _p(x), _p(save_mean), _p(save_rstd), _p(rowcoef), _p(sums), int(relu), N, C, S,
-             _p(ws), ws.numel(), st)
-        dbeta = sums[0::2].float() if has_beta else None
-        dgamma = sums[1::2].float() if gamma is not None else None
-        gsums = sums.clone()
-        dist.all_reduce(gsums, op=dist.ReduceOp.SUM, group=group)
         dx = torch.empty_like(x)
-        call("dram_bn_bwd_apply_sums", _p(dy), _p(x), _p(gamma), _p(save_mean), _p(save_rstd), _p(rowcoef), _p(gsums),
-             float(total), _p(dx), int(relu), N, C, S, _p(ws), ws.numel(), st)
+        dgamma, dbeta = sync_bn_backward(dy, x, gamma, save_mean, save_rstd, rowcoef, total, group, relu, dx, has_beta)
         return dx, dgamma, dbeta, None, None, None, None, None, None
 
 
