@@ -1,4 +1,4 @@
-// 2x2x2 max-pool, trilinear (align_corners=True) resize and crop-concat for fp32 NCDHW, gfx950.
+// Max-pool (2x2x2 and any window), trilinear (align_corners=True) resize and crop-concat for fp32 NCDHW, gfx950.
 //
 // Replaces the ATen max_pool3d / upsample_trilinear3d / cat dispatches (+ backward) of
 // reference dram/parts.py:191 (MaxPool3d(2,2,0)), parts.py:149 and models.py:146
@@ -93,6 +93,76 @@ __global__ __launch_bounds__(256) void maxpool2_bwd_vec_kernel(const float* __re
         g.x += old.x; g.y += old.y; g.z += old.z; g.w += old.w;
     }
     *q = g;
+}
+
+// ---------------------------------------------------------------- max pool, any window
+// nn.MaxPool3d(kernel, stride, padding) with dilation 1 and floor mode; the geometry is a kernel argument (one kernel for
+// every window).  Host-checked: kernel 1..5, stride 1..5, padding 0..k/2 per axis, every output extent >= 1.
+struct PoolGeom {
+    int D, H, W, Do, Ho, Wo;
+    int kd, kh, kw, sd, sh, sw, pd, ph, pw;
+};
+
+// thread per pooled output, x fastest.  The window is scanned in (z,y,x) order, positions in the padding are skipped (with
+// p <= k/2 at least one position is real); same update as maxpool2_fwd_kernel (ATen: `val > maxval || isnan(val)`, from
+// maxval = -inf at the first real position): the first maximum wins ties, a NaN propagates and the last NaN of the scan keeps
+// the index.  idx = (dz*kh + dy)*kw + dx inside the unclipped window (<= 124).
+__global__ __launch_bounds__(256) void maxpool_fwd_kernel(const float* __restrict__ x, float* __restrict__ out,
+                                                          uint8_t* __restrict__ idx, const PoolGeom g) {
+    const int64_t plane = blockIdx.y;  // n*C + c
+    const int64_t So = (int64_t)g.Do * g.Ho * g.Wo;
+    const int64_t e64 = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (e64 >= So) return;
+    const int e = (int)e64;
+    const int xo = e % g.Wo, yo = (e / g.Wo) % g.Ho, zo = e / (g.Wo * g.Ho);
+    const int z0 = zo * g.sd - g.pd, y0 = yo * g.sh - g.ph, x0 = xo * g.sw - g.pw;      // window origin (may lie in the padding)
+    const int dz0 = max(0, -z0), dy0 = max(0, -y0), dx0 = max(0, -x0);                  // first / one past the last real offset
+    const int dz1 = min(g.kd, g.D - z0), dy1 = min(g.kh, g.H - y0), dx1 = min(g.kw, g.W - x0);
+    const float* p = x + plane * ((int64_t)g.D * g.H * g.W) + ((int64_t)z0 * g.H + y0) * g.W + x0;
+    float best = -INFINITY;
+    int bi = (dz0 * g.kh + dy0) * g.kw + dx0;
+    for (int dz = dz0; dz < dz1; ++dz) {
+        for (int dy = dy0; dy < dy1; ++dy) {
+            const float* row = p + ((int64_t)dz * g.H + dy) * g.W;
+            const int k0 = (dz * g.kh + dy) * g.kw;
+            for (int dx = dx0; dx < dx1; ++dx) {
+                const float v = row[dx];
+                if (v > best || v != v) { best = v; bi = k0 + dx; }
+            }
+        }
+    }
+    out[plane * So + e] = best;
+    idx[plane * So + e] = (uint8_t)bi;
+}
+
+// Gather form, thread per INPUT element (coalesced dx stores, no atomics): the windows that contain the element -- at most
+// ceil(k/s) per axis -- are visited in ascending (zo, yo, xo) order and dout is added where idx names the element.  Elements
+// that no window covers (stride > kernel, the floor remainder) get +0: dx is fully written.
+__global__ __launch_bounds__(256) void maxpool_bwd_kernel(const float* __restrict__ dout, const uint8_t* __restrict__ idx,
+                                                          float* __restrict__ dx, const PoolGeom g) {
+    const int64_t plane = blockIdx.y;
+    const int64_t S = (int64_t)g.D * g.H * g.W;
+    const int64_t e64 = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (e64 >= S) return;
+    const int e = (int)e64;
+    const int xi = e % g.W, yi = (e / g.W) % g.H, zi = e / (g.W * g.H);
+    const int zp = zi + g.pd, yp = yi + g.ph, xp = xi + g.pw;                           // position in the padded volume
+    // window o holds position q iff o*s <= q < o*s + k:  ceil((q - k + 1) / s) <= o <= floor(q / s), inside the output
+    const int zo0 = zp >= g.kd ? (zp - g.kd + g.sd) / g.sd : 0, zo1 = min(zp / g.sd, g.Do - 1);
+    const int yo0 = yp >= g.kh ? (yp - g.kh + g.sh) / g.sh : 0, yo1 = min(yp / g.sh, g.Ho - 1);
+    const int xo0 = xp >= g.kw ? (xp - g.kw + g.sw) / g.sw : 0, xo1 = min(xp / g.sw, g.Wo - 1);
+    const int64_t obase = plane * ((int64_t)g.Do * g.Ho * g.Wo);
+    float acc = 0.f;
+    for (int zo = zo0; zo <= zo1; ++zo) {
+        const int kz = (zp - zo * g.sd) * g.kh;
+        for (int yo = yo0; yo <= yo1; ++yo) {
+            const int kzy = (kz + yp - yo * g.sh) * g.kw + xp;
+            const int64_t orow = obase + ((int64_t)zo * g.Ho + yo) * g.Wo;
+            for (int xo = xo0; xo <= xo1; ++xo)
+                if (idx[orow + xo] == kzy - xo * g.sw) acc += dout[orow + xo];
+        }
+    }
+    dx[plane * S + e] = acc;
 }
 
 // ---------------------------------------------------------------- trilinear, align_corners=True
@@ -738,6 +808,50 @@ extern "C" int dram_maxpool3d_2_bwd(const float* dout, const uint8_t* idx, float
 extern "C" int dram_maxpool3d_2_bwd_acc(const float* dout, const uint8_t* idx, float* dx, int N, int C, int D, int H,
                                         int W, void* stream) {
     return maxpool_bwd_run("maxpool3d_2_bwd_acc", dout, idx, dx, N, C, D, H, W, 1, stream);
+}
+
+// Checks an nn.MaxPool3d geometry (dilation 1, floor mode) and fills `g`; nothing is launched on a refusal.
+static int pool_geometry(const char* who, int N, int C, int D, int H, int W, int kd, int kh, int kw, int sd, int sh, int sw,
+                         int pd, int ph, int pw, PoolGeom& g) {
+    DRAM_REQUIRE(N > 0 && C > 0 && D > 0 && H > 0 && W > 0, "%s: empty tensor [%d, %d, %d, %d, %d]", who, N, C, D, H, W);
+    const int n[3] = {D, H, W}, k[3] = {kd, kh, kw}, s[3] = {sd, sh, sw}, p[3] = {pd, ph, pw};
+    int o[3];
+    for (int a = 0; a < 3; ++a) {
+        DRAM_REQUIRE(k[a] >= 1 && k[a] <= 5 && s[a] >= 1 && s[a] <= 5,
+                     "%s: kernel %d / stride %d on axis %d; supported: kernel 1..5, stride 1..5", who, k[a], s[a], a);
+        DRAM_REQUIRE(p[a] >= 0 && p[a] <= k[a] / 2, "%s: padding %d on axis %d must be 0..kernel/2 = %d", who, p[a], a, k[a] / 2);
+        DRAM_REQUIRE(n[a] + 2 * p[a] >= k[a], "%s: axis %d: extent %d with padding %d is below the kernel %d (output extent 0)",
+                     who, a, n[a], p[a], k[a]);
+        o[a] = (n[a] + 2 * p[a] - k[a]) / s[a] + 1;
+    }
+    int rc = check_planes(who, (int64_t)N * C, (int64_t)D * H * W);
+    if (rc) return rc;
+    rc = check_planes(who, (int64_t)N * C, (int64_t)o[0] * o[1] * o[2]);     // (stride 1 with padding: up to one more per axis)
+    if (rc) return rc;
+    g = PoolGeom{D, H, W, o[0], o[1], o[2], kd, kh, kw, sd, sh, sw, pd, ph, pw};
+    return DRAM_OK;
+}
+
+extern "C" int dram_maxpool3d_fwd(const float* x, float* out, uint8_t* idx, int N, int C, int D, int H, int W, int kd, int kh,
+                                  int kw, int sd, int sh, int sw, int pd, int ph, int pw, void* stream) {
+    PoolGeom g;
+    int rc = pool_geometry("maxpool3d_fwd", N, C, D, H, W, kd, kh, kw, sd, sh, sw, pd, ph, pw, g);
+    if (rc) return rc;
+    DRAM_REQUIRE(x && out && idx, "maxpool3d_fwd: null pointer");
+    dim3 grid((unsigned)cdiv64((int64_t)g.Do * g.Ho * g.Wo, 256), N * C);
+    hipLaunchKernelGGL(maxpool_fwd_kernel, grid, dim3(256), 0, (hipStream_t)stream, x, out, idx, g);
+    return check_launch("maxpool3d_fwd");
+}
+
+extern "C" int dram_maxpool3d_bwd(const float* dout, const uint8_t* idx, float* dx, int N, int C, int D, int H, int W, int kd,
+                                  int kh, int kw, int sd, int sh, int sw, int pd, int ph, int pw, void* stream) {
+    PoolGeom g;
+    int rc = pool_geometry("maxpool3d_bwd", N, C, D, H, W, kd, kh, kw, sd, sh, sw, pd, ph, pw, g);
+    if (rc) return rc;
+    DRAM_REQUIRE(dout && idx && dx, "maxpool3d_bwd: null pointer");
+    dim3 grid((unsigned)cdiv64((int64_t)D * H * W, 256), N * C);
+    hipLaunchKernelGGL(maxpool_bwd_kernel, grid, dim3(256), 0, (hipStream_t)stream, dout, idx, dx, g);
+    return check_launch("maxpool3d_bwd");
 }
 
 // 16-byte path of the forward resize: x magnification >= 1.67, rows of >= 4 source columns, 16-byte aligned output rows

@@ -48,6 +48,8 @@ SIGNATURES = {
     "dram_relu_bwd": (I, [P, P, P, L, P]),
     "dram_maxpool3d_2_fwd": (I, [P, P, P, I, I, I, I, I, P]),
     "dram_maxpool3d_2_bwd": (I, [P, P, P, I, I, I, I, I, P]),
+    "dram_maxpool3d_fwd": (I, [P, P, P] + [I] * 14 + [P]),
+    "dram_maxpool3d_bwd": (I, [P, P, P] + [I] * 14 + [P]),
     "dram_upsample_trilinear_ac_fwd": (I, [P, P, I, I, I, I, I, I, I, I, P]),
     "dram_upsample_trilinear_ac_bwd": (I, [P, P, I, I, I, I, I, I, I, I, P]),
     "dram_upsample_trilinear_ac_bwd_ws_bytes": (Z, [I, I, I, I, I, I, I, I]),

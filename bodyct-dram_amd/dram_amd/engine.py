@@ -18,7 +18,8 @@ Saved for backward per stage: the raw output and {a, b, mean, rstd} -- about 0.4
 (DESIGN.md section 5), with values bit-identical to that path's (same fmaf / fmaxf on the same inputs).
 
 Not an oracle and not a fallback: every step is a kernel of libdram_hip.so.  Networks the engine does not cover
-(PReLU, dropout, `lite` blocks, conv kernels other than 3x3x3, checkpoint_mode="recompute") run the per-op path.
+(PReLU, dropout, `lite` blocks, conv kernels other than 3x3x3, max-pools other than kernel 2 / stride 2 / padding 0,
+checkpoint_mode="recompute") run the per-op path.
 "sbn" (cross-rank BatchNorm, parts.py:32-33) is covered: the per-rank statistics of the conv epilogue are combined over the
 process group (_sync_forward_stats), and so are the two sums of the norm's backward.
 
@@ -127,7 +128,7 @@ def supports(model):
             if any(_stage_modules(seq) is None for seq in blk.conv_blocks):
                 return False
         for ds in model.ds_modules:
-            if not isinstance(ds.maxpool, HipMaxPool3d):
+            if not isinstance(ds.maxpool, HipMaxPool3d) or not ds.maxpool.is_2x2x2():    # (_pool launches the 2x2x2 kernel)
                 return False
         for us in (model.us_modules or []):
             if not isinstance(us.upsample, HipUpsample) or us.upsample.mode != "trilinear" or not us.upsample.align_corners:

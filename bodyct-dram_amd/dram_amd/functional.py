@@ -770,6 +770,65 @@ def max_pool3d_2(x):
     return MaxPool2Fn.apply(x)
 
 
+POOL_LIMITS = "kernel 1..5, stride 1..5 and padding 0..kernel/2 per axis, dilation 1, ceil_mode=False"
+
+
+def max_pool3d_geometry(shape, kernel_size, stride=None, padding=0):
+    """(kernel, stride, padding, output size), each a 3-tuple, of nn.MaxPool3d(kernel_size, stride, padding) with dilation 1
+    and floor mode on an input whose last three dimensions are shape[-3:].  Ints mean all three axes and stride=None the
+    kernel size, as in torch.  ValueError where torch refuses too (padding above kernel/2, an output extent below 1);
+    NotImplementedError for sizes the kernel does not take."""
+    def triple(v, name):
+        t = tuple(int(e) for e in v) if isinstance(v, (tuple, list)) else (int(v),) * 3
+        if len(t) != 3:
+            raise ValueError(f"max_pool3d: {name} needs 1 or 3 values, got {v}")
+        return t
+    k = triple(kernel_size, "kernel_size")
+    s = k if stride is None or (isinstance(stride, (tuple, list)) and len(stride) == 0) else triple(stride, "stride")
+    p = triple(padding, "padding")
+    if min(k) < 1 or min(s) < 1 or min(p) < 0:
+        raise ValueError(f"max_pool3d: kernel {k} and stride {s} must be positive and padding {p} non-negative")
+    if max(k) > 5 or max(s) > 5:
+        raise NotImplementedError(f"max_pool3d: kernel {k} / stride {s} is not implemented; supported: {POOL_LIMITS}")
+    if any(pp > kk // 2 for kk, pp in zip(k, p)):
+        raise ValueError(f"max_pool3d: padding {p} must be at most half of the kernel {k}")
+    size = tuple(int(n) for n in shape[-3:])
+    out = tuple((n + 2 * pp - kk) // ss + 1 if n + 2 * pp >= kk else 0 for n, kk, ss, pp in zip(size, k, s, p))
+    if len(size) != 3 or min(size) < 1 or min(out) < 1:
+        raise ValueError(f"max_pool3d: input {size} with kernel {k}, stride {s} and padding {p} gives output size {out}")
+    return k, s, p, out
+
+
+class MaxPoolFn(Function):
+    """nn.MaxPool3d(kernel_size, stride, padding) with dilation 1 and floor mode (pool_ksize / pool_strides / pool_pad of
+    reference parts.py:157-196).  Keeps the uint8 window offsets of the maxima and the geometry."""
+
+    @staticmethod
+    def forward(ctx, x, kernel_size, stride, padding):
+        x = _chk(x, "maxpool input", 5)
+        N, C, D, H, W = x.shape
+        k, s, p, osz = max_pool3d_geometry(x.shape, kernel_size, stride, padding)
+        out = torch.empty((N, C) + osz, dtype=torch.float32, device=x.device)
+        idx = torch.empty(out.shape, dtype=torch.uint8, device=x.device)
+        call("dram_maxpool3d_fwd", _p(x), _p(out), _p(idx), N, C, D, H, W, *k, *s, *p, _stream())
+        ctx.save_for_backward(idx)
+        ctx.geometry = (N, C, D, H, W, *k, *s, *p)
+        return out
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, dout):
+        (idx,) = ctx.saved_tensors
+        dout = _chk(dout, "maxpool grad_output", 5)
+        dx = torch.empty(ctx.geometry[:5], dtype=torch.float32, device=dout.device)
+        call("dram_maxpool3d_bwd", _p(dout), _p(idx), _p(dx), *ctx.geometry, _stream())
+        return dx, None, None, None
+
+
+def max_pool3d(x, kernel_size, stride=None, padding=0):
+    return MaxPoolFn.apply(x, kernel_size, stride, padding)
+
+
 # --------------------------------------------------------------------------- trilinear resize
 # workspace cap of the two-stage trilinear backward (the z-reduced intermediate of a group of planes)
 TRI_BWD_WS_CAP = 1 << 30

@@ -146,15 +146,37 @@ class HipDropout(nn.Dropout):
 
 
 class HipMaxPool3d(nn.MaxPool3d):
-    """nn.MaxPool3d(2, 2, 0) (parts.py:191)."""
+    """nn.MaxPool3d(kernel_size, stride, padding) (pool_ksize / pool_strides / pool_pad of ConvPoolBlock5d, parts.py:157-196;
+    DC3D builds 2 / 2 / 0, parts.py:191).  2 / 2 / 0 runs the dedicated 2x2x2 kernels, every other geometry within LIMITS the
+    general ones; anything else raises NotImplementedError at the first forward."""
 
-    def forward(self, x):
+    LIMITS = HF.POOL_LIMITS + ", return_indices=False"
+
+    def geometry(self):
+        """(kernel, stride, padding) as 3-tuples; NotImplementedError for what no kernel takes."""
         def _t(v):
             return tuple(v) if isinstance(v, (tuple, list)) else (v,) * 3
-        if _t(self.kernel_size) != (2, 2, 2) or _t(self.stride) != (2, 2, 2) or _t(self.padding) != (0, 0, 0) \
-                or _t(self.dilation) != (1, 1, 1) or self.ceil_mode or self.return_indices:
-            raise NotImplementedError("HipMaxPool3d: only kernel 2 / stride 2 / padding 0 is implemented")
-        return HF.max_pool3d_2(x)
+        if _t(self.dilation) != (1, 1, 1) or self.ceil_mode or self.return_indices:
+            raise NotImplementedError(f"HipMaxPool3d: dilation {self.dilation}, ceil_mode={self.ceil_mode}, return_indices="
+                                      f"{self.return_indices} is not implemented; supported: {self.LIMITS}")
+        k = _t(self.kernel_size)
+        s = k if self.stride is None else _t(self.stride)
+        if not all(1 <= a <= 5 for a in k + s):
+            raise NotImplementedError(f"HipMaxPool3d: kernel {k} / stride {s} is not implemented; supported: {self.LIMITS}")
+        return k, s, _t(self.padding)
+
+    def is_2x2x2(self):
+        """Kernel 2 / stride 2 / padding 0, dilation 1, floor mode: what the dedicated kernels (and the fused engine) run."""
+        try:
+            return self.geometry() == ((2, 2, 2), (2, 2, 2), (0, 0, 0))
+        except NotImplementedError:
+            return False
+
+    def forward(self, x):
+        k, s, p = self.geometry()
+        if (k, s, p) == ((2, 2, 2), (2, 2, 2), (0, 0, 0)):
+            return HF.max_pool3d_2(x)
+        return HF.max_pool3d(x, k, s, p)
 
 
 class HipUpsample(nn.Upsample):

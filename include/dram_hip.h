@@ -187,6 +187,20 @@ int dram_relu_bwd(const float* dy, const float* y, float* dx, int64_t n, void* s
 int dram_maxpool3d_2_fwd(const float* x, float* out, uint8_t* idx, int N, int C, int D, int H, int W, void* stream);
 int dram_maxpool3d_2_bwd(const float* dout, const uint8_t* idx, float* dx, int N, int C, int D, int H, int W, void* stream);
 
+/* ---- nn.MaxPool3d(kernel, stride, padding), dilation 1, floor mode (pool_ksize / pool_strides / pool_pad of
+ * ConvPoolBlock5d, parts.py:157-196) ----
+ * Per axis: kernel 1..5, stride 1..5, padding 0..kernel/2 (torch's rule), output extent (n + 2p - k) / s + 1 >= 1;
+ * anything else is DRAM_EINVAL and nothing is launched.  out, idx: [N,C,Do,Ho,Wo].  The window is scanned in (z,y,x) order
+ * and positions in the padding are skipped; idx (uint8) = (dz*kh + dy)*kw + dx inside the unclipped window (<= 124) of the
+ * first maximum -- a NaN propagates and the last NaN of the scan takes the index -- the element ATen routes the gradient to.
+ * _bwd is the gather form (one thread per input element, ascending (zo,yo,xo) over the windows that hold it, deterministic,
+ * no atomics) and writes all of dx: elements that no window covers (stride > kernel, floor remainder) get +0.
+ * A 2 / 2 / 0 pool runs dram_maxpool3d_2_* above. */
+int dram_maxpool3d_fwd(const float* x, float* out, uint8_t* idx, int N, int C, int D, int H, int W, int kd, int kh, int kw,
+                       int sd, int sh, int sw, int pd, int ph, int pw, void* stream);
+int dram_maxpool3d_bwd(const float* dout, const uint8_t* idx, float* dx, int N, int C, int D, int H, int W, int kd, int kh,
+                       int kw, int sd, int sh, int sw, int pd, int ph, int pw, void* stream);
+
 /* ---- nn.Upsample(mode='trilinear', align_corners=True) (parts.py:149 scale 2; models.py:146 to input size) ----
  * Arbitrary (D,H,W) -> (Do,Ho,Wo); source index = dst * (in-1)/(out-1) as ATen computes it.
  * The backward is the exact adjoint in gather form (deterministic, no atomics). */
