@@ -1,10 +1,11 @@
 """MI355X-native implementation of the DRAM DC3D forward/backward hot path.
 
 Host side of libdram_hip.so: ctypes binding (`_lib`), autograd Functions
-(`functional`) and nn.Module leaves (`modules`).  The drop-in modules that mirror
+(`functional`), nn.Module leaves (`modules`) and the device optimisers (`optim`).  The drop-in modules that mirror
 the reference's flat `parts.py` / `models.py` live one directory up.
 """
-from . import _lib, functional, modules  # noqa: F401
+from . import _lib, functional, modules, optim  # noqa: F401
+from .optim import SGD, Adam, AdamW  # noqa: F401
 
 # the augmentation transforms of `augment`, importable from here; the module is loaded on first use
 _AUGMENT = ("GaussianBlur", "RandomMaskOut", "RandomFlip", "RandomRotate90", "GaussianAddictive", "IntensityInverse",
@@ -13,7 +14,7 @@ _AUGMENT = ("GaussianBlur", "RandomMaskOut", "RandomFlip", "RandomRotate90", "Ga
             "RandomRotateInplane90", "RandomCrop", "StandarizeChannel", "RandomAffineTransform3D", "RandomRotate",
             "EnsembleScanAugmentation")
 
-__all__ = ["_lib", "functional", "modules", *_AUGMENT]
+__all__ = ["_lib", "functional", "modules", "optim", "Adam", "AdamW", "SGD", *_AUGMENT]
 
 
 def __getattr__(name):

@@ -148,6 +148,10 @@ SIGNATURES = {
     "dram_chunk_hist256": (I, [P, P, P, I, P, I, I, P]),
     "dram_otsu256": (I, [P, I, ctypes.c_double, P, P]),
     "dram_chunk_prepare": (I, [P, P, P, P, P, I, I, I, I, F, F, I, I, P, P, P, P, P]),
+    # optimiser update (table: host array of dram_optim_tensor)
+    "dram_optim_table_capacity": (I, []),
+    "dram_optim_adam": (I, [P, I] + [ctypes.c_double] * 5 + [I, I, I, P]),
+    "dram_optim_sgd": (I, [P, I] + [ctypes.c_double] * 4 + [I, I, P]),
 }
 
 

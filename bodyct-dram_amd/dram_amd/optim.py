@@ -1,0 +1,200 @@
+"""Device optimisers: `Adam`, `AdamW` and `SGD` whose update is one HIP launch per parameter group (csrc/optim.hip) in
+place of ATen's dozen foreach launches over every tensor of the group.
+
+The reference trains with `torch.optim.Adam(lr=1e-4)` under `ExponentialLR(gamma=0.9)` (st_dram_ref.py; an SGD-with-momentum
+block is commented out beside it) and `job_runner.py` saves and reloads `optimizer.state_dict()` with every checkpoint.  The
+classes here derive from torch's own and replace `step()` alone: constructor arguments, their validation, `param_groups`, the
+per-parameter state (keys, dtypes, devices; `step` stays torch's fp32 scalar on the host) and so `state_dict()` /
+`load_state_dict()` are torch's, and a checkpoint written by either loads into the other.  `lr` is read from `param_groups`
+at every step, so LR schedulers work unchanged.
+
+`step()` builds a host table of (p, grad, exp_avg, exp_avg_sq[, max_exp_avg_sq]) pointers and the per-parameter bias
+corrections -- the gradient pointers change every step under `zero_grad(set_to_none=True)` -- and hands it to
+`dram_optim_adam` / `dram_optim_sgd` in chunks of `TABLE_CAPACITY` tensors, on the current stream.  It never synchronises
+with the device and reads no device value; the table travels in the kernel arguments, so there is no buffer to copy or keep
+alive.  (A captured graph would replay one step's pointers and bias corrections: graph-captured steps are not supported.)
+Like every op of this package there is no fallback: parameters and gradients must be dense fp32 on a ROCm device.
+"""
+import math
+import struct
+
+import torch
+
+from ._lib import call, lib
+
+__all__ = ["Adam", "AdamW", "SGD", "TABLE_CAPACITY"]
+
+TABLE_CAPACITY = int(lib.dram_optim_table_capacity())   # tensors per launch (the table is a kernel argument)
+
+_ENTRY = struct.Struct("@5Pqff")                        # dram_optim_tensor of include/dram_hip.h
+assert _ENTRY.size == 56
+
+
+def _no_tensor_lr(lr):
+    if isinstance(lr, torch.Tensor):
+        raise TypeError("dram_amd.optim: lr must be a Python number, got a tensor (a tensor lr lives on the device and "
+                        "step() reads no device value)")
+
+
+def _chk_param(p, name):
+    """The parameter and its gradient as the kernel needs them (the style of functional._chk); returns the gradient,
+    made contiguous."""
+    g = p.grad
+    if not p.is_cuda:
+        raise RuntimeError(f"{name}: parameter is on {p.device}; the DRAM HIP path only runs on a ROCm device "
+                           f"(there is no CPU fallback)")
+    if g.is_sparse:
+        raise RuntimeError(f"{name}: sparse gradients are not supported")
+    if p.dtype != torch.float32 or g.dtype != torch.float32:
+        raise TypeError(f"{name}: expected float32 parameter and gradient, got {p.dtype} and {g.dtype}")
+    if g.device != p.device:
+        raise RuntimeError(f"{name}: gradient is on {g.device}, parameter on {p.device}")
+    if not p.is_contiguous():
+        raise ValueError(f"{name}: parameter of shape {tuple(p.shape)} is not contiguous (it is updated in place)")
+    return g.contiguous()
+
+
+def _with_grad(group, name):
+    """(parameter, contiguous gradient) of the group's parameters that have one, all checked before any state changes; a
+    parameter whose .grad is None is skipped as torch skips it (its step count does not advance)."""
+    return [(p, _chk_param(p, name)) for p in group["params"] if p.grad is not None]
+
+
+def _chk_state(t, p, name):
+    if t.dtype != torch.float32 or t.device != p.device or t.shape != p.shape or not t.is_contiguous():
+        raise RuntimeError(f"{name}: state tensor {tuple(t.shape)} {t.dtype} on {t.device} does not match its parameter "
+                           f"{tuple(p.shape)} {p.dtype} on {p.device}")
+    return t
+
+
+def _host_step(state, name):
+    s = state["step"]
+    if not torch.is_tensor(s):
+        s = state["step"] = torch.tensor(float(s), dtype=torch.float32)
+    if s.is_cuda:
+        raise RuntimeError(f"{name}: the step count is a device tensor (capturable or fused state); reload the state "
+                           f"through load_state_dict, which moves it to the host")
+    return s
+
+
+def _launch(entry, rows, *scalars):
+    """rows: (device, p, g, m, v, vmax, s0, s1) with tensors or None; one launch per device and TABLE_CAPACITY rows.
+    The rows' tensors stay referenced by the caller's lists until the launches are issued."""
+    by_dev = {}
+    for r in rows:
+        if r[1].numel() > 0:
+            by_dev.setdefault(r[0], []).append(r)
+    for dev, rs in by_dev.items():
+        with torch.cuda.device(dev):
+            stream = torch.cuda.current_stream().cuda_stream
+            for lo in range(0, len(rs), TABLE_CAPACITY):
+                part = rs[lo:lo + TABLE_CAPACITY]
+                buf = bytearray(_ENTRY.size * len(part))
+                for i, (_, p, g, m, v, vmax, s0, s1) in enumerate(part):
+                    _ENTRY.pack_into(buf, i * _ENTRY.size, p.data_ptr(), g.data_ptr(), 0 if m is None else m.data_ptr(),
+                                     0 if v is None else v.data_ptr(), 0 if vmax is None else vmax.data_ptr(), p.numel(),
+                                     s0, s1)
+                call(entry, bytes(buf), len(part), *scalars, stream)
+
+
+class _AdamStep:
+    """step() of Adam and AdamW (torch.optim.AdamW is torch.optim.Adam with decoupled_weight_decay=True)."""
+
+    def __setstate__(self, state):
+        super().__setstate__(state)
+        for group in self.param_groups:                # a checkpoint of a capturable / fused torch optimiser
+            group["foreach"], group["capturable"], group["fused"], group["differentiable"] = None, False, None, False
+            for p in group["params"]:
+                s = self.state.get(p, {}).get("step")
+                if torch.is_tensor(s) and s.is_cuda:
+                    self.state[p]["step"] = s.detach().to("cpu", torch.float32)
+
+    @torch.no_grad()
+    def step(self, closure=None):
+        loss = None
+        if closure is not None:
+            with torch.enable_grad():
+                loss = closure()
+        name = f"dram_amd.optim.{type(self).__name__}"
+        for group in self.param_groups:
+            lr = group["lr"]
+            _no_tensor_lr(lr)
+            beta1, beta2 = (float(b) for b in group["betas"])
+            amsgrad = bool(group["amsgrad"])
+            rows = []
+            for p, g in _with_grad(group, name):
+                state = self.state[p]
+                if len(state) == 0:
+                    state["step"] = torch.tensor(0.0, dtype=torch.float32)
+                    state["exp_avg"] = torch.zeros_like(p, memory_format=torch.preserve_format)
+                    state["exp_avg_sq"] = torch.zeros_like(p, memory_format=torch.preserve_format)
+                    if amsgrad:
+                        state["max_exp_avg_sq"] = torch.zeros_like(p, memory_format=torch.preserve_format)
+                step = _host_step(state, name)
+                step += 1
+                t = float(step)
+                rows.append((p.device, p, g, _chk_state(state["exp_avg"], p, name), _chk_state(state["exp_avg_sq"], p, name),
+                             _chk_state(state["max_exp_avg_sq"], p, name) if amsgrad else None,
+                             float(lr) / (1.0 - beta1 ** t), math.sqrt(1.0 - beta2 ** t)))
+            _launch("dram_optim_adam", rows, float(lr), beta1, beta2, float(group["eps"]), float(group["weight_decay"]),
+                    int(bool(group["decoupled_weight_decay"])), int(amsgrad), int(bool(group["maximize"])))
+        return loss
+
+
+class Adam(_AdamStep, torch.optim.Adam):
+    """torch.optim.Adam (arguments, validation, state and state dict) with the update on csrc/optim.hip."""
+
+    def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=0, amsgrad=False, *, maximize=False,
+                 decoupled_weight_decay=False):
+        _no_tensor_lr(lr)
+        super().__init__(params, lr, betas, eps, weight_decay, amsgrad, maximize=maximize,
+                         decoupled_weight_decay=decoupled_weight_decay)
+
+
+class AdamW(_AdamStep, torch.optim.AdamW):
+    """torch.optim.AdamW (arguments, validation, state and state dict) with the update on csrc/optim.hip."""
+
+    def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=1e-2, amsgrad=False, *, maximize=False):
+        _no_tensor_lr(lr)
+        super().__init__(params, lr, betas, eps, weight_decay, amsgrad, maximize=maximize)
+
+
+class SGD(torch.optim.SGD):
+    """torch.optim.SGD (arguments, validation, state and state dict) with the update on csrc/optim.hip."""
+
+    def __init__(self, params, lr=1e-3, momentum=0, dampening=0, weight_decay=0, nesterov=False, *, maximize=False):
+        _no_tensor_lr(lr)
+        if isinstance(weight_decay, torch.Tensor):
+            raise TypeError("dram_amd.optim: weight_decay must be a Python number, got a tensor")
+        super().__init__(params, lr, momentum, dampening, weight_decay, nesterov, maximize=maximize)
+
+    def __setstate__(self, state):
+        super().__setstate__(state)
+        for group in self.param_groups:
+            group["foreach"], group["fused"], group["differentiable"] = None, None, False
+
+    @torch.no_grad()
+    def step(self, closure=None):
+        loss = None
+        if closure is not None:
+            with torch.enable_grad():
+                loss = closure()
+        name = "dram_amd.optim.SGD"
+        for group in self.param_groups:
+            lr = group["lr"]
+            _no_tensor_lr(lr)
+            momentum = float(group["momentum"])
+            rows = []
+            for p, g in _with_grad(group, name):
+                buf, first = None, 0.0
+                if momentum != 0:
+                    state = self.state[p]
+                    buf = state.get("momentum_buffer")
+                    if buf is None:                    # torch: buf = clone(g'); here the kernel writes g' into it
+                        buf = state["momentum_buffer"] = torch.empty_like(p, memory_format=torch.preserve_format)
+                        first = 1.0
+                    _chk_state(buf, p, name)
+                rows.append((p.device, p, g, buf, None, None, first, 0.0))
+            _launch("dram_optim_sgd", rows, float(lr), momentum, float(group["dampening"]), float(group["weight_decay"]),
+                    int(bool(group["nesterov"])), int(bool(group["maximize"])))
+        return loss

@@ -165,7 +165,10 @@ class DataParallelTrainer:
     module of DC3DATGeneric) joins after backward.  xGMI is point-to-point (7 links/GPU): the 65 MB take < 1 ms as a ring
     all-reduce against a multi-second step, so this hides little here -- it is the stated design and costs nothing.
     Per-rank BatchNorm statistics (the reference's default "bn") need no exchange.  `p.grad` of every parameter is a view
-    into its bucket after the step (no per-step torch.cat, no copy back)."""
+    into its bucket after the step (no per-step torch.cat, no copy back).
+
+    `optimizer` is any torch.optim.Optimizer over the model's parameters; dram_amd.optim.Adam / AdamW / SGD (one HIP launch
+    per parameter group, bucket views at any offset included) go in unchanged."""
 
     def __init__(self, model, optimizer, loss_fn=None, loss_factors=(2.0, 1.0), bucket_mb=32, overlap=True):
         self.model, self.opt = model, optimizer

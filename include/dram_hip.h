@@ -701,6 +701,39 @@ int dram_chunk_prepare(const int16_t* scans, const uint8_t* lobes, const uint8_t
                        int N, int Do, int Ho, int Wo, float wmin, float wmax, int pwmin, int pwmax, float* image,
                        float* lobe_out, float* lesion_out, float* vessel_out, void* stream);
 
+/* ---- the optimiser update (st_dram_ref.py: torch.optim.Adam(lr=1e-4) under ExponentialLR; the SGD block beside it):
+ *      multi-tensor Adam / AdamW / SGD on fp32 tensors, one launch per table of up to DRAM_OPTIM_TABLE_CAPACITY tensors.
+ * `table` is HOST memory, read before the call returns (it travels to the device in the kernel arguments): per tensor the
+ *   device pointers p (parameter), g (gradient), m, v, vmax of n contiguous floats each (1 <= n < 2^31; 4-byte aligned, any
+ *   offset: a tensor whose pointers are all 16-byte aligned moves as 16-byte accesses, any other one element per lane) and two
+ *   per-tensor scalars.  The tensors of a table must not overlap.  Neither entry synchronises, allocates or reads device memory
+ *   from the host.
+ * dram_optim_adam: per element, t = the tensor's own step count after increment, bc1 = 1 - beta1^t, bc2 = 1 - beta2^t:
+ *     g' = maximize ? -g : g;  decoupled (AdamW): p *= 1 - lr * weight_decay;  else: g' += weight_decay * p;
+ *     m = beta1 * m + (1 - beta1) * g';  v = beta2 * v + (1 - beta2) * g'^2;  vuse = amsgrad ? (vmax = max(vmax, v)) : v;
+ *     p -= s0 * m / (sqrt(vuse) / s1 + eps)        with s0 = lr / bc1 and s1 = sqrt(bc2) formed by the caller in double.
+ *   m, v: exp_avg, exp_avg_sq; vmax: max_exp_avg_sq (read only with amsgrad).  `lr` enters only the AdamW decay.
+ * dram_optim_sgd (torch.optim.SGD's rule): g' = maximize ? -g : g;  g' += weight_decay * p;  with momentum != 0:
+ *     buf = s0 != 0 ? g' : momentum * buf + (1 - dampening) * g';  g' = nesterov ? g' + momentum * buf : buf;   p -= lr * g'.
+ *   m: momentum_buffer (ignored when momentum == 0; s0 != 0 marks the tensor's first step, where buf need not be initialised);
+ *   v, vmax, s1 unused. ---- */
+#define DRAM_OPTIM_TABLE_CAPACITY 64
+typedef struct dram_optim_tensor {
+    float* p;
+    const float* g;
+    float* m;
+    float* v;
+    float* vmax;
+    int64_t n;
+    float s0;
+    float s1;
+} dram_optim_tensor;
+int dram_optim_table_capacity(void);
+int dram_optim_adam(const dram_optim_tensor* table, int count, double lr, double beta1, double beta2, double eps,
+                    double weight_decay, int decoupled, int amsgrad, int maximize, void* stream);
+int dram_optim_sgd(const dram_optim_tensor* table, int count, double lr, double momentum, double dampening,
+                   double weight_decay, int nesterov, int maximize, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
