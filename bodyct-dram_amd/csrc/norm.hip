@@ -801,20 +801,88 @@ __global__ __launch_bounds__(256) void bn_parts_moments_kernel(const double* __r
     }
 }
 
-static inline bool vec_ok(const void* p, int64_t S) { return (S % 4 == 0) && (((uintptr_t)p) % 16 == 0); }
+static inline bool vec_ok(const void* p, int64_t S) { return S % 4 == 0 && aligned16(p); }
+
+static inline int nchunks_of(int64_t S) { return (int)cdiv64(S, CHUNK); }
+
+// grid of every row kernel: chunks on x, rows on y (at most 65535: check_norm)
+static inline dim3 row_grid(int64_t rows, int64_t S) { return dim3((unsigned)nchunks_of(S), (unsigned)rows); }
 
 static int check_norm(const char* who, int kind, int G, int N, int C, int64_t S) {
     DRAM_REQUIRE(N > 0 && C > 0 && S > 0, "%s: non-positive dimension", who);
     DRAM_REQUIRE(kind == DRAM_NORM_BATCH || kind == DRAM_NORM_GROUP, "%s: unknown norm kind %d", who, kind);
     if (kind == DRAM_NORM_GROUP) DRAM_REQUIRE(G > 0 && C % G == 0, "%s: C=%d not divisible by G=%d", who, C, G);
-    DRAM_REQUIRE((int64_t)N * C <= 65535 * 64LL, "%s: too many rows", who);
+    DRAM_REQUIRE((int64_t)N * C <= 65535, "%s: N*C > 65535 rows not supported", who);
     return DRAM_OK;
 }
 
-static inline int nchunks_of(int64_t S) { return (int)cdiv64(S, CHUNK); }
+// The norm workspace: [chunk partials, 2 floats per (row, chunk) | row sums, 2 doubles per row | pqr, 3 floats per row], each
+// part aligned up to 256 bytes.  This is its only definition: dram_norm_ws_bytes is `bytes` on a null base, and the split sync-BN
+// backward hands `rowsum` from dram_bn_bwd_sums to dram_bn_bwd_apply_sums through it.
+struct NormWs { float* part; double* rowsum; float* pqr; size_t bytes; };
 
-// rows go on grid.y (max 65535): fold when N*C is larger
-static inline dim3 row_grid(int nchunks, int64_t rows) { return dim3((unsigned)nchunks, (unsigned)rows); }
+static NormWs norm_ws_layout(void* ws, int N, int C, int64_t S) {
+    const size_t rows = (size_t)N * C;
+    const size_t part_bytes = align_up(rows * nchunks_of(S) * 2 * sizeof(float), 256);
+    const size_t rowsum_bytes = align_up(rows * 2 * sizeof(double), 256);
+    const uintptr_t w = (uintptr_t)ws;
+    return {(float*)w, (double*)(w + part_bytes), (float*)(w + part_bytes + rowsum_bytes),
+            part_bytes + rowsum_bytes + align_up(rows * 3 * sizeof(float), 256)};
+}
+
+// What every entry point with the norm workspace checks after its own pointers; fills `L` from `ws`.
+static int norm_begin(const char* who, int kind, int G, int N, int C, int64_t S, void* ws, size_t ws_bytes, NormWs& L) {
+    int rc = check_norm(who, kind, G, N, C, S);
+    if (rc) return rc;
+    L = norm_ws_layout(ws, N, C, S);
+    if (ws_bytes < L.bytes) {
+        set_error("%s: workspace too small", who);
+        return DRAM_EWS;
+    }
+    return DRAM_OK;
+}
+
+// One launch function per row kernel: the only place that names it and that picks its 16-byte or scalar instantiation.
+static void launch_row_moments(const float* x, float* part, bool vec, int64_t rows, int64_t S, hipStream_t st) {
+    auto* k = vec ? row_moments_kernel<true> : row_moments_kernel<false>;
+    hipLaunchKernelGGL(k, row_grid(rows, S), dim3(256), 0, st, x, part, S, nchunks_of(S));
+}
+
+static void launch_row_affine_act(const float* x, float* y, const float* rowcoef, int relu, int64_t rows, int64_t S,
+                                  hipStream_t st) {
+    auto* k = vec_ok(x, S) && vec_ok(y, S) ? row_affine_act_kernel<true> : row_affine_act_kernel<false>;
+    hipLaunchKernelGGL(k, row_grid(rows, S), dim3(256), 0, st, x, y, rowcoef, S, relu);
+}
+
+// The two row stages of the norm backward.  `src` says where the row kernels take the incoming gradient from (GradPlain /
+// GradHead / GradPoolAdd; `dy` is what that policy's at() expects), `src_vec` whether its operands allow the 16-byte kernels.
+// Reduce stage: per (row, chunk) sums into L.part, then per row into L.rowsum.  `dx` only takes part in the choice of the
+// kernel, so that a call which runs both stages reduces at the width it applies at; null where the caller has none.
+template <class SRC>
+static void bwd_reduce_rows(const SRC& src, bool src_vec, const float* dy, const float* x, const float* rowcoef,
+                            const float* save_mean, const float* save_rstd, const float* dx, const NormWs& L, int kind, int C,
+                            int Gk, int relu, int64_t rows, int64_t S, hipStream_t st) {
+    const int nch = nchunks_of(S);
+    auto* k = src_vec && vec_ok(x, S) && vec_ok(dx, S) ? row_bwd_reduce_kernel<true, SRC> : row_bwd_reduce_kernel<false, SRC>;
+    hipLaunchKernelGGL(k, row_grid(rows, S), dim3(256), 0, st, dy, x, rowcoef, save_mean, save_rstd, L.part, S, nch, kind, C, Gk,
+                       relu, src);
+    hipLaunchKernelGGL(row_sum_chunks_kernel, dim3((unsigned)cdiv64(rows, 256)), dim3(256), 0, st, L.part, L.rowsum, (int)rows,
+                       nch);
+}
+
+// Apply stage: dx from the per-row {p, q, r} that a finalize kernel left in L.pqr.
+template <class SRC>
+static void launch_row_bwd_apply(const SRC& src, bool src_vec, const float* dy, const float* x, const float* rowcoef,
+                                 float* dx, const NormWs& L, int relu, int64_t rows, int64_t S, hipStream_t st) {
+    auto* k = src_vec && vec_ok(x, S) && vec_ok(dx, S) ? row_bwd_apply_kernel<true, SRC> : row_bwd_apply_kernel<false, SRC>;
+    hipLaunchKernelGGL(k, row_grid(rows, S), dim3(256), 0, st, dy, x, rowcoef, L.pqr, dx, S, relu, src);
+}
+
+static void launch_bn_eval_coef(const float* gamma, const float* beta, const float* running_mean, const float* running_var,
+                                float* save_mean, float* save_rstd, float* rowcoef, float eps, int N, int C, hipStream_t st) {
+    hipLaunchKernelGGL(bn_eval_coef_kernel, dim3((unsigned)cdiv64((int64_t)N * C, 256)), dim3(256), 0, st, gamma, beta,
+                       running_mean, running_var, eps, N, C, save_mean, save_rstd, rowcoef);
+}
 
 }  // namespace dram
 
@@ -822,10 +890,7 @@ using namespace dram;
 
 extern "C" size_t dram_norm_ws_bytes(int N, int C, int64_t S) {
     if (N <= 0 || C <= 0 || S <= 0) return 0;
-    const size_t rows = (size_t)N * C;
-    // chunk partials (2 floats) + row sums (2 doubles) + pqr (3 floats)
-    return align_up(rows * nchunks_of(S) * 2 * sizeof(float), 256) + align_up(rows * 2 * sizeof(double), 256) +
-           align_up(rows * 3 * sizeof(float), 256);
+    return norm_ws_layout(nullptr, N, C, S).bytes;
 }
 
 extern "C" int dram_norm_fwd_train(const float* x, const float* gamma, const float* beta, float* y, float* save_mean,
@@ -833,26 +898,17 @@ extern "C" int dram_norm_fwd_train(const float* x, const float* gamma, const flo
                                    float momentum, float eps, int kind, int G, int relu, int N, int C, int64_t S,
                                    void* ws, size_t ws_bytes, void* stream) {
     DRAM_REQUIRE(x && y && save_mean && save_rstd && rowcoef && ws, "norm_fwd_train: null pointer");
-    int rc = check_norm("norm_fwd_train", kind, G, N, C, S);
+    NormWs L;
+    int rc = norm_begin("norm_fwd_train", kind, G, N, C, S, ws, ws_bytes, L);
     if (rc) return rc;
-    DRAM_REQUIRE((int64_t)N * C <= 65535, "norm_fwd_train: N*C > 65535 rows not supported");
-    if (ws_bytes < dram_norm_ws_bytes(N, C, S)) {
-        set_error("norm_fwd_train: workspace too small");
-        return DRAM_EWS;
-    }
     hipStream_t st = (hipStream_t)stream;
-    const int nch = nchunks_of(S);
     const int64_t rows = (int64_t)N * C;
-    float* part = (float*)ws;
-    const bool vec = vec_ok(x, S) && vec_ok(y, S);
-    if (vec) hipLaunchKernelGGL(row_moments_kernel<true>, row_grid(nch, rows), dim3(256), 0, st, x, part, S, nch);
-    else hipLaunchKernelGGL(row_moments_kernel<false>, row_grid(nch, rows), dim3(256), 0, st, x, part, S, nch);
+    launch_row_moments(x, L.part, vec_ok(x, S) && vec_ok(y, S), rows, S, st);
     const int nstat = kind == DRAM_NORM_BATCH ? C : N * G;
-    hipLaunchKernelGGL(norm_finalize_kernel, dim3(nstat), dim3(256), 0, st, part, nch, S, kind, N, C,
+    hipLaunchKernelGGL(norm_finalize_kernel, dim3(nstat), dim3(256), 0, st, L.part, nchunks_of(S), S, kind, N, C,
                        kind == DRAM_NORM_BATCH ? 1 : G, gamma, beta, eps, save_mean, save_rstd, rowcoef,
                        running_mean, running_var, momentum);
-    if (vec) hipLaunchKernelGGL(row_affine_act_kernel<true>, row_grid(nch, rows), dim3(256), 0, st, x, y, rowcoef, S, relu);
-    else hipLaunchKernelGGL(row_affine_act_kernel<false>, row_grid(nch, rows), dim3(256), 0, st, x, y, rowcoef, S, relu);
+    launch_row_affine_act(x, y, rowcoef, relu, rows, S, st);
     return check_launch("norm_fwd_train");
 }
 
@@ -862,71 +918,38 @@ extern "C" int dram_bn_fwd_eval(const float* x, const float* gamma, const float*
     DRAM_REQUIRE(x && y && running_mean && running_var && save_mean && save_rstd && rowcoef, "bn_fwd_eval: null pointer");
     int rc = check_norm("bn_fwd_eval", DRAM_NORM_BATCH, 1, N, C, S);
     if (rc) return rc;
-    DRAM_REQUIRE((int64_t)N * C <= 65535, "bn_fwd_eval: N*C > 65535 rows not supported");
     hipStream_t st = (hipStream_t)stream;
-    const int nch = nchunks_of(S);
-    const int64_t rows = (int64_t)N * C;
-    hipLaunchKernelGGL(bn_eval_coef_kernel, dim3((unsigned)cdiv64(rows, 256)), dim3(256), 0, st, gamma, beta,
-                       running_mean, running_var, eps, N, C, save_mean, save_rstd, rowcoef);
-    if (vec_ok(x, S) && vec_ok(y, S))
-        hipLaunchKernelGGL(row_affine_act_kernel<true>, row_grid(nch, rows), dim3(256), 0, st, x, y, rowcoef, S, relu);
-    else
-        hipLaunchKernelGGL(row_affine_act_kernel<false>, row_grid(nch, rows), dim3(256), 0, st, x, y, rowcoef, S, relu);
+    launch_bn_eval_coef(gamma, beta, running_mean, running_var, save_mean, save_rstd, rowcoef, eps, N, C, st);
+    launch_row_affine_act(x, y, rowcoef, relu, (int64_t)N * C, S, st);
     return check_launch("bn_fwd_eval");
 }
 
-// The one launch sequence of the norm backward: reduce, row sums, finalize, apply.  `src` says where the row kernels take the
-// incoming gradient from (GradPlain / GradHead / GradPoolAdd; `dy` is what that policy's at() expects), `src_vec` whether its
-// operands allow the 16-byte kernels.
+// The one launch sequence of the norm backward: reduce stage, finalize, apply stage.
 template <class SRC>
 static int norm_bwd_run(const char* who, const SRC& src, bool src_vec, const float* dy, const float* x, const float* gamma,
                         const float* save_mean, const float* save_rstd, const float* rowcoef, float* dx, float* dgamma,
                         float* dbeta, int kind, int G, int relu, int batch_stats, int N, int C, int64_t S, void* ws,
                         size_t ws_bytes, void* stream) {
     DRAM_REQUIRE(dy && x && save_mean && save_rstd && rowcoef && dx && ws, "%s: null pointer", who);
-    int rc = check_norm(who, kind, G, N, C, S);
+    DRAM_REQUIRE(kind != DRAM_NORM_GROUP || batch_stats, "%s: GroupNorm always uses batch statistics", who);
+    NormWs L;
+    int rc = norm_begin(who, kind, G, N, C, S, ws, ws_bytes, L);
     if (rc) return rc;
-    DRAM_REQUIRE((int64_t)N * C <= 65535, "%s: N*C > 65535 rows not supported", who);
-    DRAM_REQUIRE(kind == DRAM_NORM_BATCH || batch_stats, "%s: GroupNorm always uses batch statistics", who);
-    if (ws_bytes < dram_norm_ws_bytes(N, C, S)) {
-        set_error("%s: workspace too small", who);
-        return DRAM_EWS;
-    }
     hipStream_t st = (hipStream_t)stream;
-    const int nch = nchunks_of(S);
     const int64_t rows = (int64_t)N * C;
-    char* w = (char*)ws;
-    float* part = (float*)w;
-    w += align_up((size_t)rows * nch * 2 * sizeof(float), 256);
-    double* rowsum = (double*)w;
-    w += align_up((size_t)rows * 2 * sizeof(double), 256);
-    float* pqr = (float*)w;
-    const int Gk = kind == DRAM_NORM_BATCH ? 1 : G;
-    const bool vec = src_vec && vec_ok(x, S) && vec_ok(dx, S);
-    if (vec)
-        hipLaunchKernelGGL((row_bwd_reduce_kernel<true, SRC>), row_grid(nch, rows), dim3(256), 0, st, dy, x, rowcoef,
-                           save_mean, save_rstd, part, S, nch, kind, C, Gk, relu, src);
-    else
-        hipLaunchKernelGGL((row_bwd_reduce_kernel<false, SRC>), row_grid(nch, rows), dim3(256), 0, st, dy, x, rowcoef,
-                           save_mean, save_rstd, part, S, nch, kind, C, Gk, relu, src);
-    hipLaunchKernelGGL(row_sum_chunks_kernel, dim3((unsigned)cdiv64(rows, 256)), dim3(256), 0, st, part, rowsum,
-                       (int)rows, nch);
+    bwd_reduce_rows(src, src_vec, dy, x, rowcoef, save_mean, save_rstd, dx, L, kind, C, kind == DRAM_NORM_BATCH ? 1 : G, relu,
+                    rows, S, st);
     if (kind == DRAM_NORM_BATCH) {
-        hipLaunchKernelGGL(bn_bwd_finalize_kernel, dim3(cdiv(C, 64)), dim3(64), 0, st, rowsum, gamma, save_mean,
-                           save_rstd, dgamma, dbeta, pqr, N, C, S, batch_stats);
+        hipLaunchKernelGGL(bn_bwd_finalize_kernel, dim3(cdiv(C, 64)), dim3(64), 0, st, L.rowsum, gamma, save_mean,
+                           save_rstd, dgamma, dbeta, L.pqr, N, C, S, batch_stats);
     } else {
-        hipLaunchKernelGGL(gn_bwd_finalize_rows_kernel, dim3(cdiv(N * G, 64)), dim3(64), 0, st, rowsum, gamma,
-                           save_mean, save_rstd, pqr, N, C, G, S);
+        hipLaunchKernelGGL(gn_bwd_finalize_rows_kernel, dim3(cdiv(N * G, 64)), dim3(64), 0, st, L.rowsum, gamma,
+                           save_mean, save_rstd, L.pqr, N, C, G, S);
         if (dgamma || dbeta)
-            hipLaunchKernelGGL(gn_bwd_finalize_params_kernel, dim3(cdiv(C, 64)), dim3(64), 0, st, rowsum, dgamma,
+            hipLaunchKernelGGL(gn_bwd_finalize_params_kernel, dim3(cdiv(C, 64)), dim3(64), 0, st, L.rowsum, dgamma,
                                dbeta, N, C);
     }
-    if (vec)
-        hipLaunchKernelGGL((row_bwd_apply_kernel<true, SRC>), row_grid(nch, rows), dim3(256), 0, st, dy, x, rowcoef, pqr, dx, S,
-                           relu, src);
-    else
-        hipLaunchKernelGGL((row_bwd_apply_kernel<false, SRC>), row_grid(nch, rows), dim3(256), 0, st, dy, x, rowcoef, pqr, dx, S,
-                           relu, src);
+    launch_row_bwd_apply(src, src_vec, dy, x, rowcoef, dx, L, relu, rows, S, st);
     return check_launch(who);
 }
 
@@ -971,78 +994,46 @@ extern "C" int dram_norm_bwd_pool_add(const float* dy, const float* gp, const ui
 extern "C" int dram_bn_stats(const float* x, double* mean_m2, int N, int C, int64_t S, void* ws, size_t ws_bytes,
                              void* stream) {
     DRAM_REQUIRE(x && mean_m2 && ws, "bn_stats: null pointer");
-    int rc = check_norm("bn_stats", DRAM_NORM_BATCH, 1, N, C, S);
+    NormWs L;
+    int rc = norm_begin("bn_stats", DRAM_NORM_BATCH, 1, N, C, S, ws, ws_bytes, L);
     if (rc) return rc;
-    DRAM_REQUIRE((int64_t)N * C <= 65535, "bn_stats: N*C > 65535 rows not supported");
-    if (ws_bytes < dram_norm_ws_bytes(N, C, S)) {
-        set_error("bn_stats: workspace too small");
-        return DRAM_EWS;
-    }
     hipStream_t st = (hipStream_t)stream;
-    const int nch = nchunks_of(S);
-    const int64_t rows = (int64_t)N * C;
-    float* part = (float*)ws;
-    if (vec_ok(x, S)) hipLaunchKernelGGL(row_moments_kernel<true>, row_grid(nch, rows), dim3(256), 0, st, x, part, S, nch);
-    else hipLaunchKernelGGL(row_moments_kernel<false>, row_grid(nch, rows), dim3(256), 0, st, x, part, S, nch);
-    hipLaunchKernelGGL(bn_stats_finalize_kernel, dim3(C), dim3(256), 0, st, part, nch, S, N, C, mean_m2);
+    launch_row_moments(x, L.part, vec_ok(x, S), (int64_t)N * C, S, st);
+    hipLaunchKernelGGL(bn_stats_finalize_kernel, dim3(C), dim3(256), 0, st, L.part, nchunks_of(S), S, N, C, mean_m2);
     return check_launch("bn_stats");
 }
 
+// The split sync-BN backward: the reduce stage of norm_bwd_run and the per-channel sums, which leave for the all-reduce ...
 extern "C" int dram_bn_bwd_sums(const float* dy, const float* x, const float* save_mean, const float* save_rstd,
                                 const float* rowcoef, double* sums, int relu, int N, int C, int64_t S, void* ws,
                                 size_t ws_bytes, void* stream) {
     DRAM_REQUIRE(dy && x && save_mean && save_rstd && rowcoef && sums && ws, "bn_bwd_sums: null pointer");
-    int rc = check_norm("bn_bwd_sums", DRAM_NORM_BATCH, 1, N, C, S);
+    NormWs L;
+    int rc = norm_begin("bn_bwd_sums", DRAM_NORM_BATCH, 1, N, C, S, ws, ws_bytes, L);
     if (rc) return rc;
-    DRAM_REQUIRE((int64_t)N * C <= 65535, "bn_bwd_sums: N*C > 65535 rows not supported");
-    if (ws_bytes < dram_norm_ws_bytes(N, C, S)) {
-        set_error("bn_bwd_sums: workspace too small");
-        return DRAM_EWS;
-    }
     hipStream_t st = (hipStream_t)stream;
-    const int nch = nchunks_of(S);
-    const int64_t rows = (int64_t)N * C;
-    float* part = (float*)ws;
-    double* rowsum = (double*)((char*)ws + align_up((size_t)rows * nch * 2 * sizeof(float), 256));
-    if (vec_ok(x, S) && vec_ok(dy, S))
-        hipLaunchKernelGGL((row_bwd_reduce_kernel<true, GradPlain>), row_grid(nch, rows), dim3(256), 0, st, dy, x, rowcoef, save_mean,
-                           save_rstd, part, S, nch, DRAM_NORM_BATCH, C, 1, relu, GradPlain{});
-    else
-        hipLaunchKernelGGL((row_bwd_reduce_kernel<false, GradPlain>), row_grid(nch, rows), dim3(256), 0, st, dy, x, rowcoef, save_mean,
-                           save_rstd, part, S, nch, DRAM_NORM_BATCH, C, 1, relu, GradPlain{});
-    hipLaunchKernelGGL(row_sum_chunks_kernel, dim3((unsigned)cdiv64(rows, 256)), dim3(256), 0, st, part, rowsum, (int)rows, nch);
-    hipLaunchKernelGGL(bn_bwd_sums_kernel, dim3(cdiv(C, 64)), dim3(64), 0, st, rowsum, sums, N, C);
+    bwd_reduce_rows(GradPlain{}, vec_ok(dy, S), dy, x, rowcoef, save_mean, save_rstd, nullptr, L, DRAM_NORM_BATCH, C, 1, relu,
+                    (int64_t)N * C, S, st);
+    hipLaunchKernelGGL(bn_bwd_sums_kernel, dim3(cdiv(C, 64)), dim3(64), 0, st, L.rowsum, sums, N, C);
     return check_launch("bn_bwd_sums");
 }
 
+// ... and, from the reduced sums, {p, q, r} and the apply stage.
 extern "C" int dram_bn_bwd_apply_sums(const float* dy, const float* x, const float* gamma, const float* save_mean,
                                       const float* save_rstd, const float* rowcoef, const double* sums, double count,
                                       float* dx, int relu, int N, int C, int64_t S, void* ws, size_t ws_bytes,
                                       void* stream) {
     DRAM_REQUIRE(dy && x && save_mean && save_rstd && rowcoef && sums && dx && ws, "bn_bwd_apply_sums: null pointer");
-    int rc = check_norm("bn_bwd_apply_sums", DRAM_NORM_BATCH, 1, N, C, S);
+    DRAM_REQUIRE(count > 0.0, "bn_bwd_apply_sums: bad dimensions");
+    NormWs L;
+    int rc = norm_begin("bn_bwd_apply_sums", DRAM_NORM_BATCH, 1, N, C, S, ws, ws_bytes, L);
     if (rc) return rc;
-    DRAM_REQUIRE((int64_t)N * C <= 65535 && count > 0.0, "bn_bwd_apply_sums: bad dimensions");
-    if (ws_bytes < dram_norm_ws_bytes(N, C, S)) {
-        set_error("bn_bwd_apply_sums: workspace too small");
-        return DRAM_EWS;
-    }
     hipStream_t st = (hipStream_t)stream;
-    const int nch = nchunks_of(S);
-    const int64_t rows = (int64_t)N * C;
-    float* pqr = (float*)((char*)ws + align_up((size_t)rows * nch * 2 * sizeof(float), 256) +
-                          align_up((size_t)rows * 2 * sizeof(double), 256));
     hipLaunchKernelGGL(bn_pqr_from_sums_kernel, dim3(cdiv(C, 64)), dim3(64), 0, st, sums, count, gamma, save_mean, save_rstd,
-                       pqr, N, C);
-    if (vec_ok(x, S) && vec_ok(dy, S) && vec_ok(dx, S))
-        hipLaunchKernelGGL((row_bwd_apply_kernel<true, GradPlain>), row_grid(nch, rows), dim3(256), 0, st, dy, x, rowcoef, pqr, dx, S,
-                           relu, GradPlain{});
-    else
-        hipLaunchKernelGGL((row_bwd_apply_kernel<false, GradPlain>), row_grid(nch, rows), dim3(256), 0, st, dy, x, rowcoef, pqr, dx, S,
-                           relu, GradPlain{});
+                       L.pqr, N, C);
+    launch_row_bwd_apply(GradPlain{}, vec_ok(dy, S), dy, x, rowcoef, dx, L, relu, (int64_t)N * C, S, st);
     return check_launch("bn_bwd_apply_sums");
 }
-
 
 // ---- statistics that arrive from the conv epilogue ---------------------------------------------------------------
 static inline int parts_groups(int nparts) { return cdiv(nparts, PARTS_PER_GROUP); }
@@ -1050,6 +1041,22 @@ static inline int parts_groups(int nparts) { return cdiv(nparts, PARTS_PER_GROUP
 extern "C" size_t dram_norm_parts_ws_bytes(int N, int C, int nparts) {
     if (N <= 0 || C <= 0 || nparts <= 0) return 0;
     return (size_t)N * C * parts_groups(nparts) * 3 * sizeof(double);
+}
+
+// What both users of the parts workspace begin with: the checks, then the partials of each row reduced to `groups`
+// {mean, M2, count} triples in `part2`, which is the whole workspace.
+static int parts_reduce(const char* who, const float* parts, int nparts, int kind, int G, int N, int C, int64_t S, void* ws,
+                        size_t ws_bytes, hipStream_t st, double*& part2, int& groups) {
+    int rc = check_norm(who, kind, G, N, C, S);
+    if (rc) return rc;
+    if (ws_bytes < dram_norm_parts_ws_bytes(N, C, nparts)) {
+        set_error("%s: workspace too small", who);
+        return DRAM_EWS;
+    }
+    part2 = (double*)ws;
+    groups = parts_groups(nparts);
+    hipLaunchKernelGGL(parts_reduce_kernel, dim3(groups, N * C), dim3(256), 0, st, parts, part2, nparts, groups);
+    return DRAM_OK;
 }
 
 // Training-mode statistics of BatchNorm / GroupNorm from the {mean, M2, count} partials that the fused convolution
@@ -1060,17 +1067,11 @@ extern "C" int dram_norm_finalize_parts(const float* parts, int nparts, const fl
                                         float* running_var, float momentum, float eps, int kind, int G, int N, int C,
                                         int64_t S, void* ws, size_t ws_bytes, void* stream) {
     DRAM_REQUIRE(parts && save_mean && save_rstd && rowcoef && ws && nparts > 0, "norm_finalize_parts: null pointer");
-    int rc = check_norm("norm_finalize_parts", kind, G, N, C, S);
-    if (rc) return rc;
-    DRAM_REQUIRE((int64_t)N * C <= 65535, "norm_finalize_parts: N*C > 65535 rows not supported");
-    if (ws_bytes < dram_norm_parts_ws_bytes(N, C, nparts)) {
-        set_error("norm_finalize_parts: workspace too small");
-        return DRAM_EWS;
-    }
     hipStream_t st = (hipStream_t)stream;
-    const int groups = parts_groups(nparts);
-    double* part2 = (double*)ws;
-    hipLaunchKernelGGL(parts_reduce_kernel, dim3(groups, N * C), dim3(256), 0, st, parts, part2, nparts, groups);
+    double* part2;
+    int groups;
+    int rc = parts_reduce("norm_finalize_parts", parts, nparts, kind, G, N, C, S, ws, ws_bytes, st, part2, groups);
+    if (rc) return rc;
     const int Gk = kind == DRAM_NORM_BATCH ? 1 : G;
     const int nstat = kind == DRAM_NORM_BATCH ? C : N * G;
     const double expect = (double)(kind == DRAM_NORM_BATCH ? N : C / G) * (double)S;
@@ -1085,17 +1086,11 @@ extern "C" int dram_norm_finalize_parts(const float* parts, int nparts, const fl
 extern "C" int dram_bn_parts_stats(const float* parts, int nparts, double* mean_m2, int N, int C, int64_t S, void* ws,
                                    size_t ws_bytes, void* stream) {
     DRAM_REQUIRE(parts && mean_m2 && ws && nparts > 0, "bn_parts_stats: null pointer");
-    int rc = check_norm("bn_parts_stats", DRAM_NORM_BATCH, 1, N, C, S);
-    if (rc) return rc;
-    DRAM_REQUIRE((int64_t)N * C <= 65535, "bn_parts_stats: N*C > 65535 rows not supported");
-    if (ws_bytes < dram_norm_parts_ws_bytes(N, C, nparts)) {
-        set_error("bn_parts_stats: workspace too small");
-        return DRAM_EWS;
-    }
     hipStream_t st = (hipStream_t)stream;
-    const int groups = parts_groups(nparts);
-    double* part2 = (double*)ws;
-    hipLaunchKernelGGL(parts_reduce_kernel, dim3(groups, N * C), dim3(256), 0, st, parts, part2, nparts, groups);
+    double* part2;
+    int groups;
+    int rc = parts_reduce("bn_parts_stats", parts, nparts, DRAM_NORM_BATCH, 1, N, C, S, ws, ws_bytes, st, part2, groups);
+    if (rc) return rc;
     hipLaunchKernelGGL(bn_parts_moments_kernel, dim3(C), dim3(256), 0, st, part2, groups, N, C, (double)N * (double)S, mean_m2);
     return check_launch("bn_parts_stats");
 }
@@ -1106,12 +1101,7 @@ extern "C" int dram_row_affine_act(const float* x, const float* rowcoef, float* 
                                    void* stream) {
     DRAM_REQUIRE(x && rowcoef && y && rows > 0 && S > 0, "row_affine_act: bad arguments");
     DRAM_REQUIRE(rows <= 65535, "row_affine_act: more than 65535 rows not supported");
-    hipStream_t st = (hipStream_t)stream;
-    const int nch = nchunks_of(S);
-    if (vec_ok(x, S) && vec_ok(y, S))
-        hipLaunchKernelGGL(row_affine_act_kernel<true>, row_grid(nch, rows), dim3(256), 0, st, x, y, rowcoef, S, relu);
-    else
-        hipLaunchKernelGGL(row_affine_act_kernel<false>, row_grid(nch, rows), dim3(256), 0, st, x, y, rowcoef, S, relu);
+    launch_row_affine_act(x, y, rowcoef, relu, rows, S, (hipStream_t)stream);
     return check_launch("row_affine_act");
 }
 
@@ -1119,24 +1109,22 @@ extern "C" int dram_row_affine_act(const float* x, const float* rowcoef, float* 
 extern "C" int dram_bn_eval_coef(const float* gamma, const float* beta, const float* running_mean, const float* running_var,
                                  float* save_mean, float* save_rstd, float* rowcoef, float eps, int N, int C, void* stream) {
     DRAM_REQUIRE(running_mean && running_var && save_mean && save_rstd && rowcoef && N > 0 && C > 0, "bn_eval_coef: bad arguments");
-    const int64_t rows = (int64_t)N * C;
-    hipLaunchKernelGGL(bn_eval_coef_kernel, dim3((unsigned)cdiv64(rows, 256)), dim3(256), 0, (hipStream_t)stream, gamma, beta,
-                       running_mean, running_var, eps, N, C, save_mean, save_rstd, rowcoef);
+    launch_bn_eval_coef(gamma, beta, running_mean, running_var, save_mean, save_rstd, rowcoef, eps, N, C, (hipStream_t)stream);
     return check_launch("bn_eval_coef");
 }
+
+static inline dim3 relu_grid(int64_t n) { return dim3((unsigned)(cdiv64(n, 256) < 8192 ? cdiv64(n, 256) : 8192)); }
 
 extern "C" int dram_relu_fwd(const float* x, float* y, int64_t n, void* stream) {
     DRAM_REQUIRE(x && y && n >= 0, "relu_fwd: bad arguments");
     if (n == 0) return DRAM_OK;
-    const unsigned grid = (unsigned)(cdiv64(n, 256) < 8192 ? cdiv64(n, 256) : 8192);
-    hipLaunchKernelGGL(relu_fwd_kernel, dim3(grid), dim3(256), 0, (hipStream_t)stream, x, y, n);
+    hipLaunchKernelGGL(relu_fwd_kernel, relu_grid(n), dim3(256), 0, (hipStream_t)stream, x, y, n);
     return check_launch("relu_fwd");
 }
 
 extern "C" int dram_relu_bwd(const float* dy, const float* y, float* dx, int64_t n, void* stream) {
     DRAM_REQUIRE(dy && y && dx && n >= 0, "relu_bwd: bad arguments");
     if (n == 0) return DRAM_OK;
-    const unsigned grid = (unsigned)(cdiv64(n, 256) < 8192 ? cdiv64(n, 256) : 8192);
-    hipLaunchKernelGGL(relu_bwd_kernel, dim3(grid), dim3(256), 0, (hipStream_t)stream, dy, y, dx, n);
+    hipLaunchKernelGGL(relu_bwd_kernel, relu_grid(n), dim3(256), 0, (hipStream_t)stream, dy, y, dx, n);
     return check_launch("relu_bwd");
 }

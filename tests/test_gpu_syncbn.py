@@ -73,6 +73,46 @@ def test_sync_batchnorm_without_group_is_batchnorm():
     assert torch.equal(a(x), b(x))
 
 
+@pytest.mark.parametrize("relu", [0, 1])
+@pytest.mark.parametrize("shape", [
+    (2, 3, 1, 17, 241),     # S = 4097: two chunks of 4096 per row, odd -> the scalar row kernels
+    (2, 3, 2, 16, 160),     # S = 5120: two chunks, 16-byte aligned rows -> the 16-byte row kernels
+])
+def test_split_backward_equals_the_whole_backward(shape, relu):
+    """dram_bn_bwd_sums + dram_bn_bwd_apply_sums with count = N*S and no all-reduce in between are the two halves of
+    dram_norm_bwd (BatchNorm, batch statistics): the same row kernels on the same workspace, so dx is equal bit for bit and
+    the fp64 sums, cast to fp32, are dbeta and dgamma exactly (both sum the same fp64 row sums in the same order; this held
+    before the two entry points shared their stages with dram_norm_bwd, which is why it is equality and not a tolerance)."""
+    from dram_amd import _lib
+    N, C, S = shape[0], shape[1], shape[2] * shape[3] * shape[4]
+    gen = torch.Generator().manual_seed(S + relu)
+    x = (torch.randn(N, C, S, generator=gen) * 1.7 + 0.6).cuda()
+    dy = torch.randn(N, C, S, generator=gen).cuda()
+    gamma, beta = (torch.linspace(-1.3, 0.9, C) + 0.05).cuda(), torch.linspace(0.4, -0.3, C).cuda()
+    mean, rstd, coef = torch.empty(C, device="cuda"), torch.empty(C, device="cuda"), torch.empty(2 * N * C, device="cuda")
+    ws = torch.empty(_lib.lib.dram_norm_ws_bytes(N, C, S), dtype=torch.uint8, device="cuda")
+    st = torch.cuda.current_stream().cuda_stream
+    p = lambda t: t.data_ptr()
+    nan = lambda *size, dtype=torch.float32: torch.full(size, float("nan"), dtype=dtype, device="cuda")
+    y = nan(N, C, S)
+    _lib.call("dram_norm_fwd_train", p(x), p(gamma), p(beta), p(y), p(mean), p(rstd), p(coef), None, None, 0.1, 1e-5,
+              0, 1, relu, N, C, S, p(ws), ws.numel(), st)
+    dx, dgamma, dbeta = nan(N, C, S), nan(C), nan(C)
+    _lib.call("dram_norm_bwd", p(dy), p(x), p(gamma), p(mean), p(rstd), p(coef), p(dx), p(dgamma), p(dbeta), 0, 1, relu, 1,
+              N, C, S, p(ws), ws.numel(), st)
+    ws.fill_(0xFF)                                       # the split gets nothing from what the whole one left behind
+    dx2, sums = nan(N, C, S), nan(2 * C, dtype=torch.float64)
+    _lib.call("dram_bn_bwd_sums", p(dy), p(x), p(mean), p(rstd), p(coef), p(sums), relu, N, C, S, p(ws), ws.numel(), st)
+    _lib.call("dram_bn_bwd_apply_sums", p(dy), p(x), p(gamma), p(mean), p(rstd), p(coef), p(sums), float(N * S), p(dx2), relu,
+              N, C, S, p(ws), ws.numel(), st)
+    torch.cuda.synchronize()
+    got_dbeta, got_dgamma = sums[0::2].float(), sums[1::2].float()
+    print(f"split-bwd {shape} relu={relu}: dx max|diff| {(dx2 - dx).abs().max().item():.3e}, "
+          f"dbeta {(got_dbeta - dbeta).abs().max().item():.3e}, dgamma {(got_dgamma - dgamma).abs().max().item():.3e}")
+    assert torch.isfinite(dx).all() and torch.equal(dx2, dx)
+    assert torch.equal(got_dbeta, dbeta) and torch.equal(got_dgamma, dgamma)
+
+
 def _engine_worker(rank, world, port, out):
     """Slim DC3D with "sbn" through the FUSED ENGINE on this rank's share of a batch (statistics combined over the two
     ranks inside the engine) against one process running the whole batch with "bn" through the same engine."""

@@ -48,6 +48,48 @@ def test_argument_errors_are_reported_without_a_gpu():
     assert _lib.lib.dram_conv3d_k3_wgrad_ws_bytes(4, 64, 64, 128, 128, 128) > 0
 
 
+def _norm_workspace_calls(N, C, D, H, W, ws_bytes):
+    """(entry point, arguments) of every entry point that takes the norm workspace, on dummy non-null pointers."""
+    S, q = D * H * W, 16
+    bwd = (q, q, q, q, q, q, q, 0, 1, 0, 1, N, C)          # gamma .. dbeta, kind, G, relu, batch_stats, N, C
+    return [
+        ("dram_norm_fwd_train", (q, q, q, q, q, q, q, None, None, 0.1, 1e-5, 0, 1, 0, N, C, S, q, ws_bytes, None)),
+        ("dram_norm_bwd", (q, q, *bwd, S, q, ws_bytes, None)),
+        ("dram_norm_bwd_head", (q, q, 1, q, *bwd, S, q, ws_bytes, None)),
+        ("dram_norm_bwd_pool_add", (q, q, q, D, H, W, q, *bwd, q, ws_bytes, None)),
+        ("dram_bn_stats", (q, q, N, C, S, q, ws_bytes, None)),
+        ("dram_bn_bwd_sums", (q, q, q, q, q, q, 0, N, C, S, q, ws_bytes, None)),
+        ("dram_bn_bwd_apply_sums", (q, q, q, q, q, q, q, float(N * S), q, 0, N, C, S, q, ws_bytes, None)),
+    ]
+
+
+def test_norm_workspace_layout_and_checks():
+    """The norm workspace is [chunk partials (2 floats per row and chunk) | row sums (2 doubles per row) | pqr (3 floats per
+    row)], each part aligned up to 256 bytes; every entry point that takes it refuses one byte less and more than 65535 rows
+    before it launches anything."""
+    from dram_amd import _lib
+    up = lambda v: (v + 255) // 256 * 256
+    # N*C = 6 rows, S = 4097 = two chunks of 4096 per row
+    assert _lib.lib.dram_norm_ws_bytes(2, 3, 4097) == up(6 * 2 * 2 * 4) + up(6 * 2 * 8) + up(6 * 3 * 4) == 768
+    N, C, D, H, W = 2, 3, 2, 2, 1025
+    need = _lib.lib.dram_norm_ws_bytes(N, C, D * H * W)
+    assert need == up(6 * 2 * 2 * 4) + up(6 * 2 * 8) + up(6 * 3 * 4)
+    for name, args in _norm_workspace_calls(N, C, D, H, W, need - 1):
+        with pytest.raises(_lib.DramHipError, match="workspace too small"):
+            _lib.call(name, *args)
+    for name, args in _norm_workspace_calls(256, 256, 2, 2, 2, 1 << 40):
+        with pytest.raises(_lib.DramHipError, match="rows"):
+            _lib.call(name, *args)
+    nparts = 5
+    need = _lib.lib.dram_norm_parts_ws_bytes(N, C, nparts)
+    assert need > 0
+    with pytest.raises(_lib.DramHipError, match="workspace too small"):
+        _lib.call("dram_norm_finalize_parts", 16, nparts, 16, 16, 16, 16, 16, None, None, 0.1, 1e-5, 0, 1, N, C, 64, 16, need - 1,
+                  None)
+    with pytest.raises(_lib.DramHipError, match="workspace too small"):
+        _lib.call("dram_bn_parts_stats", 16, nparts, 16, N, C, 64, 16, need - 1, None)
+
+
 def test_kernel_choice_queries():
     """dram_conv3d_k3_fwd_choice_src / dram_conv3d_k3_wgrad_choice are pure functions of the shape (no GPU needed): the
     benchmark's layers (DC3D st_dram_ref at 128^3) get the kernels DESIGN.md names, and the two rules the old host-side
