@@ -71,8 +71,11 @@ __global__ __launch_bounds__(256) void prelu_da_kernel(const float* __restrict__
 
 // ---------------------------------------------------------------- global max
 __device__ __forceinline__ void argmax_merge(float& v, int64_t& i, float ov, int64_t oi) {
-    // ATen keeps the first maximum in scan order (and propagates NaN): larger value wins, ties -> smaller index
-    const bool take = (ov > v) || (ov != ov && v == v) || (ov == v && oi < i);
+    // ATen scans a window with `if (val > max || isnan(val)) take`: among numbers the first maximum in scan order is kept
+    // (larger value wins, ties -> smaller index); any NaN beats a number and stays, and a later NaN replaces an earlier one
+    // (two NaNs -> larger index)
+    const bool onan = ov != ov, nan = v != v;
+    const bool take = onan ? (!nan || oi > i) : (!nan && ((ov > v) || (ov == v && oi < i)));
     if (take) { v = ov; i = oi; }
 }
 
