@@ -12,6 +12,15 @@
 //
 // Every product, sum, quotient and root below is one IEEE fp32 operation (fmaf: one rounding for a*b+c); the count of
 // roundings per quantity is what tests/optim_restatement.py bounds.
+//
+// Global-norm gradient clipping (torch.nn.utils.clip_grad_norm_) rides on the same table and block mapping:
+//   grad_norm_kernel    one partial per block -- the fp64 sum of the block's exact squares (2-norm), or its max |g| with NaN kept
+//                       (inf-norm) -- each written by exactly one block into its own slot: no atomics, deterministic;
+//   grad_norm_finish    one block adds (or maxes) every partial in a fixed order and writes {total_norm, clip_coef};
+//   optim_kernel        takes `gscale`, a device pointer to that clip_coef (NULL: no scaling), read once per block, and multiplies
+//                       it into g before anything else: the gradients are read once and never written;
+//   grad_scale_kernel   g *= gscale[0] in place, for the stand-alone clip_grad_norm_.
+// Only the gradient pointer decides between the 16-byte and the one-dword instantiation in the two gradient-only kernels.
 #include "common.h"
 
 namespace dram {
@@ -46,14 +55,15 @@ struct SgdScalars {
 
 struct AdamRule {
     AdamScalars a;
-    float step_size, bc2_sqrt;
-    bool has_vmax;
+    float step_size, bc2_sqrt, gscale;
+    bool has_vmax, scaled;                            // scaled, gscale: set by optim_kernel
     __device__ __forceinline__ void load(const OptimEntry& e) { step_size = e.s0; bc2_sqrt = e.s1; has_vmax = a.amsgrad != 0; }
     __device__ __forceinline__ bool reads_m() const { return true; }
     __device__ __forceinline__ bool uses_m() const { return true; }
     __device__ __forceinline__ bool uses_v() const { return true; }
     __device__ __forceinline__ bool uses_vmax() const { return has_vmax; }
     __device__ __forceinline__ void apply(float& p, float g, float& m, float& v, float& vmax) const {
+        if (scaled) g = __fmul_rn(g, gscale);
         if (a.maximize) g = -g;
         if (a.decoupled) p = __fmul_rn(p, a.decay);
         else if (a.wd != 0.f) g = fmaf(a.wd, p, g);
@@ -68,13 +78,15 @@ struct AdamRule {
 
 struct SgdRule {
     SgdScalars a;
-    bool first, has_buf;
+    float gscale;
+    bool first, has_buf, scaled;                      // scaled, gscale: set by optim_kernel
     __device__ __forceinline__ void load(const OptimEntry& e) { first = e.s0 != 0.f; has_buf = e.m != nullptr; }
     __device__ __forceinline__ bool reads_m() const { return has_buf && !first; }
     __device__ __forceinline__ bool uses_m() const { return has_buf; }
     __device__ __forceinline__ bool uses_v() const { return false; }
     __device__ __forceinline__ bool uses_vmax() const { return false; }
     __device__ __forceinline__ void apply(float& p, float g, float& m, float&, float&) const {
+        if (scaled) g = __fmul_rn(g, gscale);
         if (a.maximize) g = -g;
         if (a.wd != 0.f) g = fmaf(a.wd, p, g);
         if (has_buf) {
@@ -122,17 +134,24 @@ __device__ __forceinline__ void optim_span(const OptimEntry& e, const Rule& r, u
     }
 }
 
-template <class Rule, class Scalars>
-__global__ __launch_bounds__(256) void optim_kernel(const OptimTable t, const Scalars s) {
-    // the last tensor whose first block is <= this block (first_block is increasing, e[0].first_block == 0)
+// The last tensor whose first block is <= this block (first_block is increasing, e[0].first_block == 0).
+__device__ __forceinline__ int optim_find(const OptimTable& t) {
     int lo = 0, hi = t.count - 1;
     while (lo < hi) {
         const int mid = (lo + hi + 1) >> 1;
         if (t.e[mid].first_block <= blockIdx.x) lo = mid; else hi = mid - 1;
     }
-    const OptimEntry e = t.e[lo];
+    return lo;
+}
+
+// gscale: NULL, or the device scalar every gradient is multiplied by (the clip coefficient grad_norm_finish wrote).
+template <class Rule, class Scalars>
+__global__ __launch_bounds__(256) void optim_kernel(const OptimTable t, const Scalars s, const float* __restrict__ gscale) {
+    const OptimEntry e = t.e[optim_find(t)];
     Rule r;
     r.a = s;
+    r.scaled = gscale != nullptr;
+    r.gscale = r.scaled ? gscale[0] : 1.f;                             // wave-uniform: one load per block
     r.load(e);
     const unsigned beg = (blockIdx.x - e.first_block) * OCHUNK;        // < n: the host gave this tensor cdiv(n, OCHUNK) blocks
     const unsigned end = e.n - beg < (unsigned)OCHUNK ? e.n : beg + OCHUNK;
@@ -143,6 +162,96 @@ __global__ __launch_bounds__(256) void optim_kernel(const OptimTable t, const Sc
         optim_span<true>(e, r, beg, vend);
     }
     optim_span<false>(e, r, vend, end);
+}
+
+// ---- gradient norm, clip coefficient, in-place scale
+// The 2-norm accumulates exact squares (the product of two fp32 numbers is exact in fp64) in fp64; the inf-norm keeps a NaN
+// once it has met one, as torch.max does (fmaxf would drop it).
+struct SumSq {
+    static __device__ __forceinline__ double zero() { return 0.0; }
+    static __device__ __forceinline__ double take(double a, float g) { return a + (double)g * (double)g; }
+    static __device__ __forceinline__ double join(double a, double b) { return a + b; }
+};
+struct MaxAbs {
+    static __device__ __forceinline__ double zero() { return 0.0; }
+    static __device__ __forceinline__ double join(double a, double b) { return (b > a || b != b) ? b : a; }
+    static __device__ __forceinline__ double take(double a, float g) { return join(a, (double)fabsf(g)); }
+};
+
+// Every lane's value joined over the 256 lanes of the block, in a fixed order; valid in thread 0.  red: 4 doubles of LDS.
+template <class Op>
+__device__ __forceinline__ double grad_block_join(double v, double* red) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v = Op::join(v, __shfl_xor(v, o, 64));
+    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
+    __syncthreads();
+    return Op::join(Op::join(red[0], red[1]), Op::join(red[2], red[3]));
+}
+
+template <class Op>
+__global__ __launch_bounds__(256) void grad_norm_kernel(const OptimTable t, double* __restrict__ partials) {
+    __shared__ double red[4];
+    const OptimEntry e = t.e[optim_find(t)];
+    const unsigned beg = (blockIdx.x - e.first_block) * OCHUNK;
+    const unsigned end = e.n - beg < (unsigned)OCHUNK ? e.n : beg + OCHUNK;
+    double acc = Op::zero();
+    unsigned vend = beg;
+    if (((uintptr_t)e.g & 15) == 0) {
+        vend = beg + ((end - beg) & ~3u);
+        for (unsigned i = beg + threadIdx.x * 4; i < vend; i += 256 * 4) {
+            float g[4];
+            optim_ld<true>(e.g, i, g);
+#pragma unroll
+            for (int k = 0; k < 4; ++k) acc = Op::take(acc, g[k]);
+        }
+    }
+    for (unsigned i = vend + threadIdx.x; i < end; i += 256) acc = Op::take(acc, e.g[i]);
+    acc = grad_block_join<Op>(acc, red);
+    if (threadIdx.x == 0) partials[blockIdx.x] = acc;
+}
+
+// out[0] = the norm, out[1] = min(1, max_norm / (norm + 1e-6)) evaluated in fp32 as torch.nn.utils.clip_grad_norm_ does, a NaN
+// kept (c > 1 is false for it; fminf would drop it).
+template <class Op, bool ROOT>
+__global__ __launch_bounds__(256) void grad_norm_finish(const double* __restrict__ partials, long long n, float max_norm,
+                                                        float* __restrict__ out) {
+    __shared__ double red[4];
+    double acc = Op::zero();
+    for (long long i = threadIdx.x; i < n; i += 256) acc = Op::join(acc, partials[i]);
+    acc = grad_block_join<Op>(acc, red);
+    if (threadIdx.x == 0) {
+        const float norm = (float)(ROOT ? sqrt(acc) : acc);
+        float c = __fdiv_rn(max_norm, __fadd_rn(norm, 1e-6f));
+        c = c > 1.f ? 1.f : c;
+        out[0] = norm;
+        out[1] = c;
+    }
+}
+
+template <bool VEC>
+__device__ __forceinline__ void grad_scale_span(float* g, float c, unsigned beg, unsigned end) {
+    constexpr unsigned W = VEC ? 4 : 1;
+    for (unsigned i = beg + threadIdx.x * W; i < end; i += 256 * W) {
+        float x[W];
+        optim_ld<VEC>(g, i, x);
+#pragma unroll
+        for (unsigned k = 0; k < W; ++k) x[k] = __fmul_rn(x[k], c);
+        optim_st<VEC>(g, i, x);
+    }
+}
+
+__global__ __launch_bounds__(256) void grad_scale_kernel(const OptimTable t, const float* __restrict__ gscale) {
+    const OptimEntry e = t.e[optim_find(t)];
+    const float c = gscale[0];
+    float* g = const_cast<float*>(e.g);
+    const unsigned beg = (blockIdx.x - e.first_block) * OCHUNK;
+    const unsigned end = e.n - beg < (unsigned)OCHUNK ? e.n : beg + OCHUNK;
+    unsigned vend = beg;
+    if (((uintptr_t)g & 15) == 0) {
+        vend = beg + ((end - beg) & ~3u);
+        grad_scale_span<true>(g, c, beg, vend);
+    }
+    grad_scale_span<false>(g, c, vend, end);
 }
 
 // Validates the caller's table and lays it out for the kernel; returns the number of blocks through *blocks.
@@ -176,19 +285,32 @@ static int optim_pack(const dram_optim_tensor* table, int count, bool need_m, bo
     return DRAM_OK;
 }
 
-}  // namespace dram
+// The same for the gradient-only kernels: g and n alone are read, every other field may be anything.
+static int grad_pack(const dram_optim_tensor* table, int count, const char* who, OptimTable& t, unsigned* blocks) {
+    DRAM_REQUIRE(table, "%s: null table", who);
+    DRAM_REQUIRE(count >= 1 && count <= DRAM_OPTIM_TABLE_CAPACITY, "%s: %d tensors in one table (1..%d)", who, count,
+                 DRAM_OPTIM_TABLE_CAPACITY);
+    uint64_t nb = 0;
+    for (int i = 0; i < DRAM_OPTIM_TABLE_CAPACITY; ++i) t.e[i] = OptimEntry{};
+    for (int i = 0; i < count; ++i) {
+        const dram_optim_tensor& s = table[i];
+        DRAM_REQUIRE(s.g, "%s: tensor %d: null gradient pointer", who, i);
+        DRAM_REQUIRE(s.n >= 1 && s.n < ((int64_t)1 << 31), "%s: tensor %d: element count %lld outside 1 .. 2^31 - 1", who, i,
+                     (long long)s.n);
+        DRAM_REQUIRE(((uintptr_t)s.g & 3) == 0, "%s: tensor %d: gradient pointer not 4-byte aligned", who, i);
+        t.e[i].g = s.g;
+        t.e[i].n = (unsigned)s.n;
+        t.e[i].first_block = (unsigned)nb;
+        nb += (uint64_t)cdiv64(s.n, OCHUNK);
+    }
+    DRAM_REQUIRE(nb < ((uint64_t)1 << 31), "%s: table needs %llu blocks (limit 2^31 - 1)", who, (unsigned long long)nb);
+    t.count = count;
+    *blocks = (unsigned)nb;
+    return DRAM_OK;
+}
 
-using namespace dram;
-
-extern "C" int dram_optim_table_capacity(void) { return DRAM_OPTIM_TABLE_CAPACITY; }
-
-extern "C" int dram_optim_adam(const dram_optim_tensor* table, int count, double lr, double beta1, double beta2, double eps,
-                               double weight_decay, int decoupled, int amsgrad, int maximize, void* stream) {
-    OptimTable t;
-    unsigned blocks = 0;
-    const int rc = optim_pack(table, count, true, true, amsgrad != 0, "optim_adam", t, &blocks);
-    if (rc != DRAM_OK) return rc;
-    AdamScalars s;
+static void adam_scalars(AdamScalars& s, double lr, double beta1, double beta2, double eps, double weight_decay, int decoupled,
+                         int amsgrad, int maximize) {
     s.beta1 = (float)beta1; s.omb1 = (float)(1.0 - beta1);
     s.beta2 = (float)beta2; s.omb2 = (float)(1.0 - beta2);
     s.eps = (float)eps;
@@ -197,16 +319,41 @@ extern "C" int dram_optim_adam(const dram_optim_tensor* table, int count, double
     s.decoupled = decoupled != 0 && weight_decay != 0.0;
     s.amsgrad = amsgrad != 0;
     s.maximize = maximize != 0;
-    hipLaunchKernelGGL((optim_kernel<AdamRule, AdamScalars>), dim3(blocks), dim3(256), 0, (hipStream_t)stream, t, s);
+}
+
+}  // namespace dram
+
+using namespace dram;
+
+extern "C" int dram_optim_table_capacity(void) { return DRAM_OPTIM_TABLE_CAPACITY; }
+
+extern "C" int dram_optim_adam_scaled(const dram_optim_tensor* table, int count, double lr, double beta1, double beta2,
+                                      double eps, double weight_decay, int decoupled, int amsgrad, int maximize,
+                                      const float* gscale, void* stream) {
+    OptimTable t;
+    unsigned blocks = 0;
+    const int rc = optim_pack(table, count, true, true, amsgrad != 0, "optim_adam", t, &blocks);
+    if (rc != DRAM_OK) return rc;
+    DRAM_REQUIRE(((uintptr_t)gscale & 3) == 0, "optim_adam: gscale not 4-byte aligned");
+    AdamScalars s;
+    adam_scalars(s, lr, beta1, beta2, eps, weight_decay, decoupled, amsgrad, maximize);
+    hipLaunchKernelGGL((optim_kernel<AdamRule, AdamScalars>), dim3(blocks), dim3(256), 0, (hipStream_t)stream, t, s, gscale);
     return check_launch("optim_adam");
 }
 
-extern "C" int dram_optim_sgd(const dram_optim_tensor* table, int count, double lr, double momentum, double dampening,
-                              double weight_decay, int nesterov, int maximize, void* stream) {
+extern "C" int dram_optim_adam(const dram_optim_tensor* table, int count, double lr, double beta1, double beta2, double eps,
+                               double weight_decay, int decoupled, int amsgrad, int maximize, void* stream) {
+    return dram_optim_adam_scaled(table, count, lr, beta1, beta2, eps, weight_decay, decoupled, amsgrad, maximize, nullptr,
+                                  stream);
+}
+
+extern "C" int dram_optim_sgd_scaled(const dram_optim_tensor* table, int count, double lr, double momentum, double dampening,
+                                     double weight_decay, int nesterov, int maximize, const float* gscale, void* stream) {
     OptimTable t;
     unsigned blocks = 0;
     const int rc = optim_pack(table, count, momentum != 0.0, false, false, "optim_sgd", t, &blocks);
     if (rc != DRAM_OK) return rc;
+    DRAM_REQUIRE(((uintptr_t)gscale & 3) == 0, "optim_sgd: gscale not 4-byte aligned");
     if (momentum == 0.0)
         for (int i = 0; i < count; ++i) t.e[i].m = nullptr;
     SgdScalars s;
@@ -216,6 +363,70 @@ extern "C" int dram_optim_sgd(const dram_optim_tensor* table, int count, double 
     s.wd = (float)weight_decay;
     s.nesterov = nesterov != 0;
     s.maximize = maximize != 0;
-    hipLaunchKernelGGL((optim_kernel<SgdRule, SgdScalars>), dim3(blocks), dim3(256), 0, (hipStream_t)stream, t, s);
+    hipLaunchKernelGGL((optim_kernel<SgdRule, SgdScalars>), dim3(blocks), dim3(256), 0, (hipStream_t)stream, t, s, gscale);
     return check_launch("optim_sgd");
+}
+
+extern "C" int dram_optim_sgd(const dram_optim_tensor* table, int count, double lr, double momentum, double dampening,
+                              double weight_decay, int nesterov, int maximize, void* stream) {
+    return dram_optim_sgd_scaled(table, count, lr, momentum, dampening, weight_decay, nesterov, maximize, nullptr, stream);
+}
+
+extern "C" size_t dram_optim_grad_norm_partials(const dram_optim_tensor* table, int count) {
+    OptimTable t;
+    unsigned blocks = 0;
+    return grad_pack(table, count, "optim_grad_norm_partials", t, &blocks) == DRAM_OK ? (size_t)blocks : 0;
+}
+
+static int norm_kind_ok(int kind, const char* who) {
+    DRAM_REQUIRE(kind == DRAM_OPTIM_NORM_2 || kind == DRAM_OPTIM_NORM_INF, "%s: norm kind %d (2: 2-norm, %d: inf-norm)", who, kind,
+                 DRAM_OPTIM_NORM_INF);
+    return DRAM_OK;
+}
+
+extern "C" int dram_optim_grad_norm(const dram_optim_tensor* table, int count, int kind, double* partials,
+                                    int64_t partial_offset, void* stream) {
+    OptimTable t;
+    unsigned blocks = 0;
+    int rc = grad_pack(table, count, "optim_grad_norm", t, &blocks);
+    if (rc != DRAM_OK) return rc;
+    if ((rc = norm_kind_ok(kind, "optim_grad_norm")) != DRAM_OK) return rc;
+    DRAM_REQUIRE(partials, "optim_grad_norm: null partials buffer");
+    DRAM_REQUIRE(((uintptr_t)partials & 7) == 0, "optim_grad_norm: partials buffer not 8-byte aligned");
+    DRAM_REQUIRE(partial_offset >= 0, "optim_grad_norm: negative partial_offset %lld", (long long)partial_offset);
+    double* dst = partials + partial_offset;
+    if (kind == DRAM_OPTIM_NORM_2)
+        hipLaunchKernelGGL((grad_norm_kernel<SumSq>), dim3(blocks), dim3(256), 0, (hipStream_t)stream, t, dst);
+    else
+        hipLaunchKernelGGL((grad_norm_kernel<MaxAbs>), dim3(blocks), dim3(256), 0, (hipStream_t)stream, t, dst);
+    return check_launch("optim_grad_norm");
+}
+
+extern "C" int dram_optim_grad_norm_finish(const double* partials, int64_t n_partials, int kind, double max_norm, float* out,
+                                           void* stream) {
+    const int rc = norm_kind_ok(kind, "optim_grad_norm_finish");
+    if (rc != DRAM_OK) return rc;
+    DRAM_REQUIRE(partials, "optim_grad_norm_finish: null partials buffer");
+    DRAM_REQUIRE(((uintptr_t)partials & 7) == 0, "optim_grad_norm_finish: partials buffer not 8-byte aligned");
+    DRAM_REQUIRE(n_partials >= 1, "optim_grad_norm_finish: %lld partials (>= 1)", (long long)n_partials);
+    DRAM_REQUIRE(out, "optim_grad_norm_finish: null out");
+    DRAM_REQUIRE(((uintptr_t)out & 3) == 0, "optim_grad_norm_finish: out not 4-byte aligned");
+    const long long n = n_partials;
+    const float mx = (float)max_norm;
+    if (kind == DRAM_OPTIM_NORM_2)
+        hipLaunchKernelGGL((grad_norm_finish<SumSq, true>), dim3(1), dim3(256), 0, (hipStream_t)stream, partials, n, mx, out);
+    else
+        hipLaunchKernelGGL((grad_norm_finish<MaxAbs, false>), dim3(1), dim3(256), 0, (hipStream_t)stream, partials, n, mx, out);
+    return check_launch("optim_grad_norm_finish");
+}
+
+extern "C" int dram_optim_grad_scale(const dram_optim_tensor* table, int count, const float* gscale, void* stream) {
+    OptimTable t;
+    unsigned blocks = 0;
+    const int rc = grad_pack(table, count, "optim_grad_scale", t, &blocks);
+    if (rc != DRAM_OK) return rc;
+    DRAM_REQUIRE(gscale, "optim_grad_scale: null gscale");
+    DRAM_REQUIRE(((uintptr_t)gscale & 3) == 0, "optim_grad_scale: gscale not 4-byte aligned");
+    hipLaunchKernelGGL(grad_scale_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream, t, gscale);
+    return check_launch("optim_grad_scale");
 }

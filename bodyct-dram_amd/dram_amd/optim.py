@@ -14,6 +14,12 @@ corrections -- the gradient pointers change every step under `zero_grad(set_to_n
 with the device and reads no device value; the table travels in the kernel arguments, so there is no buffer to copy or keep
 alive.  (A captured graph would replay one step's pointers and bias corrections: graph-captured steps are not supported.)
 Like every op of this package there is no fallback: parameters and gradients must be dense fp32 on a ROCm device.
+
+Global-norm gradient clipping runs on the same tables.  `clip_grad_norm_` is torch.nn.utils.clip_grad_norm_ (2-norm and
+inf-norm) as a norm launch per table, one finishing block and an in-place scale per table.  `set_grad_clip` on an optimiser
+folds the clipping into `step()`: the norm over the gradients of all groups, the finishing block, and the update kernels
+multiply the coefficient -- a device scalar -- into every gradient element as they read it, so the gradients are neither
+read nor written a second time.  Neither reads a device value on the host.
 """
 import math
 import struct
@@ -22,7 +28,7 @@ import torch
 
 from ._lib import call, lib
 
-__all__ = ["Adam", "AdamW", "SGD", "TABLE_CAPACITY"]
+__all__ = ["Adam", "AdamW", "SGD", "TABLE_CAPACITY", "clip_grad_norm_"]
 
 TABLE_CAPACITY = int(lib.dram_optim_table_capacity())   # tensors per launch (the table is a kernel argument)
 
@@ -77,9 +83,10 @@ def _host_step(state, name):
     return s
 
 
-def _launch(entry, rows, *scalars):
+def _launch(entry, rows, *scalars, gscale=None):
     """rows: (device, p, g, m, v, vmax, s0, s1) with tensors or None; one launch per device and TABLE_CAPACITY rows.
-    The rows' tensors stay referenced by the caller's lists until the launches are issued."""
+    The rows' tensors stay referenced by the caller's lists until the launches are issued.  gscale: None, or the one-element
+    device tensor every gradient is multiplied by as it is read (the `_scaled` entry points)."""
     by_dev = {}
     for r in rows:
         if r[1].numel() > 0:
@@ -94,10 +101,129 @@ def _launch(entry, rows, *scalars):
                     _ENTRY.pack_into(buf, i * _ENTRY.size, p.data_ptr(), g.data_ptr(), 0 if m is None else m.data_ptr(),
                                      0 if v is None else v.data_ptr(), 0 if vmax is None else vmax.data_ptr(), p.numel(),
                                      s0, s1)
-                call(entry, bytes(buf), len(part), *scalars, stream)
+                if gscale is None:
+                    call(entry, bytes(buf), len(part), *scalars, stream)
+                else:
+                    call(entry + "_scaled", bytes(buf), len(part), *scalars, gscale.data_ptr(), stream)
 
 
-class _AdamStep:
+_NORM_KINDS = {2.0: 2, math.inf: 0}                     # DRAM_OPTIM_NORM_2, DRAM_OPTIM_NORM_INF of include/dram_hip.h
+
+
+def _norm_kind(norm_type):
+    kind = _NORM_KINDS.get(float(norm_type))
+    if kind is None:
+        raise NotImplementedError(f"dram_amd.optim: norm_type={norm_type!r}; the device gradient norm supports 2.0 and inf")
+    return kind
+
+
+def _grad_tables(grads):
+    """The host tables (bytes, tensor count) over `grads`, TABLE_CAPACITY tensors each: only g and n are filled in."""
+    tables = []
+    for lo in range(0, len(grads), TABLE_CAPACITY):
+        part = grads[lo:lo + TABLE_CAPACITY]
+        buf = bytearray(_ENTRY.size * len(part))
+        for i, g in enumerate(part):
+            _ENTRY.pack_into(buf, i * _ENTRY.size, 0, g.data_ptr(), 0, 0, 0, g.numel(), 0.0, 0.0)
+        tables.append((bytes(buf), len(part)))
+    return tables
+
+
+def _one_device(grads, name):
+    devs = {g.device for g in grads}
+    if len(devs) > 1:
+        raise NotImplementedError(f"{name}: gradients on {len(devs)} devices ({', '.join(sorted(map(str, devs)))}); the global "
+                                  f"norm is computed on one device")
+    return next(iter(devs))
+
+
+def _grad_norm(grads, tables, kind, max_norm):
+    """The norm launches and the finish over non-empty contiguous fp32 gradients on one device (the current stream); returns
+    the device tensor [total_norm, clip_coef]."""
+    dev = grads[0].device
+    with torch.cuda.device(dev):
+        stream = torch.cuda.current_stream().cuda_stream
+        counts = [int(lib.dram_optim_grad_norm_partials(buf, n)) for buf, n in tables]
+        partials = torch.empty(sum(counts), dtype=torch.float64, device=dev)
+        out = torch.empty(2, dtype=torch.float32, device=dev)
+        off = 0
+        for (buf, n), c in zip(tables, counts):
+            call("dram_optim_grad_norm", buf, n, kind, partials.data_ptr(), off, stream)
+            off += c
+        call("dram_optim_grad_norm_finish", partials.data_ptr(), off, kind, float(max_norm), out.data_ptr(), stream)
+    return out
+
+
+@torch.no_grad()
+def clip_grad_norm_(parameters, max_norm, norm_type=2.0, error_if_nonfinite=False, foreach=None):
+    """torch.nn.utils.clip_grad_norm_ on csrc/optim.hip: the gradients of `parameters` are scaled in place by
+    min(1, max_norm / (total_norm + 1e-6)) and the norm before clipping comes back as a 0-dim fp32 device tensor.  norm_type
+    2.0 or inf.  Nothing is read back to the host unless error_if_nonfinite, which reads the norm and raises torch's
+    RuntimeError before any gradient is scaled.  `foreach` is accepted and ignored.  Parameters without a gradient and empty
+    tensors are skipped; without any gradient the result is a zero tensor."""
+    name = "dram_amd.optim.clip_grad_norm_"
+    kind = _norm_kind(norm_type)
+    max_norm = float(max_norm)
+    if isinstance(parameters, torch.Tensor):
+        parameters = [parameters]
+    pairs = [(p, _chk_param(p, name)) for p in parameters if p.grad is not None]
+    pairs = [(p, g) for p, g in pairs if g.numel() > 0]
+    if not pairs:
+        return torch.tensor(0.0)
+    grads = [g for _, g in pairs]
+    dev = _one_device(grads, name)
+    tables = _grad_tables(grads)
+    out = _grad_norm(grads, tables, kind, max_norm)
+    if error_if_nonfinite and not math.isfinite(float(out[0])):
+        raise RuntimeError(f"The total norm of order {float(norm_type)} for gradients from `parameters` is non-finite, so it "
+                           f"cannot be clipped. To disable this error and scale the gradients by the non-finite norm anyway, "
+                           f"set `error_if_nonfinite=False`")
+    with torch.cuda.device(dev):
+        stream = torch.cuda.current_stream().cuda_stream
+        for buf, n in tables:
+            call("dram_optim_grad_scale", buf, n, out.data_ptr() + 4, stream)
+    for p, g in pairs:
+        if g.data_ptr() != p.grad.data_ptr():          # _chk_param made a contiguous copy: the scaled values go back
+            p.grad.copy_(g)
+    return out[0]
+
+
+class _GradClip:
+    """set_grad_clip() of the optimisers below: global-norm clipping inside step()."""
+
+    _clip = None                                       # (max_norm, norm kind) or None; not part of state_dict()
+    last_grad_norm = None                              # 0-dim device tensor: the norm before clipping at the last clipped step
+    last_clip_coef = None                              # ... and the coefficient that step multiplied into the gradients
+
+    def set_grad_clip(self, max_norm, norm_type=2.0):
+        """Clip the global gradient norm (over all parameter groups together, what clip_grad_norm_(model.parameters(),
+        max_norm, norm_type) sees) inside every later step(); None turns it off, which is the default.  The clipped step
+        computes what clip_grad_norm_ followed by step() computes, bit for bit, with ONE difference: `.grad` is left
+        unscaled (the coefficient is multiplied into each gradient element as the update kernel reads it).  The norm before
+        clipping is `last_grad_norm` after the step and the coefficient `last_clip_coef`, both 0-dim device tensors that
+        nothing reads on the host.  An attribute of this object, not a param_groups key and not in
+        state_dict(): checkpoints stay torch's."""
+        self._clip = None if max_norm is None else (float(max_norm), _norm_kind(norm_type))
+
+    def _clip_pairs(self, name):
+        """Clipping off: (None, None).  On: every group's (parameter, gradient) pairs, all checked, and the one-element
+        device tensor of the clip coefficient (None without any gradient)."""
+        if self._clip is None:
+            return None, None
+        for group in self.param_groups:
+            _no_tensor_lr(group["lr"])
+        pairs = [_with_grad(group, name) for group in self.param_groups]
+        grads = [g for ps in pairs for _, g in ps if g.numel() > 0]
+        if not grads:
+            self.last_grad_norm, self.last_clip_coef = torch.tensor(0.0), torch.tensor(1.0)
+            return pairs, None
+        _one_device(grads, name)
+        out = _grad_norm(grads, _grad_tables(grads), self._clip[1], self._clip[0])
+        self.last_grad_norm, self.last_clip_coef = out[0], out[1]
+        return pairs, out[1:]
+
+
+class _AdamStep(_GradClip):
     """step() of Adam and AdamW (torch.optim.AdamW is torch.optim.Adam with decoupled_weight_decay=True)."""
 
     def __setstate__(self, state):
@@ -116,13 +242,14 @@ class _AdamStep:
             with torch.enable_grad():
                 loss = closure()
         name = f"dram_amd.optim.{type(self).__name__}"
-        for group in self.param_groups:
+        pairs, gscale = self._clip_pairs(name)
+        for gi, group in enumerate(self.param_groups):
             lr = group["lr"]
             _no_tensor_lr(lr)
             beta1, beta2 = (float(b) for b in group["betas"])
             amsgrad = bool(group["amsgrad"])
             rows = []
-            for p, g in _with_grad(group, name):
+            for p, g in (_with_grad(group, name) if pairs is None else pairs[gi]):
                 state = self.state[p]
                 if len(state) == 0:
                     state["step"] = torch.tensor(0.0, dtype=torch.float32)
@@ -137,7 +264,7 @@ class _AdamStep:
                              _chk_state(state["max_exp_avg_sq"], p, name) if amsgrad else None,
                              float(lr) / (1.0 - beta1 ** t), math.sqrt(1.0 - beta2 ** t)))
             _launch("dram_optim_adam", rows, float(lr), beta1, beta2, float(group["eps"]), float(group["weight_decay"]),
-                    int(bool(group["decoupled_weight_decay"])), int(amsgrad), int(bool(group["maximize"])))
+                    int(bool(group["decoupled_weight_decay"])), int(amsgrad), int(bool(group["maximize"])), gscale=gscale)
         return loss
 
 
@@ -159,7 +286,7 @@ class AdamW(_AdamStep, torch.optim.AdamW):
         super().__init__(params, lr, betas, eps, weight_decay, amsgrad, maximize=maximize)
 
 
-class SGD(torch.optim.SGD):
+class SGD(_GradClip, torch.optim.SGD):
     """torch.optim.SGD (arguments, validation, state and state dict) with the update on csrc/optim.hip."""
 
     def __init__(self, params, lr=1e-3, momentum=0, dampening=0, weight_decay=0, nesterov=False, *, maximize=False):
@@ -180,12 +307,13 @@ class SGD(torch.optim.SGD):
             with torch.enable_grad():
                 loss = closure()
         name = "dram_amd.optim.SGD"
-        for group in self.param_groups:
+        pairs, gscale = self._clip_pairs(name)
+        for gi, group in enumerate(self.param_groups):
             lr = group["lr"]
             _no_tensor_lr(lr)
             momentum = float(group["momentum"])
             rows = []
-            for p, g in _with_grad(group, name):
+            for p, g in (_with_grad(group, name) if pairs is None else pairs[gi]):
                 buf, first = None, 0.0
                 if momentum != 0:
                     state = self.state[p]
@@ -196,5 +324,5 @@ class SGD(torch.optim.SGD):
                     _chk_state(buf, p, name)
                 rows.append((p.device, p, g, buf, None, None, first, 0.0))
             _launch("dram_optim_sgd", rows, float(lr), momentum, float(group["dampening"]), float(group["weight_decay"]),
-                    int(bool(group["nesterov"])), int(bool(group["maximize"])))
+                    int(bool(group["nesterov"])), int(bool(group["maximize"])), gscale=gscale)
         return loss

@@ -168,10 +168,25 @@ class DataParallelTrainer:
     into its bucket after the step (no per-step torch.cat, no copy back).
 
     `optimizer` is any torch.optim.Optimizer over the model's parameters; dram_amd.optim.Adam / AdamW / SGD (one HIP launch
-    per parameter group, bucket views at any offset included) go in unchanged."""
+    per parameter group, bucket views at any offset included) go in unchanged.
 
-    def __init__(self, model, optimizer, loss_fn=None, loss_factors=(2.0, 1.0), bucket_mb=32, overlap=True):
+    `max_grad_norm` (default None: no clipping, the step as it always was) clips the global gradient norm of kind
+    `grad_norm_type` (2.0 or inf) on the device: the norm is that of the SUMMED gradient, after the all-reduce, i.e. of the
+    global batch whatever the rank count.  An optimiser with `set_grad_clip` (dram_amd.optim's) takes it into its own step();
+    any other one gets dram_amd.optim.clip_grad_norm_ between the all-reduce and its step().  `last_grad_norm` is the 0-dim
+    device tensor of the norm before clipping after every step."""
+
+    def __init__(self, model, optimizer, loss_fn=None, loss_factors=(2.0, 1.0), bucket_mb=32, overlap=True, max_grad_norm=None,
+                 grad_norm_type=2.0):
         self.model, self.opt = model, optimizer
+        self.max_grad_norm, self.grad_norm_type = max_grad_norm, grad_norm_type
+        self.last_grad_norm = None
+        self._clip_in_opt = max_grad_norm is not None and hasattr(optimizer, "set_grad_clip")
+        if self._clip_in_opt:
+            optimizer.set_grad_clip(max_grad_norm, grad_norm_type)
+        elif max_grad_norm is not None:
+            from .optim import _norm_kind
+            _norm_kind(grad_norm_type)             # refuse an unsupported norm here, not at the first step
         self.overlap = bool(overlap)               # False: every bucket is reduced after the last backward (A/B, diagnostics)
         self.loss_fn = loss_fn or DeviceIntRegRefineLoss()
         self.loss_factors = loss_factors           # LOSS_FACTORS[:2] of st_dram_ref.py:42
@@ -302,7 +317,15 @@ class DataParallelTrainer:
             tot_reg = reg.detach() if tot_reg is None else tot_reg + reg.detach()
             tot_seg = seg.detach() * share if tot_seg is None else tot_seg + seg.detach() * share
         self.allreduce_gradients()
-        self.opt.step()
+        if self.max_grad_norm is None:
+            self.opt.step()
+        elif self._clip_in_opt:
+            self.opt.step()
+            self.last_grad_norm = self.opt.last_grad_norm
+        else:
+            from .optim import clip_grad_norm_
+            self.last_grad_norm = clip_grad_norm_(self.params, self.max_grad_norm, self.grad_norm_type)
+            self.opt.step()
         return tot_reg, tot_seg
 
 

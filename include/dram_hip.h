@@ -734,6 +734,37 @@ int dram_optim_adam(const dram_optim_tensor* table, int count, double lr, double
 int dram_optim_sgd(const dram_optim_tensor* table, int count, double lr, double momentum, double dampening,
                    double weight_decay, int nesterov, int maximize, void* stream);
 
+/* ---- global-norm gradient clipping (torch.nn.utils.clip_grad_norm_) over the same tables: of every entry only g and n are
+ *      read (1 <= n < 2^31, g 4-byte aligned at any offset: 16-byte accesses where g is 16-byte aligned, one element per lane
+ *      otherwise); p, m, v, vmax, s0, s1 may be anything.  A tensor of n elements takes cdiv(n, 4096) consecutive blocks.
+ * dram_optim_grad_norm_partials: the number of partials (= blocks) a table needs; 0 and dram_last_error() for a table that
+ *   dram_optim_grad_norm would refuse.  Answers without a GPU.
+ * dram_optim_grad_norm: block b of the table writes partials[partial_offset + b] (device doubles): kind DRAM_OPTIM_NORM_2 the
+ *   sum of its elements' squares, every square exact and the sum in fp64 (within n 2^-53 relative of the exact sum: 1e20 does
+ *   not overflow, 1e-30 does not vanish); kind DRAM_OPTIM_NORM_INF the maximum of |g|, NaN if any element is.  Every partial is
+ *   written by exactly one block, in a fixed order of additions: no atomics, the same bits every run.  A second table of the
+ *   same gradient set continues at partial_offset = the partials of the tables before it.
+ * dram_optim_grad_norm_finish: one block over partials[0 .. n_partials) in a fixed order; out (device, 2 floats):
+ *     out[0] = total_norm = kind 2: (float)sqrt(sum), kind inf: max;
+ *     out[1] = clip_coef  = c > 1 ? 1 : c  with c = (float)max_norm / (total_norm + 1e-6f), every operation in fp32;
+ *   a NaN norm gives a NaN coefficient and an infinite norm the coefficient 0, as torch.clamp(max=1) leaves them.
+ * dram_optim_adam_scaled / dram_optim_sgd_scaled: dram_optim_adam / dram_optim_sgd with every gradient element replaced by the
+ *   fp32 product g * gscale[0] before anything else (maximize, weight decay, ...); gscale is a DEVICE pointer (out + 1 above),
+ *   read once per block; the gradient buffer is not written.  gscale == NULL: bit for bit the unscaled entry.
+ * dram_optim_grad_scale: g[i] = g[i] * gscale[0] in place (the table's g is written despite its const).
+ * None of them synchronises, allocates or reads device memory from the host. ---- */
+#define DRAM_OPTIM_NORM_2 2
+#define DRAM_OPTIM_NORM_INF 0
+size_t dram_optim_grad_norm_partials(const dram_optim_tensor* table, int count);
+int dram_optim_grad_norm(const dram_optim_tensor* table, int count, int kind, double* partials, int64_t partial_offset,
+                         void* stream);
+int dram_optim_grad_norm_finish(const double* partials, int64_t n_partials, int kind, double max_norm, float* out, void* stream);
+int dram_optim_adam_scaled(const dram_optim_tensor* table, int count, double lr, double beta1, double beta2, double eps,
+                           double weight_decay, int decoupled, int amsgrad, int maximize, const float* gscale, void* stream);
+int dram_optim_sgd_scaled(const dram_optim_tensor* table, int count, double lr, double momentum, double dampening,
+                          double weight_decay, int nesterov, int maximize, const float* gscale, void* stream);
+int dram_optim_grad_scale(const dram_optim_tensor* table, int count, const float* gscale, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

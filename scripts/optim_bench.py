@@ -7,6 +7,10 @@ layouts: gradients as separate tensors, and gradients as views into 32 MB flat b
 DataParallelTrainer leaves them.  step() is timed by HIP events on the launch stream: one warm-up, median, minimum and maximum
 of --reps.  Beside it: torch.optim.Adam with its defaults, torch.optim.Adam(fused=True) where the installed torch has it, and
 the time 28 bytes per element (16 read, 12 written) take at the copy rate dram_calibrate_hbm_copy reaches in the same process.
+Global-norm clipping (max_norm 1.0, the 2-norm; the random gradients have norm ~ 40, so every step clips) is timed the same way
+beside them: the clipped fused step (set_grad_clip), dram_amd.optim.clip_grad_norm_ followed by the plain step, and
+torch.nn.utils.clip_grad_norm_ followed by torch.optim.Adam.step().  Clipping in place shrinks the gradients from repetition
+to repetition; none of the kernels' work depends on their values.
 Prints one JSON line.
 """
 import argparse
@@ -85,8 +89,25 @@ def main():
                 off += k
         return out
 
+    def fused_clip(ps):
+        opt = optim.Adam(ps, lr=1e-4)
+        opt.set_grad_clip(1.0)
+        return opt
+
+    class ClipThenStep:
+        def __init__(self, clip, opt, ps):
+            self.clip, self.opt, self.ps = clip, opt, ps
+
+        def step(self):
+            self.clip(self.ps, 1.0)
+            self.opt.step()
+
     makers = {"dram_amd.optim.Adam": lambda ps: optim.Adam(ps, lr=1e-4),
-              "torch.optim.Adam": lambda ps: torch.optim.Adam(ps, lr=1e-4)}
+              "torch.optim.Adam": lambda ps: torch.optim.Adam(ps, lr=1e-4),
+              "dram_amd.optim.Adam + set_grad_clip": fused_clip,
+              "dram_amd clip_grad_norm_ + Adam": lambda ps: ClipThenStep(optim.clip_grad_norm_, optim.Adam(ps, lr=1e-4), ps),
+              "torch clip_grad_norm_ + Adam": lambda ps: ClipThenStep(torch.nn.utils.clip_grad_norm_,
+                                                                      torch.optim.Adam(ps, lr=1e-4), ps)}
     try:
         torch.optim.Adam([torch.zeros(1, device=dev, requires_grad=True)], fused=True)
         makers["torch.optim.Adam(fused=True)"] = lambda ps: torch.optim.Adam(ps, lr=1e-4, fused=True)
@@ -94,9 +115,10 @@ def main():
         result["torch_fused_unavailable"] = str(e)
 
     for layout in ("separate", "buckets_32mb"):
-        gs = grads(layout)
-        rec = {"gradients_16_byte_aligned": sum(g.data_ptr() % 16 == 0 for g in gs)}
+        rec = {}
         for name, make in makers.items():
+            gs = grads(layout)                           # fresh ones: the clipping lines scale them in place
+            rec["gradients_16_byte_aligned"] = sum(g.data_ptr() % 16 == 0 for g in gs)
             ps = [torch.randn(s, device=dev).mul_(0.1).requires_grad_() for s in shapes]
             for p, g in zip(ps, gs):
                 p.grad = g
@@ -104,11 +126,19 @@ def main():
             r = timed(opt.step)
             r["fraction_of_copy_rate"] = ideal_ms / r["ms_median"]
             rec[name] = r
-            del opt, ps
+            del opt, ps, gs
         ours, ref = rec["dram_amd.optim.Adam"], rec["torch.optim.Adam"]
         rec["ours_over_torch_default"] = ours["ms_median"] / ref["ms_median"]
         rec["no_slower_than_torch_default_within_spread"] = ours["ms_median"] <= ref["ms_median"] + max(
             ours["ms_max"] - ours["ms_min"], ref["ms_max"] - ref["ms_min"])
+        clip, two, tclip = (rec[k] for k in ("dram_amd.optim.Adam + set_grad_clip", "dram_amd clip_grad_norm_ + Adam",
+                                             "torch clip_grad_norm_ + Adam"))
+        rec["clipped_over_unclipped"] = clip["ms_median"] / ours["ms_median"]
+        rec["clipped_minus_unclipped_ms"] = clip["ms_median"] - ours["ms_median"]
+        rec["clipped_over_clip_then_step"] = clip["ms_median"] / two["ms_median"]
+        rec["clipped_over_torch_clip_then_step"] = clip["ms_median"] / tclip["ms_median"]
+        rec["clipped_no_slower_than_torch_clip_then_step_within_spread"] = clip["ms_median"] <= tclip["ms_median"] + max(
+            clip["ms_max"] - clip["ms_min"], tclip["ms_max"] - tclip["ms_min"])
         result["layouts"][layout] = rec
     line = json.dumps(result)
     print(line, flush=True)
