@@ -1,5 +1,6 @@
 // IntRegRefineLoss on the device, fused, gfx950; further down the pieces of the
-// affine-consistency losses and IntRegLoss (the hinge with an entropy term instead of the pseudo-label term).
+// affine-consistency losses, IntRegLoss (the hinge with an entropy term instead of the pseudo-label term), and the two
+// voxel-wise segmentation losses on a target that is given (BootBinCrossEntropy, BinaryCrossEntropySmooth).
 //
 // Replaces the ~30 element-wise / reduction ATen dispatches -- and the per-sample host round trips --
 // of the reference's training loss, dram/metrics.py: IntRegLoss.compute_reg_loss_with_probs (158-177),
@@ -423,6 +424,319 @@ static inline bool enc_vec4(const void* a, const void* b, const void* c, int64_t
     return S % 4 == 0 && (((uintptr_t)a | (uintptr_t)b | (uintptr_t)c) & 15) == 0;
 }
 
+
+// ---- BootBinCrossEntropy (dram/metrics.py:10-51) and BinaryCrossEntropySmooth (53-72) with a target that is GIVEN ------
+//   nll     = -log(clamp(p t + (1 - p)(1 - t), eps, 1 - eps)),  nll_hat the same with t_hat = [p > 0.5],  eps = 1e-7
+//   boot    = mean_{voi < 1e-7} nll  +  (1 - s) (alpha A + (1 - alpha) B) / (alpha T + (1 - alpha)(n_in - T))  +  s mean_{voi > 0} nll_hat
+//             A = sum_{voi > 0} t nll,  B = sum_{voi > 0} (1 - t) nll,  T = sum_{voi > 0} t,  alpha = clamp(1 - T / n_in, .25, .75)
+//   smooth  = -s (alpha P1 + (1 - alpha) P2) / (alpha T + (1 - alpha)(n - T)),   alpha = clamp(1 - T / n, .3, .7)
+//             P1 = sum t log pc,  P2 = sum (1 - t) log(1 - pc),  pc = clamp(p, 1e-6, 1 - 1e-6)
+// alpha is a function of the sums alone, so sum nll w = alpha A + (1 - alpha) B needs no second pass over the tensor.
+// Forward: block b owns elements [b SEG_CHUNK, (b + 1) SEG_CHUNK) and writes ONE fp64 partial tuple; lane l of step u owns
+// the four elements from (u 256 + l) 4 of that range.  The ownership is by element INDEX, never by address, and every sum
+// is added in one fixed order (four elements in fp32, steps in fp64, butterfly, four waves), so the bits do not depend on
+// grid size, alignment or mask type.  A tensor whose base allows it is read with one 16-byte load per lane and step (one
+// 4-byte load for a uint8 mask); a tensor that is not aligned, and the last group where n is no multiple of 4, with
+// element loads.  One block then adds the partials in a fixed order and takes the reference's `tf.sum() > 0` branch.
+// Backward: one pass, the same ownership, dp written with 16-byte stores where dp allows it.
+constexpr int SEG_CHUNK = 4096;        // elements per block = per partial tuple
+constexpr int SEG_UNROLL = SEG_CHUNK / (256 * 4);      // 16-byte loads of each tensor a lane has in flight
+constexpr int BOOT_NSUM = 7;           // n_out, sum_out nll, n_in, T, A, B, sum_in nll_hat
+constexpr int SMOOTH_NSUM = 3;         // T, P1, P2
+constexpr int SEG_TOTALS = 8;          // doubles at the head of the workspace: the totals, then the partials
+constexpr int SEG_STATE = 8;           // floats of the state the backward reads
+constexpr float SEPS = 1e-6f;
+
+template <int KIND> struct SegMask;
+template <> struct SegMask<0> { using type = uint8_t; };
+template <> struct SegMask<2> { using type = float; };
+
+// the (up to) four elements from b[i]; vec: b is aligned for one access of the whole group
+__device__ __forceinline__ void seg_load4(const float* b, int64_t i, bool vec, int cnt, float (&v)[4]) {
+    if (vec && cnt == 4) {
+        const float4 q = *reinterpret_cast<const float4*>(b + i);
+        v[0] = q.x; v[1] = q.y; v[2] = q.z; v[3] = q.w;
+    } else {
+#pragma unroll
+        for (int e = 0; e < 4; ++e) v[e] = e < cnt ? b[i + e] : 0.f;
+    }
+}
+__device__ __forceinline__ void seg_load4(const uint8_t* b, int64_t i, bool vec, int cnt, float (&v)[4]) {
+    if (vec && cnt == 4) {
+        const uchar4 q = *reinterpret_cast<const uchar4*>(b + i);
+        v[0] = (float)q.x; v[1] = (float)q.y; v[2] = (float)q.z; v[3] = (float)q.w;
+    } else {
+#pragma unroll
+        for (int e = 0; e < 4; ++e) v[e] = e < cnt ? (float)b[i + e] : 0.f;
+    }
+}
+__device__ __forceinline__ void seg_store4(float* b, int64_t i, bool vec, int cnt, const float (&v)[4]) {
+    if (vec && cnt == 4) {
+        *reinterpret_cast<float4*>(b + i) = make_float4(v[0], v[1], v[2], v[3]);
+    } else {
+#pragma unroll
+        for (int e = 0; e < 4; ++e)
+            if (e < cnt) b[i + e] = v[e];
+    }
+}
+// elements of group (u, lane) of block `blk` that lie inside [0, n): 0 .. 4
+__device__ __forceinline__ int seg_group(int64_t n, int u, int64_t& i) {
+    i = (int64_t)blockIdx.x * SEG_CHUNK + (int64_t)(u * 256 + threadIdx.x) * 4;
+    const int64_t left = n - i;
+    return left >= 4 ? 4 : (left > 0 ? (int)left : 0);
+}
+
+// acc[NS] of every lane -> part[blockIdx.x * NS + q], butterfly per wave, then the four waves in order
+template <int NS>
+__device__ __forceinline__ void seg_block_partials(const double (&acc)[NS], double (*red)[4], double* __restrict__ part) {
+#pragma unroll
+    for (int q = 0; q < NS; ++q) {
+        const double s = wave_sum_d(acc[q]);
+        if ((threadIdx.x & 63) == 0) red[q][threadIdx.x >> 6] = s;
+    }
+    __syncthreads();
+    if (threadIdx.x < NS)
+        part[(size_t)blockIdx.x * NS + threadIdx.x] =
+            ((red[threadIdx.x][0] + red[threadIdx.x][1]) + red[threadIdx.x][2]) + red[threadIdx.x][3];
+}
+// tot[q] = sum of part[b * NS + q] over the nblk blocks, in thread 0 (lanes stride over the blocks, then as above)
+template <int NS>
+__device__ __forceinline__ void seg_total(const double* __restrict__ part, int64_t nblk, double (*red)[4], double (&tot)[NS]) {
+    double s[NS];
+#pragma unroll
+    for (int q = 0; q < NS; ++q) s[q] = 0.0;
+    for (int64_t b = threadIdx.x; b < nblk; b += 256)
+#pragma unroll
+        for (int q = 0; q < NS; ++q) s[q] += part[(size_t)b * NS + q];
+#pragma unroll
+    for (int q = 0; q < NS; ++q) {
+        const double w = wave_sum_d(s[q]);
+        if ((threadIdx.x & 63) == 0) red[q][threadIdx.x >> 6] = w;
+    }
+    __syncthreads();
+#pragma unroll
+    for (int q = 0; q < NS; ++q) tot[q] = ((red[q][0] + red[q][1]) + red[q][2]) + red[q][3];
+}
+
+template <int KT, int KV>
+__global__ __launch_bounds__(256) void boot_bce_partial_kernel(const float* __restrict__ p,
+                                                               const typename SegMask<KT>::type* __restrict__ t,
+                                                               const typename SegMask<KV>::type* __restrict__ voi,
+                                                               double* __restrict__ part, int64_t n, int vecp, int vect,
+                                                               int vecv) {
+    __shared__ double red[BOOT_NSUM][4];
+    float pv[SEG_UNROLL][4], tv[SEG_UNROLL][4], vv[SEG_UNROLL][4];
+    int cnt[SEG_UNROLL];
+#pragma unroll
+    for (int u = 0; u < SEG_UNROLL; ++u) {
+        int64_t i;
+        cnt[u] = seg_group(n, u, i);
+        if (cnt[u] > 0) {
+            seg_load4(p, i, vecp != 0, cnt[u], pv[u]);
+            seg_load4(t, i, vect != 0, cnt[u], tv[u]);
+            seg_load4(voi, i, vecv != 0, cnt[u], vv[u]);
+        }
+    }
+    double acc[BOOT_NSUM] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
+#pragma unroll
+    for (int u = 0; u < SEG_UNROLL; ++u) {
+        float s[BOOT_NSUM] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+            if (e >= cnt[u]) continue;
+            const float pe = pv[u][e], te = tv[u][e], ve = vv[u][e];
+            const float nll = nlog_clamped(pe * te + (1.f - pe) * (1.f - te));
+            if (ve < LEPS) { s[0] += 1.f; s[1] += nll; }
+            if (ve > 0.f) {
+                s[2] += 1.f;
+                s[3] += te;
+                s[4] += te * nll;
+                s[5] += (1.f - te) * nll;
+                s[6] += nlog_clamped(pe > 0.5f ? pe : 1.f - pe);
+            }
+        }
+#pragma unroll
+        for (int q = 0; q < BOOT_NSUM; ++q) acc[q] += s[q];
+    }
+    seg_block_partials<BOOT_NSUM>(acc, red, part);
+}
+
+// tot (8 doubles): the seven totals.  state: [0] 1 / n_out (0 without an outside), [1] alpha, [2] 1 / sum w, [3] 1 / n_in,
+// [4] 1 if the inside part exists, else 0 (and [1..3] are 0).
+__global__ __launch_bounds__(256) void boot_bce_finish_kernel(const double* __restrict__ part, int64_t nblk, double smoothing,
+                                                              double* __restrict__ tot_out, float* __restrict__ out,
+                                                              float* __restrict__ state) {
+    __shared__ double red[BOOT_NSUM][4];
+    double tot[BOOT_NSUM];
+    seg_total<BOOT_NSUM>(part, nblk, red, tot);
+    if (threadIdx.x != 0) return;
+    const double n_out = tot[0], n_in = tot[2], T = tot[3];
+    double loss = tot[1] / n_out;          // no outside: 0 / 0 = nan, torch's mean of an empty tensor
+    double alpha = 0.0, inv_w = 0.0, inv_in = 0.0;
+    const bool inside = n_in > 0.0;        // the reference's `if tf.sum() > 0`, taken here
+    if (inside) {
+        alpha = 1.0 - T / n_in;
+        alpha = alpha < 0.25 ? 0.25 : (alpha > 0.75 ? 0.75 : alpha);
+        inv_w = 1.0 / (alpha * T + (1.0 - alpha) * (n_in - T));
+        inv_in = 1.0 / n_in;
+        loss += (1.0 - smoothing) * (alpha * tot[4] + (1.0 - alpha) * tot[5]) * inv_w + smoothing * tot[6] * inv_in;
+    }
+    out[0] = (float)loss;
+#pragma unroll
+    for (int q = 0; q < BOOT_NSUM; ++q) tot_out[q] = tot[q];
+    tot_out[BOOT_NSUM] = 0.0;
+    state[0] = n_out > 0.0 ? (float)(1.0 / n_out) : 0.f;
+    state[1] = (float)alpha; state[2] = (float)inv_w; state[3] = (float)inv_in; state[4] = inside ? 1.f : 0.f;
+    state[5] = 0.f; state[6] = 0.f; state[7] = 0.f;
+}
+
+// dp = gout * d loss / d p.  torch.clamp passes the gradient where eps <= x <= 1 - eps, bounds included, and gives 0
+// outside; t_hat and alpha are constants; the upstream gradient multiplies last, so it scales every element exactly.
+template <int KT, int KV>
+__global__ __launch_bounds__(256) void boot_bce_bwd_kernel(const float* __restrict__ p,
+                                                           const typename SegMask<KT>::type* __restrict__ t,
+                                                           const typename SegMask<KV>::type* __restrict__ voi,
+                                                           const float* __restrict__ state, const float* __restrict__ gout,
+                                                           float smoothing, float* __restrict__ dp, int64_t n, int vecp,
+                                                           int vect, int vecv, int vecd) {
+    const float g = gout[0];
+    const float inv_out = state[0], alpha = state[1], inv_w = state[2], inv_in = state[3];
+    const bool inside = state[4] > 0.f;
+    const float ca = (1.f - smoothing) * alpha * inv_w, cb = (1.f - smoothing) * (1.f - alpha) * inv_w;
+    const float ch = smoothing * inv_in;
+    float pv[SEG_UNROLL][4], tv[SEG_UNROLL][4], vv[SEG_UNROLL][4];
+    int cnt[SEG_UNROLL];
+    int64_t at[SEG_UNROLL];
+#pragma unroll
+    for (int u = 0; u < SEG_UNROLL; ++u) {
+        cnt[u] = seg_group(n, u, at[u]);
+        if (cnt[u] > 0) {
+            seg_load4(p, at[u], vecp != 0, cnt[u], pv[u]);
+            seg_load4(t, at[u], vect != 0, cnt[u], tv[u]);
+            seg_load4(voi, at[u], vecv != 0, cnt[u], vv[u]);
+        }
+    }
+#pragma unroll
+    for (int u = 0; u < SEG_UNROLL; ++u) {
+        if (cnt[u] == 0) continue;
+        float d[4] = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+            if (e >= cnt[u]) continue;
+            const float pe = pv[u][e], te = tv[u][e], ve = vv[u][e];
+            const float pt = pe * te + (1.f - pe) * (1.f - te);
+            const float dnll = (pt >= LEPS && pt <= 1.f - LEPS) ? (1.f - 2.f * te) / pt : 0.f;     // d pt / d p = 2 t - 1
+            float v = 0.f;
+            if (ve < LEPS) v = inv_out * dnll;
+            if (inside && ve > 0.f) {
+                const bool up = pe > 0.5f;
+                const float ph = up ? pe : 1.f - pe;
+                const float dh = (ph >= LEPS && ph <= 1.f - LEPS) ? (up ? -1.f : 1.f) / ph : 0.f;
+                v += (ca * te + cb * (1.f - te)) * dnll + ch * dh;
+            }
+            d[e] = __fmul_rn(g, v);
+        }
+        seg_store4(dp, at[u], vecd != 0, cnt[u], d);
+    }
+}
+
+template <int KT>
+__global__ __launch_bounds__(256) void bce_smooth_partial_kernel(const float* __restrict__ p,
+                                                                 const typename SegMask<KT>::type* __restrict__ t,
+                                                                 double* __restrict__ part, int64_t n, int vecp, int vect) {
+    __shared__ double red[SMOOTH_NSUM][4];
+    float pv[SEG_UNROLL][4], tv[SEG_UNROLL][4];
+    int cnt[SEG_UNROLL];
+#pragma unroll
+    for (int u = 0; u < SEG_UNROLL; ++u) {
+        int64_t i;
+        cnt[u] = seg_group(n, u, i);
+        if (cnt[u] > 0) {
+            seg_load4(p, i, vecp != 0, cnt[u], pv[u]);
+            seg_load4(t, i, vect != 0, cnt[u], tv[u]);
+        }
+    }
+    double acc[SMOOTH_NSUM] = {0.0, 0.0, 0.0};
+#pragma unroll
+    for (int u = 0; u < SEG_UNROLL; ++u) {
+        float s[SMOOTH_NSUM] = {0.f, 0.f, 0.f};
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+            if (e >= cnt[u]) continue;
+            const float te = tv[u][e];
+            const float pc = fminf(fmaxf(pv[u][e], SEPS), 1.f - SEPS);
+            s[0] += te;
+            s[1] += te * logf(pc);
+            s[2] += (1.f - te) * logf(1.f - pc);
+        }
+#pragma unroll
+        for (int q = 0; q < SMOOTH_NSUM; ++q) acc[q] += s[q];
+    }
+    seg_block_partials<SMOOTH_NSUM>(acc, red, part);
+}
+
+// tot (8 doubles): T, P1, P2.  state: [0] alpha, [1] 1 / sum w.
+__global__ __launch_bounds__(256) void bce_smooth_finish_kernel(const double* __restrict__ part, int64_t nblk, int64_t n,
+                                                                double smooth, double* __restrict__ tot_out,
+                                                                float* __restrict__ out, float* __restrict__ state) {
+    __shared__ double red[SMOOTH_NSUM][4];
+    double tot[SMOOTH_NSUM];
+    seg_total<SMOOTH_NSUM>(part, nblk, red, tot);
+    if (threadIdx.x != 0) return;
+    const double T = tot[0];
+    double alpha = 1.0 - T / (double)n;
+    alpha = alpha < 0.3 ? 0.3 : (alpha > 0.7 ? 0.7 : alpha);
+    const double inv_w = 1.0 / (alpha * T + (1.0 - alpha) * ((double)n - T));
+    out[0] = (float)(-smooth * (alpha * tot[1] + (1.0 - alpha) * tot[2]) * inv_w);
+#pragma unroll
+    for (int q = 0; q < SEG_TOTALS; ++q) tot_out[q] = q < SMOOTH_NSUM ? tot[q] : 0.0;
+    state[0] = (float)alpha; state[1] = (float)inv_w;
+#pragma unroll
+    for (int q = 2; q < SEG_STATE; ++q) state[q] = 0.f;
+}
+
+template <int KT>
+__global__ __launch_bounds__(256) void bce_smooth_bwd_kernel(const float* __restrict__ p,
+                                                             const typename SegMask<KT>::type* __restrict__ t,
+                                                             const float* __restrict__ state, const float* __restrict__ gout,
+                                                             float smooth, float* __restrict__ dp, int64_t n, int vecp,
+                                                             int vect, int vecd) {
+    const float g = gout[0];
+    const float alpha = state[0];
+    const float c = -smooth * state[1];
+    float pv[SEG_UNROLL][4], tv[SEG_UNROLL][4];
+    int cnt[SEG_UNROLL];
+    int64_t at[SEG_UNROLL];
+#pragma unroll
+    for (int u = 0; u < SEG_UNROLL; ++u) {
+        cnt[u] = seg_group(n, u, at[u]);
+        if (cnt[u] > 0) {
+            seg_load4(p, at[u], vecp != 0, cnt[u], pv[u]);
+            seg_load4(t, at[u], vect != 0, cnt[u], tv[u]);
+        }
+    }
+#pragma unroll
+    for (int u = 0; u < SEG_UNROLL; ++u) {
+        if (cnt[u] == 0) continue;
+        float d[4] = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+            if (e >= cnt[u]) continue;
+            const float pe = pv[u][e], te = tv[u][e];
+            float v = 0.f;
+            if (pe >= SEPS && pe <= 1.f - SEPS)         // pe is its own clamped value here
+                v = c * (alpha * te + (1.f - alpha) * (1.f - te)) * (te / pe - (1.f - te) / (1.f - pe));
+            d[e] = __fmul_rn(g, v);
+        }
+        seg_store4(dp, at[u], vecd != 0, cnt[u], d);
+    }
+}
+
+static inline int64_t seg_blocks(int64_t n) { return cdiv64(n, SEG_CHUNK); }
+static inline bool seg_kind_ok(int kind) { return kind == DRAM_SEG_MASK_U8 || kind == DRAM_SEG_MASK_F32; }
+// whether a tensor of this kind may be read one group (four elements) per access
+static inline int seg_vec(const void* b, int kind) { return ((uintptr_t)b & (kind == DRAM_SEG_MASK_U8 ? 3 : 15)) == 0; }
+
 }  // namespace dram
 
 using namespace dram;
@@ -551,4 +865,102 @@ extern "C" int dram_masked_smooth_l1_bwd(const float* a, const float* b, const f
     hipLaunchKernelGGL(masked_smooth_l1_bwd_kernel, dim3(gx, N * C), dim3(256), 0, (hipStream_t)stream, a, b, mask, out, gout,
                        da, db, C, S);
     return check_launch("masked_smooth_l1_bwd");
+}
+
+extern "C" size_t dram_seg_loss_ws_bytes(int64_t n) {
+    if (n <= 0) return 0;
+    return ((size_t)SEG_TOTALS + (size_t)seg_blocks(n) * BOOT_NSUM) * sizeof(double);
+}
+
+extern "C" int dram_seg_loss_state_floats(void) { return SEG_STATE; }
+
+extern "C" int dram_seg_loss_chunk(void) { return SEG_CHUNK; }
+
+#define SEG_REQUIRE_COMMON(who, n)                                                                   \
+    DRAM_REQUIRE((n) >= 0, who ": negative element count");                                          \
+    DRAM_REQUIRE((n) <= ((int64_t)1 << 40), who ": more than 2^40 elements") /* one block per 4096 elements, grid.x < 2^31 */
+
+// kernel<KT, KV> for the two mask kinds of a BootBinCrossEntropy call
+#define BOOT_DISPATCH(kernel, grid, st, ...)                                                                                   \
+    do {                                                                                                                       \
+        if (t_kind == DRAM_SEG_MASK_U8 && voi_kind == DRAM_SEG_MASK_U8)                                                        \
+            hipLaunchKernelGGL((kernel<0, 0>), grid, dim3(256), 0, st, p, (const uint8_t*)t, (const uint8_t*)voi, __VA_ARGS__); \
+        else if (t_kind == DRAM_SEG_MASK_U8)                                                                                   \
+            hipLaunchKernelGGL((kernel<0, 2>), grid, dim3(256), 0, st, p, (const uint8_t*)t, (const float*)voi, __VA_ARGS__);   \
+        else if (voi_kind == DRAM_SEG_MASK_U8)                                                                                 \
+            hipLaunchKernelGGL((kernel<2, 0>), grid, dim3(256), 0, st, p, (const float*)t, (const uint8_t*)voi, __VA_ARGS__);   \
+        else                                                                                                                   \
+            hipLaunchKernelGGL((kernel<2, 2>), grid, dim3(256), 0, st, p, (const float*)t, (const float*)voi, __VA_ARGS__);     \
+    } while (0)
+
+extern "C" int dram_boot_bce_fwd(const float* p, const void* t, const void* voi, int t_kind, int voi_kind, int64_t n,
+                                 double smoothing, float* out, float* state, void* ws, size_t ws_bytes, void* stream) {
+    SEG_REQUIRE_COMMON("boot_bce_fwd", n);
+    DRAM_REQUIRE(seg_kind_ok(t_kind) && seg_kind_ok(voi_kind), "boot_bce_fwd: mask kind must be 0 (uint8) or 2 (float32)");
+    if (n == 0) return DRAM_OK;
+    DRAM_REQUIRE(p && t && voi && out && state && ws, "boot_bce_fwd: null pointer");
+    DRAM_REQUIRE(((uintptr_t)ws & 7) == 0, "boot_bce_fwd: workspace must be 8-byte aligned");
+    if (ws_bytes < dram_seg_loss_ws_bytes(n)) {
+        set_error("boot_bce_fwd: workspace too small");
+        return DRAM_EWS;
+    }
+    hipStream_t st = (hipStream_t)stream;
+    const int64_t nblk = seg_blocks(n);
+    double* tot = (double*)ws;
+    double* part = tot + SEG_TOTALS;
+    BOOT_DISPATCH(boot_bce_partial_kernel, dim3((unsigned)nblk), st, part, n, seg_vec(p, DRAM_SEG_MASK_F32), seg_vec(t, t_kind),
+                  seg_vec(voi, voi_kind));
+    hipLaunchKernelGGL(boot_bce_finish_kernel, dim3(1), dim3(256), 0, st, (const double*)part, nblk, smoothing, tot, out, state);
+    return check_launch("boot_bce_fwd");
+}
+
+extern "C" int dram_boot_bce_bwd(const float* p, const void* t, const void* voi, int t_kind, int voi_kind, int64_t n,
+                                 double smoothing, const float* state, const float* gout, float* dp, void* stream) {
+    SEG_REQUIRE_COMMON("boot_bce_bwd", n);
+    DRAM_REQUIRE(seg_kind_ok(t_kind) && seg_kind_ok(voi_kind), "boot_bce_bwd: mask kind must be 0 (uint8) or 2 (float32)");
+    if (n == 0) return DRAM_OK;
+    DRAM_REQUIRE(p && t && voi && state && gout && dp, "boot_bce_bwd: null pointer");
+    BOOT_DISPATCH(boot_bce_bwd_kernel, dim3((unsigned)seg_blocks(n)), (hipStream_t)stream, state, gout, (float)smoothing, dp, n,
+                  seg_vec(p, DRAM_SEG_MASK_F32), seg_vec(t, t_kind), seg_vec(voi, voi_kind), seg_vec(dp, DRAM_SEG_MASK_F32));
+    return check_launch("boot_bce_bwd");
+}
+
+extern "C" int dram_bce_smooth_fwd(const float* p, const void* t, int t_kind, int64_t n, double smooth, float* out,
+                                   float* state, void* ws, size_t ws_bytes, void* stream) {
+    SEG_REQUIRE_COMMON("bce_smooth_fwd", n);
+    DRAM_REQUIRE(seg_kind_ok(t_kind), "bce_smooth_fwd: target kind must be 0 (uint8) or 2 (float32)");
+    if (n == 0) return DRAM_OK;
+    DRAM_REQUIRE(p && t && out && state && ws, "bce_smooth_fwd: null pointer");
+    DRAM_REQUIRE(((uintptr_t)ws & 7) == 0, "bce_smooth_fwd: workspace must be 8-byte aligned");
+    if (ws_bytes < dram_seg_loss_ws_bytes(n)) {
+        set_error("bce_smooth_fwd: workspace too small");
+        return DRAM_EWS;
+    }
+    hipStream_t st = (hipStream_t)stream;
+    const int64_t nblk = seg_blocks(n);
+    double* tot = (double*)ws;
+    double* part = tot + SEG_TOTALS;
+    const int vecp = seg_vec(p, DRAM_SEG_MASK_F32), vect = seg_vec(t, t_kind);
+    if (t_kind == DRAM_SEG_MASK_U8)
+        hipLaunchKernelGGL(bce_smooth_partial_kernel<0>, dim3((unsigned)nblk), dim3(256), 0, st, p, (const uint8_t*)t, part, n, vecp, vect);
+    else
+        hipLaunchKernelGGL(bce_smooth_partial_kernel<2>, dim3((unsigned)nblk), dim3(256), 0, st, p, (const float*)t, part, n, vecp, vect);
+    hipLaunchKernelGGL(bce_smooth_finish_kernel, dim3(1), dim3(256), 0, st, (const double*)part, nblk, n, smooth, tot, out, state);
+    return check_launch("bce_smooth_fwd");
+}
+
+extern "C" int dram_bce_smooth_bwd(const float* p, const void* t, int t_kind, int64_t n, double smooth, const float* state,
+                                   const float* gout, float* dp, void* stream) {
+    SEG_REQUIRE_COMMON("bce_smooth_bwd", n);
+    DRAM_REQUIRE(seg_kind_ok(t_kind), "bce_smooth_bwd: target kind must be 0 (uint8) or 2 (float32)");
+    if (n == 0) return DRAM_OK;
+    DRAM_REQUIRE(p && t && state && gout && dp, "bce_smooth_bwd: null pointer");
+    hipStream_t st = (hipStream_t)stream;
+    const dim3 grid((unsigned)seg_blocks(n));
+    const int vecp = seg_vec(p, DRAM_SEG_MASK_F32), vect = seg_vec(t, t_kind), vecd = seg_vec(dp, DRAM_SEG_MASK_F32);
+    if (t_kind == DRAM_SEG_MASK_U8)
+        hipLaunchKernelGGL(bce_smooth_bwd_kernel<0>, grid, dim3(256), 0, st, p, (const uint8_t*)t, state, gout, (float)smooth, dp, n, vecp, vect, vecd);
+    else
+        hipLaunchKernelGGL(bce_smooth_bwd_kernel<2>, grid, dim3(256), 0, st, p, (const float*)t, state, gout, (float)smooth, dp, n, vecp, vect, vecd);
+    return check_launch("bce_smooth_bwd");
 }

@@ -14,11 +14,17 @@ _AUGMENT = ("GaussianBlur", "RandomMaskOut", "RandomFlip", "RandomRotate90", "Ga
             "RandomRotateInplane90", "RandomCrop", "StandarizeChannel", "RandomAffineTransform3D", "RandomRotate",
             "EnsembleScanAugmentation")
 
-__all__ = ["_lib", "functional", "modules", "optim", "Adam", "AdamW", "SGD", *_AUGMENT]
+# the segmentation losses of `losses`, the same way
+_LOSSES = ("BootBinCrossEntropy", "BinaryCrossEntropySmooth")
+
+__all__ = ["_lib", "functional", "modules", "optim", "Adam", "AdamW", "SGD", *_AUGMENT, *_LOSSES]
 
 
 def __getattr__(name):
     if name in _AUGMENT:
         from . import augment
         return getattr(augment, name)
+    if name in _LOSSES:
+        from . import losses
+        return getattr(losses, name)
     raise AttributeError(f"module {__name__!r} has no attribute {name!r}")

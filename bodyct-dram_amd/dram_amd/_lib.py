@@ -119,6 +119,14 @@ SIGNATURES = {
     "dram_masked_smooth_l1_ws_bytes": (Z, [I, I, L]),
     "dram_masked_smooth_l1_fwd": (I, [P, P, P, P, P, Z, I, I, L, P]),
     "dram_masked_smooth_l1_bwd": (I, [P, P, P, P, P, P, P, I, I, L, P]),
+    # segmentation losses with a given target
+    "dram_seg_loss_ws_bytes": (Z, [L]),
+    "dram_seg_loss_state_floats": (I, []),
+    "dram_seg_loss_chunk": (I, []),
+    "dram_boot_bce_fwd": (I, [P, P, P, I, I, L, ctypes.c_double, P, P, P, Z, P]),
+    "dram_boot_bce_bwd": (I, [P, P, P, I, I, L, ctypes.c_double, P, P, P, P]),
+    "dram_bce_smooth_fwd": (I, [P, P, I, L, ctypes.c_double, P, P, P, Z, P]),
+    "dram_bce_smooth_bwd": (I, [P, P, I, L, ctypes.c_double, P, P, P, P]),
     "dram_affine_sample_fwd": (I, [P, P, P, I, I, I, I, I, P]),
     "dram_affine_sample_bwd": (I, [P, P, P, I, I, I, I, I, P]),
     # measured ceilings (bench.py)

@@ -1103,6 +1103,131 @@ def masked_smooth_l1(a, b, mask):
     return MaskedSmoothL1Fn.apply(a, b, mask)
 
 
+# --------------------------------------------------------------------------- segmentation losses with a given target
+SEG_MASK_KINDS = {torch.uint8: 0, torch.float32: 2}     # DRAM_SEG_MASK_U8, DRAM_SEG_MASK_F32 (include/dram_hip.h)
+
+
+def _seg_mask(t, name, like):
+    """A target or volume-of-interest tensor of a segmentation loss: float32, uint8 or bool (read as uint8), on the device,
+    of the probabilities' shape.  Returns (contiguous tensor, kind)."""
+    if not isinstance(t, torch.Tensor):
+        raise TypeError(f"{name}: expected a tensor")
+    if not t.is_cuda:
+        raise RuntimeError(f"{name}: tensor is on {t.device}; the DRAM HIP path only runs on a ROCm device "
+                           f"(there is no CPU fallback)")
+    if t.dtype == torch.bool:
+        t = t.contiguous().view(torch.uint8)
+    if t.dtype not in SEG_MASK_KINDS:
+        raise TypeError(f"{name}: expected float32, uint8 or bool, got {t.dtype}")
+    if t.shape != like.shape:
+        raise ValueError(f"{name}: shape {tuple(t.shape)} differs from the probabilities' {tuple(like.shape)}")
+    return t.contiguous(), SEG_MASK_KINDS[t.dtype]
+
+
+def _seg_grad(g, name):
+    g = _chk(g, name)
+    if g.numel() != 1:
+        raise ValueError(f"{name}: expected one element, got shape {tuple(g.shape)}")
+    return g
+
+
+def _seg_buffers(p):
+    """(loss, state, workspace) of a segmentation-loss forward; the loss of no elements is NaN (nothing is launched then)."""
+    n = p.numel()
+    out = torch.full((), float("nan"), dtype=torch.float32, device=p.device) if n == 0 else \
+        torch.empty((), dtype=torch.float32, device=p.device)
+    state = torch.empty(_lib.lib.dram_seg_loss_state_floats(), dtype=torch.float32, device=p.device)
+    ws = torch.empty(max(int(_lib.lib.dram_seg_loss_ws_bytes(n)) // 8, 8), dtype=torch.float64, device=p.device)
+    return out, state, ws
+
+
+def _boot_bce_launch(p, t, kt, voi, kv, smoothing):
+    out, state, ws = _seg_buffers(p)
+    call("dram_boot_bce_fwd", _p(p), _p(t), _p(voi), kt, kv, p.numel(), float(smoothing), _p(out), _p(state), _p(ws),
+         ws.numel() * 8, _stream())
+    return out, state, ws
+
+
+def boot_bce_totals(p, t, voi):
+    """The seven fp64 totals of a BootBinCrossEntropy forward, as the finish kernel leaves them at the head of the
+    workspace: n_out, sum_out nll, n_in, T, A, B, sum_in nll_hat (a device tensor; for tests and diagnostics)."""
+    p = _chk(p, "boot_bce p")
+    (t, kt), (voi, kv) = _seg_mask(t, "boot_bce t", p), _seg_mask(voi, "boot_bce voi", p)
+    return _boot_bce_launch(p, t, kt, voi, kv, 0.0)[2][:7]
+
+
+class BootBCEFn(Function):
+    """BootBinCrossEntropy.__call__ (reference dram/metrics.py:17-51) for a target that is given: one streaming pass for
+    every sum, a one-block finish that takes the reference's `tf.sum() > 0` branch on the device, one streaming pass for the
+    gradient.  Nothing is read back in either direction.  An empty tensor gives NaN, as the reference's mean of nothing."""
+
+    @staticmethod
+    def forward(ctx, p, t, voi, smoothing):
+        p = _chk(p, "boot_bce p")
+        t, kt = _seg_mask(t, "boot_bce t", p)
+        voi, kv = _seg_mask(voi, "boot_bce voi", p)
+        out, state, _ = _boot_bce_launch(p, t, kt, voi, kv, smoothing)
+        ctx.save_for_backward(p, t, voi, state)
+        ctx.kinds, ctx.smoothing = (kt, kv), float(smoothing)
+        return out
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, g):
+        p, t, voi, state = ctx.saved_tensors
+        g = _seg_grad(g, "boot_bce grad_output")
+        dp = torch.empty_like(p)
+        call("dram_boot_bce_bwd", _p(p), _p(t), _p(voi), *ctx.kinds, p.numel(), ctx.smoothing, _p(state), _p(g), _p(dp),
+             _stream())
+        return dp, None, None, None
+
+
+def boot_bce(p, t, voi, smoothing=0.1):
+    """BootBinCrossEntropy(smoothing)(p, t, voi) as a 0-dim tensor; t and voi float32, uint8 or bool."""
+    return BootBCEFn.apply(p, t, voi, smoothing)
+
+
+def _bce_smooth_launch(p, t, kt, smooth):
+    out, state, ws = _seg_buffers(p)
+    call("dram_bce_smooth_fwd", _p(p), _p(t), kt, p.numel(), float(smooth), _p(out), _p(state), _p(ws), ws.numel() * 8,
+         _stream())
+    return out, state, ws
+
+
+def bce_smooth_totals(p, t):
+    """The three fp64 totals of a BinaryCrossEntropySmooth forward: T, sum t log pc, sum (1 - t) log(1 - pc)."""
+    p = _chk(p, "bce_smooth probs")
+    t, kt = _seg_mask(t, "bce_smooth targets", p)
+    return _bce_smooth_launch(p, t, kt, 1.0)[2][:3]
+
+
+class BCESmoothFn(Function):
+    """BinaryCrossEntropySmooth.__call__ (reference dram/metrics.py:60-72): the same three launches."""
+
+    @staticmethod
+    def forward(ctx, p, t, smooth):
+        p = _chk(p, "bce_smooth probs")
+        t, kt = _seg_mask(t, "bce_smooth targets", p)
+        out, state, _ = _bce_smooth_launch(p, t, kt, smooth)
+        ctx.save_for_backward(p, t, state)
+        ctx.kind, ctx.smooth = kt, float(smooth)
+        return out
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, g):
+        p, t, state = ctx.saved_tensors
+        g = _seg_grad(g, "bce_smooth grad_output")
+        dp = torch.empty_like(p)
+        call("dram_bce_smooth_bwd", _p(p), _p(t), ctx.kind, p.numel(), ctx.smooth, _p(state), _p(g), _p(dp), _stream())
+        return dp, None, None
+
+
+def bce_smooth(p, t, smooth):
+    """BinaryCrossEntropySmooth(smooth)(p, t) as a 0-dim tensor; t float32, uint8 or bool."""
+    return BCESmoothFn.apply(p, t, smooth)
+
+
 # --------------------------------------------------------------------------- PCM local attention
 PCM_RELU, PCM_L2NORM = 1, 2
 # merge_type -> (flags, scale_mode); reference models.py:259-331 (dot-product family)

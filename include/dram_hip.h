@@ -521,6 +521,49 @@ int dram_masked_smooth_l1_fwd(const float* a, const float* b, const float* mask,
 int dram_masked_smooth_l1_bwd(const float* a, const float* b, const float* mask, const float* out,
                               const float* gout, float* da, float* db, int N, int C, int64_t S, void* stream);
 
+/* ---- the two voxel-wise segmentation losses with a target that is GIVEN: BootBinCrossEntropy (dram/metrics.py:10-51) and
+ *      BinaryCrossEntropySmooth (metrics.py:53-72), over n contiguous elements (the reference flattens too).
+ * p: float32.  t, voi: float32 (kind DRAM_SEG_MASK_F32) or uint8 (kind DRAM_SEG_MASK_U8: the kinds of dram_resample_volume),
+ * each with its own kind; any base address (a base aligned for it is read 16 bytes, or four uint8, per lane and access).
+ * BootBinCrossEntropy, eps = 1e-7, s = smoothing, every per-element value in fp32 and every sum in fp64:
+ *   pt      = p t + (1 - p)(1 - t),      nll     = -log(clamp(pt, eps, 1 - eps))
+ *   p_hat   = p > 0.5 ? p : 1 - p,       nll_hat = -log(clamp(p_hat, eps, 1 - eps))
+ *   outside = {voi < 1e-7}, inside = {voi > 0}  (the two tests as written: an element with 0 < voi < 1e-7 is in both)
+ *   n_out, n_in = their sizes;  T = sum_in t,  A = sum_in t nll,  B = sum_in (1 - t) nll
+ *   alpha   = clamp(1 - T / n_in, 0.25, 0.75),   W = alpha T + (1 - alpha)(n_in - T)
+ *   loss    = sum_out nll / n_out  +  [n_in > 0] ((1 - s)(alpha A + (1 - alpha) B) / W  +  s sum_in nll_hat / n_in)
+ *   n_out = 0 gives 0 / 0 = NaN (torch's mean of an empty tensor); n_in = 0 gives the outside term alone.  That branch,
+ *   which the reference takes on the host, is taken on the device: no entry point reads anything back.
+ *   d loss / d p = [out] d nll / n_out + [in] ((1 - s)(alpha t + (1 - alpha)(1 - t)) d nll / W + s d nll_hat / n_in),
+ *   d nll = (1 - 2 t) / pt where eps <= pt <= 1 - eps (bounds included: torch.clamp's rule) and 0 elsewhere, d nll_hat
+ *   = -+ 1 / p_hat under the same rule; t_hat and alpha are constants; t and voi get no gradient.
+ * BinaryCrossEntropySmooth, s = smooth, pc = clamp(p, 1e-6, 1 - 1e-6), 1 - pc formed in fp32 from the clamped pc:
+ *   T = sum t,  alpha = clamp(1 - T / n, 0.3, 0.7),  w = alpha t + (1 - alpha)(1 - t),  W = alpha T + (1 - alpha)(n - T)
+ *   loss = -s (alpha sum t log pc + (1 - alpha) sum (1 - t) log(1 - pc)) / W
+ *   d loss / d p = -s w (t / pc - (1 - t) / (1 - pc)) / W where 1e-6 <= p <= 1 - 1e-6, and 0 elsewhere.
+ * fwd: out = the loss (one device float); state = dram_seg_loss_state_floats() device floats for the backward
+ *   (boot: 1 / n_out or 0, alpha, 1 / W, 1 / n_in, 1 if n_in > 0 -- the last four 0 otherwise; smooth: alpha, 1 / W);
+ *   ws = dram_seg_loss_ws_bytes(n) bytes, 8-byte aligned; on return its first 8 doubles are the totals
+ *   (boot: n_out, sum_out nll, n_in, T, A, B, sum_in nll_hat; smooth: T, sum t log pc, sum (1 - t) log(1 - pc)).
+ *   One block per dram_seg_loss_chunk() elements writes one tuple of fp64 partials, one block adds them in a fixed order:
+ *   no atomics, the bits depend on the values alone -- not on alignment, mask kind or run.
+ * bwd: dp = gout[0] * d loss / d p, the multiplication by gout[0] last (one fp32 rounding).
+ * Negative n, an unknown kind and (for n > 0) a null pointer are DRAM_EINVAL before anything is launched; n == 0 launches
+ * nothing and leaves out, state and dp alone (the loss of no elements is NaN in the reference: the caller's to supply). */
+#define DRAM_SEG_MASK_U8 0
+#define DRAM_SEG_MASK_F32 2
+size_t dram_seg_loss_ws_bytes(int64_t n);
+int dram_seg_loss_state_floats(void);
+int dram_seg_loss_chunk(void);
+int dram_boot_bce_fwd(const float* p, const void* t, const void* voi, int t_kind, int voi_kind, int64_t n,
+                      double smoothing, float* out, float* state, void* ws, size_t ws_bytes, void* stream);
+int dram_boot_bce_bwd(const float* p, const void* t, const void* voi, int t_kind, int voi_kind, int64_t n,
+                      double smoothing, const float* state, const float* gout, float* dp, void* stream);
+int dram_bce_smooth_fwd(const float* p, const void* t, int t_kind, int64_t n, double smooth, float* out, float* state,
+                        void* ws, size_t ws_bytes, void* stream);
+int dram_bce_smooth_bwd(const float* p, const void* t, int t_kind, int64_t n, double smooth, const float* state,
+                        const float* gout, float* dp, void* stream);
+
 /* Rotate3DXOneShot (data_transforms.py:1186-1208): F.grid_sample(x, F.affine_grid(theta, x.size())) with the defaults
  * (trilinear, zeros padding, align_corners=False); theta12 = HOST pointer to the row-major [3][4] matrix shared by all
  * samples.  Backward = the scatter adjoint (float atomics: summation order not fixed, like ATen's). */
