@@ -737,6 +737,103 @@ static inline bool seg_kind_ok(int kind) { return kind == DRAM_SEG_MASK_U8 || ki
 // whether a tensor of this kind may be read one group (four elements) per access
 static inline int seg_vec(const void* b, int kind) { return ((uintptr_t)b & (kind == DRAM_SEG_MASK_U8 ? 3 : 15)) == 0; }
 
+
+// ---- regression targets of a batch (IntRegLoss.get_labels, dram/metrics.py:122-138; weight 172-174; keep 326-327) --------
+//   ratio_n   = fp32( sum_v lesion m ) / fp32( sum_v m )                  one fp32 division (the lesion-ratio upper bound)
+//   [lb, ub]  = [max(0, ratio - bw), min(1, ratio + bw)]                  in fp64, as the host loop's Python floats
+//   band      = [max(c_lb, lb), min(c_ub, ub)], (c_lb, c_ub) the ratio interval of the sample's CT severity score;
+//               where the two do not overlap: [lb, ub] if it lies below the class interval, the class interval if above
+//   targets_n = band rounded once to fp32,  weight_n = clamp(freq[ctss_n], 0.2, 0.8),  keep_n = ctss_n > 0
+// One pass over the two masks (8 B/voxel, the loads of enc_partial_kernel), per step the products of a lane in fp32 (at
+// most 16 of them: exact for 0/1 masks), steps and lanes in fp64, one fp64 partial pair per block; one wave per sample then
+// adds the partials in a fixed order and lane 0 does the band.  No atomics: the same input gives the same bits.
+// An empty lobe (0/0) gives NaN targets for that sample, a score outside 0..5 NaN targets and a NaN weight.
+constexpr int TGT_NSUM = 2;            // per (sample, block): sum of lesion * lobe, sum of lobe
+struct TargetsArgs {
+    float freq[6];
+    double band_width;
+};
+
+template <int V>
+__global__ __launch_bounds__(256) void targets_partial_kernel(const float* __restrict__ lobes, const float* __restrict__ lesions,
+                                                              double* __restrict__ part, int64_t S, int nblk) {
+    using T = typename EncPack<V>::type;
+    __shared__ double red[TGT_NSUM][4];
+    const int n = blockIdx.y;
+    const T* pm = reinterpret_cast<const T*>(lobes + (int64_t)n * S);
+    const T* pl = reinterpret_cast<const T*>(lesions + (int64_t)n * S);
+    const int64_t packs = S / V;
+    const int64_t step = (int64_t)nblk * 256 * ENC_UNROLL;
+    double acc[TGT_NSUM] = {0.0, 0.0};
+    for (int64_t base = (int64_t)blockIdx.x * 256 * ENC_UNROLL; base < packs; base += step) {
+        T m[ENC_UNROLL], l[ENC_UNROLL];
+        bool ok[ENC_UNROLL];
+#pragma unroll
+        for (int u = 0; u < ENC_UNROLL; ++u) {
+            const int64_t i = base + u * 256 + threadIdx.x;
+            ok[u] = i < packs;
+            if (ok[u]) { m[u] = pm[i]; l[u] = pl[i]; }
+        }
+        float sl = 0.f, sm = 0.f;
+#pragma unroll
+        for (int u = 0; u < ENC_UNROLL; ++u) {
+            if (!ok[u]) continue;
+#pragma unroll
+            for (int k = 0; k < V; ++k) {
+                const float mv = enc_lane(m[u], k);
+                sl += __fmul_rn(enc_lane(l[u], k), mv);
+                sm += mv;
+            }
+        }
+        acc[0] += sl; acc[1] += sm;
+    }
+#pragma unroll
+    for (int q = 0; q < TGT_NSUM; ++q) {
+        const double s = wave_sum_d(acc[q]);
+        if ((threadIdx.x & 63) == 0) red[q][threadIdx.x >> 6] = s;
+    }
+    __syncthreads();
+    if (threadIdx.x < TGT_NSUM)
+        part[((size_t)n * nblk + blockIdx.x) * TGT_NSUM + threadIdx.x] =
+            red[threadIdx.x][0] + red[threadIdx.x][1] + red[threadIdx.x][2] + red[threadIdx.x][3];
+}
+
+__global__ __launch_bounds__(256) void targets_finalize_kernel(const double* __restrict__ part, const int* __restrict__ ctss,
+                                                               TargetsArgs a, int N, int nblk, float* __restrict__ targets,
+                                                               float* __restrict__ weight, float* __restrict__ keep) {
+    // IntRegLoss.ctss_ratio_map (metrics.py:76-83)
+    const double c_lo[6] = {0.0, 0.001, 0.01, 0.05, 0.35, 0.5}, c_hi[6] = {0.001, 0.01, 0.05, 0.35, 0.5, 1.00001};
+    const int lane = threadIdx.x & 63;
+    for (int n = threadIdx.x >> 6; n < N; n += 4) {
+        double s[TGT_NSUM] = {0.0, 0.0};
+        for (int b = lane; b < nblk; b += 64)
+            for (int q = 0; q < TGT_NSUM; ++q) s[q] += part[((size_t)n * nblk + b) * TGT_NSUM + q];
+        for (int q = 0; q < TGT_NSUM; ++q) s[q] = wave_sum_d(s[q]);
+        if (lane != 0) continue;
+        const int c = ctss[n];
+        const bool known = c >= 0 && c <= 5;
+        const float ratio = __fdiv_rn((float)s[0], (float)s[1]);
+        const float nan = __builtin_nanf("");
+        float lo = nan, hi = nan;
+        if (known && ratio == ratio) {
+            const double lp = (double)ratio;
+            const double lb = (lp - a.band_width) > 0.0 ? lp - a.band_width : 0.0;
+            const double ub = (lp + a.band_width) < 1.0 ? lp + a.band_width : 1.0;
+            double b0 = lb > c_lo[c] ? lb : c_lo[c], b1 = ub < c_hi[c] ? ub : c_hi[c];
+            if (b1 < b0) {
+                if (ub <= c_lo[c]) { b0 = lb; b1 = ub; }
+                else { b0 = c_lo[c]; b1 = c_hi[c]; }     // lb >= c_hi: the third case cannot occur (lb <= ub, c_lo < c_hi)
+            }
+            lo = (float)b0; hi = (float)b1;
+        }
+        targets[2 * n] = lo;
+        targets[2 * n + 1] = hi;
+        const float f = known ? a.freq[c] : nan;
+        weight[n] = f != f ? f : fminf(fmaxf(f, 0.2f), 0.8f);
+        keep[n] = c > 0 ? 1.f : 0.f;
+    }
+}
+
 }  // namespace dram
 
 using namespace dram;
@@ -963,4 +1060,33 @@ extern "C" int dram_bce_smooth_bwd(const float* p, const void* t, int t_kind, in
     else
         hipLaunchKernelGGL(bce_smooth_bwd_kernel<2>, grid, dim3(256), 0, st, p, (const float*)t, state, gout, (float)smooth, dp, n, vecp, vect, vecd);
     return check_launch("bce_smooth_bwd");
+}
+
+extern "C" size_t dram_intreg_targets_ws_bytes(int N, int64_t S) {
+    if (N <= 0 || S <= 0) return 0;
+    return (size_t)N * enc_blocks_max(N, S) * TGT_NSUM * sizeof(double);
+}
+
+extern "C" int dram_intreg_targets(const float* lobes, const float* lesions, const int* ctss, const float* freq,
+                                   double band_width, float* targets, float* weight, float* keep, void* ws,
+                                   size_t ws_bytes, int N, int64_t S, void* stream) {
+    DRAM_REQUIRE(lobes && lesions && ctss && freq && targets && weight && keep && ws, "intreg_targets: null pointer");
+    DRAM_REQUIRE(N > 0 && N <= 65535 && S > 0, "intreg_targets: bad dimensions");
+    DRAM_REQUIRE(((uintptr_t)ws & 7) == 0, "intreg_targets: workspace must be 8-byte aligned");
+    if (ws_bytes < dram_intreg_targets_ws_bytes(N, S)) {
+        set_error("intreg_targets: workspace too small");
+        return DRAM_EWS;
+    }
+    hipStream_t st = (hipStream_t)stream;
+    TargetsArgs a;
+    for (int k = 0; k < 6; ++k) a.freq[k] = freq[k];
+    a.band_width = band_width;
+    const bool v4 = enc_vec4(lobes, lesions, nullptr, S);
+    const int nblk = enc_blocks(N, S, v4 ? 4 : 1);
+    double* part = (double*)ws;
+    if (v4) hipLaunchKernelGGL(targets_partial_kernel<4>, dim3(nblk, N), dim3(256), 0, st, lobes, lesions, part, S, nblk);
+    else hipLaunchKernelGGL(targets_partial_kernel<1>, dim3(nblk, N), dim3(256), 0, st, lobes, lesions, part, S, nblk);
+    hipLaunchKernelGGL(targets_finalize_kernel, dim3(1), dim3(256), 0, st, (const double*)part, ctss, a, N, nblk, targets, weight,
+                       keep);
+    return check_launch("intreg_targets");
 }

@@ -79,6 +79,8 @@ SIGNATURES = {
     "dram_intreg_enc_loss_state_floats": (I, [I]),
     "dram_intreg_enc_loss_fwd": (I, [P, P, P, P, P, P, P, Z, I, L, P]),
     "dram_intreg_enc_loss_bwd": (I, [P, P, P, P, P, P, P, I, L, P]),
+    "dram_intreg_targets_ws_bytes": (Z, [I, L]),
+    "dram_intreg_targets": (I, [P, P, P, P, ctypes.c_double, P, P, P, P, Z, I, L, P]),
     "dram_prelu_fwd": (I, [P, P, P, I, I, I, L, P]),
     "dram_prelu_bwd_ws_bytes": (Z, [I, I, L]),
     "dram_prelu_bwd": (I, [P, P, P, P, P, P, Z, I, I, I, L, P]),

@@ -1042,6 +1042,35 @@ def intreg_enc_loss(dense, lobes, lesions, targets, weight):
     return IntRegEncLossFn.apply(dense, lobes, lesions, targets, weight)
 
 
+def intreg_targets(lobes, lesions, ctss, freq, band_width):
+    """The regression band, class weight and pseudo-label switch of a batch without a host read (csrc/loss.hip,
+    dram_intreg_targets): lobes, lesions [N,1,D,H,W] on the device, `ctss` an int32 device tensor of the N CT severity
+    scores, `freq` the six class frequencies (a host sequence: they travel with the launch), `band_width` a float.
+    Returns (targets[N,2], weight[N], keep[N]).  No gradient: the targets are data."""
+    lobes, lesions = _chk(lobes.detach(), "targets lobes", 5), _chk(lesions.detach(), "targets lesions", 5)
+    N = lobes.shape[0]
+    S = lobes.numel() // max(N, 1)
+    if lobes.shape[1] != 1 or lesions.shape != lobes.shape:
+        raise ValueError("intreg_targets: lobes / lesions must both be [N,1,D,H,W]")
+    if not isinstance(ctss, torch.Tensor) or not ctss.is_cuda or ctss.dtype != torch.int32 or ctss.numel() != N:
+        raise TypeError("intreg_targets: ctss must be an int32 device tensor with one score per sample")
+    if ctss.device != lobes.device or lesions.device != lobes.device:
+        raise RuntimeError("intreg_targets: lobes, lesions and ctss must be on one device")
+    freq = [float(f) for f in freq]
+    if len(freq) != 6:
+        raise ValueError("intreg_targets: six class frequencies expected")
+    ctss = ctss.contiguous()
+    dev = lobes.device
+    targets = torch.empty((N, 2), dtype=torch.float32, device=dev)
+    weight = torch.empty(N, dtype=torch.float32, device=dev)
+    keep = torch.empty(N, dtype=torch.float32, device=dev)
+    ws = _ws(_lib.lib.dram_intreg_targets_ws_bytes(N, S), dev)
+    fr = (ctypes.c_float * 6)(*freq)
+    call("dram_intreg_targets", _p(lobes), _p(lesions), _p(ctss), ctypes.cast(fr, ctypes.c_void_p), float(band_width),
+         _p(targets), _p(weight), _p(keep), _p(ws), ws.numel(), N, S, _stream())
+    return targets, weight, keep
+
+
 class SigmoidFn(Function):
     """F.sigmoid as a differentiable device op (the affine-consistency term compares probabilities,
     reference dram/metrics.py:434,445)."""

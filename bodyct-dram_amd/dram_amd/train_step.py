@@ -10,7 +10,8 @@ round-trips every sample through numpy (metrics.py:338-352) -- never synchronise
 (`oracle.dram_oracle.fused_loss_math` spells the same fused formulation with torch ops for the CPU tests
 against the reference's golden vectors).  The regression targets depend only on the data (lesion
 ratio, CT severity score), so they are computed when the batch is built, as the reference's data
-loader side would.
+loader side would.  The affine-consistency losses build a second, transformed batch inside every call: its targets
+come from the device masks by one more kernel pair of csrc/loss.hip (`Batch.on_device`), not from a host loop.
 
 `DeviceIntRegLoss` / `DeviceIntRegAffLoss` are the reference's two losses without the pseudo-label refinement
 (metrics.py:75-308: the same hinge plus an entropy term, one more kernel pair of csrc/loss.hip); they take the places of
@@ -68,10 +69,42 @@ class Batch:
         out = loader(loader.pack(chunks))
         return cls(out["#image"], out["#lobe_reference"], out["#pseudo_lesion_reference"], ctss, freq_map, band_width)
 
+    @classmethod
+    def on_device(cls, images, lobes, lesions, ctss_dev, freq_map, band_width=1e-2, ctss=None):
+        """A batch whose masks were made on the device (the transformed copy of the affine-consistency losses), built
+        WITHOUT a host read: one kernel pair (csrc/loss.hip, dram_intreg_targets) turns the two masks, the int32 device
+        tensor `ctss_dev` of the samples' CT severity scores (`ctss_device()` of the batch they came from) and the six
+        class frequencies into what `__init__` computes with a device-to-host copy and a Python loop.  For 0/1 masks
+        `targets`, `weight` and `keep` carry the same bits as `Batch(...)`'s.  `freq_map` stays on the host (a dict over
+        0..5 or a sequence of six floats): it travels with the launch.  Two differences, both outside what a training
+        batch holds: a sample with an empty lobe gets NaN targets (the host loop turns the 0/0 into the sample's class
+        interval), and a score outside 0..5 gives NaN targets and a NaN weight where the host raises KeyError.
+        `ctss`: the host list of the scores where the caller has one (kept as `.ctss`)."""
+        from . import functional as HF
+        b = object.__new__(cls)
+        b.images, b.lobes, b.lesions = images, lobes, lesions
+        b.ctss = None if ctss is None else [float(c) for c in ctss]
+        freq = [freq_map[k] for k in range(6)]
+        b.targets, b.weight, keep = HF.intreg_targets(lobes, lesions, ctss_dev, freq, band_width)
+        b.keep = keep.view(-1, 1, 1, 1, 1)
+        b._ctss_dev = ctss_dev
+        return b
+
+    def ctss_device(self):
+        """The CT severity scores as an int32 tensor on the batch's device: uploaded at the first call, kept after that
+        (micro-batches take slices of it), so that `on_device` batches derived from this one need no upload of their own."""
+        dev = getattr(self, "_ctss_dev", None)
+        if dev is None:
+            dev = self._ctss_dev = torch.tensor([int(c) for c in self.ctss], dtype=torch.int32).to(self.images.device)
+        return dev
+
     def micro(self, lo, hi):
         b = object.__new__(Batch)
         b.images, b.lobes, b.lesions = self.images[lo:hi], self.lobes[lo:hi], self.lesions[lo:hi]
-        b.ctss, b.targets, b.weight, b.keep = self.ctss[lo:hi], self.targets[lo:hi], self.weight[lo:hi], self.keep[lo:hi]
+        b.ctss = None if self.ctss is None else self.ctss[lo:hi]
+        b.targets, b.weight, b.keep = self.targets[lo:hi], self.weight[lo:hi], self.keep[lo:hi]
+        dev = getattr(self, "_ctss_dev", None)
+        b._ctss_dev = None if dev is None else dev[lo:hi]
         return b
 
     def augmented(self, aug):
@@ -82,6 +115,7 @@ class Batch:
         b = object.__new__(Batch)
         b.images, b.lobes, b.lesions = out["#image"], out["#lobes_reference"], out["#lesions_reference"]
         b.ctss, b.targets, b.weight, b.keep = self.ctss, self.targets, self.weight, self.keep
+        b._ctss_dev = getattr(self, "_ctss_dev", None)
         return b
 
     def __len__(self):
@@ -167,6 +201,17 @@ class DataParallelTrainer:
     Per-rank BatchNorm statistics (the reference's default "bn") need no exchange.  `p.grad` of every parameter is a view
     into its bucket after the step (no per-step torch.cat, no copy back).
 
+    Losses that run the model themselves (`calls_model = True`: DeviceIntRegAffRefineLoss, DeviceIntRegAffLoss, which
+    need the model on the batch and on a transformed copy of it) are called as `loss_fn(model, micro_batch, transform=T)`
+    instead of on the model's output, and may return any number of terms: `loss_factors` may be the reference's whole
+    LOSS_FACTORS ([2.0, 1.0, 0.5, 0.5]), of which the first len(terms) are used (job_runner.py:668-669).  The FIRST term is a
+    sum over samples and adds up; EVERY later term (aff, seg, enc) is a batch mean and enters with the micro-batch's share,
+    the rule -- and, for statistics of the micro-batch inside such a term, the documented deviation -- of `seg` above.
+    `step` returns all terms.  T is drawn ONCE per step (`loss_fn.draw()`) and passed to every micro-batch: a step is one
+    transform on the rank's batch, as in the reference.  Such a loss records two forward tapes per backward, so the engine's
+    gradient sink would see every parameter twice and `_grad_sink` refuses a second delivery once the bucket is sent: for
+    these losses the sink stays off and every bucket is reduced after the last backward, exactly the `overlap=False` path.
+
     `optimizer` is any torch.optim.Optimizer over the model's parameters; dram_amd.optim.Adam / AdamW / SGD (one HIP launch
     per parameter group, bucket views at any offset included) go in unchanged.
 
@@ -189,7 +234,8 @@ class DataParallelTrainer:
             _norm_kind(grad_norm_type)             # refuse an unsupported norm here, not at the first step
         self.overlap = bool(overlap)               # False: every bucket is reduced after the last backward (A/B, diagnostics)
         self.loss_fn = loss_fn or DeviceIntRegRefineLoss()
-        self.loss_factors = loss_factors           # LOSS_FACTORS[:2] of st_dram_ref.py:42
+        self.calls_model = bool(getattr(self.loss_fn, "calls_model", False))
+        self.loss_factors = loss_factors           # LOSS_FACTORS of st_dram_ref.py:42: the first len(terms) are used
         self.world = dist.get_world_size() if dist.is_available() and dist.is_initialized() else 1
         self.params = [p for p in model.parameters() if p.requires_grad]
         self.buckets = self._make_buckets(bucket_mb * (1 << 20))
@@ -280,32 +326,52 @@ class DataParallelTrainer:
         mb = n if not micro_batch else min(micro_batch, n)
         self.opt.zero_grad(set_to_none=True)
         try:
-            b = batch.micro(0, mb)
-            dense, refined = self.model(b.images, b.lobes)
-            reg, seg = self.loss_fn(dense, b, refined=None if refined is dense else refined)
-            (self.loss_factors[0] * reg + self.loss_factors[1] * seg).backward()
+            if self.calls_model:
+                batch.ctss_device()
+            terms = self._terms(batch.micro(0, mb), self.loss_fn.draw() if self.calls_model else None)
+            self._weighted(terms, None).backward()
         finally:
             self.opt.zero_grad(set_to_none=True)
 
+    def _terms(self, b, transform):
+        """The loss terms of one micro-batch, in either calling convention (see the class docstring)."""
+        if self.calls_model:
+            return tuple(self.loss_fn(self.model, b, transform=transform))
+        dense, refined = self.model(b.images, b.lobes)
+        return tuple(self.loss_fn(dense, b, refined=None if refined is dense else refined))
+
+    def _weighted(self, terms, share):
+        """sum_k loss_factors[k] * terms[k] (job_runner.py:668-669: the first len(terms) factors); every term but the first
+        times `share` where one is given."""
+        if len(self.loss_factors) < len(terms):
+            raise ValueError(f"the loss returns {len(terms)} terms, loss_factors has {len(self.loss_factors)}")
+        loss = self.loss_factors[0] * terms[0]
+        for f, t in zip(self.loss_factors[1:], terms[1:]):
+            loss = loss + (f * t if share is None else f * t * share)
+        return loss
+
     def step(self, batch, micro_batch=None, global_batch=None):
-        """Returns the (detached, device) loss components of this rank's batch: reg summed, seg weighted by
-        the share of the global batch.  `global_batch`: number of chunks over all ranks (default: every rank
-        holds as many as this one)."""
+        """Returns the (detached, device) loss components of this rank's batch, as many as the loss returns: the first
+        (reg) summed, every later one weighted by the share of the global batch.  `global_batch`: number of chunks over
+        all ranks (default: every rank holds as many as this one)."""
         n = len(batch)
         n_glob = int(global_batch) if global_batch else n * self.world
         mb = n if not micro_batch else min(micro_batch, n)
         self.opt.zero_grad(set_to_none=True)
         self._begin()
         self.overlapped_buckets = 0
-        tot_reg = tot_seg = None
+        transform = None
+        if self.calls_model:
+            transform = self.loss_fn.draw()        # ONE transform per step, the same for every micro-batch
+            batch.ctss_device()                    # (uploaded once per batch; the micro-batches take slices)
+        totals = None
         starts = list(range(0, n, mb))
         for lo in starts:
             b = batch.micro(lo, min(n, lo + mb))
-            dense, refined = self.model(b.images, b.lobes)
-            reg, seg = self.loss_fn(dense, b, refined=None if refined is dense else refined)
+            terms = self._terms(b, transform)
             share = len(b) / n_glob
-            loss = self.loss_factors[0] * reg + self.loss_factors[1] * seg * share
-            overlap = self.overlap and self.world > 1 and lo == starts[-1]
+            loss = self._weighted(terms, share)
+            overlap = self.overlap and not self.calls_model and self.world > 1 and lo == starts[-1]
             if overlap:
                 self.model.grad_sink = self._grad_sink
             try:
@@ -314,8 +380,8 @@ class DataParallelTrainer:
                 if overlap:
                     self.model.grad_sink = None
                     self.overlapped_buckets = sum(w is not None for w in self._works)
-            tot_reg = reg.detach() if tot_reg is None else tot_reg + reg.detach()
-            tot_seg = seg.detach() * share if tot_seg is None else tot_seg + seg.detach() * share
+            parts = [terms[0].detach()] + [t.detach() * share for t in terms[1:]]
+            totals = parts if totals is None else [a + p for a, p in zip(totals, parts)]
         self.allreduce_gradients()
         if self.max_grad_norm is None:
             self.opt.step()
@@ -326,7 +392,7 @@ class DataParallelTrainer:
             from .optim import clip_grad_norm_
             self.last_grad_norm = clip_grad_norm_(self.params, self.max_grad_norm, self.grad_norm_type)
             self.opt.step()
-        return tot_reg, tot_seg
+        return tuple(totals)
 
 
 class DeviceIntRegAffRefineLoss:
@@ -362,9 +428,18 @@ class DeviceIntRegAffRefineLoss:
         apply.p = chosen
         return apply
 
-    def __call__(self, model, batch):
+    calls_model = True      # DataParallelTrainer: call loss_fn(model, batch, transform=T), not loss_fn(model(batch), batch)
+
+    def draw(self):
+        """One random transform T, for `__call__(..., transform=T)`: every host-side random draw of the loss happens here."""
+        return self.get_affine_transform()
+
+    def __call__(self, model, batch, transform=None):
+        """`transform`: a T from `draw()` (the trainer passes one T to every micro-batch of a step); None draws one.  With a
+        given T the call reads nothing back from the device: the transformed copy's regression targets come from
+        `Batch.on_device`, the scores from `batch.ctss_device()` (uploaded once per batch)."""
         from . import functional as HF
-        T = self.get_affine_transform()
+        T = self.draw() if transform is None else transform
         aff_images = T({"#image": batch.images})["#image"]
         aff_lobes = T({"#reference": batch.lobes})["#reference"].contiguous()
         aff_lesions = T({"#reference": batch.lesions})["#reference"].contiguous()
@@ -372,7 +447,8 @@ class DeviceIntRegAffRefineLoss:
         reg, seg = self.loss(dense, batch, refined=refined)
         probs_T = T({"#image": HF.sigmoid(dense)})["#image"]
         cls_T = T({"#image": cls})["#image"]
-        aff = Batch(aff_images.detach(), aff_lobes, aff_lesions, batch.ctss, self.freq_map, band_width=self.band_width)
+        aff = Batch.on_device(aff_images.detach(), aff_lobes, aff_lesions, batch.ctss_device(), self.freq_map,
+                              band_width=self.band_width, ctss=batch.ctss)
         a_dense, a_refined, a_cls = model(aff.images, aff.lobes)
         a_reg, a_seg = self.loss(a_dense, aff, refined=a_refined)
         aff_loss = HF.masked_smooth_l1(probs_T, HF.sigmoid(a_dense), aff.lobes)
@@ -412,16 +488,24 @@ class DeviceIntRegAffLoss:
         apply.p = chosen
         return apply
 
-    def __call__(self, model, batch):
+    calls_model = True      # as DeviceIntRegAffRefineLoss
+
+    def draw(self):
+        """One random transform T, for `__call__(..., transform=T)`: every host-side random draw of the loss happens here."""
+        return self.get_affine_transform()
+
+    def __call__(self, model, batch, transform=None):
+        """`transform`: as DeviceIntRegAffRefineLoss.__call__."""
         from . import functional as HF
-        T = self.get_affine_transform()
+        T = self.draw() if transform is None else transform
         aff_images = T({"#image": batch.images})["#image"]
         aff_lobes = T({"#reference": batch.lobes})["#reference"].contiguous()
         aff_lesions = T({"#reference": batch.lesions})["#reference"].contiguous()
         dense = model(batch.images, batch.lobes)[0]
         reg, enc = self.loss(dense, batch)
         probs_T = T({"#image": HF.sigmoid(dense)})["#image"]
-        aff = Batch(aff_images.detach(), aff_lobes, aff_lesions, batch.ctss, self.freq_map, band_width=self.band_width)
+        aff = Batch.on_device(aff_images.detach(), aff_lobes, aff_lesions, batch.ctss_device(), self.freq_map,
+                              band_width=self.band_width, ctss=batch.ctss)
         a_dense = model(aff.images, aff.lobes)[0]
         a_reg, _ = self.loss(a_dense, aff)
         aff_loss = HF.masked_smooth_l1(probs_T, HF.sigmoid(a_dense), aff.lobes)

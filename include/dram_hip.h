@@ -365,6 +365,21 @@ int dram_intreg_enc_loss_fwd(const float* dense, const float* lobes, const float
 int dram_intreg_enc_loss_bwd(const float* dense, const float* lobes, const float* targets, const float* weight,
                              const float* state, const float* gout, float* ddense, int N, int64_t S, void* stream);
 
+/* ---- the regression targets of a batch on the device: IntRegLoss.get_labels (dram/metrics.py:122-138), the class weight
+ *      (172-174) and the pseudo-label switch (326-327), for a batch whose masks were made on the device (the transformed
+ *      copy of the affine-consistency losses) ----
+ * lobes, lesions: [N,1,D,H,W] (S = D*H*W); ctss: DEVICE int32[N], the CT severity scores 0..5; freq: HOST array of the six
+ * class frequencies (copied into the launch); band_width: the half width of the band.
+ * ratio = fp32(sum lesions*lobes) / fp32(sum lobes), one fp32 division of sums that are exact for 0/1 masks (fp64 partials
+ * added in a fixed order, no atomics); the band arithmetic in fp64 on that value, rounded once to fp32.
+ * targets[N][2] = the band, weight[N] = clamp(freq[ctss], 0.2, 0.8), keep[N] = ctss > 0 ? 1 : 0.  A sample with an empty
+ * lobe (0/0) gets NaN targets, a score outside 0..5 NaN targets and a NaN weight; the other samples are unaffected.
+ * ws: 8-byte aligned, dram_intreg_targets_ws_bytes(N, S) bytes. */
+size_t dram_intreg_targets_ws_bytes(int N, int64_t S);
+int dram_intreg_targets(const float* lobes, const float* lesions, const int* ctss, const float* freq, double band_width,
+                        float* targets, float* weight, float* keep, void* ws, size_t ws_bytes, int N, int64_t S,
+                        void* stream);
+
 /* ---- PCM local attention on the voxel grid: dram/models.py PCM.init_graph 221-258 (the
  *      neighbour graph becomes E stencil offsets), merge_func 259-331 (dot-product and geo families), compute_cross_x
  *      365-397, forward / update_all 333-363.
