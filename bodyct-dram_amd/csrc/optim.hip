@@ -1,5 +1,6 @@
-// The optimiser update of the training step (st_dram_ref.py: torch.optim.Adam; the SGD-with-momentum block beside it), gfx950:
-// multi-tensor Adam / AdamW / SGD, one launch per table of up to DRAM_OPTIM_TABLE_CAPACITY tensors.
+// The optimiser update of the training step (st_dram_ref.py: torch.optim.Adam; the SGD-with-momentum, AdaBound and RAdam lines
+// commented out beside it), gfx950: multi-tensor Adam / AdamW / SGD / RAdam / AdaBound, one launch per table of up to
+// DRAM_OPTIM_TABLE_CAPACITY tensors.
 //
 // The table travels in the kernel arguments (no device buffer, no copy, nothing to keep alive; the gradient pointers change
 // every step, so the host rebuilds it each step anyway).  The host gives every tensor cdiv(n, OCHUNK) consecutive blocks and
@@ -8,7 +9,8 @@
 // n % 4 elements one by one (span<false>); a tensor with any misaligned pointer -- a gradient that is a view into a flat
 // all-reduce bucket at an arbitrary offset -- takes span<false> throughout: one dword per lane, consecutive lanes on
 // consecutive addresses.  Each element is read and written by exactly one lane: no atomics, no LDS, deterministic.
-// HBM traffic per element: Adam 16 B read + 12 B written (amsgrad: +4 +4); SGD with momentum 12 B + 8 B.
+// HBM traffic per element: Adam, RAdam and AdaBound 16 B read + 12 B written (amsgrad / amsbound: +4 +4); SGD with momentum
+// 12 B + 8 B.
 //
 // Every product, sum, quotient and root below is one IEEE fp32 operation (fmaf: one rounding for a*b+c); the count of
 // roundings per quantity is what tests/optim_restatement.py bounds.
@@ -32,9 +34,10 @@ struct OptimEntry {            // 56 bytes
     const float* g;
     float* m;                  // Adam: exp_avg; SGD: momentum_buffer (NULL without momentum)
     float* v;                  // Adam: exp_avg_sq
-    float* vmax;               // Adam with amsgrad: max_exp_avg_sq, else NULL
+    float* vmax;               // Adam with amsgrad, AdaBound with amsbound: max_exp_avg_sq, else NULL
     unsigned n, first_block;
-    float s0, s1;              // Adam: lr / bc1, sqrt(bc2); SGD: s0 != 0 on the tensor's first step (buf = g')
+    float s0, s1;              // Adam: lr / bc1, sqrt(bc2); SGD: s0 != 0 on the tensor's first step (buf = g');
+                               // RAdam: the whole step factor, s1 != 0 when rectified; AdaBound: lr sqrt(bc2) / bc1
 };
 struct OptimTable {
     OptimEntry e[DRAM_OPTIM_TABLE_CAPACITY];
@@ -94,6 +97,64 @@ struct SgdRule {
             g = a.nesterov ? fmaf(a.mu, m, g) : m;
         }
         p = fmaf(-a.lr, g, p);
+    }
+};
+
+// RAdam (torch.optim.RAdam; the RAdam line of st_dram_ref.py's OPTIMIZER block).  Whether a tensor is rectified depends on its
+// step count alone, so the host decides and folds the whole step factor into s0; eps joins the RAW root, not Adam's
+// sqrt(v) / sqrt(bc2).
+struct RAdamScalars {
+    float beta1, omb1, beta2, omb2, eps, wd, decay;   // as AdamScalars
+    int decoupled, maximize;
+};
+struct RAdamRule {
+    RAdamScalars a;
+    float step, gscale;
+    bool rect, scaled;                                // scaled, gscale: set by optim_kernel
+    __device__ __forceinline__ void load(const OptimEntry& e) { step = e.s0; rect = e.s1 != 0.f; }
+    __device__ __forceinline__ bool reads_m() const { return true; }
+    __device__ __forceinline__ bool uses_m() const { return true; }
+    __device__ __forceinline__ bool uses_v() const { return true; }
+    __device__ __forceinline__ bool uses_vmax() const { return false; }
+    __device__ __forceinline__ void apply(float& p, float g, float& m, float& v, float&) const {
+        if (scaled) g = __fmul_rn(g, gscale);
+        if (a.maximize) g = -g;
+        if (a.decoupled) p = __fmul_rn(p, a.decay);
+        else if (a.wd != 0.f) g = fmaf(a.wd, p, g);
+        m = fmaf(a.beta1, m, __fmul_rn(a.omb1, g));
+        v = fmaf(a.beta2, v, __fmul_rn(a.omb2, __fmul_rn(g, g)));
+        const float upd = rect ? __fdiv_rn(m, __fadd_rn(__fsqrt_rn(v), a.eps)) : m;
+        p = fmaf(-step, upd, p);
+    }
+};
+
+// AdaBound (Luo et al. 2019; the adabound.AdaBound line of st_dram_ref.py's OPTIMIZER block).  lower and upper depend on the
+// step count and travel as launch scalars: the host issues one launch per distinct step count.  The clamp is written as two
+// comparisons so that a NaN quotient stays a NaN, as torch.clamp leaves it.
+struct AdaBoundScalars {
+    float beta1, omb1, beta2, omb2, eps, wd, lower, upper;
+    int amsbound;
+};
+struct AdaBoundRule {
+    AdaBoundScalars a;
+    float step_size, gscale;
+    bool has_vmax, scaled;                            // scaled, gscale: set by optim_kernel
+    __device__ __forceinline__ void load(const OptimEntry& e) { step_size = e.s0; has_vmax = a.amsbound != 0; }
+    __device__ __forceinline__ bool reads_m() const { return true; }
+    __device__ __forceinline__ bool uses_m() const { return true; }
+    __device__ __forceinline__ bool uses_v() const { return true; }
+    __device__ __forceinline__ bool uses_vmax() const { return has_vmax; }
+    __device__ __forceinline__ void apply(float& p, float g, float& m, float& v, float& vmax) const {
+        if (scaled) g = __fmul_rn(g, gscale);
+        if (a.wd != 0.f) g = fmaf(a.wd, p, g);
+        m = fmaf(a.beta1, m, __fmul_rn(a.omb1, g));
+        v = fmaf(a.beta2, v, __fmul_rn(a.omb2, __fmul_rn(g, g)));
+        float vuse = v;
+        if (has_vmax) { vmax = fmaxf(vmax, v); vuse = vmax; }
+        float rate = __fdiv_rn(step_size, __fadd_rn(__fsqrt_rn(vuse), a.eps));
+        rate = rate < a.lower ? a.lower : rate;
+        rate = rate > a.upper ? a.upper : rate;
+        p = fmaf(-rate, m, p);
     }
 };
 
@@ -370,6 +431,58 @@ extern "C" int dram_optim_sgd_scaled(const dram_optim_tensor* table, int count, 
 extern "C" int dram_optim_sgd(const dram_optim_tensor* table, int count, double lr, double momentum, double dampening,
                               double weight_decay, int nesterov, int maximize, void* stream) {
     return dram_optim_sgd_scaled(table, count, lr, momentum, dampening, weight_decay, nesterov, maximize, nullptr, stream);
+}
+
+extern "C" int dram_optim_radam_scaled(const dram_optim_tensor* table, int count, double lr, double beta1, double beta2,
+                                       double eps, double weight_decay, int decoupled, int maximize, const float* gscale,
+                                       void* stream) {
+    OptimTable t;
+    unsigned blocks = 0;
+    const int rc = optim_pack(table, count, true, true, false, "optim_radam", t, &blocks);
+    if (rc != DRAM_OK) return rc;
+    DRAM_REQUIRE(((uintptr_t)gscale & 3) == 0, "optim_radam: gscale not 4-byte aligned");
+    RAdamScalars s;
+    s.beta1 = (float)beta1; s.omb1 = (float)(1.0 - beta1);
+    s.beta2 = (float)beta2; s.omb2 = (float)(1.0 - beta2);
+    s.eps = (float)eps;
+    s.wd = (float)weight_decay;
+    s.decay = (float)(1.0 - lr * weight_decay);
+    s.decoupled = decoupled != 0 && weight_decay != 0.0;
+    s.maximize = maximize != 0;
+    hipLaunchKernelGGL((optim_kernel<RAdamRule, RAdamScalars>), dim3(blocks), dim3(256), 0, (hipStream_t)stream, t, s, gscale);
+    return check_launch("optim_radam");
+}
+
+extern "C" int dram_optim_radam(const dram_optim_tensor* table, int count, double lr, double beta1, double beta2, double eps,
+                                double weight_decay, int decoupled, int maximize, void* stream) {
+    return dram_optim_radam_scaled(table, count, lr, beta1, beta2, eps, weight_decay, decoupled, maximize, nullptr, stream);
+}
+
+extern "C" int dram_optim_adabound_scaled(const dram_optim_tensor* table, int count, double beta1, double beta2, double eps,
+                                          double weight_decay, int amsbound, double lower, double upper, const float* gscale,
+                                          void* stream) {
+    OptimTable t;
+    unsigned blocks = 0;
+    const int rc = optim_pack(table, count, true, true, amsbound != 0, "optim_adabound", t, &blocks);
+    if (rc != DRAM_OK) return rc;
+    DRAM_REQUIRE(((uintptr_t)gscale & 3) == 0, "optim_adabound: gscale not 4-byte aligned");
+    DRAM_REQUIRE(lower <= upper, "optim_adabound: lower bound %g above upper bound %g", lower, upper);
+    AdaBoundScalars s;
+    s.beta1 = (float)beta1; s.omb1 = (float)(1.0 - beta1);
+    s.beta2 = (float)beta2; s.omb2 = (float)(1.0 - beta2);
+    s.eps = (float)eps;
+    s.wd = (float)weight_decay;
+    s.lower = (float)lower;
+    s.upper = (float)upper;
+    s.amsbound = amsbound != 0;
+    hipLaunchKernelGGL((optim_kernel<AdaBoundRule, AdaBoundScalars>), dim3(blocks), dim3(256), 0, (hipStream_t)stream, t, s,
+                       gscale);
+    return check_launch("optim_adabound");
+}
+
+extern "C" int dram_optim_adabound(const dram_optim_tensor* table, int count, double beta1, double beta2, double eps,
+                                   double weight_decay, int amsbound, double lower, double upper, void* stream) {
+    return dram_optim_adabound_scaled(table, count, beta1, beta2, eps, weight_decay, amsbound, lower, upper, nullptr, stream);
 }
 
 extern "C" size_t dram_optim_grad_norm_partials(const dram_optim_tensor* table, int count) {

@@ -5,7 +5,7 @@ Host side of libdram_hip.so: ctypes binding (`_lib`), autograd Functions
 the reference's flat `parts.py` / `models.py` live one directory up.
 """
 from . import _lib, functional, modules, optim  # noqa: F401
-from .optim import SGD, Adam, AdamW  # noqa: F401
+from .optim import SGD, AdaBound, Adam, AdamW, RAdam  # noqa: F401
 
 # the augmentation transforms of `augment`, importable from here; the module is loaded on first use
 _AUGMENT = ("GaussianBlur", "RandomMaskOut", "RandomFlip", "RandomRotate90", "GaussianAddictive", "IntensityInverse",
@@ -17,7 +17,7 @@ _AUGMENT = ("GaussianBlur", "RandomMaskOut", "RandomFlip", "RandomRotate90", "Ga
 # the segmentation losses of `losses`, the same way
 _LOSSES = ("BootBinCrossEntropy", "BinaryCrossEntropySmooth")
 
-__all__ = ["_lib", "functional", "modules", "optim", "Adam", "AdamW", "SGD", *_AUGMENT, *_LOSSES]
+__all__ = ["_lib", "functional", "modules", "optim", "Adam", "AdamW", "SGD", "RAdam", "AdaBound", *_AUGMENT, *_LOSSES]
 
 
 def __getattr__(name):

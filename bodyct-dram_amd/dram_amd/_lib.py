@@ -162,12 +162,16 @@ SIGNATURES = {
     "dram_optim_table_capacity": (I, []),
     "dram_optim_adam": (I, [P, I] + [ctypes.c_double] * 5 + [I, I, I, P]),
     "dram_optim_sgd": (I, [P, I] + [ctypes.c_double] * 4 + [I, I, P]),
+    "dram_optim_radam": (I, [P, I] + [ctypes.c_double] * 5 + [I, I, P]),
+    "dram_optim_adabound": (I, [P, I] + [ctypes.c_double] * 4 + [I] + [ctypes.c_double] * 2 + [P]),
     # global-norm gradient clipping over the same tables
     "dram_optim_grad_norm_partials": (Z, [P, I]),
     "dram_optim_grad_norm": (I, [P, I, I, P, L, P]),
     "dram_optim_grad_norm_finish": (I, [P, L, I, ctypes.c_double, P, P]),
     "dram_optim_adam_scaled": (I, [P, I] + [ctypes.c_double] * 5 + [I, I, I, P, P]),
     "dram_optim_sgd_scaled": (I, [P, I] + [ctypes.c_double] * 4 + [I, I, P, P]),
+    "dram_optim_radam_scaled": (I, [P, I] + [ctypes.c_double] * 5 + [I, I, P, P]),
+    "dram_optim_adabound_scaled": (I, [P, I] + [ctypes.c_double] * 4 + [I] + [ctypes.c_double] * 2 + [P, P]),
     "dram_optim_grad_scale": (I, [P, I, P, P]),
 }
 

@@ -1,17 +1,19 @@
-"""Device optimisers: `Adam`, `AdamW` and `SGD` whose update is one HIP launch per parameter group (csrc/optim.hip) in
-place of ATen's dozen foreach launches over every tensor of the group.
+"""Device optimisers: `Adam`, `AdamW`, `SGD`, `RAdam` and `AdaBound` whose update is one HIP launch per parameter group
+(csrc/optim.hip) in place of ATen's dozen foreach launches over every tensor of the group.
 
 The reference trains with `torch.optim.Adam(lr=1e-4)` under `ExponentialLR(gamma=0.9)` (st_dram_ref.py; an SGD-with-momentum
 block is commented out beside it) and `job_runner.py` saves and reloads `optimizer.state_dict()` with every checkpoint.  The
 classes here derive from torch's own and replace `step()` alone: constructor arguments, their validation, `param_groups`, the
 per-parameter state (keys, dtypes, devices; `step` stays torch's fp32 scalar on the host) and so `state_dict()` /
 `load_state_dict()` are torch's, and a checkpoint written by either loads into the other.  `lr` is read from `param_groups`
-at every step, so LR schedulers work unchanged.
+at every step, so LR schedulers work unchanged.  `RAdam` (the settings file's engine.models.optimizer.RAdam line) derives
+from torch.optim.RAdam in the same way.  `AdaBound` (its adabound.AdaBound line) has no torch counterpart: it is a
+torch.optim.Optimizer with the constructor, state keys and arithmetic of the `adabound` package.
 
 `step()` builds a host table of (p, grad, exp_avg, exp_avg_sq[, max_exp_avg_sq]) pointers and the per-parameter bias
 corrections -- the gradient pointers change every step under `zero_grad(set_to_none=True)` -- and hands it to
-`dram_optim_adam` / `dram_optim_sgd` in chunks of `TABLE_CAPACITY` tensors, on the current stream.  It never synchronises
-with the device and reads no device value; the table travels in the kernel arguments, so there is no buffer to copy or keep
+`dram_optim_adam` / `dram_optim_sgd` / `dram_optim_radam` / `dram_optim_adabound` in chunks of `TABLE_CAPACITY` tensors,
+on the current stream.  It never synchronises with the device and reads no device value; the table travels in the kernel arguments, so there is no buffer to copy or keep
 alive.  (A captured graph would replay one step's pointers and bias corrections: graph-captured steps are not supported.)
 Like every op of this package there is no fallback: parameters and gradients must be dense fp32 on a ROCm device.
 
@@ -28,7 +30,7 @@ import torch
 
 from ._lib import call, lib
 
-__all__ = ["Adam", "AdamW", "SGD", "TABLE_CAPACITY", "clip_grad_norm_"]
+__all__ = ["Adam", "AdamW", "SGD", "RAdam", "AdaBound", "TABLE_CAPACITY", "clip_grad_norm_"]
 
 TABLE_CAPACITY = int(lib.dram_optim_table_capacity())   # tensors per launch (the table is a kernel argument)
 
@@ -284,6 +286,145 @@ class AdamW(_AdamStep, torch.optim.AdamW):
     def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=1e-2, amsgrad=False, *, maximize=False):
         _no_tensor_lr(lr)
         super().__init__(params, lr, betas, eps, weight_decay, amsgrad, maximize=maximize)
+
+
+class RAdam(_GradClip, torch.optim.RAdam):
+    """torch.optim.RAdam (arguments, validation, state and state dict) with the update on csrc/optim.hip.  Whether a tensor
+    takes the rectified update depends on its step count alone: the host decides per tensor and hands the kernel one step
+    factor."""
+
+    def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=0, decoupled_weight_decay=False, *,
+                 maximize=False):
+        _no_tensor_lr(lr)
+        super().__init__(params, lr, betas, eps, weight_decay, decoupled_weight_decay, maximize=maximize)
+
+    def __setstate__(self, state):
+        super().__setstate__(state)
+        for group in self.param_groups:                # a checkpoint of a capturable torch optimiser
+            group["foreach"], group["capturable"], group["differentiable"] = None, False, False
+            for p in group["params"]:
+                s = self.state.get(p, {}).get("step")
+                if torch.is_tensor(s) and s.is_cuda:
+                    self.state[p]["step"] = s.detach().to("cpu", torch.float32)
+
+    @torch.no_grad()
+    def step(self, closure=None):
+        loss = None
+        if closure is not None:
+            with torch.enable_grad():
+                loss = closure()
+        name = "dram_amd.optim.RAdam"
+        pairs, gscale = self._clip_pairs(name)
+        for gi, group in enumerate(self.param_groups):
+            lr = group["lr"]
+            _no_tensor_lr(lr)
+            beta1, beta2 = (float(b) for b in group["betas"])
+            rho_inf = 2.0 / (1.0 - beta2) - 1.0
+            rows = []
+            for p, g in (_with_grad(group, name) if pairs is None else pairs[gi]):
+                state = self.state[p]
+                if len(state) == 0:
+                    state["step"] = torch.tensor(0.0, dtype=torch.float32)
+                    state["exp_avg"] = torch.zeros_like(p, memory_format=torch.preserve_format)
+                    state["exp_avg_sq"] = torch.zeros_like(p, memory_format=torch.preserve_format)
+                step = _host_step(state, name)
+                step += 1
+                t = float(step)
+                bc1, bc2 = 1.0 - beta1 ** t, 1.0 - beta2 ** t
+                rho_t = rho_inf - 2.0 * t * beta2 ** t / bc2
+                if rho_t > 5.0:
+                    rect = math.sqrt((rho_t - 4.0) * (rho_t - 2.0) * rho_inf / ((rho_inf - 4.0) * (rho_inf - 2.0) * rho_t))
+                    s0, s1 = float(lr) * rect * math.sqrt(bc2) / bc1, 1.0
+                else:
+                    s0, s1 = float(lr) / bc1, 0.0
+                rows.append((p.device, p, g, _chk_state(state["exp_avg"], p, name), _chk_state(state["exp_avg_sq"], p, name),
+                             None, s0, s1))
+            _launch("dram_optim_radam", rows, float(lr), beta1, beta2, float(group["eps"]), float(group["weight_decay"]),
+                    int(bool(group["decoupled_weight_decay"])), int(bool(group["maximize"])), gscale=gscale)
+        return loss
+
+
+class AdaBound(_GradClip, torch.optim.Optimizer):
+    """AdaBound (Luo et al. 2019) with the constructor, the state and the arithmetic of the `adabound` package (0.0.5), the
+    update on csrc/optim.hip:
+
+        g' = g + wd p;  m = b1 m + (1 - b1) g';  v = b2 v + (1 - b2) g'^2;  vuse = amsbound ? (vmax = max(vmax, v)) : v
+        p -= clamp(lr sqrt(bc2) / bc1 / (sqrt(vuse) + eps), lower, upper) * m
+        lower = final (1 - 1 / (gamma t + 1)),  upper = final (1 + 1 / (gamma t)),  final = final_lr * lr / base_lr
+
+    `base_lrs` holds every group's lr at construction (an attribute, not in state_dict(), as in the package), so an LR
+    scheduler scales the bounds with the rate.  State per parameter: `step` (a host fp32 scalar tensor; an int from a
+    checkpoint the package wrote is taken over), `exp_avg`, `exp_avg_sq` and, with amsbound, `max_exp_avg_sq`.  The bounds
+    depend on the step count and are launch scalars: a group whose parameters all have the same count -- the ordinary case
+    -- is one launch, and every further distinct count one more."""
+
+    def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), final_lr=0.1, gamma=1e-3, eps=1e-8, weight_decay=0,
+                 amsbound=False):
+        _no_tensor_lr(lr)
+        if not 0.0 <= lr:
+            raise ValueError(f"Invalid learning rate: {lr}")
+        if not 0.0 <= eps:
+            raise ValueError(f"Invalid epsilon value: {eps}")
+        if not 0.0 <= betas[0] < 1.0:
+            raise ValueError(f"Invalid beta parameter at index 0: {betas[0]}")
+        if not 0.0 <= betas[1] < 1.0:
+            raise ValueError(f"Invalid beta parameter at index 1: {betas[1]}")
+        if not 0.0 <= final_lr:
+            raise ValueError(f"Invalid final learning rate: {final_lr}")
+        if not 0.0 <= gamma < 1.0:
+            raise ValueError(f"Invalid gamma parameter: {gamma}")
+        defaults = dict(lr=lr, betas=betas, final_lr=final_lr, gamma=gamma, eps=eps, weight_decay=weight_decay,
+                        amsbound=amsbound)
+        super().__init__(params, defaults)
+        self.base_lrs = [group["lr"] for group in self.param_groups]
+
+    def __setstate__(self, state):
+        super().__setstate__(state)
+        for group in self.param_groups:
+            group.setdefault("amsbound", False)
+
+    def add_param_group(self, param_group):
+        super().add_param_group(param_group)
+        if hasattr(self, "base_lrs"):                  # a group added after construction: its lr then is its base
+            self.base_lrs.append(self.param_groups[-1]["lr"])
+
+    @torch.no_grad()
+    def step(self, closure=None):
+        loss = None
+        if closure is not None:
+            with torch.enable_grad():
+                loss = closure()
+        name = "dram_amd.optim.AdaBound"
+        pairs, gscale = self._clip_pairs(name)
+        for gi, (group, base_lr) in enumerate(zip(self.param_groups, self.base_lrs)):
+            lr = group["lr"]
+            _no_tensor_lr(lr)
+            beta1, beta2 = (float(b) for b in group["betas"])
+            amsbound = bool(group["amsbound"])
+            gamma = float(group["gamma"])
+            final = float(group["final_lr"]) * float(lr) / float(base_lr)
+            by_step = {}
+            for p, g in (_with_grad(group, name) if pairs is None else pairs[gi]):
+                state = self.state[p]
+                if len(state) == 0:
+                    state["step"] = torch.tensor(0.0, dtype=torch.float32)
+                    state["exp_avg"] = torch.zeros_like(p, memory_format=torch.preserve_format)
+                    state["exp_avg_sq"] = torch.zeros_like(p, memory_format=torch.preserve_format)
+                    if amsbound:
+                        state["max_exp_avg_sq"] = torch.zeros_like(p, memory_format=torch.preserve_format)
+                step = _host_step(state, name)
+                step += 1
+                t = float(step)
+                by_step.setdefault(t, []).append(
+                    (p.device, p, g, _chk_state(state["exp_avg"], p, name), _chk_state(state["exp_avg_sq"], p, name),
+                     _chk_state(state["max_exp_avg_sq"], p, name) if amsbound else None,
+                     float(lr) * math.sqrt(1.0 - beta2 ** t) / (1.0 - beta1 ** t), 0.0))
+            for t, rows in by_step.items():
+                lower = final * (1.0 - 1.0 / (gamma * t + 1.0))
+                upper = final * (1.0 + 1.0 / (gamma * t)) if gamma != 0.0 else math.inf
+                _launch("dram_optim_adabound", rows, beta1, beta2, float(group["eps"]), float(group["weight_decay"]),
+                        int(amsbound), lower, upper, gscale=gscale)
+        return loss
 
 
 class SGD(_GradClip, torch.optim.SGD):

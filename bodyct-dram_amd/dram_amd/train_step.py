@@ -212,8 +212,8 @@ class DataParallelTrainer:
     gradient sink would see every parameter twice and `_grad_sink` refuses a second delivery once the bucket is sent: for
     these losses the sink stays off and every bucket is reduced after the last backward, exactly the `overlap=False` path.
 
-    `optimizer` is any torch.optim.Optimizer over the model's parameters; dram_amd.optim.Adam / AdamW / SGD (one HIP launch
-    per parameter group, bucket views at any offset included) go in unchanged.
+    `optimizer` is any torch.optim.Optimizer over the model's parameters; dram_amd.optim.Adam / AdamW / SGD / RAdam /
+    AdaBound (one HIP launch per parameter group, bucket views at any offset included) go in unchanged.
 
     `max_grad_norm` (default None: no clipping, the step as it always was) clips the global gradient norm of kind
     `grad_norm_type` (2.0 or inf) on the device: the norm is that of the SUMMED gradient, after the all-reduce, i.e. of the

@@ -774,7 +774,18 @@ int dram_chunk_prepare(const int16_t* scans, const uint8_t* lobes, const uint8_t
  * dram_optim_sgd (torch.optim.SGD's rule): g' = maximize ? -g : g;  g' += weight_decay * p;  with momentum != 0:
  *     buf = s0 != 0 ? g' : momentum * buf + (1 - dampening) * g';  g' = nesterov ? g' + momentum * buf : buf;   p -= lr * g'.
  *   m: momentum_buffer (ignored when momentum == 0; s0 != 0 marks the tensor's first step, where buf need not be initialised);
- *   v, vmax, s1 unused. ---- */
+ *   v, vmax, s1 unused.
+ * dram_optim_radam (torch.optim.RAdam's rule; st_dram_ref.py:99 "engine.models.optimizer.RAdam", whose rectified branch it is):
+ *     g', the weight decay (decoupled or not), m and v as for dram_optim_adam;
+ *     p -= s0 * (s1 != 0 ? m / (sqrt(v) + eps) : m)       eps joins the RAW root (Adam: sqrt(v) / sqrt(bc2) + eps)
+ *   with, formed by the caller in double: rho_inf = 2 / (1 - beta2) - 1, rho_t = rho_inf - 2 t beta2^t / bc2; rectified
+ *   (rho_t > 5, a function of t alone): s0 = lr * rect * sqrt(bc2) / bc1, rect = sqrt((rho_t - 4)(rho_t - 2) rho_inf /
+ *   ((rho_inf - 4)(rho_inf - 2) rho_t)), s1 != 0; otherwise s0 = lr / bc1, s1 = 0.  vmax unused.
+ * dram_optim_adabound (Luo et al. 2019 as the adabound package 0.0.5 evaluates it; st_dram_ref.py:81 "adabound.AdaBound"):
+ *     g' = g + weight_decay * p;  m, v as above;  vuse = amsbound ? (vmax = max(vmax, v)) : v;
+ *     p -= clamp(s0 / (sqrt(vuse) + eps), lower, upper) * m      with s0 = lr * sqrt(bc2) / bc1 formed by the caller in double.
+ *   lower = final (1 - 1 / (gamma t + 1)) and upper = final (1 + 1 / (gamma t)), final = final_lr * lr / base_lr, depend on t and
+ *   are launch scalars (lower <= upper): the caller issues one launch per distinct step count.  A NaN quotient stays a NaN. ---- */
 #define DRAM_OPTIM_TABLE_CAPACITY 64
 typedef struct dram_optim_tensor {
     float* p;
@@ -791,6 +802,10 @@ int dram_optim_adam(const dram_optim_tensor* table, int count, double lr, double
                     double weight_decay, int decoupled, int amsgrad, int maximize, void* stream);
 int dram_optim_sgd(const dram_optim_tensor* table, int count, double lr, double momentum, double dampening,
                    double weight_decay, int nesterov, int maximize, void* stream);
+int dram_optim_radam(const dram_optim_tensor* table, int count, double lr, double beta1, double beta2, double eps,
+                     double weight_decay, int decoupled, int maximize, void* stream);
+int dram_optim_adabound(const dram_optim_tensor* table, int count, double beta1, double beta2, double eps, double weight_decay,
+                        int amsbound, double lower, double upper, void* stream);
 
 /* ---- global-norm gradient clipping (torch.nn.utils.clip_grad_norm_) over the same tables: of every entry only g and n are
  *      read (1 <= n < 2^31, g 4-byte aligned at any offset: 16-byte accesses where g is 16-byte aligned, one element per lane
@@ -806,7 +821,8 @@ int dram_optim_sgd(const dram_optim_tensor* table, int count, double lr, double 
  *     out[0] = total_norm = kind 2: (float)sqrt(sum), kind inf: max;
  *     out[1] = clip_coef  = c > 1 ? 1 : c  with c = (float)max_norm / (total_norm + 1e-6f), every operation in fp32;
  *   a NaN norm gives a NaN coefficient and an infinite norm the coefficient 0, as torch.clamp(max=1) leaves them.
- * dram_optim_adam_scaled / dram_optim_sgd_scaled: dram_optim_adam / dram_optim_sgd with every gradient element replaced by the
+ * dram_optim_adam_scaled / dram_optim_sgd_scaled / dram_optim_radam_scaled / dram_optim_adabound_scaled: the entry of the same
+ *   name without the suffix, with every gradient element replaced by the
  *   fp32 product g * gscale[0] before anything else (maximize, weight decay, ...); gscale is a DEVICE pointer (out + 1 above),
  *   read once per block; the gradient buffer is not written.  gscale == NULL: bit for bit the unscaled entry.
  * dram_optim_grad_scale: g[i] = g[i] * gscale[0] in place (the table's g is written despite its const).
@@ -821,6 +837,10 @@ int dram_optim_adam_scaled(const dram_optim_tensor* table, int count, double lr,
                            double weight_decay, int decoupled, int amsgrad, int maximize, const float* gscale, void* stream);
 int dram_optim_sgd_scaled(const dram_optim_tensor* table, int count, double lr, double momentum, double dampening,
                           double weight_decay, int nesterov, int maximize, const float* gscale, void* stream);
+int dram_optim_radam_scaled(const dram_optim_tensor* table, int count, double lr, double beta1, double beta2, double eps,
+                            double weight_decay, int decoupled, int maximize, const float* gscale, void* stream);
+int dram_optim_adabound_scaled(const dram_optim_tensor* table, int count, double beta1, double beta2, double eps,
+                               double weight_decay, int amsbound, double lower, double upper, const float* gscale, void* stream);
 int dram_optim_grad_scale(const dram_optim_tensor* table, int count, const float* gscale, void* stream);
 
 #ifdef __cplusplus

@@ -11,6 +11,10 @@ Global-norm clipping (max_norm 1.0, the 2-norm; the random gradients have norm ~
 beside them: the clipped fused step (set_grad_clip), dram_amd.optim.clip_grad_norm_ followed by the plain step, and
 torch.nn.utils.clip_grad_norm_ followed by torch.optim.Adam.step().  Clipping in place shrinks the gradients from repetition
 to repetition; none of the kernels' work depends on their values.
+dram_amd.optim.RAdam and AdaBound are timed in the same process, plain and clipped: they move the same 28 bytes per element as
+Adam, so the Adam time of the same run is what they are held against (`*_over_adam`), beside torch.optim.RAdam with its
+defaults and with foreach=True.  AdaBound has no torch counterpart.  Every optimiser is stepped 6 times before it is timed,
+so that RAdam is timed in its rectified branch (the one with the root and the quotient).
 Prints one JSON line.
 """
 import argparse
@@ -39,8 +43,9 @@ def main():
     dev = torch.device("cuda")
     st = torch.cuda.current_stream().cuda_stream
 
-    def timed(fn, reps=args.reps):
-        fn()
+    def timed(fn, reps=args.reps, warm=1):
+        for _ in range(warm):
+            fn()
         torch.cuda.synchronize()
         ms = []
         for _ in range(reps):
@@ -89,8 +94,8 @@ def main():
                 off += k
         return out
 
-    def fused_clip(ps):
-        opt = optim.Adam(ps, lr=1e-4)
+    def fused_clip(ps, cls=optim.Adam, **kw):
+        opt = cls(ps, lr=1e-4, **kw)
         opt.set_grad_clip(1.0)
         return opt
 
@@ -108,6 +113,12 @@ def main():
               "dram_amd clip_grad_norm_ + Adam": lambda ps: ClipThenStep(optim.clip_grad_norm_, optim.Adam(ps, lr=1e-4), ps),
               "torch clip_grad_norm_ + Adam": lambda ps: ClipThenStep(torch.nn.utils.clip_grad_norm_,
                                                                       torch.optim.Adam(ps, lr=1e-4), ps)}
+    makers.update({"dram_amd.optim.RAdam": lambda ps: optim.RAdam(ps, lr=1e-4),
+                   "dram_amd.optim.RAdam + set_grad_clip": lambda ps: fused_clip(ps, optim.RAdam),
+                   "torch.optim.RAdam": lambda ps: torch.optim.RAdam(ps, lr=1e-4),
+                   "torch.optim.RAdam(foreach=True)": lambda ps: torch.optim.RAdam(ps, lr=1e-4, foreach=True),
+                   "dram_amd.optim.AdaBound": lambda ps: optim.AdaBound(ps, lr=1e-4, final_lr=0.01),
+                   "dram_amd.optim.AdaBound + set_grad_clip": lambda ps: fused_clip(ps, optim.AdaBound, final_lr=0.01)})
     try:
         torch.optim.Adam([torch.zeros(1, device=dev, requires_grad=True)], fused=True)
         makers["torch.optim.Adam(fused=True)"] = lambda ps: torch.optim.Adam(ps, lr=1e-4, fused=True)
@@ -123,7 +134,7 @@ def main():
             for p, g in zip(ps, gs):
                 p.grad = g
             opt = make(ps)
-            r = timed(opt.step)
+            r = timed(opt.step, warm=6)
             r["fraction_of_copy_rate"] = ideal_ms / r["ms_median"]
             rec[name] = r
             del opt, ps, gs
@@ -139,13 +150,20 @@ def main():
         rec["clipped_over_torch_clip_then_step"] = clip["ms_median"] / tclip["ms_median"]
         rec["clipped_no_slower_than_torch_clip_then_step_within_spread"] = clip["ms_median"] <= tclip["ms_median"] + max(
             clip["ms_max"] - clip["ms_min"], tclip["ms_max"] - tclip["ms_min"])
+        for k in ("RAdam", "AdaBound"):
+            plain, clipped = rec[f"dram_amd.optim.{k}"], rec[f"dram_amd.optim.{k} + set_grad_clip"]
+            rec[f"{k.lower()}_over_adam"] = plain["ms_median"] / ours["ms_median"]
+            rec[f"{k.lower()}_clipped_over_adam_clipped"] = clipped["ms_median"] / clip["ms_median"]
+        rec["radam_over_torch_default"] = rec["dram_amd.optim.RAdam"]["ms_median"] / rec["torch.optim.RAdam"]["ms_median"]
+        rec["radam_over_torch_foreach"] = (rec["dram_amd.optim.RAdam"]["ms_median"]
+                                           / rec["torch.optim.RAdam(foreach=True)"]["ms_median"])
         result["layouts"][layout] = rec
     line = json.dumps(result)
     print(line, flush=True)
     for layout, rec in result["layouts"].items():
         for name in makers:
             r = rec[name]
-            print(f"{layout:>13} {name:<30} {r['ms_median']:7.3f} ms (min {r['ms_min']:.3f}, max {r['ms_max']:.3f})  "
+            print(f"{layout:>13} {name:<40} {r['ms_median']:7.3f} ms (min {r['ms_min']:.3f}, max {r['ms_max']:.3f})  "
                   f"{r['fraction_of_copy_rate']:.3f} of 28 B/element at the copy rate ({ideal_ms:.3f} ms)", flush=True)
     if args.out:
         os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
