@@ -1,0 +1,267 @@
+"""tests/infer_kernel_cases.py against the oracle and torch on the CPU: every restatement that tests/test_gpu_infer_kernels.py
+compares a kernel of csrc/infer.hip with is shown here to be the reference's operation, so that the GPU tests cannot pass
+against a wrong reference.  Host code only."""
+from fractions import Fraction
+
+import numpy as np
+import pytest
+import torch
+import torch.nn.functional as F
+
+import infer_kernel_cases as K
+from oracle import dram_oracle as O
+
+
+# ------------------------------------------------------------------------------------------------ shapes
+def test_shapes_reach_the_paths_they_are_meant_for():
+    """The kernel constants the inputs are sized against (csrc/infer.hip)."""
+    cdiv = lambda a, b: -(-a // b)
+    assert cdiv(K.N_PAST_HIST_CAP, 256 * 16) > 2048 and K.N_PAST_HIST_CAP % (256 * 16) not in (0, 256)
+    assert cdiv(K.N_PAST_THRESHOLD_CAP, 256) > 4096 and K.N_PAST_THRESHOLD_CAP % 256 != 0
+    assert K.N_BIN_EDGES == 256 * 16 + 77
+    m = K.bbox_band_map(32)
+    assert m.shape[1] > K.BBOX_ROWS and m.shape[2] % 16 == 0 and K.bbox_band_map(33).shape[2] % 16 == 1
+    assert set(np.unique(m[:, K.BBOX_ROWS:])) >= {1, 3, 5} and 3 not in m[:, :K.BBOX_ROWS] and 1 in m[:, :K.BBOX_ROWS]
+    assert (m[0, 10, 16:32] == 2).all() and len(np.unique(m[0, 10, 0:16])) > 1
+    assert (m == 4).sum() == 1 and (m == 5).sum() == 1 and m[0, 0, 0] == 4 and m[-1, -1, -1] == 5
+    e = K.bbox_band_map(32, True)
+    assert {7, 200} <= set(np.unique(e)) and (e[2, 30, 16:32] == 200).all()
+    assert K.CHUNK_R ** 3 % 256 != 0 and len(K.CHUNKS_8) == K.MAX_CHUNKS and len(set(K.CHUNKS_8)) == K.MAX_CHUNKS
+    D, H, W = K.VOLUME
+    for c in K.CHUNKS_ABC + K.CHUNKS_8 + K.PASTE_CHUNKS:
+        assert min(c[:3]) > 0 and c[0] + c[3] <= D and c[1] + c[4] <= H and c[2] + c[5] <= W       # non-zero origins, inside
+    a, b, c = K.CHUNKS_ABC
+    assert a[3] < K.CHUNK_R < min(a[4], a[5]) and c[5] == 4 and a[6] != b[6]
+    overlap = lambda p, q: all(max(p[k], q[k]) < min(p[k] + p[k + 3], q[k] + q[k + 3]) for k in range(3))
+    assert overlap(a, b) and overlap(K.PASTE_CHUNKS[0], K.PASTE_CHUNKS[1])
+    assert [tuple(p[3:6]) for p in K.PASTE_CHUNKS[:2]] == [(5, 20, 31), (9, 7, 2)] and K.PASTE_CHUNKS[2][3] == 1
+    assert (5 * 20 * 31) % 256 != 0
+    dense, lobe, htp0 = K.paste_inputs()
+    p, q = K.PASTE_CHUNKS[:2]
+    both = tuple(slice(max(p[k], q[k]), min(p[k] + p[k + 3], q[k] + q[k + 3])) for k in range(3))
+    assert (lobe[both] == p[6]).any() and (lobe[both] == q[6]).any()                # each label occurs in the overlap
+    assert len(np.unique(htp0)) == htp0.size and htp0.max() < 0
+    s = 1.0 / (1.0 + np.exp(-dense.astype(np.float64)))
+    assert s.min() < 0.01 and s.max() > 0.99 and np.abs(np.diff(s, axis=-1)).max() > 0.9     # steep: an index error is not small
+
+
+# ------------------------------------------------------------------------------------------------ bounding boxes
+@pytest.mark.parametrize("extra", [False, True], ids=["plain", "with_7_and_200"])
+@pytest.mark.parametrize("name", sorted(K.BBOX_MAPS))
+def test_bboxes_ref_with_border_and_clamp_is_find_crops(name, extra):
+    """bboxes_ref + the border-and-clamp arithmetic of LobeInference.run == O.find_crops(lobe == label, spacing, 5 mm), for
+    every label of every bounding-box input; an absent label keeps (INT_MAX x 3, -1 x 3)."""
+    lobe = K.BBOX_MAPS[name](extra)
+    spacing = (2.5, 1.0, 0.7)
+    boxes = K.bboxes_ref(lobe, 255)
+    assert boxes.dtype == np.int32 and boxes.shape == (255, 6)
+    present = set(int(v) for v in np.unique(lobe)[1:])
+    for label in range(1, 256):
+        if label not in present:
+            assert boxes[label - 1].tolist() == [K.INT_MAX] * 3 + [-1] * 3
+            continue
+        start, size = K.crop_from_box(boxes[label - 1], lobe.shape, spacing, 5.0)
+        sl = O.find_crops(lobe == label, spacing, 5.0)
+        assert [s.start for s in sl] == start and [s.stop - s.start for s in sl] == size
+        tight = O.find_crops(lobe == label, spacing, 0.0)
+        assert [s.start for s in tight] == boxes[label - 1, :3].tolist()
+        assert [s.stop - 1 for s in tight] == boxes[label - 1, 3:].tolist()
+    assert np.array_equal(K.bboxes_ref(lobe, 6), boxes[:6])
+    if name == "empty":
+        assert not present
+
+
+def test_bbox_band_map_boxes_by_hand():
+    """The boxes the band map is built to give, written out."""
+    b = K.bboxes_ref(K.bbox_band_map(32), 6)
+    assert b.tolist() == [[1, 60, 4, 1, 67, 11], [0, 10, 1, 0, 10, 31], [2, 66, 20, 2, 69, 24], [0, 0, 0, 0, 0, 0],
+                          [2, 69, 31, 2, 69, 31], [0, 10, 3, 0, 10, 8]]
+    b33 = K.bboxes_ref(K.bbox_band_map(33), 6)
+    b[4, 2] = b[4, 5] = 32
+    assert np.array_equal(b33, b)
+
+
+# ------------------------------------------------------------------------------------------------ paste
+def test_paste_reference_is_F_interpolate_after_sigmoid():
+    """One chunk covering the whole volume, an all-ones lobe: lobe_paste_ref is F.interpolate(torch.sigmoid(dense), size,
+    mode="trilinear", align_corners=True) (job_runner.py:765-767) run in fp32 on the CPU.  The two share the fp32 index rule and
+    differ by fp32 rounding of the sigmoid and of the 8 products and 7 adds: the same 16 * 2^-24 as the GPU test.  Non-cubic
+    sizes, one axis with out == 1 (scale 0), one upsampled, one downsampled."""
+    R = 6
+    for size in ((1, 9, 4), (5, 20, 31), (9, 7, 2), (6, 1, 13)):
+        dense = (4.0 * K.rng(7).standard_normal((1, R, R, R))).astype(np.float32)
+        lobe = np.ones(size, dtype=np.uint8)
+        htp0 = np.full(size, -3.0, dtype=np.float32)
+        ref, written = K.lobe_paste_ref(dense, lobe, ((0, 0, 0) + size + (1,),), R, htp0)
+        assert written.all() and ref.dtype == np.float64
+        got = F.interpolate(torch.sigmoid(torch.from_numpy(dense)[None]), size=size, mode="trilinear", align_corners=True)
+        assert got.dtype == torch.float32
+        err = np.abs(got[0, 0].numpy().astype(np.float64) - ref).max()
+        print(f"infer-kernel-accuracy: torch-CPU-fp32 paste {size}: max err {err:.3e} (bound {K.PASTE_TOL:.3e})")
+        assert err <= K.PASTE_TOL
+        # and it is not the half-pixel grid: that one differs by far more than rounding
+        other = F.interpolate(torch.sigmoid(torch.from_numpy(dense)[None]), size=size, mode="trilinear", align_corners=False)
+        assert np.abs(other[0, 0].numpy() - ref).max() > 1e-2
+
+
+def test_ac_axis_is_the_published_rule():
+    i0, i1, l0, l1 = K.ac_axis(6, 1)                              # out == 1: scale 0
+    assert i0.tolist() == [0] and i1.tolist() == [1] and l1.tolist() == [0.0] and l0.tolist() == [1.0]
+    i0, i1, l0, l1 = K.ac_axis(6, 6)                              # identity
+    assert i0.tolist() == list(range(6)) and i1.tolist() == [1, 2, 3, 4, 5, 5] and not l1.any()
+    i0, i1, l0, l1 = K.ac_axis(6, 31)
+    assert l1.dtype == np.float32 and l0.dtype == np.float32 and i0[-1] == 5 and i1[-1] == 5 and i0[0] == 0
+    assert (l1 >= 0).all() and (l1 < 1).all()
+    assert i0.tolist() == [int(np.float32(5) / np.float32(30) * np.float32(o)) for o in range(31)]
+
+
+def test_paste_reference_leaves_foreign_voxels_alone():
+    dense, lobe, htp0 = K.paste_inputs()
+    ref, written = K.lobe_paste_ref(dense, lobe, K.PASTE_CHUNKS, K.PASTE_R, htp0)
+    want = np.zeros(K.VOLUME, dtype=bool)
+    for c in K.PASTE_CHUNKS:
+        want[K.box(c)] |= lobe[K.box(c)] == c[6]
+    assert np.array_equal(written, want) and 0 < written.sum() < written.size
+    assert np.array_equal(ref[~written], htp0[~written].astype(np.float64))
+    assert (ref[written] > 0).all() and (ref[written] < 1).all()
+
+
+# ------------------------------------------------------------------------------------------------ crop
+def test_lobe_chunks_ref_is_evaluate_scans_model_input():
+    """O.evaluate_scan hands every lobe's model input -- find_crops, mask to -2048, windowing, resample_itk_linear -- to its
+    `forward` argument, so the input is taken from there and none of those steps is restated here.  lobe_chunks_ref windows
+    in fp32 by the kernel's documented formula, (clip(v) - wmin) * (1 / (wmax - wmin)); the oracle divides by 700 in fp32.
+    Every fp32 rounding is at most u = 2^-24 relative, on values in [0, 1]: the oracle's quotient carries one, the product two
+    (1 / 700 and the multiplication), the resampling is a convex combination in fp64 (it adds nothing of this size) and each
+    side rounds its result to fp32 once more: five roundings between the two, 6 u with room for the second-order terms."""
+    from dram_amd.inference import synthetic_ct
+    R = 10
+    scan, lobe, spacing = synthetic_ct((24, 40, 44), (1.5, 1.0, 1.0), seed=7, n_lesions=4)
+    seen = []
+
+    def forward(t):
+        seen.append(t[0, 0].numpy().copy())
+        return torch.zeros_like(t)
+    O.evaluate_scan(None, None, None, scan, lobe, spacing, resample=R, window=K.WINDOW, forward=forward)
+    labels = [int(v) for v in np.unique(lobe)[1:]]
+    assert labels == [1, 2, 3, 4, 5] and len(seen) == 5
+    boxes = K.bboxes_ref(lobe, 255)
+    chunks = []
+    for label in labels:
+        start, size = K.crop_from_box(boxes[label - 1], lobe.shape, spacing, 5.0)
+        chunks.append(tuple(start + size + [label]))
+    ref = K.lobe_chunks_ref(scan, lobe, chunks, R, K.WINDOW)
+    assert ref.dtype == np.float32 and ref.shape == (5, R, R, R)
+    for l in range(5):
+        assert seen[l].dtype == np.float32 and seen[l].max() > 0.2
+        assert np.abs(ref[l].astype(np.float64) - seen[l]).max() <= 6 * K.U
+
+
+def test_constant_scan_gives_the_resampled_checkerboard():
+    """A scan constant at the window maximum: chunk A's expected output is the checkerboard of its own label resampled, with
+    no windowing arithmetic in between -- a known pattern that is neither 0 nor 1."""
+    scan, lobe = K.chunk_volume(constant_scan=True)
+    a = K.CHUNKS_ABC[0]
+    ref = K.lobe_chunks_ref(scan, lobe, K.CHUNKS_ABC, K.CHUNK_R, K.WINDOW)
+    board = (lobe[K.box(a)] == a[6]).astype(np.float32)
+    assert sorted(np.unique(lobe[K.box(a)]).tolist()) == [1, 4] and abs(board.mean() - 0.5) < 0.01
+    assert np.array_equal(ref[0], O.resample_itk_linear(board, (K.CHUNK_R,) * 3))
+    assert ref[0, 0, 0, 0] == 1.0 and ref[0].std() > 0.1 and ((ref[0] > 0.05) & (ref[0] < 0.95)).mean() > 0.5
+    assert (ref[2][:, :, 11] == 0).all() and (ref[2][:, :, 10] != 0).any()          # chunk C: c = 11 * 4 / 12 >= 3.5
+    scan2, _ = K.chunk_volume()
+    assert scan2.min() < K.WINDOW[0] < K.WINDOW[1] < scan2.max()
+    eight = K.lobe_chunks_ref(scan2, lobe, K.CHUNKS_8, K.CHUNK_R, K.WINDOW)
+    for i in range(K.MAX_CHUNKS):                                                    # distinct slots: a swapped slot shows
+        for j in range(i):
+            assert np.abs(eight[i] - eight[j]).max() > 0.1
+
+
+# ------------------------------------------------------------------------------------------------ histogram
+def exact_bin(v):
+    """float32(v) * 255f truncated, by exact arithmetic: a 24-bit significand times 255 fits 32 bits, so the fp64 product is
+    exact and np.float32 of it is the one rounding of the fp32 multiply."""
+    exact = Fraction(float(v)) * 255
+    p64 = np.float64(v) * 255.0
+    assert Fraction(float(p64)) == exact
+    return int(np.float32(p64))
+
+
+def test_bin_edges_by_hand():
+    """Which bin float32(v) * 255f truncates into, for v = float32(k / 255) and its two fp32 neighbours.  k / 255 rounds UP to
+    fp32 for k = 1, 127, 128 and 254, and its product with 255 rounds to k exactly; the neighbour below falls into bin
+    k - 1, the neighbour above stays in bin k.  255 / 255 = 1.0; the neighbour above clips to 1.0."""
+    by_hand = {0: (0, 0, 0), 1: (0, 1, 1), 127: (126, 127, 127), 128: (127, 128, 128), 254: (253, 254, 254), 255: (254, 255, 255)}
+    counts = {0: 4, 1: 2, 126: 1, 127: 3, 128: 2, 253: 1, 254: 3, 255: 2}
+    vals = []
+    for k, bins in by_hand.items():
+        nb = K.f32_neighbours(np.float32(k) / np.float32(255))
+        assert nb[1] == np.float32(k / 255) and nb[0] < nb[1] < nb[2]
+        assert float(nb[1]).hex() == {0: "0x0.0p+0", 1: "0x1.0101020000000p-8", 127: "0x1.fdfdfe0000000p-2",
+                                      128: "0x1.0101020000000p-1", 254: "0x1.fdfdfe0000000p-1", 255: "0x1.0000000000000p+0"}[k]
+        for v, want in zip(nb, bins):
+            assert exact_bin(np.clip(v, 0, 1)) == want, (k, v)
+            h, s, sa, n = K.lung_hist_ref(np.array([v]), np.array([1], dtype=np.uint8))
+            assert n == 1 and h[want] == 1 and h.sum() == 1 and s == float(v) and sa == abs(float(v))
+        vals += list(nb)
+    vals = np.array(vals, dtype=np.float32)
+    hist, s, sa, n = K.lung_hist_ref(vals, np.full(18, 2, dtype=np.uint8))
+    want = np.zeros(256, dtype=np.int64)
+    for b, c in counts.items():
+        want[b] = c
+    assert n == 18 and np.array_equal(hist, want)
+    # outside the lungs nothing counts
+    hist, s, sa, n = K.lung_hist_ref(vals, np.zeros(18, dtype=np.uint8))
+    assert n == 0 and not hist.any() and s == 0.0
+    # the extras: -0.0 and a negative value in bin 0; 1.0, its upper neighbour, 7.5 and +inf in bin 255
+    for v, want in zip(K.HIST_EXTRAS, (0, 0, 255, 255, 255, 255)):
+        assert K.lung_hist_ref(np.array([v], dtype=np.float32), np.array([5], dtype=np.uint8))[0][want] == 1
+
+
+def test_bin_edge_input_holds_every_edge():
+    htp, lobe, inf_at = K.bin_edge_input()
+    assert htp.shape == (K.N_BIN_EDGES,) and htp.dtype == np.float32 and np.isinf(htp).sum() == 1 and not np.isnan(htp).any()
+    assert lobe[inf_at] > 0 and set(np.unique(lobe)) == {0, 1, 2, 3, 4, 5} and 0.3 < (lobe == 0).mean() < 0.45
+    have = set(htp.tolist())
+    for k in range(256):
+        assert all(float(v) in have for v in K.f32_neighbours(np.float32(k) / np.float32(255)))
+    assert all(float(np.float32(v)) in have for v in K.HIST_EXTRAS) and np.signbit(htp[htp == 0]).any()
+    hist, s, sa, n = K.lung_hist_ref(htp, lobe)
+    assert hist.sum() == n == int((lobe > 0).sum()) and s == float("inf")
+    assert all(exact_bin(np.clip(v, 0, 1)) == int(np.clip(v, 0, 1) * np.float32(255)) for v in htp[~np.isinf(htp)])
+    assert (hist > 0).all()                                        # every bin is reached
+
+
+# ------------------------------------------------------------------------------------------------ threshold
+def test_threshold_comparison_is_fp32_under_this_numpy():
+    """Recorded as what the installed numpy does: a float32 array compared with a PYTHON float (what binary_cam's Otsu
+    branch returns: min(otsu * scaler, 255.0) / 255.0) is compared in fp32 -- the scalar is rounded to fp32 first --, which
+    is what threshold_kernel and lesion_post_kernel do with `float th`.  128 / 255 rounds UP to fp32, so the voxel holding
+    float32(128 / 255) is NOT above the threshold in fp32 and would be in fp64.  (A numpy.float64 SCALAR -- binary_cam's
+    one-colour branch, u[0] / 255.0 -- promotes the comparison to fp64 under this numpy; LobeInference passes a Python float.)"""
+    th = 128 / 255
+    v = np.array([np.float32(th)])
+    assert isinstance(th, float) and float(v[0]) > th               # rounded up
+    assert not (v > th)[0]                                          # fp32 comparison
+    assert (v.astype(np.float64) > th)[0]                           # what an fp64 comparison would say
+    assert (v > np.float64(th))[0]                                  # ... and what a float64 scalar gets
+    assert np.float32(th) == K.THRESHOLD
+    htp = K.threshold_input()
+    ref = K.threshold_ref(htp, th)
+    assert np.array_equal(ref, htp > th) and np.array_equal(ref, htp > K.THRESHOLD)
+    lo, mid, hi = K.f32_neighbours(K.THRESHOLD)
+    for start in (0, 517 * 256 + 3, K.THRESHOLD_GRID_CAP + 1, htp.size - 4):
+        assert htp[start:start + 3].tolist() == [lo, mid, hi] and np.isnan(htp[start + 3])
+        assert ref[start:start + 4].tolist() == [False, False, True, False]       # strict; NaN is not above anything
+    assert 0.45 < ref.mean() < 0.55
+
+
+# ------------------------------------------------------------------------------------------------ the counting kernels
+def test_scan_hist_ref_is_binary_cams_view(golden_dir):
+    """scan_hist_ref uses the oracle's windowing twice, as lesion_post_process and binary_cam do; on the golden scan it gives
+    the reference's own histogram."""
+    import os
+    z = np.load(os.path.join(golden_dir, "infer_tail.npz"))
+    assert np.array_equal(K.scan_hist_ref(z["scan"], z["lobe"]), z["hist"])
+    a, b = z["a"], z["b"]
+    c = K.mask_overlap_ref(a, b)
+    assert (c[0] + 1e-5) / (c[1] + 1e-5) == float(z["iou"]) and (2.0 * c[0] + 1e-5) / (c[2] + c[3] + 1e-5) == float(z["dice"])
