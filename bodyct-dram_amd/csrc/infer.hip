@@ -15,7 +15,7 @@
 // Resampling grid: the reference resamples the crop with SimpleITK; the crop -> R^3 step runs on the grid of that
 // ResampleImageFilter call (itk_axis, volume_math.h); the way back is the reference's own F.interpolate(...,
 // align_corners=True) (job_runner.py:767).
-#include "volume_math.h"
+#include "lobe_chunk.h"
 
 namespace dram {
 
@@ -80,33 +80,6 @@ __global__ __launch_bounds__(256) void label_bboxes_kernel(const uint8_t* __rest
         atomicMin(bx + 0, z); atomicMin(bx + 1, ly0[l]); atomicMin(bx + 2, lx0[l]);
         atomicMax(bx + 3, z); atomicMax(bx + 4, ly1[l]); atomicMax(bx + 5, lx1[l]);
     }
-}
-
-struct Chunk {   // crop window [z0,z0+dz) x [y0,y0+dy) x [x0,x0+dx) of lobe `label`
-    int z0, y0, x0, dz, dy, dx, label, pad;
-};
-constexpr int MAX_CHUNKS = 8;
-struct ChunkList {
-    Chunk c[MAX_CHUNKS];
-};
-
-__device__ __forceinline__ void ac_index(int in, int out, int o, int& i0, int& i1, float& l0, float& l1) {
-    const float scale = out > 1 ? (float)(in - 1) / (float)(out - 1) : 0.f;   // ATen area_pixel_compute_scale
-    const float src = scale * (float)o;
-    i0 = (int)src;
-    if (i0 > in - 1) i0 = in - 1;
-    i1 = i0 + (i0 < in - 1 ? 1 : 0);
-    l1 = src - (float)i0;
-    l0 = 1.f - l1;
-}
-
-// One axis of the crop -> R^3 grid: Resample('fixed_size') (data_transforms.py:170-175 -> utils.resample, utils.py:371-381:
-// sitkLinear, new_spacing = spacing * size_in / size_out), so c = o * size_in / size_out (itk_axis, volume_math.h); fp32 weights.
-__device__ __forceinline__ ItkAxis fixed_size_axis(int in, int out, int o, float& l0, float& l1) {
-    const ItkAxis a = itk_axis((double)o * (double)in / (double)out, in);
-    l1 = (float)a.t;
-    l0 = 1.f - l1;
-    return a;
 }
 
 // out[l][R][R][R]: windowed, lobe-masked crop resampled to R^3
@@ -296,19 +269,6 @@ extern "C" int dram_label_bboxes(const uint8_t* lobe, int* boxes, int nlabels, i
     return check_launch("label_bboxes");
 }
 
-static int fill_chunks(const char* who, ChunkList& cl, const int* chunks, int L, int D, int H, int W) {
-    DRAM_REQUIRE(chunks && L > 0 && L <= MAX_CHUNKS, "%s: between 1 and %d chunks", who, MAX_CHUNKS);
-    for (int l = 0; l < L; ++l) {
-        Chunk& c = cl.c[l];
-        c.z0 = chunks[l * 7 + 0]; c.y0 = chunks[l * 7 + 1]; c.x0 = chunks[l * 7 + 2];
-        c.dz = chunks[l * 7 + 3]; c.dy = chunks[l * 7 + 4]; c.dx = chunks[l * 7 + 5];
-        c.label = chunks[l * 7 + 6]; c.pad = 0;
-        DRAM_REQUIRE(c.z0 >= 0 && c.y0 >= 0 && c.x0 >= 0 && c.dz > 0 && c.dy > 0 && c.dx > 0 && c.z0 + c.dz <= D &&
-                         c.y0 + c.dy <= H && c.x0 + c.dx <= W, "%s: chunk %d outside the volume", who, l);
-    }
-    return DRAM_OK;
-}
-
 // chunks: host array of L x {z0,y0,x0,dz,dy,dx,label}
 extern "C" int dram_lobe_chunks(const int16_t* scan, const uint8_t* lobe, float* out, const int* chunks, int L, int D,
                                 int H, int W, int R, float wmin, float wmax, void* stream) {
@@ -329,11 +289,7 @@ extern "C" int dram_lobe_paste(const float* dense, const uint8_t* lobe, float* h
     ChunkList cl;
     int rc = fill_chunks("lobe_paste", cl, chunks, L, D, H, W);
     if (rc) return rc;
-    int64_t mx = 0;
-    for (int l = 0; l < L; ++l) {
-        const int64_t v = (int64_t)cl.c[l].dz * cl.c[l].dy * cl.c[l].dx;
-        mx = v > mx ? v : mx;
-    }
+    const int64_t mx = max_chunk_voxels(cl, L);
     DRAM_REQUIRE(mx < 0x7fffffffLL, "lobe_paste: chunk too large");
     hipLaunchKernelGGL(lobe_paste_kernel, dim3((unsigned)cdiv64(mx, 256), L), dim3(256), 0, (hipStream_t)stream, dense,
                        lobe, htp, cl, H, W, R);

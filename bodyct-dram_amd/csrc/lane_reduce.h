@@ -12,6 +12,7 @@
 //     pair write disjoint banks of one destination (no select),
 //   * DPP quad_perm + v_cndmask for the steps inside a quad (bank masks cannot tell the lanes of a quad apart).
 // All lanes of the wave must be active.
+// Also here: the maximum over a wave and over a 256-thread block (wave_max, block_max_256) on the same DPP controls.
 #pragma once
 
 namespace dram {
@@ -27,6 +28,27 @@ __device__ __forceinline__ void lr_row_swap(float& a, float& b) {
 template <int CTRL>
 __device__ __forceinline__ float lr_dpp(float v) {     // quad_perm 0x00-0xFF, row_mirror 0x140, row_half_mirror 0x141
     return __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), CTRL, 0xF, 0xF, false));
+}
+
+// Maximum over the 64 lanes of a wave, in every lane: pairs, quads, 8 and 16 lanes by DPP (a mirror serves as well as an
+// exchange: after each step the group holds one value), then the rows of 16 by two lane exchanges.  fmaxf: a NaN is dropped.
+__device__ __forceinline__ float wave_max(float v) {
+    v = fmaxf(v, lr_dpp<0xB1>(v));                  // quad_perm [1,0,3,2]
+    v = fmaxf(v, lr_dpp<0x4E>(v));                  // quad_perm [2,3,0,1]
+    v = fmaxf(v, lr_dpp<0x141>(v));                 // row_half_mirror
+    v = fmaxf(v, lr_dpp<0x140>(v));                 // row_mirror
+    v = fmaxf(v, __shfl_xor(v, 16, 64));
+    v = fmaxf(v, __shfl_xor(v, 32, 64));
+    return v;
+}
+
+// Block-wide maximum for 256-thread blocks; `red` is >= 4 floats of LDS.  Result in every thread.
+__device__ __forceinline__ float block_max_256(float v, float* red) {
+    v = wave_max(v);
+    __syncthreads();
+    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
+    __syncthreads();
+    return fmaxf(fmaxf(red[0], red[1]), fmaxf(red[2], red[3]));
 }
 
 // lanes whose partner bit is clear: lo + partner's lo; lanes whose bit is set: hi + partner's hi.

@@ -65,6 +65,9 @@ SIGNATURES = {
     "dram_label_bboxes": (I, [P, P, I, I, I, I, P]),
     "dram_lobe_chunks": (I, [P, P, P, P, I, I, I, I, I, F, F, P]),
     "dram_lobe_paste": (I, [P, P, P, P, I, I, I, I, I, P]),
+    "dram_lobe_chunk_masks": (I, [P, P, P, I, I, I, I, I, P]),
+    "dram_lobe_cam_max": (I, [P, P, P, I, I, I, P, P, P]),
+    "dram_lobe_cam_paste": (I, [P, P, P, P, P, P, I, I, I, I, I, I, P]),
     "dram_lung_hist256": (I, [P, P, P, P, L, P]),
     "dram_threshold_mask": (I, [P, P, F, L, P]),
     "dram_scan_hist256": (I, [P, P, P, I, I, L, P]),

@@ -14,6 +14,14 @@ reference's call -- sitk.ResampleImageFilter with the identity transform, the cr
 spacing * size_in / size_out, linear, default value 0 (utils.py:371-381) -- from ITK's published semantics: output voxel o
 samples continuous input index o * size_in / size_out, zero beyond size_in - 0.5 (csrc/infer.hip:itk_index).  SimpleITK is not
 available here, so that step's parity is unpinned; the way back is the reference's own F.interpolate(align_corners=True).
+
+`LobeInference(head="cam")` runs the head of the reference's inference entry point instead (`LesionSegTest.run`,
+job_runner.py:985-1004; csrc/infer_cam.hip): the dense output is pooled over the resampled lobe mask, the arg-max is the lobe's
+class (torch.max's rule: first of equal maxima, a NaN counts as the maximum), and what is pasted is the ReLU'd map of that
+class's channel divided by its maximum over the crop -- zero for class 0, and NaN where the reference gives NaN (a channel that
+is <= 0 over the whole crop).  It is meant for `out_ch > 1` models; with one channel every lobe is class 0 and the map is zero.
+The result then also holds `lobe_cls` ({label: class}), `pool` ([lobes, out_ch]) and `lobe_mask`; `lobewise_records` turns
+`lobe_cls` into the reference's lobe-wise records.
 """
 import ctypes
 import math
@@ -82,14 +90,19 @@ def resample_volume(vol, spacing, required_spacing, new_size, interpolator="line
 class LobeInference:
     """model: a models.DC3D on the GPU.  run(scan_i16, lobe_u8, spacing) -> dict.  Every label 1..max_labels
     present in the uint8 lobe map is visited in ascending order (evaluate_scan: `np.unique(lobe)[1:]`,
-    job_runner.py:729); a label above max_labels raises instead of being silently left out of the heat map."""
+    job_runner.py:729); a label above max_labels raises instead of being silently left out of the heat map.
+    head: "sigmoid" (default) pastes sigmoid(dense) like evaluate_scan; "cam" runs the lobe-wise class head of
+    LesionSegTest.run (module docstring) and adds lobe_cls / pool / lobe_mask to the result."""
 
     MAX_CHUNKS = 8     # chunks per kernel call / model batch (csrc/infer.hip MAX_CHUNKS)
 
     def __init__(self, model, resample_size=80, window=(-1000.0, -300.0), border_mm=5.0, max_labels=255,
-                 post_window=(-1150, 350), post_scaler=0.75):
+                 post_window=(-1150, 350), post_scaler=0.75, head="sigmoid"):
         if not 1 <= int(max_labels) <= 255:
             raise ValueError("max_labels must be in 1..255 (uint8 label map)")
+        if head not in ("sigmoid", "cam"):
+            raise ValueError("head must be 'sigmoid' (evaluate_scan) or 'cam' (LesionSegTest.run)")
+        self.head = head
         self.model, self.R, self.window, self.border, self.max_labels = model, int(resample_size), window, border_mm, int(max_labels)
         # the brightness gate of LesionSegTest.run: windowing()'s default span (utils.py:189, job_runner.py:1006) and the 0.75
         # on its Otsu threshold (job_runner.py:1007)
@@ -130,11 +143,20 @@ class LobeInference:
                 stop.append(min(size, int(h) + 1 + pad))
             chunks.append(start + [b - a for a, b in zip(start, stop)] + [label])
         htp = torch.zeros((D, H, W), dtype=torch.float32, device=dev)
+        cam = self.head == "cam"
         if not chunks:
-            return {"htp": htp, "mask": torch.zeros((D, H, W), dtype=torch.uint8, device=dev), "threshold": 0.0,
-                    "lesion_ratio": 0.0, "ctss": 0, "chunks": []}
+            res = {"htp": htp, "mask": torch.zeros((D, H, W), dtype=torch.uint8, device=dev), "threshold": 0.0,
+                   "lesion_ratio": 0.0, "ctss": 0, "chunks": []}
+            if cam:
+                res["lobe_cls"] = {}
+            return res
         R = self.R
         x = torch.empty((len(chunks), 1, R, R, R), dtype=torch.float32, device=dev)
+        if cam:   # the resampled lobe masks, and per chunk: pooled channels, class, maximum of the class's map over the crop
+            lobe_mask = torch.empty((len(chunks), 1, R, R, R), dtype=torch.float32, device=dev)
+            cls = torch.empty(len(chunks), dtype=torch.int32, device=dev)
+            cmax = torch.empty(len(chunks), dtype=torch.float32, device=dev)
+            pools = []
         was_training = self.model.training
         self.model.eval()
         try:
@@ -145,14 +167,20 @@ class LobeInference:
                 xg = x[g0:g0 + L]
                 call("dram_lobe_chunks", scan.data_ptr(), lobe.data_ptr(), xg.data_ptr(), carr, L, D, H, W, R,
                      float(self.window[0]), float(self.window[1]), st)
+                if cam:
+                    self._cam_group(xg, lobe_mask[g0:g0 + L], cls[g0:g0 + L], cmax[g0:g0 + L], pools, lobe, htp, carr, L, D, H, W, st)
+                    continue
                 _, dense = self.model(xg, None)   # one batch of L lobe chunks; the 2nd output is used (job_runner.py:764)
                 call("dram_lobe_paste", dense.contiguous().data_ptr(), lobe.data_ptr(), htp.data_ptr(), carr, L, D, H, W, R, st)
         finally:
             self.model.train(was_training)
-        hist = torch.empty(256, dtype=torch.int64, device=dev)
+        hist = torch.empty(256 + (len(chunks) if cam else 0), dtype=torch.int64, device=dev)
         ssum = torch.empty(1, dtype=torch.float64, device=dev)
         call("dram_lung_hist256", htp.data_ptr(), lobe.data_ptr(), hist.data_ptr(), ssum.data_ptr(), htp.numel(), st)
+        if cam:
+            hist[256:].copy_(cls)                                            # the classes ride along with the histogram read-back
         hist_h = hist.cpu().numpy()
+        hist_h, cls_h = hist_h[:256], hist_h[256:]
         n_lung = int(hist_h.sum())
         th = binary_cam_threshold(hist_h)
         mask = torch.empty((D, H, W), dtype=torch.uint8, device=dev)
@@ -160,10 +188,28 @@ class LobeInference:
         ratio = float(ssum.item()) / max(n_lung, 1)                          # (htp * (lobe>0)).sum() / (lobe>0).sum()
         res = {"htp": htp, "mask": mask, "threshold": th, "lesion_ratio": ratio, "ctss": ratio_to_label(ratio),
                "chunks": chunks, "input": x}
+        if cam:
+            res.update(lobe_cls={c[6]: int(k) for c, k in zip(chunks, cls_h)}, pool=torch.cat(pools), lobe_mask=lobe_mask)
         if vessel is not None or lesion is not None or original_size is not None:
             res.update(self.post_process(scan, lobe, htp, th, vessel, lesion, mask, spacing=spacing,
                                          original_spacing=original_spacing, original_size=original_size))
         return res
+
+    def _cam_group(self, xg, mg, cls, cmax, pools, lobe, htp, carr, L, D, H, W, st):
+        """The lobe-wise class head of LesionSegTest.run (job_runner.py:985-1004) for one batch of L chunks: the model sees the
+        image chunk and the resampled lobe mask, the dense output is pooled over that mask, and the class, the maximum of its
+        ReLU'd map over the crop and the paste follow on the device (csrc/infer_cam.hip)."""
+        import models
+        R = self.R
+        call("dram_lobe_chunk_masks", lobe.data_ptr(), mg.data_ptr(), carr, L, D, H, W, R, st)
+        _, dense = self.model(xg, mg)                                        # the 2nd output (job_runner.py:985)
+        dense = dense.contiguous()
+        C = int(dense.shape[1])
+        pool = models.pooling_dense_features(dense, mg).contiguous()         # [L, C]: masked mean (models.py:45-47)
+        pools.append(pool)
+        call("dram_lobe_cam_max", dense.data_ptr(), pool.data_ptr(), carr, L, C, R, cls.data_ptr(), cmax.data_ptr(), st)
+        call("dram_lobe_cam_paste", dense.data_ptr(), lobe.data_ptr(), htp.data_ptr(), carr, cls.data_ptr(), cmax.data_ptr(),
+             L, C, D, H, W, R, st)
 
     @torch.no_grad()
     def post_process(self, scan, lobe, htp, th, vessel=None, lesion=None, mask=None, spacing=None, original_spacing=None,
@@ -211,6 +257,24 @@ class LobeInference:
             out.update(iou=(c[0] + s) / (c[1] + s), dice=(2.0 * c[0] + s) / (c[2] + c[3] + s),
                        iou_post=(c[4] + s) / (c[5] + s), dice_post=(2.0 * c[4] + s) / (c[6] + c[7] + s))
         return out
+
+
+def lobewise_records(result, targets, labels=range(1, 6)):
+    """The lobe-wise predictions against the targets that LesionSegTest.run collects (job_runner.py:954-960, 988-992, 1033)
+    from the result of a `head="cam"` run.  targets: {label: class}.  Returns (preds, targets, acc): the two lists that feed
+    the confusion matrix, one entry per label of `labels`, and the scan's accuracy, np.mean over the lobes that are present.
+    An absent lobe contributes its target as its prediction to the lists and nothing to acc; with no lobe present acc is
+    NaN (the reference's np.mean of an empty list)."""
+    lobe_cls = result["lobe_cls"]
+    preds, tgts, accs = [], [], []
+    for label in labels:
+        target = int(targets[label])
+        pred = int(lobe_cls[label]) if label in lobe_cls else target
+        preds.append(pred)
+        tgts.append(target)
+        if label in lobe_cls:
+            accs.append(pred == target)
+    return preds, tgts, float(np.mean(accs)) if accs else float("nan")
 
 
 def iou(predict, target, smooth=1e-5):

@@ -266,6 +266,29 @@ int dram_lung_hist256(const float* htp, const uint8_t* lobe, unsigned long long*
 /* mask[v] = htp[v] > th. */
 int dram_threshold_mask(const float* htp, uint8_t* mask, float th, int64_t n, void* stream);
 
+/* ---- the lobe-wise class head of LesionSegTest.run (dram/job_runner.py:985-1004; csrc/infer_cam.hip): what the reference's
+ *      inference entry point runs per lobe in place of evaluate_scan's sigmoid -- pool the dense output over the resampled
+ *      lobe mask (dram_masked_mean_fwd), class = arg-max, resize every channel to the crop, ReLU, take the class's channel,
+ *      divide by its maximum over the crop, zero when the class is 0, paste where the lobe is.  `chunks` as above.
+ * dram_lobe_chunk_masks: out[L,1,R,R,R] = 1.0 where the nearest-neighbour sample of (lobe == label) on the crop -> R^3 grid of
+ *   dram_lobe_chunks is set, else 0.0; 0.0 beyond the crop's buffer (ITK's default value).  Nearest = round half up, as in
+ *   dram_resample_volume.
+ * dram_lobe_cam_max: dense [L,C,R,R,R], pool [L,C] (device).  cls_out[l] (int32) = argmax_c pool[l,c] by torch.max's CPU rule:
+ *   the first occurrence of the maximum wins and a NaN counts as the maximum (the first NaN wins).  max_out[l] (float, zeroed
+ *   here) = max over ALL dz*dy*dx voxels of the crop box, outside-lobe voxels included, of relu(resize(dense[l,cls_out[l]])),
+ *   resize = trilinear with align_corners=True as in dram_lobe_paste; the order is the reference's (resize, ReLU, select, max).
+ * dram_lobe_cam_paste: for every voxel of chunk l with lobe == label: htp = 0 if cls[l] == 0, else
+ *   relu(resize(dense[l,cls[l]])) / max[l], the IEEE quotient: 0/0 = NaN when the whole channel is <= 0 over the box, as in the
+ *   reference.  cls, max: device arrays (those of dram_lobe_cam_max; no host round trip).  Each voxel is written by the chunk
+ *   whose label it carries, so boxes of different labels may overlap.
+ * Only channel cls[l] of dense[l] is read.  `dense` is finite by contract: ReLU and the maximum drop a NaN (fmaxf), so a voxel
+ *   that a NaN reaches is pasted as 0 and is left out of the maximum, where the reference's lobe would turn NaN as a whole. */
+int dram_lobe_chunk_masks(const uint8_t* lobe, float* out, const int* chunks, int L, int D, int H, int W, int R, void* stream);
+int dram_lobe_cam_max(const float* dense, const float* pool, const int* chunks, int L, int C, int R, int* cls_out,
+                      float* max_out, void* stream);
+int dram_lobe_cam_paste(const float* dense, const uint8_t* lobe, float* htp, const int* chunks, const int* cls, const float* max,
+                        int L, int C, int D, int H, int W, int R, void* stream);
+
 /* ---- the post-processing tail of LesionSegTest.run (dram/job_runner.py:1003-1012, 1033-1037) ----
  * w_scan = windowing(scan, from_span=(wmin, wmax), to_span=(0, 1)) (utils.py:189-198; the reference calls it with the default
  * span (-1150, 350), job_runner.py:1006), in fp64 exactly as numpy evaluates it.
