@@ -1,19 +1,22 @@
-// IntRegRefineLoss on the device, fused, gfx950; further down the pieces of the
-// affine-consistency losses, IntRegLoss (the hinge with an entropy term instead of the pseudo-label term), and the two
-// voxel-wise segmentation losses on a target that is given (BootBinCrossEntropy, BinaryCrossEntropySmooth).
+// The training losses and their targets on the device, gfx950.  In this order: the pieces every section shares; the fused
+// IntRegRefineLoss; the pieces of the affine-consistency losses; IntRegLoss (the hinge with an
+// entropy term instead of the pseudo-label term); the two voxel-wise segmentation losses on a target that is given
+// (BootBinCrossEntropy, BinaryCrossEntropySmooth); the regression targets of a batch; the C entry points.
 //
-// Replaces the ~30 element-wise / reduction ATen dispatches -- and the per-sample host round trips --
-// of the reference's training loss, dram/metrics.py: IntRegLoss.compute_reg_loss_with_probs (158-177),
-// IntRegRefineLoss.compute_seg_loss (331-358) with BootBinCrossEntropy (17-51), __call__ (360-373).
-//
-//   p      = sigmoid(refined), pd = sigmoid(dense)   (DC3D: refined is dense; DC3DATGeneric: the PCM output)
-//   reg    = sum_n max((r_n - c_n)^2 - K_n, 0) / w_n,   r_n = sum_v pd m / sum_v m   (m = lobe mask)
-//   t      = [pd > 0.5] [m] [lesion > 0] keep_n          (pseudo label, no gradient)
-//   seg    = mean_{m=0} -log(1-p)  +  (1-s) * (alpha A + (1-alpha) B) / (alpha T + (1-alpha)(n_in - T))  +  s * mean_{m=1} -log(max(p,1-p))
-//            A = sum_{t=1} -log p,  B = sum_{m=1,t=0} -log(1-p),  T = sum t,  alpha = clamp(1 - T/n_in, .25, .75)
-//            (all logs of values clamped to [eps, 1-eps], eps = 1e-7, as torch.clamp: zero gradient outside)
-// One streaming pass produces every sum (HBM-bound: 12 B/voxel read), a one-block fp64 finalise turns
-// them into the two scalars, and the backward is one more streaming pass (12 B read + 4 B written).
+// Every loss is a streaming pass that leaves one tuple of partial sums per block, a one-block kernel that adds the partials
+// in a fixed order and forms the scalars, and a streaming backward.  No atomics anywhere: the same input gives the same
+// bits.  The shared pieces, each defined once below:
+//   stream_packs<V>     the grid-stride walk of one sample over two tensors, ENC_UNROLL 16-byte (V = 4) or 4-byte (V = 1)
+//                       loads of each in flight per lane; all-or-nothing alignment, chosen on the host (enc_vec4)
+//   block_partials<NS>  NS fp64 sums of every lane -> one tuple per block: butterfly per wave, then the four waves in order
+//   block_totals<NS>    the same combine, read side: the result stays in registers of the one finishing block
+//   sample_totals<NS>   one wave adds the tuples of one sample: lanes stride over the blocks, then a butterfly
+//   Hinge               the interval hinge of one sample: its value in fp64 (finalise kernels), its gradient factor in fp32
+//   seg_load_groups     the groups of four elements a lane of a segmentation kernel owns, by element index, with a per-tensor
+//                       alignment flag and a ragged tail (seg_load4 / seg_store4)
+// loss_partial_kernel and the masked smooth-L1 kernels predate these and keep their fp32 chunk sums (block_sum_256).
+#include <type_traits>
+
 #include "common.h"
 
 namespace dram {
@@ -33,6 +36,130 @@ __device__ __forceinline__ void sigmoid_pq(float d, float& p, float& q) {
 }
 __device__ __forceinline__ float nlog_clamped(float v) { return -logf(fminf(fmaxf(v, LEPS), 1.f - LEPS)); }
 
+// ---- shared pieces -------------------------------------------------------------------------------------------------------
+constexpr int ENC_UNROLL = 4;          // loads of each tensor a lane has in flight
+
+template <int V> struct EncPack;
+template <> struct EncPack<4> { using type = float4; };
+template <> struct EncPack<1> { using type = float; };
+__device__ __forceinline__ float enc_lane(const float4& v, int i) { return i == 0 ? v.x : i == 1 ? v.y : i == 2 ? v.z : v.w; }
+__device__ __forceinline__ float enc_lane(const float& v, int) { return v; }
+__device__ __forceinline__ void enc_set(float4& v, int i, float x) { (i == 0 ? v.x : i == 1 ? v.y : i == 2 ? v.z : v.w) = x; }
+__device__ __forceinline__ void enc_set(float& v, int, float x) { v = x; }
+
+// What a lane holds in one step of stream_packs: pack u is pack base + u * 256 + threadIdx.x of the sample, where ok[u].
+template <int V> struct PackStep {
+    typename EncPack<V>::type a[ENC_UNROLL], b[ENC_UNROLL];
+    bool ok[ENC_UNROLL];
+    int64_t base;
+    // elem(k, a, b) for every element the lane holds, in (u, k) order; done(pack index) after the elements of each pack
+    template <class Elem, class Done>
+    __device__ __forceinline__ void each(Elem&& elem, Done&& done) const {
+#pragma unroll
+        for (int u = 0; u < ENC_UNROLL; ++u) {
+            if (!ok[u]) continue;
+#pragma unroll
+            for (int k = 0; k < V; ++k) elem(k, enc_lane(a[u], k), enc_lane(b[u], k));
+            done(base + u * 256 + threadIdx.x);
+        }
+    }
+    template <class Elem>
+    __device__ __forceinline__ void each(Elem&& elem) const { each(elem, [](int64_t) {}); }
+};
+// The nblk blocks of a sample walk its S / V packs of a[] and b[] with a grid stride; step(PackStep) once per step.
+// V = 4: S is a multiple of 4 and both bases are 16-byte aligned, so every sample starts on a 16-byte boundary and a pack is
+// inside [0, S) whenever its first element is.  V = 1: any S, any alignment.
+template <int V, class Step>
+__device__ __forceinline__ void stream_packs(const float* __restrict__ a, const float* __restrict__ b, int64_t S, int nblk,
+                                             Step&& step) {
+    using T = typename EncPack<V>::type;
+    const T* pa = reinterpret_cast<const T*>(a);
+    const T* pb = reinterpret_cast<const T*>(b);
+    const int64_t packs = S / V;                             // packs of this sample
+    const int64_t stride = (int64_t)nblk * 256 * ENC_UNROLL;   // packs all blocks of the sample cover per step
+    for (int64_t base = (int64_t)blockIdx.x * 256 * ENC_UNROLL; base < packs; base += stride) {
+        PackStep<V> st;
+        st.base = base;
+#pragma unroll
+        for (int u = 0; u < ENC_UNROLL; ++u) {
+            const int64_t i = base + u * 256 + threadIdx.x;
+            st.ok[u] = i < packs;
+            if (st.ok[u]) { st.a[u] = pa[i]; st.b[u] = pb[i]; }
+        }
+        step(st);
+    }
+}
+
+// acc[NS] of every lane -> dst[q]: butterfly per wave, then the four waves in order
+template <int NS>
+__device__ __forceinline__ void block_partials(const double (&acc)[NS], double (*red)[4], double* __restrict__ dst) {
+#pragma unroll
+    for (int q = 0; q < NS; ++q) {
+        const double s = wave_sum_d(acc[q]);
+        if ((threadIdx.x & 63) == 0) red[q][threadIdx.x >> 6] = s;
+    }
+    __syncthreads();
+    if (threadIdx.x < NS)
+        dst[threadIdx.x] = ((red[threadIdx.x][0] + red[threadIdx.x][1]) + red[threadIdx.x][2]) + red[threadIdx.x][3];
+}
+// the same combine with the result in tot[] of every thread
+template <int NS>
+__device__ __forceinline__ void block_totals(const double (&s)[NS], double (*red)[4], double (&tot)[NS]) {
+#pragma unroll
+    for (int q = 0; q < NS; ++q) {
+        const double w = wave_sum_d(s[q]);
+        if ((threadIdx.x & 63) == 0) red[q][threadIdx.x >> 6] = w;
+    }
+    __syncthreads();
+#pragma unroll
+    for (int q = 0; q < NS; ++q) tot[q] = ((red[q][0] + red[q][1]) + red[q][2]) + red[q][3];
+}
+// s[q] = sum over the nblk tuples part[(n * nblk + b) * NS + q] of sample n, in every lane of the calling wave
+template <int NS>
+__device__ __forceinline__ void sample_totals(const double* __restrict__ part, int n, int nblk, double (&s)[NS]) {
+#pragma unroll
+    for (int q = 0; q < NS; ++q) s[q] = 0.0;
+    for (int b = threadIdx.x & 63; b < nblk; b += 64)
+#pragma unroll
+        for (int q = 0; q < NS; ++q) s[q] += part[((size_t)n * nblk + b) * NS + q];
+#pragma unroll
+    for (int q = 0; q < NS; ++q) s[q] = wave_sum_d(s[q]);
+}
+
+// The interval hinge of sample n, max((r - c)^2 - K, 0) / w with c = (lo + hi) / 2 and K = (hi - lo)^2 / 4, of the lobe's
+// mean probability r = sum_v p m / nm.
+struct Hinge {
+    float lo, hi, w;
+    __device__ __forceinline__ Hinge(const float* __restrict__ targets, const float* __restrict__ weight, int n)
+        : lo(targets[2 * n]), hi(targets[2 * n + 1]), w(weight[n]) {}
+    __device__ __forceinline__ double value(double r) const {
+        const double l = lo, h = hi;
+        const double K = 0.25 * (h - l) * (h - l);
+        const double v = (r - 0.5 * (h + l)) * (r - 0.5 * (h + l)) - K;
+        return (v > 0.0 ? v : 0.0) / (double)w;
+    }
+    // g0 * d value / d p_v for a lobe voxel v
+    __device__ __forceinline__ float grad(float r, float nm, float g0) const {
+        const float c = 0.5f * (hi + lo), K = 0.25f * (hi - lo) * (hi - lo);
+        const float hinge = ((r - c) * (r - c) - K) > 0.f ? 1.f : 0.f;
+        return g0 * hinge * 2.f * (r - c) / (w * nm);
+    }
+};
+
+
+// ---- IntRegRefineLoss, fused ------------------------------------------------------------------------------------------------
+// Replaces the ~30 element-wise / reduction ATen dispatches -- and the per-sample host round trips --
+// of the reference's training loss, dram/metrics.py: IntRegLoss.compute_reg_loss_with_probs (158-177),
+// IntRegRefineLoss.compute_seg_loss (331-358) with BootBinCrossEntropy (17-51), __call__ (360-373).
+//
+//   p      = sigmoid(refined), pd = sigmoid(dense)   (DC3D: refined is dense; DC3DATGeneric: the PCM output)
+//   reg    = sum_n max((r_n - c_n)^2 - K_n, 0) / w_n,   r_n = sum_v pd m / sum_v m   (m = lobe mask)
+//   t      = [pd > 0.5] [m] [lesion > 0] keep_n          (pseudo label, no gradient)
+//   seg    = mean_{m=0} -log(1-p)  +  (1-s) * (alpha A + (1-alpha) B) / (alpha T + (1-alpha)(n_in - T))  +  s * mean_{m=1} -log(max(p,1-p))
+//            A = sum_{t=1} -log p,  B = sum_{m=1,t=0} -log(1-p),  T = sum t,  alpha = clamp(1 - T/n_in, .25, .75)
+//            (all logs of values clamped to [eps, 1-eps], eps = 1e-7, as torch.clamp: zero gradient outside)
+// One streaming pass produces every sum (HBM-bound: 12 B/voxel read), a one-block fp64 finalise turns
+// them into the two scalars, and the backward is one more streaming pass (12 B read + 4 B written).
 __global__ __launch_bounds__(256) void loss_partial_kernel(const float* __restrict__ dense, const float* __restrict__ refined,
                                                            const float* __restrict__ lobes,
                                                            const float* __restrict__ lesions, const float* __restrict__ keep,
@@ -97,10 +224,7 @@ __global__ __launch_bounds__(256) void loss_finalize_kernel(const float* __restr
             const double r = s[0] / s[1];
             state[4 + 2 * n] = (float)r;
             state[5 + 2 * n] = (float)s[1];
-            const double lo = targets[2 * n], hi = targets[2 * n + 1];
-            const double K = 0.25 * (hi - lo) * (hi - lo);
-            const double h = (r - 0.5 * (hi + lo)) * (r - 0.5 * (hi + lo)) - K;
-            regs += (h > 0.0 ? h : 0.0) / (double)weight[n];
+            regs += Hinge(targets, weight, n).value(r);
             for (int q = 0; q < NSUM; ++q) tot[q] += s[q];
         }
         const double n_in = tot[1], n_out = tot[3], T = tot[4];
@@ -130,10 +254,7 @@ __global__ __launch_bounds__(256) void loss_bwd_kernel(const float* __restrict__
     const float g0 = gout[0], g1 = gout[1];
     const float alpha = state[0], wsum = state[1], n_in = state[2], n_out = state[3];
     const float r = state[4 + 2 * n], nm = state[5 + 2 * n];
-    const float lo = targets[2 * n], hi = targets[2 * n + 1];
-    const float c = 0.5f * (hi + lo), K = 0.25f * (hi - lo) * (hi - lo);
-    const float hinge = ((r - c) * (r - c) - K) > 0.f ? 1.f : 0.f;
-    const float greg = g0 * hinge * 2.f * (r - c) / (weight[n] * nm);       // d reg / d p_v for m_v = 1
+    const float greg = Hinge(targets, weight, n).grad(r, nm, g0);          // d reg / d p_v for m_v = 1
     const float kp = keep[n];
     const float c_out = n_out > 0.f ? g1 / n_out : 0.f;
     const float c_a = n_in > 0.f ? g1 * (1.f - smoothing) * alpha / wsum : 0.f;
@@ -218,16 +339,13 @@ __global__ __launch_bounds__(256) void masked_smooth_l1_partial_kernel(const flo
 // out[0] = mean, out[1] = count; fixed-order fp64 sum by one block
 __global__ __launch_bounds__(256) void masked_smooth_l1_finalize_kernel(const float* __restrict__ part, int64_t items,
                                                                         float* __restrict__ out) {
-    __shared__ double rs[4], rc[4];
-    double s = 0.0, c = 0.0;
-    for (int64_t i = threadIdx.x; i < items; i += 256) { s += part[2 * i]; c += part[2 * i + 1]; }
-    s = wave_sum_d(s); c = wave_sum_d(c);
-    if ((threadIdx.x & 63) == 0) { rs[threadIdx.x >> 6] = s; rc[threadIdx.x >> 6] = c; }
-    __syncthreads();
+    __shared__ double red[2][4];
+    double s[2] = {0.0, 0.0}, tot[2];
+    for (int64_t i = threadIdx.x; i < items; i += 256) { s[0] += part[2 * i]; s[1] += part[2 * i + 1]; }
+    block_totals<2>(s, red, tot);
     if (threadIdx.x == 0) {
-        const double S = rs[0] + rs[1] + rs[2] + rs[3], Cn = rc[0] + rc[1] + rc[2] + rc[3];
-        out[0] = (float)(S / Cn);          // an empty selection gives nan, like torch's mean of an empty tensor
-        out[1] = (float)Cn;
+        out[0] = (float)(tot[0] / tot[1]);          // an empty selection gives nan, like torch's mean of an empty tensor
+        out[1] = (float)tot[1];
     }
 }
 __global__ void masked_smooth_l1_bwd_kernel(const float* __restrict__ a, const float* __restrict__ b,
@@ -260,12 +378,10 @@ static inline int loss_chunks(int64_t S) { return (int)cdiv64(S, LCHUNK); }
 // exactly 0 once p rounds to 1) and the 1e-7 is added after, so every logarithm sees at least 1e-7 and no finite logit
 // gives a non-finite value.  The lesion mask does not enter: it reaches the loss through the regression band `targets`
 // only (get_labels, 122-138), which the caller computes with the batch.
-// Forward: one pass over dense and lobes (8 B/voxel), every lane with four 16-byte loads per tensor in flight per step;
-// a block walks its sample with a grid stride, keeps its three sums in fp64 across steps and writes one fp64 partial
-// triple; one block then adds the partials in a fixed order.  No atomics: the same input gives the same bits.
+// Forward: one pass over dense and lobes (8 B/voxel, stream_packs); a block keeps its three sums in fp64 across steps and
+// writes one fp64 partial triple; one block then adds the partials in a fixed order.
 // Backward: one pass, 8 B/voxel read and 4 B/voxel written.
 constexpr int ENC_NSUM = 3;            // per (sample, block): sum of p inside the lobe, lobe voxels, sum of the entropy terms
-constexpr int ENC_UNROLL = 4;          // loads of each tensor a lane has in flight
 constexpr int ENC_MAX_BLOCKS = 2048;   // blocks of one launch (about 8 per CU), shared between the samples
 
 __device__ __forceinline__ float enc_term(float p) {
@@ -278,76 +394,36 @@ __device__ __forceinline__ float enc_term_dp(float p) {
     return -logf(p + LEPS) - p / (p + LEPS) + logf(q + LEPS) + q / (q + LEPS);
 }
 
-template <int V> struct EncPack;
-template <> struct EncPack<4> { using type = float4; };
-template <> struct EncPack<1> { using type = float; };
-__device__ __forceinline__ float enc_lane(const float4& v, int i) { return i == 0 ? v.x : i == 1 ? v.y : i == 2 ? v.z : v.w; }
-__device__ __forceinline__ float enc_lane(const float& v, int) { return v; }
-__device__ __forceinline__ void enc_set(float4& v, int i, float x) { (i == 0 ? v.x : i == 1 ? v.y : i == 2 ? v.z : v.w) = x; }
-__device__ __forceinline__ void enc_set(float& v, int, float x) { v = x; }
-
-// V = 4: S is a multiple of 4 and both bases are 16-byte aligned, so every sample starts on a 16-byte boundary and a
-// pack is inside [0, S) whenever its first element is.  V = 1: any S, any alignment.
 template <int V>
 __global__ __launch_bounds__(256) void enc_partial_kernel(const float* __restrict__ dense, const float* __restrict__ lobes,
                                                           double* __restrict__ part, int64_t S, int nblk) {
-    using T = typename EncPack<V>::type;
     __shared__ double red[ENC_NSUM][4];
     const int n = blockIdx.y;
-    const T* pd = reinterpret_cast<const T*>(dense + (int64_t)n * S);
-    const T* pm = reinterpret_cast<const T*>(lobes + (int64_t)n * S);
-    const int64_t packs = S / V;                             // packs of this sample
-    const int64_t step = (int64_t)nblk * 256 * ENC_UNROLL;   // packs all blocks of the sample cover per step
     double acc[ENC_NSUM] = {0.0, 0.0, 0.0};
-    for (int64_t base = (int64_t)blockIdx.x * 256 * ENC_UNROLL; base < packs; base += step) {
-        T d[ENC_UNROLL], m[ENC_UNROLL];
-        bool ok[ENC_UNROLL];
-#pragma unroll
-        for (int u = 0; u < ENC_UNROLL; ++u) {
-            const int64_t i = base + u * 256 + threadIdx.x;
-            ok[u] = i < packs;
-            if (ok[u]) { d[u] = pd[i]; m[u] = pm[i]; }
-        }
+    stream_packs<V>(dense + (int64_t)n * S, lobes + (int64_t)n * S, S, nblk, [&](const PackStep<V>& st) {
         float sp = 0.f, nm = 0.f, ent = 0.f;
-#pragma unroll
-        for (int u = 0; u < ENC_UNROLL; ++u) {
-            if (!ok[u]) continue;
-#pragma unroll
-            for (int k = 0; k < V; ++k) {
-                float p, q;
-                sigmoid_pq(enc_lane(d[u], k), p, q);
-                if (enc_lane(m[u], k) > 0.f) { sp += p; nm += 1.f; }
-                ent += enc_term(p);
-            }
-        }
+        st.each([&](int, float d, float m) {
+            float p, q;
+            sigmoid_pq(d, p, q);
+            if (m > 0.f) { sp += p; nm += 1.f; }
+            ent += enc_term(p);
+        });
         acc[0] += sp; acc[1] += nm; acc[2] += ent;
-    }
-#pragma unroll
-    for (int q = 0; q < ENC_NSUM; ++q) {
-        const double s = wave_sum_d(acc[q]);
-        if ((threadIdx.x & 63) == 0) red[q][threadIdx.x >> 6] = s;
-    }
-    __syncthreads();
-    if (threadIdx.x < ENC_NSUM)
-        part[((size_t)n * nblk + blockIdx.x) * ENC_NSUM + threadIdx.x] =
-            red[threadIdx.x][0] + red[threadIdx.x][1] + red[threadIdx.x][2] + red[threadIdx.x][3];
+    });
+    block_partials<ENC_NSUM>(acc, red, part + ((size_t)n * nblk + blockIdx.x) * ENC_NSUM);
 }
 
-// state: per sample {r_n, nm_n}.  One wave per sample adds that sample's partials (lanes stride over the blocks, then a
-// butterfly: a fixed order), thread 0 combines the samples in index order.
+// state: per sample {r_n, nm_n}.  One wave per sample adds that sample's partials, thread 0 combines the samples in index
+// order.
 __global__ __launch_bounds__(256) void enc_finalize_kernel(const double* __restrict__ part, double* __restrict__ ssum,
                                                            const float* __restrict__ targets, const float* __restrict__ weight,
                                                            int N, int64_t S, int nblk, float* __restrict__ out,
                                                            float* __restrict__ state) {
-    const int lane = threadIdx.x & 63;
     for (int n = threadIdx.x >> 6; n < N; n += 4) {
-        double s[ENC_NSUM] = {0.0, 0.0, 0.0};
-        for (int b = lane; b < nblk; b += 64)
-            for (int q = 0; q < ENC_NSUM; ++q) s[q] += part[((size_t)n * nblk + b) * ENC_NSUM + q];
-        for (int q = 0; q < ENC_NSUM; ++q) {
-            const double t = wave_sum_d(s[q]);
-            if (lane == 0) ssum[(size_t)n * ENC_NSUM + q] = t;
-        }
+        double s[ENC_NSUM];
+        sample_totals<ENC_NSUM>(part, n, nblk, s);
+        if ((threadIdx.x & 63) == 0)
+            for (int q = 0; q < ENC_NSUM; ++q) ssum[(size_t)n * ENC_NSUM + q] = s[q];
     }
     __syncthreads();
     if (threadIdx.x == 0) {
@@ -357,10 +433,7 @@ __global__ __launch_bounds__(256) void enc_finalize_kernel(const double* __restr
             const double r = s[0] / s[1];
             state[2 * n] = (float)r;
             state[2 * n + 1] = (float)s[1];
-            const double lo = targets[2 * n], hi = targets[2 * n + 1];
-            const double K = 0.25 * (hi - lo) * (hi - lo);
-            const double h = (r - 0.5 * (hi + lo)) * (r - 0.5 * (hi + lo)) - K;
-            regs += (h > 0.0 ? h : 0.0) / (double)weight[n];
+            regs += Hinge(targets, weight, n).value(r);
             ent += s[2];
         }
         out[0] = (float)regs;
@@ -378,41 +451,22 @@ __global__ __launch_bounds__(256) void enc_bwd_kernel(const float* __restrict__ 
     const int n = blockIdx.y;
     const float g0 = gout[0], g1 = gout[1];
     const float r = state[2 * n], nm = state[2 * n + 1];
-    const float lo = targets[2 * n], hi = targets[2 * n + 1];
-    const float c = 0.5f * (hi + lo), K = 0.25f * (hi - lo) * (hi - lo);
-    const float hinge = ((r - c) * (r - c) - K) > 0.f ? 1.f : 0.f;
-    const float greg = g0 * hinge * 2.f * (r - c) / (weight[n] * nm);       // d reg / d p_v for m_v = 1
+    const float greg = Hinge(targets, weight, n).grad(r, nm, g0);          // d reg / d p_v for m_v = 1
     const float genc = (float)((double)g1 / ((double)N * (double)S));
     const bool with_enc = g1 != 0.f;                         // the transformed batch of IntRegAffLoss takes reg alone
-    const T* pd = reinterpret_cast<const T*>(dense + (int64_t)n * S);
-    const T* pm = reinterpret_cast<const T*>(lobes + (int64_t)n * S);
     T* po = reinterpret_cast<T*>(ddense + (int64_t)n * S);
-    const int64_t packs = S / V;
-    const int64_t step = (int64_t)gridDim.x * 256 * ENC_UNROLL;
-    for (int64_t base = (int64_t)blockIdx.x * 256 * ENC_UNROLL; base < packs; base += step) {
-        T d[ENC_UNROLL], m[ENC_UNROLL];
-        bool ok[ENC_UNROLL];
-#pragma unroll
-        for (int u = 0; u < ENC_UNROLL; ++u) {
-            const int64_t i = base + u * 256 + threadIdx.x;
-            ok[u] = i < packs;
-            if (ok[u]) { d[u] = pd[i]; m[u] = pm[i]; }
-        }
-#pragma unroll
-        for (int u = 0; u < ENC_UNROLL; ++u) {
-            if (!ok[u]) continue;
-            T g;
-#pragma unroll
-            for (int k = 0; k < V; ++k) {
+    stream_packs<V>(dense + (int64_t)n * S, lobes + (int64_t)n * S, S, (int)gridDim.x, [&](const PackStep<V>& st) {
+        T g;
+        st.each(
+            [&](int k, float d, float m) {
                 float p, q;
-                sigmoid_pq(enc_lane(d[u], k), p, q);
-                float gp = enc_lane(m[u], k) > 0.f ? greg : 0.f;
+                sigmoid_pq(d, p, q);
+                float gp = m > 0.f ? greg : 0.f;
                 if (with_enc) gp += genc * enc_term_dp(p);
                 enc_set(g, k, gp * p * (1.f - p));
-            }
-            po[base + u * 256 + threadIdx.x] = g;
-        }
-    }
+            },
+            [&](int64_t i) { po[i] = g; });
+    });
 }
 
 static inline int enc_blocks(int N, int64_t S, int V) {      // blocks per sample: a function of (N, S, V) alone
@@ -420,9 +474,9 @@ static inline int enc_blocks(int N, int64_t S, int V) {      // blocks per sampl
     return (int)(want < cap ? want : cap);
 }
 static inline int enc_blocks_max(int N, int64_t S) { return enc_blocks(N, S, 1); }
-static inline bool enc_vec4(const void* a, const void* b, const void* c, int64_t S) {
-    return S % 4 == 0 && (((uintptr_t)a | (uintptr_t)b | (uintptr_t)c) & 15) == 0;
-}
+// whether a launch over these tensors may take V = 4
+template <class... P>
+static inline bool enc_vec4(int64_t S, const P*... tensor) { return S % 4 == 0 && ((... | (uintptr_t)tensor) & 15) == 0; }
 
 
 // ---- BootBinCrossEntropy (dram/metrics.py:10-51) and BinaryCrossEntropySmooth (53-72) with a target that is GIVEN ------
@@ -486,20 +540,24 @@ __device__ __forceinline__ int seg_group(int64_t n, int u, int64_t& i) {
     return left >= 4 ? 4 : (left > 0 ? (int)left : 0);
 }
 
-// acc[NS] of every lane -> part[blockIdx.x * NS + q], butterfly per wave, then the four waves in order
-template <int NS>
-__device__ __forceinline__ void seg_block_partials(const double (&acc)[NS], double (*red)[4], double* __restrict__ part) {
+// One tensor of a segmentation kernel: its base, whether the base allows one access per group, and where its values go
+template <class T> struct SegSrc {
+    const T* b;
+    int vec;
+    float (*v)[4];
+    __device__ __forceinline__ SegSrc(const T* b_, int vec_, float (*v_)[4]) : b(b_), vec(vec_), v(v_) {}
+};
+// The groups of this lane: cnt[u] elements from index at[u], and their values of every tensor in src (read in that order)
+template <class... T>
+__device__ __forceinline__ void seg_load_groups(int64_t n, int (&cnt)[SEG_UNROLL], int64_t (&at)[SEG_UNROLL], SegSrc<T>... src) {
 #pragma unroll
-    for (int q = 0; q < NS; ++q) {
-        const double s = wave_sum_d(acc[q]);
-        if ((threadIdx.x & 63) == 0) red[q][threadIdx.x >> 6] = s;
+    for (int u = 0; u < SEG_UNROLL; ++u) {
+        cnt[u] = seg_group(n, u, at[u]);
+        if (cnt[u] > 0) (seg_load4(src.b, at[u], src.vec != 0, cnt[u], src.v[u]), ...);
     }
-    __syncthreads();
-    if (threadIdx.x < NS)
-        part[(size_t)blockIdx.x * NS + threadIdx.x] =
-            ((red[threadIdx.x][0] + red[threadIdx.x][1]) + red[threadIdx.x][2]) + red[threadIdx.x][3];
 }
-// tot[q] = sum of part[b * NS + q] over the nblk blocks, in thread 0 (lanes stride over the blocks, then as above)
+
+// tot[q] = sum of part[b * NS + q] over the nblk blocks (lanes stride over the blocks, then block_totals)
 template <int NS>
 __device__ __forceinline__ void seg_total(const double* __restrict__ part, int64_t nblk, double (*red)[4], double (&tot)[NS]) {
     double s[NS];
@@ -508,14 +566,7 @@ __device__ __forceinline__ void seg_total(const double* __restrict__ part, int64
     for (int64_t b = threadIdx.x; b < nblk; b += 256)
 #pragma unroll
         for (int q = 0; q < NS; ++q) s[q] += part[(size_t)b * NS + q];
-#pragma unroll
-    for (int q = 0; q < NS; ++q) {
-        const double w = wave_sum_d(s[q]);
-        if ((threadIdx.x & 63) == 0) red[q][threadIdx.x >> 6] = w;
-    }
-    __syncthreads();
-#pragma unroll
-    for (int q = 0; q < NS; ++q) tot[q] = ((red[q][0] + red[q][1]) + red[q][2]) + red[q][3];
+    block_totals<NS>(s, red, tot);
 }
 
 template <int KT, int KV>
@@ -527,16 +578,8 @@ __global__ __launch_bounds__(256) void boot_bce_partial_kernel(const float* __re
     __shared__ double red[BOOT_NSUM][4];
     float pv[SEG_UNROLL][4], tv[SEG_UNROLL][4], vv[SEG_UNROLL][4];
     int cnt[SEG_UNROLL];
-#pragma unroll
-    for (int u = 0; u < SEG_UNROLL; ++u) {
-        int64_t i;
-        cnt[u] = seg_group(n, u, i);
-        if (cnt[u] > 0) {
-            seg_load4(p, i, vecp != 0, cnt[u], pv[u]);
-            seg_load4(t, i, vect != 0, cnt[u], tv[u]);
-            seg_load4(voi, i, vecv != 0, cnt[u], vv[u]);
-        }
-    }
+    int64_t at[SEG_UNROLL];
+    seg_load_groups(n, cnt, at, SegSrc(p, vecp, pv), SegSrc(t, vect, tv), SegSrc(voi, vecv, vv));
     double acc[BOOT_NSUM] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
 #pragma unroll
     for (int u = 0; u < SEG_UNROLL; ++u) {
@@ -558,7 +601,7 @@ __global__ __launch_bounds__(256) void boot_bce_partial_kernel(const float* __re
 #pragma unroll
         for (int q = 0; q < BOOT_NSUM; ++q) acc[q] += s[q];
     }
-    seg_block_partials<BOOT_NSUM>(acc, red, part);
+    block_partials<BOOT_NSUM>(acc, red, part + (size_t)blockIdx.x * BOOT_NSUM);
 }
 
 // tot (8 doubles): the seven totals.  state: [0] 1 / n_out (0 without an outside), [1] alpha, [2] 1 / sum w, [3] 1 / n_in,
@@ -607,15 +650,7 @@ __global__ __launch_bounds__(256) void boot_bce_bwd_kernel(const float* __restri
     float pv[SEG_UNROLL][4], tv[SEG_UNROLL][4], vv[SEG_UNROLL][4];
     int cnt[SEG_UNROLL];
     int64_t at[SEG_UNROLL];
-#pragma unroll
-    for (int u = 0; u < SEG_UNROLL; ++u) {
-        cnt[u] = seg_group(n, u, at[u]);
-        if (cnt[u] > 0) {
-            seg_load4(p, at[u], vecp != 0, cnt[u], pv[u]);
-            seg_load4(t, at[u], vect != 0, cnt[u], tv[u]);
-            seg_load4(voi, at[u], vecv != 0, cnt[u], vv[u]);
-        }
-    }
+    seg_load_groups(n, cnt, at, SegSrc(p, vecp, pv), SegSrc(t, vect, tv), SegSrc(voi, vecv, vv));
 #pragma unroll
     for (int u = 0; u < SEG_UNROLL; ++u) {
         if (cnt[u] == 0) continue;
@@ -647,15 +682,8 @@ __global__ __launch_bounds__(256) void bce_smooth_partial_kernel(const float* __
     __shared__ double red[SMOOTH_NSUM][4];
     float pv[SEG_UNROLL][4], tv[SEG_UNROLL][4];
     int cnt[SEG_UNROLL];
-#pragma unroll
-    for (int u = 0; u < SEG_UNROLL; ++u) {
-        int64_t i;
-        cnt[u] = seg_group(n, u, i);
-        if (cnt[u] > 0) {
-            seg_load4(p, i, vecp != 0, cnt[u], pv[u]);
-            seg_load4(t, i, vect != 0, cnt[u], tv[u]);
-        }
-    }
+    int64_t at[SEG_UNROLL];
+    seg_load_groups(n, cnt, at, SegSrc(p, vecp, pv), SegSrc(t, vect, tv));
     double acc[SMOOTH_NSUM] = {0.0, 0.0, 0.0};
 #pragma unroll
     for (int u = 0; u < SEG_UNROLL; ++u) {
@@ -672,7 +700,7 @@ __global__ __launch_bounds__(256) void bce_smooth_partial_kernel(const float* __
 #pragma unroll
         for (int q = 0; q < SMOOTH_NSUM; ++q) acc[q] += s[q];
     }
-    seg_block_partials<SMOOTH_NSUM>(acc, red, part);
+    block_partials<SMOOTH_NSUM>(acc, red, part + (size_t)blockIdx.x * SMOOTH_NSUM);
 }
 
 // tot (8 doubles): T, P1, P2.  state: [0] alpha, [1] 1 / sum w.
@@ -707,14 +735,7 @@ __global__ __launch_bounds__(256) void bce_smooth_bwd_kernel(const float* __rest
     float pv[SEG_UNROLL][4], tv[SEG_UNROLL][4];
     int cnt[SEG_UNROLL];
     int64_t at[SEG_UNROLL];
-#pragma unroll
-    for (int u = 0; u < SEG_UNROLL; ++u) {
-        cnt[u] = seg_group(n, u, at[u]);
-        if (cnt[u] > 0) {
-            seg_load4(p, at[u], vecp != 0, cnt[u], pv[u]);
-            seg_load4(t, at[u], vect != 0, cnt[u], tv[u]);
-        }
-    }
+    seg_load_groups(n, cnt, at, SegSrc(p, vecp, pv), SegSrc(t, vect, tv));
 #pragma unroll
     for (int u = 0; u < SEG_UNROLL; ++u) {
         if (cnt[u] == 0) continue;
@@ -744,9 +765,9 @@ static inline int seg_vec(const void* b, int kind) { return ((uintptr_t)b & (kin
 //   band      = [max(c_lb, lb), min(c_ub, ub)], (c_lb, c_ub) the ratio interval of the sample's CT severity score;
 //               where the two do not overlap: [lb, ub] if it lies below the class interval, the class interval if above
 //   targets_n = band rounded once to fp32,  weight_n = clamp(freq[ctss_n], 0.2, 0.8),  keep_n = ctss_n > 0
-// One pass over the two masks (8 B/voxel, the loads of enc_partial_kernel), per step the products of a lane in fp32 (at
-// most 16 of them: exact for 0/1 masks), steps and lanes in fp64, one fp64 partial pair per block; one wave per sample then
-// adds the partials in a fixed order and lane 0 does the band.  No atomics: the same input gives the same bits.
+// One pass over the two masks (8 B/voxel, stream_packs), per step the products of a lane in fp32 (at most 16 of them: exact
+// for 0/1 masks), steps and lanes in fp64, one fp64 partial pair per block; one wave per sample then adds the partials and
+// its lane 0 does the band.
 // An empty lobe (0/0) gives NaN targets for that sample, a score outside 0..5 NaN targets and a NaN weight.
 constexpr int TGT_NSUM = 2;            // per (sample, block): sum of lesion * lobe, sum of lobe
 struct TargetsArgs {
@@ -757,45 +778,18 @@ struct TargetsArgs {
 template <int V>
 __global__ __launch_bounds__(256) void targets_partial_kernel(const float* __restrict__ lobes, const float* __restrict__ lesions,
                                                               double* __restrict__ part, int64_t S, int nblk) {
-    using T = typename EncPack<V>::type;
     __shared__ double red[TGT_NSUM][4];
     const int n = blockIdx.y;
-    const T* pm = reinterpret_cast<const T*>(lobes + (int64_t)n * S);
-    const T* pl = reinterpret_cast<const T*>(lesions + (int64_t)n * S);
-    const int64_t packs = S / V;
-    const int64_t step = (int64_t)nblk * 256 * ENC_UNROLL;
     double acc[TGT_NSUM] = {0.0, 0.0};
-    for (int64_t base = (int64_t)blockIdx.x * 256 * ENC_UNROLL; base < packs; base += step) {
-        T m[ENC_UNROLL], l[ENC_UNROLL];
-        bool ok[ENC_UNROLL];
-#pragma unroll
-        for (int u = 0; u < ENC_UNROLL; ++u) {
-            const int64_t i = base + u * 256 + threadIdx.x;
-            ok[u] = i < packs;
-            if (ok[u]) { m[u] = pm[i]; l[u] = pl[i]; }
-        }
+    stream_packs<V>(lobes + (int64_t)n * S, lesions + (int64_t)n * S, S, nblk, [&](const PackStep<V>& st) {
         float sl = 0.f, sm = 0.f;
-#pragma unroll
-        for (int u = 0; u < ENC_UNROLL; ++u) {
-            if (!ok[u]) continue;
-#pragma unroll
-            for (int k = 0; k < V; ++k) {
-                const float mv = enc_lane(m[u], k);
-                sl += __fmul_rn(enc_lane(l[u], k), mv);
-                sm += mv;
-            }
-        }
+        st.each([&](int, float m, float l) {
+            sl += __fmul_rn(l, m);
+            sm += m;
+        });
         acc[0] += sl; acc[1] += sm;
-    }
-#pragma unroll
-    for (int q = 0; q < TGT_NSUM; ++q) {
-        const double s = wave_sum_d(acc[q]);
-        if ((threadIdx.x & 63) == 0) red[q][threadIdx.x >> 6] = s;
-    }
-    __syncthreads();
-    if (threadIdx.x < TGT_NSUM)
-        part[((size_t)n * nblk + blockIdx.x) * TGT_NSUM + threadIdx.x] =
-            red[threadIdx.x][0] + red[threadIdx.x][1] + red[threadIdx.x][2] + red[threadIdx.x][3];
+    });
+    block_partials<TGT_NSUM>(acc, red, part + ((size_t)n * nblk + blockIdx.x) * TGT_NSUM);
 }
 
 __global__ __launch_bounds__(256) void targets_finalize_kernel(const double* __restrict__ part, const int* __restrict__ ctss,
@@ -803,13 +797,10 @@ __global__ __launch_bounds__(256) void targets_finalize_kernel(const double* __r
                                                                float* __restrict__ weight, float* __restrict__ keep) {
     // IntRegLoss.ctss_ratio_map (metrics.py:76-83)
     const double c_lo[6] = {0.0, 0.001, 0.01, 0.05, 0.35, 0.5}, c_hi[6] = {0.001, 0.01, 0.05, 0.35, 0.5, 1.00001};
-    const int lane = threadIdx.x & 63;
     for (int n = threadIdx.x >> 6; n < N; n += 4) {
-        double s[TGT_NSUM] = {0.0, 0.0};
-        for (int b = lane; b < nblk; b += 64)
-            for (int q = 0; q < TGT_NSUM; ++q) s[q] += part[((size_t)n * nblk + b) * TGT_NSUM + q];
-        for (int q = 0; q < TGT_NSUM; ++q) s[q] = wave_sum_d(s[q]);
-        if (lane != 0) continue;
+        double s[TGT_NSUM];
+        sample_totals<TGT_NSUM>(part, n, nblk, s);
+        if ((threadIdx.x & 63) != 0) continue;
         const int c = ctss[n];
         const bool known = c >= 0 && c <= 5;
         const float ratio = __fdiv_rn((float)s[0], (float)s[1]);
@@ -838,6 +829,30 @@ __global__ __launch_bounds__(256) void targets_finalize_kernel(const double* __r
 
 using namespace dram;
 
+// ---- C entry points --------------------------------------------------------------------------------------------------------
+// Checks the entry points share (`who` is a string literal).  Every check comes before the first launch.
+static inline bool rows_ok(int N, int64_t S) { return N > 0 && N <= 65535 && S > 0; }      // one grid.y row per sample
+#define LOSS_REQUIRE_WS(who, ws, align, have, need)                                                                 \
+    do {                                                                                                            \
+        DRAM_REQUIRE(((uintptr_t)(ws) & ((align) - 1)) == 0, who ": workspace must be " #align "-byte aligned");    \
+        if ((have) < (need)) {                                                                                      \
+            set_error(who ": workspace too small");                                                                 \
+            return DRAM_EWS;                                                                                        \
+        }                                                                                                           \
+    } while (0)
+
+// launch(Int<4>) or launch(Int<1>): the instantiation of a stream_packs kernel
+template <int K> using Int = std::integral_constant<int, K>;
+template <class F> static inline void with_pack_width(bool v4, F&& launch) {
+    if (v4) launch(Int<4>());
+    else launch(Int<1>());
+}
+// launch(Int<KIND>, typed pointer): the instantiation of a segmentation kernel for one mask; nests for two masks
+template <class F> static inline void with_mask(const void* m, int kind, F&& launch) {
+    if (kind == DRAM_SEG_MASK_U8) launch(Int<DRAM_SEG_MASK_U8>(), (const uint8_t*)m);
+    else launch(Int<DRAM_SEG_MASK_F32>(), (const float*)m);
+}
+
 extern "C" size_t dram_intreg_loss_ws_bytes(int N, int64_t S) {
     if (N <= 0 || S <= 0) return 0;
     return align_up((size_t)N * loss_chunks(S) * NSUM * sizeof(float), 256) + (size_t)N * NSUM * sizeof(double);
@@ -850,11 +865,8 @@ extern "C" int dram_intreg_loss_fwd(const float* dense, const float* refined, co
                                     float* out, float* state, void* ws, size_t ws_bytes, int N, int64_t S, void* stream) {
     if (!refined) refined = dense;
     DRAM_REQUIRE(dense && lobes && lesions && keep && targets && weight && out && state && ws, "intreg_loss_fwd: null pointer");
-    DRAM_REQUIRE(N > 0 && N <= 65535 && S > 0, "intreg_loss_fwd: bad dimensions");
-    if (ws_bytes < dram_intreg_loss_ws_bytes(N, S)) {
-        set_error("intreg_loss_fwd: workspace too small");
-        return DRAM_EWS;
-    }
+    DRAM_REQUIRE(rows_ok(N, S), "intreg_loss_fwd: bad dimensions");
+    LOSS_REQUIRE_WS("intreg_loss_fwd", ws, 8, ws_bytes, dram_intreg_loss_ws_bytes(N, S));      // fp64 sums at a multiple of 256 bytes
     hipStream_t st = (hipStream_t)stream;
     const int nch = loss_chunks(S);
     hipLaunchKernelGGL(loss_partial_kernel, dim3(nch, N), dim3(256), 0, st, dense, refined, lobes, lesions, keep, (float*)ws, S, nch);
@@ -870,10 +882,10 @@ extern "C" int dram_intreg_loss_bwd(const float* dense, const float* refined, co
     if (!refined || refined == dense) { refined = dense; drefined = nullptr; }
     else DRAM_REQUIRE(drefined, "intreg_loss_bwd: drefined is required when refined differs from dense");
     DRAM_REQUIRE(dense && lobes && lesions && keep && targets && weight && state && gout && ddense, "intreg_loss_bwd: null pointer");
-    DRAM_REQUIRE(N > 0 && N <= 65535 && S > 0, "intreg_loss_bwd: bad dimensions");
+    DRAM_REQUIRE(rows_ok(N, S), "intreg_loss_bwd: bad dimensions");
     const unsigned gx = (unsigned)(cdiv64(S, 256 * 8) < 4096 ? cdiv64(S, 256 * 8) : 4096);
-    hipLaunchKernelGGL(loss_bwd_kernel, dim3(gx ? gx : 1, N), dim3(256), 0, (hipStream_t)stream, dense, refined, lobes, lesions,
-                       keep, targets, weight, state, gout, smoothing, ddense, drefined, S);
+    hipLaunchKernelGGL(loss_bwd_kernel, dim3(gx, N), dim3(256), 0, (hipStream_t)stream, dense, refined, lobes, lesions, keep,
+                       targets, weight, state, gout, smoothing, ddense, drefined, S);
     return check_launch("intreg_loss_bwd");
 }
 
@@ -888,19 +900,16 @@ extern "C" int dram_intreg_enc_loss_fwd(const float* dense, const float* lobes, 
                                         float* out, float* state, void* ws, size_t ws_bytes, int N, int64_t S,
                                         void* stream) {
     DRAM_REQUIRE(dense && lobes && targets && weight && out && state && ws, "intreg_enc_loss_fwd: null pointer");
-    DRAM_REQUIRE(N > 0 && N <= 65535 && S > 0, "intreg_enc_loss_fwd: bad dimensions");
-    DRAM_REQUIRE(((uintptr_t)ws & 7) == 0, "intreg_enc_loss_fwd: workspace must be 8-byte aligned");
-    if (ws_bytes < dram_intreg_enc_loss_ws_bytes(N, S)) {
-        set_error("intreg_enc_loss_fwd: workspace too small");
-        return DRAM_EWS;
-    }
+    DRAM_REQUIRE(rows_ok(N, S), "intreg_enc_loss_fwd: bad dimensions");
+    LOSS_REQUIRE_WS("intreg_enc_loss_fwd", ws, 8, ws_bytes, dram_intreg_enc_loss_ws_bytes(N, S));
     hipStream_t st = (hipStream_t)stream;
-    const bool v4 = enc_vec4(dense, lobes, nullptr, S);
+    const bool v4 = enc_vec4(S, dense, lobes);
     const int nblk = enc_blocks(N, S, v4 ? 4 : 1);
     double* part = (double*)ws;
     double* ssum = part + (size_t)N * nblk * ENC_NSUM;
-    if (v4) hipLaunchKernelGGL(enc_partial_kernel<4>, dim3(nblk, N), dim3(256), 0, st, dense, lobes, part, S, nblk);
-    else hipLaunchKernelGGL(enc_partial_kernel<1>, dim3(nblk, N), dim3(256), 0, st, dense, lobes, part, S, nblk);
+    with_pack_width(v4, [&](auto V) {
+        hipLaunchKernelGGL(enc_partial_kernel<V.value>, dim3(nblk, N), dim3(256), 0, st, dense, lobes, part, S, nblk);
+    });
     hipLaunchKernelGGL(enc_finalize_kernel, dim3(1), dim3(256), 0, st, (const double*)part, ssum, targets, weight, N, S, nblk,
                        out, state);
     return check_launch("intreg_enc_loss_fwd");
@@ -910,13 +919,13 @@ extern "C" int dram_intreg_enc_loss_bwd(const float* dense, const float* lobes, 
                                         const float* state, const float* gout, float* ddense, int N, int64_t S,
                                         void* stream) {
     DRAM_REQUIRE(dense && lobes && targets && weight && state && gout && ddense, "intreg_enc_loss_bwd: null pointer");
-    DRAM_REQUIRE(N > 0 && N <= 65535 && S > 0, "intreg_enc_loss_bwd: bad dimensions");
-    const bool v4 = enc_vec4(dense, lobes, ddense, S);
+    DRAM_REQUIRE(rows_ok(N, S), "intreg_enc_loss_bwd: bad dimensions");
+    const bool v4 = enc_vec4(S, dense, lobes, ddense);
     const int nblk = enc_blocks(N, S, v4 ? 4 : 1);
-    if (v4) hipLaunchKernelGGL(enc_bwd_kernel<4>, dim3(nblk, N), dim3(256), 0, (hipStream_t)stream, dense, lobes, targets, weight,
-                               state, gout, ddense, N, S);
-    else hipLaunchKernelGGL(enc_bwd_kernel<1>, dim3(nblk, N), dim3(256), 0, (hipStream_t)stream, dense, lobes, targets, weight,
-                            state, gout, ddense, N, S);
+    with_pack_width(v4, [&](auto V) {
+        hipLaunchKernelGGL(enc_bwd_kernel<V.value>, dim3(nblk, N), dim3(256), 0, (hipStream_t)stream, dense, lobes, targets,
+                           weight, state, gout, ddense, N, S);
+    });
     return check_launch("intreg_enc_loss_bwd");
 }
 
@@ -943,10 +952,7 @@ extern "C" int dram_masked_smooth_l1_fwd(const float* a, const float* b, const f
                                          size_t ws_bytes, int N, int C, int64_t S, void* stream) {
     DRAM_REQUIRE(a && b && mask && out && ws, "masked_smooth_l1_fwd: null pointer");
     DRAM_REQUIRE(N > 0 && C > 0 && S > 0 && (int64_t)N * C <= 65535, "masked_smooth_l1_fwd: bad dimensions");
-    if (ws_bytes < dram_masked_smooth_l1_ws_bytes(N, C, S)) {
-        set_error("masked_smooth_l1_fwd: workspace too small");
-        return DRAM_EWS;
-    }
+    LOSS_REQUIRE_WS("masked_smooth_l1_fwd", ws, 4, ws_bytes, dram_masked_smooth_l1_ws_bytes(N, C, S));
     hipStream_t st = (hipStream_t)stream;
     const int nch = loss_chunks(S);
     hipLaunchKernelGGL(masked_smooth_l1_partial_kernel, dim3(nch, N * C), dim3(256), 0, st, a, b, mask, (float*)ws, C, S, nch);
@@ -977,36 +983,23 @@ extern "C" int dram_seg_loss_chunk(void) { return SEG_CHUNK; }
     DRAM_REQUIRE((n) >= 0, who ": negative element count");                                          \
     DRAM_REQUIRE((n) <= ((int64_t)1 << 40), who ": more than 2^40 elements") /* one block per 4096 elements, grid.x < 2^31 */
 
-// kernel<KT, KV> for the two mask kinds of a BootBinCrossEntropy call
-#define BOOT_DISPATCH(kernel, grid, st, ...)                                                                                   \
-    do {                                                                                                                       \
-        if (t_kind == DRAM_SEG_MASK_U8 && voi_kind == DRAM_SEG_MASK_U8)                                                        \
-            hipLaunchKernelGGL((kernel<0, 0>), grid, dim3(256), 0, st, p, (const uint8_t*)t, (const uint8_t*)voi, __VA_ARGS__); \
-        else if (t_kind == DRAM_SEG_MASK_U8)                                                                                   \
-            hipLaunchKernelGGL((kernel<0, 2>), grid, dim3(256), 0, st, p, (const uint8_t*)t, (const float*)voi, __VA_ARGS__);   \
-        else if (voi_kind == DRAM_SEG_MASK_U8)                                                                                 \
-            hipLaunchKernelGGL((kernel<2, 0>), grid, dim3(256), 0, st, p, (const float*)t, (const uint8_t*)voi, __VA_ARGS__);   \
-        else                                                                                                                   \
-            hipLaunchKernelGGL((kernel<2, 2>), grid, dim3(256), 0, st, p, (const float*)t, (const float*)voi, __VA_ARGS__);     \
-    } while (0)
-
 extern "C" int dram_boot_bce_fwd(const float* p, const void* t, const void* voi, int t_kind, int voi_kind, int64_t n,
                                  double smoothing, float* out, float* state, void* ws, size_t ws_bytes, void* stream) {
     SEG_REQUIRE_COMMON("boot_bce_fwd", n);
     DRAM_REQUIRE(seg_kind_ok(t_kind) && seg_kind_ok(voi_kind), "boot_bce_fwd: mask kind must be 0 (uint8) or 2 (float32)");
     if (n == 0) return DRAM_OK;
     DRAM_REQUIRE(p && t && voi && out && state && ws, "boot_bce_fwd: null pointer");
-    DRAM_REQUIRE(((uintptr_t)ws & 7) == 0, "boot_bce_fwd: workspace must be 8-byte aligned");
-    if (ws_bytes < dram_seg_loss_ws_bytes(n)) {
-        set_error("boot_bce_fwd: workspace too small");
-        return DRAM_EWS;
-    }
+    LOSS_REQUIRE_WS("boot_bce_fwd", ws, 8, ws_bytes, dram_seg_loss_ws_bytes(n));
     hipStream_t st = (hipStream_t)stream;
     const int64_t nblk = seg_blocks(n);
     double* tot = (double*)ws;
     double* part = tot + SEG_TOTALS;
-    BOOT_DISPATCH(boot_bce_partial_kernel, dim3((unsigned)nblk), st, part, n, seg_vec(p, DRAM_SEG_MASK_F32), seg_vec(t, t_kind),
-                  seg_vec(voi, voi_kind));
+    with_mask(t, t_kind, [&](auto KT, auto tp) {
+        with_mask(voi, voi_kind, [&](auto KV, auto vp) {
+            hipLaunchKernelGGL((boot_bce_partial_kernel<KT.value, KV.value>), dim3((unsigned)nblk), dim3(256), 0, st, p, tp, vp, part,
+                               n, seg_vec(p, DRAM_SEG_MASK_F32), seg_vec(t, t_kind), seg_vec(voi, voi_kind));
+        });
+    });
     hipLaunchKernelGGL(boot_bce_finish_kernel, dim3(1), dim3(256), 0, st, (const double*)part, nblk, smoothing, tot, out, state);
     return check_launch("boot_bce_fwd");
 }
@@ -1017,8 +1010,13 @@ extern "C" int dram_boot_bce_bwd(const float* p, const void* t, const void* voi,
     DRAM_REQUIRE(seg_kind_ok(t_kind) && seg_kind_ok(voi_kind), "boot_bce_bwd: mask kind must be 0 (uint8) or 2 (float32)");
     if (n == 0) return DRAM_OK;
     DRAM_REQUIRE(p && t && voi && state && gout && dp, "boot_bce_bwd: null pointer");
-    BOOT_DISPATCH(boot_bce_bwd_kernel, dim3((unsigned)seg_blocks(n)), (hipStream_t)stream, state, gout, (float)smoothing, dp, n,
-                  seg_vec(p, DRAM_SEG_MASK_F32), seg_vec(t, t_kind), seg_vec(voi, voi_kind), seg_vec(dp, DRAM_SEG_MASK_F32));
+    with_mask(t, t_kind, [&](auto KT, auto tp) {
+        with_mask(voi, voi_kind, [&](auto KV, auto vp) {
+            hipLaunchKernelGGL((boot_bce_bwd_kernel<KT.value, KV.value>), dim3((unsigned)seg_blocks(n)), dim3(256), 0,
+                               (hipStream_t)stream, p, tp, vp, state, gout, (float)smoothing, dp, n, seg_vec(p, DRAM_SEG_MASK_F32),
+                               seg_vec(t, t_kind), seg_vec(voi, voi_kind), seg_vec(dp, DRAM_SEG_MASK_F32));
+        });
+    });
     return check_launch("boot_bce_bwd");
 }
 
@@ -1028,20 +1026,15 @@ extern "C" int dram_bce_smooth_fwd(const float* p, const void* t, int t_kind, in
     DRAM_REQUIRE(seg_kind_ok(t_kind), "bce_smooth_fwd: target kind must be 0 (uint8) or 2 (float32)");
     if (n == 0) return DRAM_OK;
     DRAM_REQUIRE(p && t && out && state && ws, "bce_smooth_fwd: null pointer");
-    DRAM_REQUIRE(((uintptr_t)ws & 7) == 0, "bce_smooth_fwd: workspace must be 8-byte aligned");
-    if (ws_bytes < dram_seg_loss_ws_bytes(n)) {
-        set_error("bce_smooth_fwd: workspace too small");
-        return DRAM_EWS;
-    }
+    LOSS_REQUIRE_WS("bce_smooth_fwd", ws, 8, ws_bytes, dram_seg_loss_ws_bytes(n));
     hipStream_t st = (hipStream_t)stream;
     const int64_t nblk = seg_blocks(n);
     double* tot = (double*)ws;
     double* part = tot + SEG_TOTALS;
-    const int vecp = seg_vec(p, DRAM_SEG_MASK_F32), vect = seg_vec(t, t_kind);
-    if (t_kind == DRAM_SEG_MASK_U8)
-        hipLaunchKernelGGL(bce_smooth_partial_kernel<0>, dim3((unsigned)nblk), dim3(256), 0, st, p, (const uint8_t*)t, part, n, vecp, vect);
-    else
-        hipLaunchKernelGGL(bce_smooth_partial_kernel<2>, dim3((unsigned)nblk), dim3(256), 0, st, p, (const float*)t, part, n, vecp, vect);
+    with_mask(t, t_kind, [&](auto KT, auto tp) {
+        hipLaunchKernelGGL(bce_smooth_partial_kernel<KT.value>, dim3((unsigned)nblk), dim3(256), 0, st, p, tp, part, n,
+                           seg_vec(p, DRAM_SEG_MASK_F32), seg_vec(t, t_kind));
+    });
     hipLaunchKernelGGL(bce_smooth_finish_kernel, dim3(1), dim3(256), 0, st, (const double*)part, nblk, n, smooth, tot, out, state);
     return check_launch("bce_smooth_fwd");
 }
@@ -1052,13 +1045,11 @@ extern "C" int dram_bce_smooth_bwd(const float* p, const void* t, int t_kind, in
     DRAM_REQUIRE(seg_kind_ok(t_kind), "bce_smooth_bwd: target kind must be 0 (uint8) or 2 (float32)");
     if (n == 0) return DRAM_OK;
     DRAM_REQUIRE(p && t && state && gout && dp, "bce_smooth_bwd: null pointer");
-    hipStream_t st = (hipStream_t)stream;
-    const dim3 grid((unsigned)seg_blocks(n));
-    const int vecp = seg_vec(p, DRAM_SEG_MASK_F32), vect = seg_vec(t, t_kind), vecd = seg_vec(dp, DRAM_SEG_MASK_F32);
-    if (t_kind == DRAM_SEG_MASK_U8)
-        hipLaunchKernelGGL(bce_smooth_bwd_kernel<0>, grid, dim3(256), 0, st, p, (const uint8_t*)t, state, gout, (float)smooth, dp, n, vecp, vect, vecd);
-    else
-        hipLaunchKernelGGL(bce_smooth_bwd_kernel<2>, grid, dim3(256), 0, st, p, (const float*)t, state, gout, (float)smooth, dp, n, vecp, vect, vecd);
+    with_mask(t, t_kind, [&](auto KT, auto tp) {
+        hipLaunchKernelGGL(bce_smooth_bwd_kernel<KT.value>, dim3((unsigned)seg_blocks(n)), dim3(256), 0, (hipStream_t)stream, p, tp,
+                           state, gout, (float)smooth, dp, n, seg_vec(p, DRAM_SEG_MASK_F32), seg_vec(t, t_kind),
+                           seg_vec(dp, DRAM_SEG_MASK_F32));
+    });
     return check_launch("bce_smooth_bwd");
 }
 
@@ -1071,21 +1062,18 @@ extern "C" int dram_intreg_targets(const float* lobes, const float* lesions, con
                                    double band_width, float* targets, float* weight, float* keep, void* ws,
                                    size_t ws_bytes, int N, int64_t S, void* stream) {
     DRAM_REQUIRE(lobes && lesions && ctss && freq && targets && weight && keep && ws, "intreg_targets: null pointer");
-    DRAM_REQUIRE(N > 0 && N <= 65535 && S > 0, "intreg_targets: bad dimensions");
-    DRAM_REQUIRE(((uintptr_t)ws & 7) == 0, "intreg_targets: workspace must be 8-byte aligned");
-    if (ws_bytes < dram_intreg_targets_ws_bytes(N, S)) {
-        set_error("intreg_targets: workspace too small");
-        return DRAM_EWS;
-    }
+    DRAM_REQUIRE(rows_ok(N, S), "intreg_targets: bad dimensions");
+    LOSS_REQUIRE_WS("intreg_targets", ws, 8, ws_bytes, dram_intreg_targets_ws_bytes(N, S));
     hipStream_t st = (hipStream_t)stream;
     TargetsArgs a;
     for (int k = 0; k < 6; ++k) a.freq[k] = freq[k];
     a.band_width = band_width;
-    const bool v4 = enc_vec4(lobes, lesions, nullptr, S);
+    const bool v4 = enc_vec4(S, lobes, lesions);
     const int nblk = enc_blocks(N, S, v4 ? 4 : 1);
     double* part = (double*)ws;
-    if (v4) hipLaunchKernelGGL(targets_partial_kernel<4>, dim3(nblk, N), dim3(256), 0, st, lobes, lesions, part, S, nblk);
-    else hipLaunchKernelGGL(targets_partial_kernel<1>, dim3(nblk, N), dim3(256), 0, st, lobes, lesions, part, S, nblk);
+    with_pack_width(v4, [&](auto V) {
+        hipLaunchKernelGGL(targets_partial_kernel<V.value>, dim3(nblk, N), dim3(256), 0, st, lobes, lesions, part, S, nblk);
+    });
     hipLaunchKernelGGL(targets_finalize_kernel, dim3(1), dim3(256), 0, st, (const double*)part, ctss, a, N, nblk, targets, weight,
                        keep);
     return check_launch("intreg_targets");

@@ -117,11 +117,13 @@ def test_intreg_loss_saturated_logits(n, shape):
         assert (got - ref).abs().max().item() <= 1e-4 * ref.abs().max().item()
 
 
-def test_intreg_loss_uses_refined_when_given():
+# 9x17x23 = 3519 voxels; 21x23x19 = 9177, an odd count past 8192: nine blocks per sample, the last one partly filled
+@pytest.mark.parametrize("shape", [(9, 17, 23), (21, 23, 19)], ids=["9x17x23", "21x23x19"])
+def test_intreg_loss_uses_refined_when_given(shape):
     """The reference takes the model's second output for both terms (metrics.py:206-209): with `refined` given, both follow
     it and `dense` gets no gradient."""
     from dram_amd.train_step import Batch, DeviceIntRegLoss
-    dense, lobes, lesions, images, ctss = _random_case(3, (9, 17, 23), 2.0)
+    dense, lobes, lesions, images, ctss = _random_case(3, shape, 2.0)
     refined = torch.randn(dense.shape, generator=torch.Generator().manual_seed(3)) * 2.0
     batch = Batch(images.cuda(), lobes.cuda(), lesions.cuda(), ctss, FREQ, band_width=BAND)
     r64 = refined.double().requires_grad_(True)

@@ -48,6 +48,34 @@ def test_argument_errors_are_reported_without_a_gpu():
     assert _lib.lib.dram_conv3d_k3_wgrad_ws_bytes(4, 64, 64, 128, 128, 128) > 0
 
 
+def test_loss_workspace_alignment_errors_are_reported_without_a_gpu():
+    """dram_intreg_loss_fwd keeps fp64 sums in its workspace and dram_masked_smooth_l1_fwd floats: a workspace that is not
+    8-byte / 4-byte aligned is refused (DRAM_EINVAL) before anything is launched, an aligned one that is too small still
+    with DRAM_EWS."""
+    from dram_amd import _lib
+    q = 16                                  # a dummy non-null, 16-byte aligned pointer: every check comes before the launch
+    N, C, S = 3, 2, 5 * 7 * 9
+    need = _lib.lib.dram_intreg_loss_ws_bytes(N, S)
+    refine = lambda ws, ws_bytes: (q, None, q, q, q, q, q, 0.1, q, q, ws, ws_bytes, N, S, None)
+    assert need > 0
+    assert _lib.lib.dram_intreg_loss_fwd(*refine(q + 4, need)) == -1
+    with pytest.raises(_lib.DramHipError, match="intreg_loss_fwd: workspace must be 8-byte aligned"):
+        _lib.call("dram_intreg_loss_fwd", *refine(q + 4, need))
+    assert _lib.lib.dram_intreg_loss_fwd(*refine(q, need - 1)) == -2
+    with pytest.raises(_lib.DramHipError, match="intreg_loss_fwd: workspace too small"):
+        _lib.call("dram_intreg_loss_fwd", *refine(q, need - 1))
+    need = _lib.lib.dram_masked_smooth_l1_ws_bytes(N, C, S)
+    smooth = lambda ws, ws_bytes: (q, q, q, q, ws, ws_bytes, N, C, S, None)
+    assert need > 0
+    for off in (1, 2, 3):
+        assert _lib.lib.dram_masked_smooth_l1_fwd(*smooth(q + off, need)) == -1
+    with pytest.raises(_lib.DramHipError, match="masked_smooth_l1_fwd: workspace must be 4-byte aligned"):
+        _lib.call("dram_masked_smooth_l1_fwd", *smooth(q + 2, need))
+    assert _lib.lib.dram_masked_smooth_l1_fwd(*smooth(q + 4, need - 1)) == -2
+    with pytest.raises(_lib.DramHipError, match="masked_smooth_l1_fwd: workspace too small"):
+        _lib.call("dram_masked_smooth_l1_fwd", *smooth(q + 4, need - 1))
+
+
 def _norm_workspace_calls(N, C, D, H, W, ws_bytes):
     """(entry point, arguments) of every entry point that takes the norm workspace, on dummy non-null pointers."""
     S, q = D * H * W, 16
