@@ -898,11 +898,48 @@ extern "C" int dram_upsample_trilinear_ac_fwd_lazy(const float* x, const float* 
     return check_launch("upsample_trilinear_ac_fwd_lazy");
 }
 
-// Two-stage backward (z first, then y/x) through a caller-provided workspace; planes are processed in groups
-// that fit the workspace.  Falls back to the single-stage kernel when the shape does not qualify.
-static bool tri_two_stage_ok(const float* dy, int D, int H, int W, int Do, int Ho, int Wo) {
-    return Do > D && (Wo % 4) == 0 && (((uintptr_t)dy) & 15) == 0 && max_taps_host(D, Do) <= MAXT &&
-           max_taps_host(H, Ho) <= MAXT && max_taps_host(W, Wo) <= MAXT && (int64_t)D * Ho * Wo < 0x7fffffffLL;
+// Backward of the align_corners=True resize: which kernels a call launches, decided in one place for both entry points and
+// for dram_upsample_trilinear_ac_bwd_choice.  Host arithmetic only.
+//   two-stage (z first, then y/x, through a caller-provided workspace; planes are processed in groups that fit it): z is
+//   magnified, rows of dy and of the workspace are whole 16-byte pieces, the tap kernels serve every axis and the workspace
+//   holds at least TRI_CPT planes.  Its second stage is the 16-byte yx4 kernel where dx allows it and the x scale lies in its
+//   window, the tap (gather) kernel with an identity z axis otherwise.
+//   one-stage: the tap (gather) kernel, or the general kernel when an axis has more than MAXT taps per input.
+enum { TRI_BWD_Z_YX4 = 0, TRI_BWD_Z_GATHER = 1, TRI_BWD_GATHER = 2, TRI_BWD_GENERAL = 3 };
+struct TriBwdChoice {
+    int route;        // TRI_BWD_*
+    int64_t group;    // planes per workspace round of the two-stage routes (a multiple of TRI_CPT); 0 on the others
+};
+static TriBwdChoice tri_bwd_choice(bool dy_mis, bool dx_mis, bool ws_mis, size_t ws_bytes, int D, int H, int W, int Do, int Ho,
+                                   int Wo) {
+    TriBwdChoice c;
+    c.group = 0;
+    const bool taps_ok = max_taps_host(D, Do) <= MAXT && max_taps_host(H, Ho) <= MAXT && max_taps_host(W, Wo) <= MAXT;
+    const size_t per_plane = (size_t)D * Ho * Wo * sizeof(float);
+    int64_t group = (int64_t)(ws_bytes / per_plane);
+    group -= group % TRI_CPT;
+    const bool two_stage = group >= TRI_CPT && !ws_mis && Do > D && (Wo % 4) == 0 && !dy_mis && taps_ok &&
+                           (int64_t)D * Ho * Wo < 0x7fffffffLL;
+    if (!two_stage) {
+        c.route = taps_ok ? TRI_BWD_GATHER : TRI_BWD_GENERAL;
+        return c;
+    }
+    c.group = group;
+    // (a group starts a multiple of TRI_CPT planes into dx, i.e. a multiple of 32 bytes: every group is aligned as dx is)
+    const float sx = make_axis(W, Wo).scale;
+    c.route = sx >= 0.4546f && sx <= 1.f && (W % 4) == 0 && !dx_mis ? TRI_BWD_Z_YX4 : TRI_BWD_Z_GATHER;
+    return c;
+}
+
+extern "C" int dram_upsample_trilinear_ac_bwd_choice(int dy_mis, int dx_mis, int ws_mis, size_t ws_bytes, int N, int C, int D,
+                                                     int H, int W, int Do, int Ho, int Wo, int64_t* group) {
+    DRAM_REQUIRE(group, "upsample_trilinear_ac_bwd_choice: null pointer");
+    DRAM_REQUIRE(D > 0 && H > 0 && W > 0 && Do > 0 && Ho > 0 && Wo > 0, "upsample_trilinear_ac_bwd_choice: bad sizes");
+    int rc = check_planes("upsample_trilinear_ac_bwd_choice", (int64_t)N * C, (int64_t)D * H * W);
+    if (rc) return rc;
+    const TriBwdChoice c = tri_bwd_choice(dy_mis != 0, dx_mis != 0, ws_mis != 0, ws_bytes, D, H, W, Do, Ho, Wo);
+    *group = c.group;
+    return c.route;
 }
 
 extern "C" size_t dram_upsample_trilinear_ac_bwd_ws_bytes(int N, int C, int D, int H, int W, int Do, int Ho, int Wo) {
@@ -910,26 +947,37 @@ extern "C" size_t dram_upsample_trilinear_ac_bwd_ws_bytes(int N, int C, int D, i
     return (size_t)N * C * D * Ho * Wo * sizeof(float);
 }
 
+static int tri_bwd_one_stage(const TriBwdChoice& c, const float* dy, float* dx, int planes, int D, int H, int W, int Do, int Ho,
+                             int Wo, hipStream_t st) {
+    if (c.route == TRI_BWD_GATHER) {
+        dim3 grid(cdiv(D * H * W, 256), cdiv(planes, TRI_CPT));
+        hipLaunchKernelGGL(trilinear_bwd_kernel, grid, dim3(256), 0, st, dy, dx, make_axis(D, Do), make_axis(H, Ho),
+                           make_axis(W, Wo), planes);
+    } else {   // magnification above ~2.5x on some axis
+        dim3 grid(cdiv(D * H * W, 256), planes);
+        hipLaunchKernelGGL(trilinear_bwd_general_kernel, grid, dim3(256), 0, st, dy, dx, make_axis(D, Do), make_axis(H, Ho),
+                           make_axis(W, Wo));
+    }
+    return check_launch("upsample_trilinear_ac_bwd");
+}
+
 extern "C" int dram_upsample_trilinear_ac_bwd_ws(const float* dy, float* dx, void* ws, size_t ws_bytes, int N, int C,
                                                  int D, int H, int W, int Do, int Ho, int Wo, void* stream) {
     DRAM_REQUIRE(dy && dx, "upsample_trilinear_ac_bwd: null pointer");
     DRAM_REQUIRE(D > 0 && H > 0 && W > 0 && Do > 0 && Ho > 0 && Wo > 0, "upsample_trilinear_ac_bwd: bad sizes");
-    const size_t per_plane = (size_t)D * Ho * Wo * sizeof(float);
-    int64_t group = ws ? (int64_t)(ws_bytes / per_plane) : 0;
-    group -= group % TRI_CPT;
-    if (group < TRI_CPT || (((uintptr_t)ws) & 15) != 0 || !tri_two_stage_ok(dy, D, H, W, Do, Ho, Wo))
-        return dram_upsample_trilinear_ac_bwd(dy, dx, N, C, D, H, W, Do, Ho, Wo, stream);
     int rc = check_planes("upsample_trilinear_ac_bwd", (int64_t)N * C, (int64_t)D * H * W);
     if (rc) return rc;
     hipStream_t st = (hipStream_t)stream;
-    const int64_t planes = (int64_t)N * C;
+    const TriBwdChoice c = tri_bwd_choice(!aligned16(dy), !aligned16(dx), !aligned16(ws), ws ? ws_bytes : 0, D, H, W, Do, Ho, Wo);
+    if (c.route == TRI_BWD_GATHER || c.route == TRI_BWD_GENERAL) return tri_bwd_one_stage(c, dy, dx, N * C, D, H, W, Do, Ho, Wo, st);
+    const int64_t planes = (int64_t)N * C, group = c.group;
     const Axis az = make_axis(D, Do), ay = make_axis(H, Ho), ax = make_axis(W, Wo), idz = make_axis(D, D);
     const int64_t So = (int64_t)Do * Ho * Wo, S = (int64_t)D * H * W;
     for (int64_t p0 = 0; p0 < planes; p0 += group) {
         const int g = (int)((planes - p0) < group ? (planes - p0) : group);
         hipLaunchKernelGGL(trilinear_bwd_z_kernel, dim3(cdiv(D * Ho * (Wo / 4), 256), cdiv(g, TRI_CPT)), dim3(256), 0, st,
                            dy + p0 * So, (float*)ws, az, Ho, Wo, g);
-        if (ax.scale >= 0.4546f && ax.scale <= 1.f && (W % 4) == 0 && ((((uintptr_t)(dx + p0 * S)) & 15) == 0))
+        if (c.route == TRI_BWD_Z_YX4)
             hipLaunchKernelGGL(trilinear_bwd_yx4_kernel, dim3(cdiv(D * H * (W / 4), 256), cdiv(g, TRI_CPT)), dim3(256), 0, st,
                                (const float*)ws, dx + p0 * S, D, ay, ax, g);
         else
@@ -945,16 +993,9 @@ extern "C" int dram_upsample_trilinear_ac_bwd(const float* dy, float* dx, int N,
     DRAM_REQUIRE(D > 0 && H > 0 && W > 0 && Do > 0 && Ho > 0 && Wo > 0, "upsample_trilinear_ac_bwd: bad sizes");
     int rc = check_planes("upsample_trilinear_ac_bwd", (int64_t)N * C, (int64_t)D * H * W);
     if (rc) return rc;
-    if (max_taps_host(D, Do) <= MAXT && max_taps_host(H, Ho) <= MAXT && max_taps_host(W, Wo) <= MAXT) {
-        dim3 grid(cdiv(D * H * W, 256), cdiv(N * C, TRI_CPT));
-        hipLaunchKernelGGL(trilinear_bwd_kernel, grid, dim3(256), 0, (hipStream_t)stream, dy, dx, make_axis(D, Do),
-                           make_axis(H, Ho), make_axis(W, Wo), N * C);
-    } else {   // magnification above ~2.5x on some axis
-        dim3 grid(cdiv(D * H * W, 256), N * C);
-        hipLaunchKernelGGL(trilinear_bwd_general_kernel, grid, dim3(256), 0, (hipStream_t)stream, dy, dx,
-                           make_axis(D, Do), make_axis(H, Ho), make_axis(W, Wo));
-    }
-    return check_launch("upsample_trilinear_ac_bwd");
+    // no workspace: one of the one-stage routes
+    const TriBwdChoice c = tri_bwd_choice(!aligned16(dy), !aligned16(dx), false, 0, D, H, W, Do, Ho, Wo);
+    return tri_bwd_one_stage(c, dy, dx, N * C, D, H, W, Do, Ho, Wo, (hipStream_t)stream);
 }
 
 static int check_crop(const char* who, int D, int H, int W, int D2, int H2, int W2, int oz, int oy, int ox) {

@@ -832,6 +832,23 @@ def max_pool3d(x, kernel_size, stride=None, padding=0):
 # --------------------------------------------------------------------------- trilinear resize
 # workspace cap of the two-stage trilinear backward (the z-reduced intermediate of a group of planes)
 TRI_BWD_WS_CAP = 1 << 30
+TRI_BWD_ROUTES = ("z+yx4", "z+gather", "gather", "general")
+
+
+def trilinear_bwd_choice(dy, dx, ws, in_shape):
+    """(route, group) of a dram_upsample_trilinear_ac_bwd_ws call with these tensors (ws: the uint8 workspace, or None) --
+    asked of the library itself (dram_upsample_trilinear_ac_bwd_choice: the same choice the launch goes through).  route:
+    "z+yx4" / "z+gather" = trilinear_bwd_z_kernel into the workspace, then trilinear_bwd_yx4_kernel / trilinear_bwd_kernel,
+    `group` planes per round; "gather" = trilinear_bwd_kernel alone; "general" = trilinear_bwd_general_kernel (group 0)."""
+    N, C, D, H, W = in_shape
+    Do, Ho, Wo = dy.shape[-3:]
+    group = ctypes.c_int64(0)
+    route = _lib.lib.dram_upsample_trilinear_ac_bwd_choice(
+        int(dy.data_ptr() % 16 != 0), int(dx.data_ptr() % 16 != 0), int(ws is not None and ws.data_ptr() % 16 != 0),
+        ws.numel() * ws.element_size() if ws is not None else 0, N, C, D, H, W, Do, Ho, Wo, ctypes.byref(group))
+    if route < 0:
+        raise _lib.DramHipError(f"dram_upsample_trilinear_ac_bwd_choice: {_lib.lib.dram_last_error().decode()}")
+    return TRI_BWD_ROUTES[route], int(group.value)
 
 
 def trilinear_ac_backward(dy, in_shape):

@@ -214,6 +214,14 @@ int dram_upsample_trilinear_ac_bwd(const float* dy, float* dx, int N, int C, int
 size_t dram_upsample_trilinear_ac_bwd_ws_bytes(int N, int C, int D, int H, int W, int Do, int Ho, int Wo);
 int dram_upsample_trilinear_ac_bwd_ws(const float* dy, float* dx, void* ws, size_t ws_bytes, int N, int C,
                                       int D, int H, int W, int Do, int Ho, int Wo, void* stream);
+/* Which kernels such a call launches (the same choice both entry points above go through; host arithmetic only, no HIP
+ * call).  *_mis: that pointer is NOT 16-byte aligned; ws_bytes = 0: no workspace (dram_upsample_trilinear_ac_bwd).
+ * Returns 0 = two-stage, trilinear_bwd_z_kernel + trilinear_bwd_yx4_kernel; 1 = two-stage, trilinear_bwd_z_kernel +
+ * trilinear_bwd_kernel on the z-reduced copy; 2 = trilinear_bwd_kernel alone; 3 = trilinear_bwd_general_kernel (an axis
+ * with more than 6 taps per input); negative on bad sizes.  *group: planes per workspace round of the two-stage routes
+ * (a multiple of 8), 0 on the others. */
+int dram_upsample_trilinear_ac_bwd_choice(int dy_mis, int dx_mis, int ws_mis, size_t ws_bytes, int N, int C, int D, int H,
+                                          int W, int Do, int Ho, int Wo, int64_t* group);
 
 /* ---- crop_concat_5d (parts.py:37-46) ----
  * out[N,C1+C2,D,H,W] = cat(t1[N,C1,D,H,W], t2[N,C2,D2,H2,W2][..., oz:oz+D, oy:oy+H, ox:ox+W]). */

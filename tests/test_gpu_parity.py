@@ -658,6 +658,8 @@ def test_maxpool_with_ties(shape):
                                   ((2, 9, 4, 4, 4), None, 2), ((1, 5, 9, 10, 40), None, 2), ((2, 3, 16, 16, 16), None, 2),
                                   ((1, 2, 6, 7, 33), (12, 15, 60), None),
                                   # the LDS-tiled forward kernel: ragged tiles in z and y, plane tail, widest rows, 3x along x
+                                  # (that is the forward; the backward of (1, 1, 3, 4, 128) x2 is trilinear_bwd_general_kernel, z 3 -> 6
+                                  # having seven taps -- the backward kernels are pinned in tests/test_gpu_trilinear_bwd.py)
                                   ((1, 3, 8, 12, 64), None, 2), ((1, 1, 3, 4, 128), None, 2), ((1, 6, 5, 11, 8), (10, 23, 24), None)])
 def test_trilinear_align_corners(case):
     from dram_amd import functional as HF
