@@ -2739,6 +2739,38 @@ extern "C" int dram_conv3d_k3_wgrad_choice(int N, int C1, int C2, int Cout, int 
     return id->kind;
 }
 
+// Every row of the nine tables, one kernel_name() per line: what the two choice queries above can answer.
+template <typename Args>
+static void append_rows(const KernelTable<Args>& t, char* buf, size_t cap, size_t& used, int& rows) {
+    for (int r = 0; r < t.n; ++r, ++rows) {
+        char name[128];
+        kernel_name(t.rows[r].id, name, sizeof(name));
+        // (snprintf returns the length of the whole line whether or not it fitted: `used` goes on counting past cap)
+        used += (size_t)snprintf(used < cap ? buf + used : nullptr, used < cap ? cap - used : 0, "%s\n", name);
+    }
+}
+extern "C" int dram_conv3d_k3_kernel_rows(char* buf, size_t cap) {
+    DRAM_REQUIRE(buf && cap > 0, "conv3d_k3_kernel_rows: null buffer");
+    size_t used = 0;
+    int rows = 0;
+    append_rows(kFwdRows, buf, cap, used, rows);
+    append_rows(kFwdWzRows, buf, cap, used, rows);
+    append_rows(kFwdC1Rows, buf, cap, used, rows);
+    append_rows(kFwdWzyRows, buf, cap, used, rows);
+    append_rows(kWgradRows, buf, cap, used, rows);
+    append_rows(kWgradVecRows, buf, cap, used, rows);
+    append_rows(kWgradWzRows, buf, cap, used, rows);
+    append_rows(kWgradC1Rows, buf, cap, used, rows);
+    append_rows(kWgradWzyRows, buf, cap, used, rows);
+    if (used >= cap) {
+        buf[0] = '\0';
+        set_error("conv3d_k3_kernel_rows: %zu bytes for %d names, the buffer holds %zu", used + 1, rows, cap);
+        return DRAM_EINVAL;
+    }
+    buf[used] = '\0';
+    return rows;
+}
+
 extern "C" int dram_conv3d_k3_launch_counts(unsigned long long* counts, int n) {
     DRAM_REQUIRE(counts && n > 0, "conv3d_k3_launch_counts: null pointer");
     for (int i = 0; i < n; ++i) counts[i] = i < DRAM_K3_KINDS ? g_launches[i].load(std::memory_order_relaxed) : 0ull;

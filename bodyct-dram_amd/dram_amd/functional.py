@@ -93,6 +93,18 @@ def conv_wgrad_kernel_name(N, dhw, Cout, C1, C2=0, lazy=False):
     return buf.value.decode()
 
 
+def conv_kernel_rows():
+    """Names of all 3x3x3 conv kernel instantiations of the library, in the spelling of conv_fwd_kernel_name and
+    conv_wgrad_kernel_name (dram_conv3d_k3_kernel_rows: the row tables every launch goes through)."""
+    buf = ctypes.create_string_buffer(8192)
+    n = _lib.lib.dram_conv3d_k3_kernel_rows(buf, len(buf))
+    if n < 0:
+        raise _lib.DramHipError(f"dram_conv3d_k3_kernel_rows: {_lib.lib.dram_last_error().decode()}")
+    rows = buf.value.decode().splitlines()
+    assert len(rows) == n
+    return rows
+
+
 def conv_launch_counts():
     """Launches per 3x3x3 conv kernel family (index = K3_*) since the library was loaded."""
     arr = (ctypes.c_ulonglong * K3_KINDS)()

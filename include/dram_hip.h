@@ -511,6 +511,9 @@ int dram_conv3d_k3_fwd_choice_src(int Cin, int Cout, int D, int H, int W, int ds
 /* backward-weights with x = x1[.,C1,..] ++ crop(x2[.,C2,..]) (C2 = 0: one tensor); lazy != 0: the *_fused variant
  * with at least one lazily normalised source. */
 int dram_conv3d_k3_wgrad_choice(int N, int C1, int C2, int Cout, int D, int H, int W, int lazy, char* name, size_t cap);
+/* every instantiation the two queries above can name, one per line in the same spelling, into buf[cap]; returns their
+ * number (DRAM_EINVAL: cap too small).  Needs no device. */
+int dram_conv3d_k3_kernel_rows(char* buf, size_t cap);
 /* launches per kernel family (index = DRAM_K3_*) since the library was loaded, into counts[0..n) */
 int dram_conv3d_k3_launch_counts(unsigned long long* counts, int n);
 
