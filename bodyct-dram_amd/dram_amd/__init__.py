@@ -17,7 +17,10 @@ _AUGMENT = ("GaussianBlur", "RandomMaskOut", "RandomFlip", "RandomRotate90", "Ga
 # the segmentation losses of `losses`, the same way
 _LOSSES = ("BootBinCrossEntropy", "BinaryCrossEntropySmooth")
 
-__all__ = ["_lib", "functional", "modules", "optim", "Adam", "AdamW", "SGD", "RAdam", "AdaBound", *_AUGMENT, *_LOSSES]
+# the lesion-wise report of `lesions`, the same way
+_LESIONS = ("label_components", "component_stats", "remove_small", "lobe_burden", "lesion_report")
+
+__all__ = ["_lib", "functional", "modules", "optim", "Adam", "AdamW", "SGD", "RAdam", "AdaBound", *_AUGMENT, *_LOSSES, *_LESIONS]
 
 
 def __getattr__(name):
@@ -27,4 +30,7 @@ def __getattr__(name):
     if name in _LOSSES:
         from . import losses
         return getattr(losses, name)
+    if name in _LESIONS:
+        from . import lesions
+        return getattr(lesions, name)
     raise AttributeError(f"module {__name__!r} has no attribute {name!r}")

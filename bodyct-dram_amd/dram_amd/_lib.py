@@ -163,6 +163,12 @@ SIGNATURES = {
     "dram_chunk_hist256": (I, [P, P, P, I, P, I, I, P]),
     "dram_otsu256": (I, [P, I, ctypes.c_double, P, P]),
     "dram_chunk_prepare": (I, [P, P, P, P, P, I, I, I, I, F, F, I, I, P, P, P, P, P]),
+    # lesion-wise report: connected components, their statistics, LUT relabelling, per-lobe burden
+    "dram_cc_ws_bytes": (Z, [I, I, I]),
+    "dram_cc_label": (I, [P, P, P, I, I, I, I, P, Z, P]),
+    "dram_cc_stats": (I, [P, P, I, P, P, P, I, I, I, P]),
+    "dram_cc_relabel": (I, [P, P, I, P, P, L, P]),
+    "dram_lobe_burden": (I, [P, P, P, L, P]),
     # optimiser update (table: host array of dram_optim_tensor)
     "dram_optim_table_capacity": (I, []),
     "dram_optim_adam": (I, [P, I] + [ctypes.c_double] * 5 + [I, I, I, P]),

@@ -793,6 +793,34 @@ int dram_chunk_prepare(const int16_t* scans, const uint8_t* lobes, const uint8_t
                        int N, int Do, int Ho, int Wo, float wmin, float wmax, int pwmin, int pwmax, float* image,
                        float* lobe_out, float* lesion_out, float* vessel_out, void* stream);
 
+/* ---- lesion-wise report at inference: what a consumer of the final lesion mask otherwise does on the host with
+ *      scipy.ndimage.label / find_objects, and the CT severity score of IntRegLoss.ctss_ratio_map (dram/metrics.py:76-83) per
+ *      lobe.  Volumes are contiguous [D,H,W] on the DEVICE, D*H*W < 2^31; masks and lobes uint8 (non-zero = set), labels int32.
+ *      Null pointers, non-positive sizes and D*H*W >= 2^31 are DRAM_EINVAL before anything is launched.  None of the entries
+ *      synchronises, allocates or reads device memory from the host.
+ * dram_cc_label: labels = 0 on the background, 1..n on the components of `mask` under `connectivity` 1, 2 or 3 (6, 18 or 26
+ *   neighbours, scipy.ndimage.generate_binary_structure(3, connectivity)), numbered by the raster order of their first voxel
+ *   (scipy.ndimage.label's numbering); *count (device int32) = n.  Union-find on the linear index: six launches whatever the
+ *   data, integer min-atomics, the result does not depend on their order (the same bits every run).  ws: dram_cc_ws_bytes(D, H,
+ *   W) bytes, 4-byte aligned (too small: DRAM_EWS); dram_cc_ws_bytes answers without a GPU, 0 for sizes that dram_cc_label
+ *   refuses.  labels doubles as the parent array while the call runs.
+ * dram_cc_stats: for k in 1..n (n >= 1): voxels[k-1] = the number of voxels with labels == k, bbox[(k-1)*6 ..] = {z0, z1, y0, y1,
+ *   x0, x1} half-open (the slices of scipy.ndimage.find_objects; {D, 0, H, 0, W, 0} for a k without voxels), hits[k-1] = how many
+ *   of them have other != 0.  other and hits are NULL together.  The outputs are initialised here.  A voxel whose label lies
+ *   outside 0..n is the caller's error: it is skipped.
+ * dram_cc_relabel: out_labels[i] = lut[labels[i]], lut: n + 1 device int32 with lut[0] = 0 (a label outside 0..n maps to 0);
+ *   out_mask[i] = out_labels[i] != 0.  Either output may be NULL; out_labels may be labels.  1 <= nvox < 2^31, n >= 0.
+ * dram_lobe_burden: counts[v*2 + 0] = voxels with lobe == v, counts[v*2 + 1] = those of them with mask != 0, v in 0..255 (512
+ *   int64, zeroed here).  16-byte loads where mask and lobe are 16-byte aligned, any alignment works.  1 <= nvox < 2^31. ---- */
+size_t dram_cc_ws_bytes(int D, int H, int W);
+int dram_cc_label(const uint8_t* mask, int32_t* labels, int32_t* count, int connectivity, int D, int H, int W, void* ws,
+                  size_t ws_bytes, void* stream);
+int dram_cc_stats(const int32_t* labels, const uint8_t* other, int n, int64_t* voxels, int32_t* bbox, int64_t* hits, int D, int H,
+                  int W, void* stream);
+int dram_cc_relabel(const int32_t* labels, const int32_t* lut, int n, int32_t* out_labels, uint8_t* out_mask, int64_t nvox,
+                    void* stream);
+int dram_lobe_burden(const uint8_t* mask, const uint8_t* lobe, int64_t* counts, int64_t nvox, void* stream);
+
 /* ---- the optimiser update (st_dram_ref.py: torch.optim.Adam(lr=1e-4) under ExponentialLR; the SGD block beside it):
  *      multi-tensor Adam / AdamW / SGD on fp32 tensors, one launch per table of up to DRAM_OPTIM_TABLE_CAPACITY tensors.
  * `table` is HOST memory, read before the call returns (it travels to the device in the kernel arguments): per tensor the
