@@ -53,7 +53,6 @@ __global__ __launch_bounds__(256) void row_moments_kernel(const float* __restric
     const int len = (int)((S - beg) < CHUNK ? (S - beg) : CHUNK);
     const float* p = x + row * S + beg;
     float v[32];
-    int cnt = 0;
     float s = 0.f;
     if (VEC) {
         // All 8 loads first, from clamped (always valid) addresses, and only then the arithmetic: a load inside
@@ -81,7 +80,6 @@ __global__ __launch_bounds__(256) void row_moments_kernel(const float* __restric
             s += v[q];
         }
     }
-    (void)cnt;
     const float mean = block_sum_256(s, red) / (float)len;
     float m2 = 0.f;
     if (VEC) {
@@ -487,7 +485,9 @@ __global__ void bn_bwd_finalize_kernel(const double* __restrict__ rowsum, const 
     double k2 = 0.0, k3 = 0.0;
     if (batch_stats) { k2 = -k1 * s2 / M; k3 = -k1 * s1 / M; }
     // dx = k1*dy' + k2*xhat + k3, xhat = (x-mean)*rstd
-    const float p = (float)k1, q = (float)(k2 * rstd), r = (float)(k3 - k2 * rstd * mean);
+    float p = (float)k1, q = (float)(k2 * rstd), r = (float)(k3 - k2 * rstd * mean);
+    // One value per channel: y = beta whatever x is, so dx is exactly 0 (p*dy' + r would leave the rounding of k1*dy').
+    if (batch_stats && M == 1.0) p = q = r = 0.f;
     for (int n = 0; n < N; ++n) {
         float* o = pqr + 3 * ((size_t)n * C + c);
         o[0] = p; o[1] = q; o[2] = r;
@@ -654,7 +654,8 @@ __global__ void bn_pqr_from_sums_kernel(const double* __restrict__ sums, double 
     const double rstd = save_rstd[c], mean = save_mean[c];
     const double k1 = g * rstd;
     const double k2 = -k1 * sums[2 * c + 1] / count, k3 = -k1 * sums[2 * c] / count;
-    const float p = (float)k1, q = (float)(k2 * rstd), r = (float)(k3 - k2 * rstd * mean);
+    float p = (float)k1, q = (float)(k2 * rstd), r = (float)(k3 - k2 * rstd * mean);
+    if (count == 1.0) p = q = r = 0.f;      // as bn_bwd_finalize_kernel: one value per channel has dx = 0
     for (int n = 0; n < N; ++n) {
         float* o = pqr + 3 * ((size_t)n * C + c);
         o[0] = p; o[1] = q; o[2] = r;
