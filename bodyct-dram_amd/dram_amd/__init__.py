@@ -20,7 +20,11 @@ _LOSSES = ("BootBinCrossEntropy", "BinaryCrossEntropySmooth")
 # the lesion-wise report of `lesions`, the same way
 _LESIONS = ("label_components", "component_stats", "remove_small", "lobe_burden", "lesion_report")
 
-__all__ = ["_lib", "functional", "modules", "optim", "Adam", "AdamW", "SGD", "RAdam", "AdaBound", *_AUGMENT, *_LOSSES, *_LESIONS]
+# the surface-distance metrics of `surface`, the same way
+_SURFACE = ("distance_transform", "mask_surface", "surface_distances")
+
+__all__ = ["_lib", "functional", "modules", "optim", "Adam", "AdamW", "SGD", "RAdam", "AdaBound", *_AUGMENT, *_LOSSES, *_LESIONS,
+           *_SURFACE]
 
 
 def __getattr__(name):
@@ -33,4 +37,7 @@ def __getattr__(name):
     if name in _LESIONS:
         from . import lesions
         return getattr(lesions, name)
+    if name in _SURFACE:
+        from . import surface
+        return getattr(surface, name)
     raise AttributeError(f"module {__name__!r} has no attribute {name!r}")

@@ -169,6 +169,12 @@ SIGNATURES = {
     "dram_cc_stats": (I, [P, P, I, P, P, P, I, I, I, P]),
     "dram_cc_relabel": (I, [P, P, I, P, P, L, P]),
     "dram_lobe_burden": (I, [P, P, P, L, P]),
+    # surface-distance metrics: exact Euclidean distance transform, mask surface, compaction over a surface
+    "dram_edt_max_dim": (I, []),
+    "dram_edt_ws_bytes": (Z, [I, I, I]),
+    "dram_edt": (I, [P, P] + [ctypes.c_double] * 3 + [I, I, I, P, Z, P]),
+    "dram_mask_surface": (I, [P, P, P, I, I, I, P]),
+    "dram_surface_gather": (I, [P, P, P, P, L, L, P]),
     # optimiser update (table: host array of dram_optim_tensor)
     "dram_optim_table_capacity": (I, []),
     "dram_optim_adam": (I, [P, I] + [ctypes.c_double] * 5 + [I, I, I, P]),

@@ -8,26 +8,15 @@ and from the heat map only).
     rep = lesion_report(res["mask_post"], lobe, spacing, min_volume_mm3=10.0)
 
 Kernels: csrc/components.hip (union-find labelling in a fixed number of launches, component statistics with integer atomics,
-look-up-table relabelling, per-lobe burden).  Only small per-component tables travel to the host.
+look-up-table relabelling, per-lobe burden); the boundary metrics against a reference come from `surface`.  Only small
+per-component tables travel to the host.
 """
 import numpy as np
 import torch
 
 from ._lib import call, lib
 from .inference import ratio_to_label
-
-
-def _device_u8(v, device=None):
-    v = torch.as_tensor(v)
-    if device is None:
-        device = v.device if v.is_cuda else torch.device("cuda", torch.cuda.current_device())
-    if v.dtype != torch.uint8:
-        v = v != 0
-    return v.to(device=device, dtype=torch.uint8).contiguous()
-
-
-def _stream():
-    return torch.cuda.current_stream().cuda_stream
+from .surface import _device_u8, _stream, surface_distances
 
 
 def label_components(mask, connectivity=1):
@@ -118,7 +107,7 @@ def lobe_burden(mask, lobe):
     return counts.cpu().numpy()
 
 
-def lesion_report(mask, lobe, spacing, connectivity=1, min_volume_mm3=0.0, reference=None):
+def lesion_report(mask, lobe, spacing, connectivity=1, min_volume_mm3=0.0, reference=None, surface=False, tolerances_mm=()):
     """The lesion-wise report of a [D,H,W] lesion mask (e.g. `LobeInference.run(...)["mask_post"]`, or the "original" entries
     on the scan's own grid) with its lobe map and voxel spacing (z, y, x) in mm.
 
@@ -130,7 +119,8 @@ def lesion_report(mask, lobe, spacing, connectivity=1, min_volume_mm3=0.0, refer
             quotient of the two integer counts of the filtered mask, ctss = inference.ratio_to_label(ratio);
     and with a `reference` mask: n_reference (its components under the same connectivity), n_found (those of them that the
     filtered mask touches), sensitivity (n_found / n_reference, NaN without reference lesions), n_false (kept components that do
-    not touch the reference)."""
+    not touch the reference); and with `surface=True` on top of that: surface = `surface.surface_distances` of the filtered mask
+    against the reference (Hausdorff distance, HD95, average symmetric surface distance, surface Dice at `tolerances_mm`)."""
     mask = _device_u8(mask)
     dev = mask.device
     lobe = torch.as_tensor(lobe).to(device=dev, dtype=torch.uint8).contiguous()
@@ -140,6 +130,8 @@ def lesion_report(mask, lobe, spacing, connectivity=1, min_volume_mm3=0.0, refer
         reference = _device_u8(reference, dev)
         if reference.shape != mask.shape:
             raise ValueError("lesion_report: reference and mask must have the same shape")
+    elif surface:
+        raise ValueError("lesion_report: surface=True needs a reference mask")
     voxel_volume = float(np.prod(np.asarray(spacing, dtype=np.float64)))
     labels, n = label_components(mask, connectivity)
     stats = component_stats(labels, n, reference)
@@ -160,4 +152,6 @@ def lesion_report(mask, lobe, spacing, connectivity=1, min_volume_mm3=0.0, refer
         n_found = int(np.count_nonzero(found))
         out.update(n_reference=n_ref, n_found=n_found, sensitivity=n_found / n_ref if n_ref else float("nan"),
                    n_false=int(np.count_nonzero(stats["hits"][keep] == 0)))
+        if surface:
+            out["surface"] = surface_distances(kept_mask, reference, spacing, tolerances_mm=tolerances_mm)
     return out

@@ -821,6 +821,30 @@ int dram_cc_relabel(const int32_t* labels, const int32_t* lut, int n, int32_t* o
                     void* stream);
 int dram_lobe_burden(const uint8_t* mask, const uint8_t* lobe, int64_t* counts, int64_t nvox, void* stream);
 
+/* ---- surface-distance metrics at inference (Hausdorff, its percentiles, average symmetric surface distance, surface Dice):
+ *      what a consumer otherwise does on the host with scipy.ndimage.distance_transform_edt and binary_erosion.  Volumes are
+ *      contiguous [D,H,W] on the DEVICE, D*H*W < 2^31; masks uint8 (non-zero = set).  Null pointers and refused sizes are
+ *      DRAM_EINVAL before anything is launched.  None of the entries synchronises, allocates or reads device memory from the host.
+ * dram_edt: dist[v] = the distance in mm from voxel v to the nearest voxel with feature != 0 under the voxel spacing (sz, sy, sx)
+ *   (each in (0, 1e6]): 0 on a feature, +inf everywhere when there is none.  Defined bit for bit:
+ *     dist = (float) sqrt(d2),  d2 = min over features of  fl(fl(fl(dx^2 * wx) + fl(dy^2 * wy)) + fl(dz^2 * wz))  in fp64,
+ *   wz = fl(sz * sz), wy, wx likewise and dx, dy, dz the integer offsets; computed by three separable passes (x: nearest feature of
+ *   the row; y, z: the plain minimum over the line), which give exactly that value because rounded addition is monotone.  Every
+ *   dimension at most dram_edt_max_dim() (>= 1024).  ws: dram_edt_ws_bytes(D, H, W) bytes, 8-byte aligned (too small: DRAM_EWS);
+ *   dram_edt_ws_bytes and dram_edt_max_dim answer without a GPU, the former 0 for sizes that dram_edt refuses.
+ * dram_mask_surface: surf[v] = 1 where mask[v] is set and one of its six face neighbours is unset or outside the volume, else 0
+ *   (mask & ~scipy.ndimage.binary_erosion(mask, generate_binary_structure(3, 1), border_value=0)); *count (device int64, zeroed
+ *   here) = the number of surface voxels.
+ * dram_surface_gather: out[0 .. n) = dist[v] for the n voxels with surf[v] != 0, in no particular order; *cursor (device int64,
+ *   zeroed here) = n.  Slots at or past `capacity` (the floats that out holds) are not written.  1 <= nvox < 2^31. ---- */
+int dram_edt_max_dim(void);
+size_t dram_edt_ws_bytes(int D, int H, int W);
+int dram_edt(const uint8_t* feature, float* dist, double sz, double sy, double sx, int D, int H, int W, void* ws, size_t ws_bytes,
+             void* stream);
+int dram_mask_surface(const uint8_t* mask, uint8_t* surf, int64_t* count, int D, int H, int W, void* stream);
+int dram_surface_gather(const uint8_t* surf, const float* dist, float* out, int64_t* cursor, int64_t capacity, int64_t nvox,
+                        void* stream);
+
 /* ---- the optimiser update (st_dram_ref.py: torch.optim.Adam(lr=1e-4) under ExponentialLR; the SGD block beside it):
  *      multi-tensor Adam / AdamW / SGD on fp32 tensors, one launch per table of up to DRAM_OPTIM_TABLE_CAPACITY tensors.
  * `table` is HOST memory, read before the call returns (it travels to the device in the kernel arguments): per tensor the
