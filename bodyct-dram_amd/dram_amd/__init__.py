@@ -23,8 +23,11 @@ _LESIONS = ("label_components", "component_stats", "remove_small", "lobe_burden"
 # the surface-distance metrics of `surface`, the same way
 _SURFACE = ("distance_transform", "mask_surface", "surface_distances")
 
+# the pseudo-vessel mask of `vessels`, the same way
+_VESSELS = ("gaussian_derivative_taps", "hessian", "vesselness", "vessel_mask", "pseudo_vessel_mask")
+
 __all__ = ["_lib", "functional", "modules", "optim", "Adam", "AdamW", "SGD", "RAdam", "AdaBound", *_AUGMENT, *_LOSSES, *_LESIONS,
-           *_SURFACE]
+           *_SURFACE, *_VESSELS]
 
 
 def __getattr__(name):
@@ -40,4 +43,7 @@ def __getattr__(name):
     if name in _SURFACE:
         from . import surface
         return getattr(surface, name)
+    if name in _VESSELS:
+        from . import vessels
+        return getattr(vessels, name)
     raise AttributeError(f"module {__name__!r} has no attribute {name!r}")

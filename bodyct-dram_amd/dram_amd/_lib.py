@@ -175,6 +175,13 @@ SIGNATURES = {
     "dram_edt": (I, [P, P] + [ctypes.c_double] * 3 + [I, I, I, P, Z, P]),
     "dram_mask_surface": (I, [P, P, P, I, I, I, P]),
     "dram_surface_gather": (I, [P, P, P, P, L, L, P]),
+    # pseudo-vessel mask: Hessian of Gaussian, Frangi's c, eigenvalues and vesselness, mask
+    "dram_vessel_max_radius": (I, []),
+    "dram_hessian_ws_bytes": (Z, [I, I, I]),
+    "dram_hessian": (I, [P, I, F, F, P, P, P, I, I, I, P, P, Z, P]),
+    "dram_hessian_norm_max": (I, [P, P, L, P, P]),
+    "dram_vesselness": (I, [P, L, ctypes.c_double, ctypes.c_double, P, P, I, P, P]),
+    "dram_vessel_mask": (I, [P, P, F, P, L, P]),
     # optimiser update (table: host array of dram_optim_tensor)
     "dram_optim_table_capacity": (I, []),
     "dram_optim_adam": (I, [P, I] + [ctypes.c_double] * 5 + [I, I, I, P]),

@@ -112,6 +112,8 @@ class LobeInference:
     def run(self, scan, lobe, spacing, vessel=None, lesion=None, original_spacing=None, original_size=None):
         """`vessel` (uint8 [D,H,W], optional): the vessel mask of LesionSegTest.run; with it (or with `lesion`) the result also
         holds the post-processed mask `mask_post` = mask & (windowed scan > brightness threshold) & ~vessel (job_runner.py:1006-1010).
+        `vessel` may also be a callable `fn(scan_dev, lobe_dev, spacing) -> uint8 [D,H,W]` that produces the mask; it is called once
+        on the device tensors held here (`dram_amd.vessels.pseudo_vessel_mask`, or a functools.partial of it, fits as it is).
         `lesion` (uint8 [D,H,W], optional): the reference mask; adds iou / iou_post / dice / dice_post (job_runner.py:1033-1037),
         computed at the working resolution unless `original_spacing` and `original_size` ((z, y, x), the scan's metadata) are
         given: then, like job_runner.py:1016-1032, the masks (nearest neighbour), the scan and the heat map (linear) first go
@@ -123,6 +125,8 @@ class LobeInference:
         if scan.dim() != 3 or scan.shape != lobe.shape:
             raise ValueError("scan and lobe must be [D,H,W] arrays of the same shape")
         D, H, W = scan.shape
+        if callable(vessel):
+            vessel = vessel(scan, lobe, spacing)
         st = torch.cuda.current_stream().cuda_stream
         boxes = torch.empty(self.max_labels * 6, dtype=torch.int32, device=dev)
         call("dram_label_bboxes", lobe.data_ptr(), boxes.data_ptr(), self.max_labels, D, H, W, st)

@@ -845,6 +845,52 @@ int dram_mask_surface(const uint8_t* mask, uint8_t* surf, int64_t* count, int D,
 int dram_surface_gather(const uint8_t* surf, const float* dist, float* out, int64_t* cursor, int64_t capacity, int64_t nvox,
                         void* stream);
 
+/* ---- pseudo-vessel mask (csrc/vessel.hip): Frangi's multi-scale Hessian vesselness, the producer of the `vessel` input of
+ *      dram_lesion_post (the reference reads one pseudo_vessels .mha file per scan, dram/dataset.py:379-383, and does not say how they were made).
+ *      Volumes are contiguous [D,H,W] on the DEVICE, S = D*H*W < 2^31.  Null pointers, refused sizes and a radius over the cap
+ *      are DRAM_EINVAL, a workspace that is too small DRAM_EWS, both before anything is launched.  None of the entries
+ *      synchronises, allocates or reads device memory from the host.
+ * Scales and taps: for a scale s in mm and the spacing (z, y, x) the caller forms, per axis a, sv[a] = s / spacing[a], the radius
+ *   radius[a] = int(4.0 * sv[a] + 0.5) (scipy's truncate = 4.0) and the 1-D taps of order 0, 1, 2 of
+ *   scipy.ndimage.gaussian_filter1d(sigma = sv[a], order = o) in fp64, rounds them once to fp32 and hands them over as the DEVICE
+ *   table taps[3 axes z, y, x][3 orders][dram_vessel_max_radius() + 1]: taps[a][o][j] multiplies the sample at distance +j, the
+ *   sample at -j gets the same weight (orders 0, 2) or its negative (order 1); entries past radius[a] must be zero.
+ *   dram_vessel_max_radius() = 32 serves s = 4 mm at 0.5 mm spacing; a larger radius is refused, not clamped.
+ * dram_hessian: h6[6][S] fp32 in the order zz, yy, xx, zy, zx, yx,  H_ab = fl(sv[a] * sv[b]) * (d^2/da db of G * I) in voxel units, the
+ *   scale-normalised second derivative per mm^2.  scan: dtype DRAM_VESSEL_INT16 or DRAM_VESSEL_FLOAT32; every voxel is converted
+ *   to fp32 and clamped to [clip_lo, clip_hi] on load (-inf, +inf: no clamp; a NaN stays).  Boundary: scipy's mode='reflect'
+ *   (d c b a | a b c d), index i -> i mod 2n, then 2n-1-i when >= n, so an axis shorter than the radius is legal.  Three separable
+ *   passes x, y, z (x: orders 0, 1, 2; y: the six combinations; z: one order per output), each output rounded to fp32; one
+ *   output of one pass is, with w = taps[a][o], v the line and m = 4 * ceil(radius[a] / 4):
+ *       acc = fl(w[0] * v[i]) (order 1: 0);  for j = 1 .. m:  acc = fma(w[j], fl(v[i+j] + v[i-j]), acc)   (order 1: fl(v[i+j] - v[i-j]))
+ *   and the z pass multiplies by fl(sv[a] * sv[b]) (the product in fp64) last; a zero result is stored as +0.  No value depends on the launch geometry, the tile
+ *   or the size of the volume around it beyond the reflection.  ws: dram_hessian_ws_bytes(D, H, W) bytes (nine fp32 volumes),
+ *   4-byte aligned; the x pass moves 16 bytes per lane when W % 4 == 0 and ws is 16-byte aligned.  dram_hessian_ws_bytes and
+ *   dram_vessel_max_radius answer without a GPU, the former 0 for sizes that dram_hessian refuses.
+ * dram_hessian_norm_max: c_out[0] (device fp32) = Frangi's c: half the largest Frobenius norm of H over the voxels with lobe != 0
+ *   (lobe == NULL: all voxels), 1 when that maximum is 0 (also: no voxel).  The norm is
+ *   (float) sqrt(zz^2 + yy^2 + xx^2 + 2 (zy^2 + zx^2 + yx^2)) in fp64, summed left to right without fused multiply-adds; the maximum
+ *   is an integer max-atomic on the bit patterns: exact and order-free.
+ * dram_vesselness: per voxel the eigenvalues l1, l2, l3 of H by ascending magnitude, equal magnitudes by ascending value
+ *   (numpy.linalg.eigvalsh, then a stable argsort of the magnitudes), solved in fp64 from the fp32 entries by five cyclic Jacobi
+ *   sweeps, and with Ra = |l2| / |l3|, Rb = |l1| / sqrt(|l2 l3|), S2 = l1^2 + l2^2 + l3^2, c = c_dev[0] (device fp32):
+ *       V = (1 - exp(-Ra^2 / 2 alpha^2)) * exp(-Rb^2 / 2 beta^2) * (1 - exp(-S2 / 2 c^2))      (bright tube on dark)
+ *   in fp64 (1 - exp(-x) as -expm1(-x)), rounded once to fp32; exactly 0 when l2 >= 0 or l3 >= 0 or the expression is not finite.
+ *   vmax[i] = accumulate ? max(vmax[i], V) : V -- the running maximum over scales.  eig ([3][S] fp64, may be NULL) receives
+ *   l1, l2, l3.
+ * dram_vessel_mask: mask[i] = (vmax[i] >= threshold) && (lobe == NULL || lobe[i] != 0).  (dram_threshold_mask is a strict > and
+ *   has no lobe gate.) ---- */
+#define DRAM_VESSEL_INT16 0
+#define DRAM_VESSEL_FLOAT32 1
+int dram_vessel_max_radius(void);
+size_t dram_hessian_ws_bytes(int D, int H, int W);
+int dram_hessian(const void* scan, int dtype, float clip_lo, float clip_hi, const float* taps, const int* radius, const double* sv,
+                 int D, int H, int W, float* h6, void* ws, size_t ws_bytes, void* stream);
+int dram_hessian_norm_max(const float* h6, const uint8_t* lobe, int64_t S, float* c_out, void* stream);
+int dram_vesselness(const float* h6, int64_t S, double alpha, double beta, const float* c_dev, float* vmax, int accumulate,
+                    double* eig, void* stream);
+int dram_vessel_mask(const float* vmax, const uint8_t* lobe, float threshold, uint8_t* mask, int64_t n, void* stream);
+
 /* ---- the optimiser update (st_dram_ref.py: torch.optim.Adam(lr=1e-4) under ExponentialLR; the SGD block beside it):
  *      multi-tensor Adam / AdamW / SGD on fp32 tensors, one launch per table of up to DRAM_OPTIM_TABLE_CAPACITY tensors.
  * `table` is HOST memory, read before the call returns (it travels to the device in the kernel arguments): per tensor the
