@@ -26,8 +26,11 @@ _SURFACE = ("distance_transform", "mask_surface", "surface_distances")
 # the pseudo-vessel mask of `vessels`, the same way
 _VESSELS = ("gaussian_derivative_taps", "hessian", "vesselness", "vessel_mask", "pseudo_vessel_mask")
 
+# the views of test-time augmentation at inference (`inference`), the same way
+_INFERENCE = ("tta_views",)
+
 __all__ = ["_lib", "functional", "modules", "optim", "Adam", "AdamW", "SGD", "RAdam", "AdaBound", *_AUGMENT, *_LOSSES, *_LESIONS,
-           *_SURFACE, *_VESSELS]
+           *_SURFACE, *_VESSELS, *_INFERENCE]
 
 
 def __getattr__(name):
@@ -46,4 +49,7 @@ def __getattr__(name):
     if name in _VESSELS:
         from . import vessels
         return getattr(vessels, name)
+    if name in _INFERENCE:
+        from . import inference
+        return getattr(inference, name)
     raise AttributeError(f"module {__name__!r} has no attribute {name!r}")

@@ -182,6 +182,10 @@ SIGNATURES = {
     "dram_hessian_norm_max": (I, [P, P, L, P, P]),
     "dram_vesselness": (I, [P, L, ctypes.c_double, ctypes.c_double, P, P, I, P, P]),
     "dram_vessel_mask": (I, [P, P, F, P, L, P]),
+    # test-time augmentation for the per-lobe inference (views: host array of V x {perm[3], flip[3]})
+    "dram_tta_expand": (I, [P, P, I, I, P, I, P]),
+    "dram_tta_combine": (I, [P, P, P, I, I, P, I, P]),
+    "dram_lobe_paste_prob": (I, [P, P, P, P, P, P, I, I, I, I, I, P]),
     # optimiser update (table: host array of dram_optim_tensor)
     "dram_optim_table_capacity": (I, []),
     "dram_optim_adam": (I, [P, I] + [ctypes.c_double] * 5 + [I, I, I, P]),

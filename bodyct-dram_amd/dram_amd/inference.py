@@ -22,8 +22,15 @@ class's channel divided by its maximum over the crop -- zero for class 0, and Na
 is <= 0 over the whole crop).  It is meant for `out_ch > 1` models; with one channel every lobe is class 0 and the map is zero.
 The result then also holds `lobe_cls` ({label: class}), `pool` ([lobes, out_ch]) and `lobe_mask`; `lobewise_records` turns
 `lobe_cls` into the reference's lobe-wise records.
+
+`LobeInference(tta=...)` is test-time augmentation, which the reference does not have: every chunk goes through the model in V
+signed-permutation views (`tta_views`; the flips and 90-degree rotations the model is trained to be consistent under), the heat
+map is the mean of the V sigmoid maps and the result gains `spread`, their population standard deviation -- both formed at the
+chunk's resolution, then resized and pasted like the single-view map (include/dram_hip.h, "test-time augmentation";
+csrc/infer_tta.hip).  `tta=None` (the default) is the path described above, unchanged.
 """
 import ctypes
+import itertools
 import math
 
 import numpy as np
@@ -67,6 +74,39 @@ def binary_cam_threshold(hist, scaler=1.0):
 
 _RESAMPLE_KINDS = {torch.uint8: 0, torch.int16: 1, torch.float32: 2}
 
+TTA_MAX_VIEWS = 48     # DRAM_TTA_MAX_VIEWS (include/dram_hip.h): the signed permutations of three axes
+
+
+def tta_views(kind):
+    """The views of test-time augmentation as a tuple of (perm, flip) pairs in `dram_spatial_permute_flip`'s convention
+    (viewed[o] = x[i], i[perm[k]] = flip[k] ? R-1-o[k] : o[k]).
+    "flip": the 8 flip combinations under the identity permutation, ordered by the flip bits read as a binary number with z
+    the high bit -- the identity first.  "full": all 48 signed permutations, by permutation in lexicographic order, then by
+    flips as above -- the identity first.  Anything else is taken as a sequence of (perm, flip) pairs, validated (1 to 48
+    views, perm a permutation of (0, 1, 2), flips 0 or 1; a repeated view counts that many times) and returned."""
+    flips = [((n >> 2) & 1, (n >> 1) & 1, n & 1) for n in range(8)]
+    if isinstance(kind, str):
+        if kind == "flip":
+            return tuple(((0, 1, 2), f) for f in flips)
+        if kind == "full":
+            return tuple((p, f) for p in itertools.permutations(range(3)) for f in flips)
+        raise ValueError(f"tta_views: unknown kind {kind!r} ('flip', 'full' or a sequence of (perm, flip) pairs)")
+    try:
+        views = tuple((tuple(perm), tuple(flip)) for perm, flip in kind)
+    except TypeError:
+        raise ValueError("tta_views: 'flip', 'full' or a sequence of (perm, flip) pairs") from None
+    if not 1 <= len(views) <= TTA_MAX_VIEWS:
+        raise ValueError(f"tta_views: between 1 and {TTA_MAX_VIEWS} views, got {len(views)}")
+    out = []
+    for perm, flip in views:
+        if len(perm) != 3 or any(isinstance(a, bool) or not isinstance(a, (int, np.integer)) for a in perm) or \
+                sorted(int(a) for a in perm) != [0, 1, 2]:
+            raise ValueError(f"tta_views: perm {perm!r} is not a permutation of (0, 1, 2)")
+        if len(flip) != 3 or any(not isinstance(f, (bool, int, np.integer)) or int(f) not in (0, 1) for f in flip):
+            raise ValueError(f"tta_views: flip {flip!r}: three values, each 0 or 1")
+        out.append((tuple(int(a) for a in perm), tuple(int(f) for f in flip)))
+    return tuple(out)
+
 
 def resample_volume(vol, spacing, required_spacing, new_size, interpolator="linear"):
     """`utils.resample(narray, spacing, required_spacing=..., new_size=..., interpolator=...)` (dram/utils.py:414-434) of a
@@ -92,17 +132,28 @@ class LobeInference:
     present in the uint8 lobe map is visited in ascending order (evaluate_scan: `np.unique(lobe)[1:]`,
     job_runner.py:729); a label above max_labels raises instead of being silently left out of the heat map.
     head: "sigmoid" (default) pastes sigmoid(dense) like evaluate_scan; "cam" runs the lobe-wise class head of
-    LesionSegTest.run (module docstring) and adds lobe_cls / pool / lobe_mask to the result."""
+    LesionSegTest.run (module docstring) and adds lobe_cls / pool / lobe_mask to the result.
+    tta: None (default: one view, the path above), "flip", "full" or a sequence of (perm, flip) views (`tta_views`): the chunks
+    are cropped once, every view of them goes through the model in batches of `tta_batch` chunks, "htp" is the mean of the
+    views' sigmoid maps and the result gains "spread" (float32 [D,H,W], their population standard deviation resized and pasted
+    like the heat map, zero outside the lobes) and "views"; "input" stays the canonical chunks.  Only with head="sigmoid"."""
 
     MAX_CHUNKS = 8     # chunks per kernel call / model batch (csrc/infer.hip MAX_CHUNKS)
 
     def __init__(self, model, resample_size=80, window=(-1000.0, -300.0), border_mm=5.0, max_labels=255,
-                 post_window=(-1150, 350), post_scaler=0.75, head="sigmoid"):
+                 post_window=(-1150, 350), post_scaler=0.75, head="sigmoid", tta=None, tta_batch=8):
         if not 1 <= int(max_labels) <= 255:
             raise ValueError("max_labels must be in 1..255 (uint8 label map)")
         if head not in ("sigmoid", "cam"):
             raise ValueError("head must be 'sigmoid' (evaluate_scan) or 'cam' (LesionSegTest.run)")
         self.head = head
+        self.views = None if tta is None else tta_views(tta)
+        if self.views is not None and head == "cam":
+            raise NotImplementedError("tta with head='cam': the class head takes an arg-max per lobe, and how the views' "
+                                      "classes are to be combined is not defined; test-time augmentation needs head='sigmoid'")
+        if isinstance(tta_batch, bool) or not isinstance(tta_batch, (int, np.integer)) or tta_batch < 1:
+            raise ValueError("tta_batch must be a positive integer (chunks per model call)")
+        self.tta_batch = int(tta_batch)
         self.model, self.R, self.window, self.border, self.max_labels = model, int(resample_size), window, border_mm, int(max_labels)
         # the brightness gate of LesionSegTest.run: windowing()'s default span (utils.py:189, job_runner.py:1006) and the 0.75
         # on its Otsu threshold (job_runner.py:1007)
@@ -148,11 +199,14 @@ class LobeInference:
             chunks.append(start + [b - a for a, b in zip(start, stop)] + [label])
         htp = torch.zeros((D, H, W), dtype=torch.float32, device=dev)
         cam = self.head == "cam"
+        spread = None if self.views is None else torch.zeros((D, H, W), dtype=torch.float32, device=dev)
         if not chunks:
             res = {"htp": htp, "mask": torch.zeros((D, H, W), dtype=torch.uint8, device=dev), "threshold": 0.0,
                    "lesion_ratio": 0.0, "ctss": 0, "chunks": []}
             if cam:
                 res["lobe_cls"] = {}
+            if spread is not None:
+                res.update(spread=spread, views=self.views)
             return res
         R = self.R
         x = torch.empty((len(chunks), 1, R, R, R), dtype=torch.float32, device=dev)
@@ -174,6 +228,9 @@ class LobeInference:
                 if cam:
                     self._cam_group(xg, lobe_mask[g0:g0 + L], cls[g0:g0 + L], cmax[g0:g0 + L], pools, lobe, htp, carr, L, D, H, W, st)
                     continue
+                if spread is not None:
+                    self._tta_group(xg, lobe, htp, spread, carr, L, D, H, W, st)
+                    continue
                 _, dense = self.model(xg, None)   # one batch of L lobe chunks; the 2nd output is used (job_runner.py:764)
                 call("dram_lobe_paste", dense.contiguous().data_ptr(), lobe.data_ptr(), htp.data_ptr(), carr, L, D, H, W, R, st)
         finally:
@@ -194,10 +251,28 @@ class LobeInference:
                "chunks": chunks, "input": x}
         if cam:
             res.update(lobe_cls={c[6]: int(k) for c, k in zip(chunks, cls_h)}, pool=torch.cat(pools), lobe_mask=lobe_mask)
+        if spread is not None:
+            res.update(spread=spread, views=self.views)
         if vessel is not None or lesion is not None or original_size is not None:
             res.update(self.post_process(scan, lobe, htp, th, vessel, lesion, mask, spacing=spacing,
                                          original_spacing=original_spacing, original_size=original_size))
         return res
+
+    def _tta_group(self, xg, lobe, htp, spread, carr, L, D, H, W, st):
+        """Test-time augmentation for one group of L chunks (csrc/infer_tta.hip): all V views in one launch, the V * L viewed
+        chunks through the model in batches of tta_batch -- a batch may end inside one view and start the next --, then mean
+        and spread over the views at the chunk's resolution and both pasted in one walk over the crops."""
+        R, V = self.R, len(self.views)
+        varr = (ctypes.c_int * (6 * V))(*[a for perm, flip in self.views for a in perm + flip])
+        xv = torch.empty((V * L, 1, R, R, R), dtype=torch.float32, device=xg.device)
+        call("dram_tta_expand", xg.data_ptr(), xv.data_ptr(), L, R, varr, V, st)
+        dense = torch.empty_like(xv)
+        for b0 in range(0, V * L, self.tta_batch):
+            dense[b0:b0 + self.tta_batch].copy_(self.model(xv[b0:b0 + self.tta_batch], None)[1])
+        mean = torch.empty((2, L, R, R, R), dtype=torch.float32, device=xg.device)
+        call("dram_tta_combine", dense.data_ptr(), mean[0].data_ptr(), mean[1].data_ptr(), L, R, varr, V, st)
+        call("dram_lobe_paste_prob", mean[0].data_ptr(), mean[1].data_ptr(), lobe.data_ptr(), htp.data_ptr(), spread.data_ptr(),
+             carr, L, D, H, W, R, st)
 
     def _cam_group(self, xg, mg, cls, cmax, pools, lobe, htp, carr, L, D, H, W, st):
         """The lobe-wise class head of LesionSegTest.run (job_runner.py:985-1004) for one batch of L chunks: the model sees the

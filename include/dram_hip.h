@@ -891,6 +891,45 @@ int dram_vesselness(const float* h6, int64_t S, double alpha, double beta, const
                     double* eig, void* stream);
 int dram_vessel_mask(const float* vmax, const uint8_t* lobe, float threshold, uint8_t* mask, int64_t n, void* stream);
 
+/* ---- test-time augmentation for the per-lobe inference (csrc/infer_tta.hip; no counterpart in the reference): the chunks go
+ *      through the model in V orientations, the heat map is the mean of the V sigmoid maps and the spread map their standard
+ *      deviation.
+ * A VIEW is a signed permutation {perm[3], flip[3]} of the spatial axes of an R^3 chunk in dram_spatial_permute_flip's convention:
+ *   xv[o] = x[i] with i[perm[k]] = flip[k] ? R-1-o[k] : o[k].  `views` is a HOST array of V x 6 ints {perm[0..2], flip[0..2]},
+ *   1 <= V <= DRAM_TTA_MAX_VIEWS; a view may occur more than once and then counts that many times.
+ * For chunk l and a point i of the canonical (unviewed) grid, with o_v(i) the point of view v that shows i (o[k] = flip[k] ?
+ *   R-1-i[perm[k]] : i[perm[k]], the inverse of the move above):
+ *       p_v(i) = 1 / (1 + expf(-dense[v][l][o_v(i)]))                        (dram_lobe_paste's sigmoid expression)
+ *       m(i)   = (p_0 + p_1 + ... + p_{V-1}) / (float)V                      fp32 additions in view order, pairwise
+ *       s(i)   = sqrtf(((p_0 - m)^2 + ... + (p_{V-1} - m)^2) / (float)V)     the POPULATION standard deviation, same order,
+ *   every operation rounded on its own (no fused multiply-add).  Both sums run over the binary tree of the view index: views
+ *   2j and 2j+1 are added first, then pairs of pairs and so on, the earlier views on the left; V's binary digits leave complete
+ *   blocks ([0,32) and [32,48) for V = 48; [0,2) and {2} for V = 3), which are joined from the last one upwards
+ *   (B_1 + (B_2 + (B_3 + ...))).  Added this way 2, 4 or 8 equal probabilities give m equal to that probability bit for bit and
+ *   s == 0, and 3 or 48 equal ones are off by the two roundings of 3p and of the division at most; added left to right the
+ *   partial sums 3p, 5p, 6p, 7p, ... each round and 48 equal values end up to 11 ulp off.
+ * The ensemble is formed at the chunk's resolution; the heat map is m resized to the crop and pasted by dram_lobe_paste's rule,
+ *   the spread map is s resized and pasted the same way.  The resize is linear, so the pasted mean is the mean of the pasted
+ *   views up to rounding; the pasted spread is the RESIZED chunk-level deviation, NOT the deviation of the resized views.
+ * dram_tta_expand: x [L,1,R,R,R] -> xv [V,L,1,R,R,R], every view of every chunk in one launch; xv[v] equals
+ *   dram_spatial_permute_flip(x, perm_v, flip_v) bit for bit (data movement only).
+ * dram_tta_combine: dense [V,L,1,R,R,R] -> mean [L,R^3] and spread [L,R^3] (spread may be NULL) in one pass: every element of
+ *   dense is read once and the V probabilities of a point stay in registers.  A block owns an 8 x 8 x 16 box of the canonical
+ *   grid: views that keep x in place (perm[2] == 2) are read along their rows, ascending or descending; views that move x are
+ *   read in their own order in runs of 8 or 16 consecutive floats and turned through LDS.
+ * dram_lobe_paste_prob: dram_lobe_paste without the sigmoid, on one or two fields [L,R^3] in one walk over the crop: for every
+ *   voxel of chunk l with lobe == label, htp = resize(prob[l]) and, when given, htp2 = resize(prob2[l]) (prob2 and htp2 are both
+ *   NULL or both set); the same align-corners indices, weights and 8-term combination; every other voxel is left untouched.
+ *   `chunks` as for dram_lobe_paste (L <= 8).
+ * V outside 1..DRAM_TTA_MAX_VIEWS, a perm that is not a permutation of {0,1,2}, a flip other than 0 or 1, L outside 1..8, R < 2
+ *   and a null required pointer are DRAM_EINVAL before anything is launched.  None of the entries synchronises, allocates or
+ *   reads device memory from the host. ---- */
+#define DRAM_TTA_MAX_VIEWS 48
+int dram_tta_expand(const float* x, float* xv, int L, int R, const int* views, int V, void* stream);
+int dram_tta_combine(const float* dense, float* mean, float* spread, int L, int R, const int* views, int V, void* stream);
+int dram_lobe_paste_prob(const float* prob, const float* prob2, const uint8_t* lobe, float* htp, float* htp2, const int* chunks,
+                         int L, int D, int H, int W, int R, void* stream);
+
 /* ---- the optimiser update (st_dram_ref.py: torch.optim.Adam(lr=1e-4) under ExponentialLR; the SGD block beside it):
  *      multi-tensor Adam / AdamW / SGD on fp32 tensors, one launch per table of up to DRAM_OPTIM_TABLE_CAPACITY tensors.
  * `table` is HOST memory, read before the call returns (it travels to the device in the kernel arguments): per tensor the
