@@ -205,6 +205,12 @@ __global__ __launch_bounds__(256) void loss_partial_kernel(const float* __restri
 // state: [0] alpha, [1] wsum, [2] n_in, [3] n_out, then per sample {r_n, nm_n}
 // Deterministic: per-sample sums in fp64 by one thread each (fixed chunk order), then thread 0 combines the
 // samples in index order.
+// An empty sum contributes 0 (tests/test_gpu_refine_loss_kernels.py):
+//   no outside voxel in the batch   the outside mean is 0 and so is its gradient (torch: the mean of an empty tensor, NaN)
+//   no inside voxel in the batch    the inside terms are 0, alpha = 0, wsum = 1 (the reference's `if tf.sum() > 0`)
+//   a sample with an empty lobe     adds 0 to reg whatever its targets (NaN included, which Batch.on_device gives such a
+//                                   sample); its nm_n is 0 and its r_n is NaN, which the backward reads into a factor that
+//                                   no voxel uses.  Every other state entry, both losses and every gradient stay finite.
 __global__ __launch_bounds__(256) void loss_finalize_kernel(const float* __restrict__ part, double* __restrict__ ssum,
                                                             const float* __restrict__ targets,
                                                             const float* __restrict__ weight, float smoothing, int N,

@@ -1,7 +1,9 @@
 """GPU parity of the training step around DC3D: the fused IntRegRefineLoss kernels
-(csrc/loss.hip, through the C ABI) against the reference's golden loss vector and against the CPU
-oracle's restatement in fp64, and one full DataParallelTrainer step of the slim DC3D against the
-oracle's forward + autograd."""
+(csrc/loss.hip, through train_step.DeviceIntRegRefineLoss and its autograd function) against the
+reference's golden loss vector and against the CPU oracle's restatement in fp64, and one full
+DataParallelTrainer step of the slim DC3D against the oracle's forward + autograd.  The three kernels
+on their own, through the C ABI on raw pointers, per regime and past one chunk:
+tests/test_gpu_refine_loss_kernels.py."""
 import os
 
 import numpy as np
