@@ -20,6 +20,9 @@ _LOSSES = ("BootBinCrossEntropy", "BinaryCrossEntropySmooth")
 # the lesion-wise report of `lesions`, the same way
 _LESIONS = ("label_components", "component_stats", "remove_small", "lobe_burden", "lesion_report")
 
+# the lesion density report of `density`, the same way
+_DENSITY = ("label_density", "hist_summary", "label_report")
+
 # the surface-distance metrics of `surface`, the same way
 _SURFACE = ("distance_transform", "mask_surface", "surface_distances")
 
@@ -30,7 +33,7 @@ _VESSELS = ("gaussian_derivative_taps", "hessian", "vesselness", "vessel_mask", 
 _INFERENCE = ("tta_views",)
 
 __all__ = ["_lib", "functional", "modules", "optim", "Adam", "AdamW", "SGD", "RAdam", "AdaBound", *_AUGMENT, *_LOSSES, *_LESIONS,
-           *_SURFACE, *_VESSELS, *_INFERENCE]
+           *_DENSITY, *_SURFACE, *_VESSELS, *_INFERENCE]
 
 
 def __getattr__(name):
@@ -43,6 +46,9 @@ def __getattr__(name):
     if name in _LESIONS:
         from . import lesions
         return getattr(lesions, name)
+    if name in _DENSITY:
+        from . import density
+        return getattr(density, name)
     if name in _SURFACE:
         from . import surface
         return getattr(surface, name)

@@ -169,6 +169,10 @@ SIGNATURES = {
     "dram_cc_stats": (I, [P, P, I, P, P, P, I, I, I, P]),
     "dram_cc_relabel": (I, [P, P, I, P, P, L, P]),
     "dram_lobe_burden": (I, [P, P, P, L, P]),
+    # lesion density report: per-label moments and histograms of the scan, their percentiles and band counts
+    "dram_label_density_plan": (I, [I, I, I]),
+    "dram_label_density": (I, [P, P, I, P, I, P, P, P, P, P, P, I, I, I, L, P]),
+    "dram_hist_summary": (I, [P, I, I, I, I, P, I, P, I, P, P, P]),
     # surface-distance metrics: exact Euclidean distance transform, mask surface, compaction over a surface
     "dram_edt_max_dim": (I, []),
     "dram_edt_ws_bytes": (Z, [I, I, I]),

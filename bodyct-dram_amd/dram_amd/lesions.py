@@ -107,7 +107,8 @@ def lobe_burden(mask, lobe):
     return counts.cpu().numpy()
 
 
-def lesion_report(mask, lobe, spacing, connectivity=1, min_volume_mm3=0.0, reference=None, surface=False, tolerances_mm=()):
+def lesion_report(mask, lobe, spacing, connectivity=1, min_volume_mm3=0.0, reference=None, surface=False, tolerances_mm=(),
+                  scan=None, percentiles_permille=(150, 500, 850), band_edges_hu=(-950, -750, -300)):
     """The lesion-wise report of a [D,H,W] lesion mask (e.g. `LobeInference.run(...)["mask_post"]`, or the "original" entries
     on the scan's own grid) with its lobe map and voxel spacing (z, y, x) in mm.
 
@@ -120,9 +121,17 @@ def lesion_report(mask, lobe, spacing, connectivity=1, min_volume_mm3=0.0, refer
     and with a `reference` mask: n_reference (its components under the same connectivity), n_found (those of them that the
     filtered mask touches), sensitivity (n_found / n_reference, NaN without reference lesions), n_false (kept components that do
     not touch the reference); and with `surface=True` on top of that: surface = `surface.surface_distances` of the filtered mask
-    against the reference (Hausdorff distance, HD95, average symmetric surface distance, surface Dice at `tolerances_mm`)."""
+    against the reference (Hausdorff distance, HD95, average symmetric surface distance, surface Dice at `tolerances_mm`);
+    and with `scan` (int16 [D,H,W], Hounsfield units): density = {"lesions": `density.label_report` over the kept components,
+    one row per lesion in the order of volumes_ml, "lobes": {label: {"parenchyma": the report row of the whole lobe, "lesion":
+    that of the lobe's voxels inside the kept mask}}} at `percentiles_permille` and `band_edges_hu`.  Without `scan` nothing of
+    that is computed and the result has no such key."""
     mask = _device_u8(mask)
     dev = mask.device
+    if scan is not None:
+        scan = torch.as_tensor(scan)
+        if scan.dtype != torch.int16 or scan.shape != mask.shape:
+            raise ValueError("lesion_report: scan must be an int16 [D,H,W] volume of the mask's shape")
     lobe = torch.as_tensor(lobe).to(device=dev, dtype=torch.uint8).contiguous()
     if mask.dim() != 3 or lobe.shape != mask.shape:
         raise ValueError("lesion_report: mask and lobe must be [D,H,W] volumes of the same shape")
@@ -154,4 +163,14 @@ def lesion_report(mask, lobe, spacing, connectivity=1, min_volume_mm3=0.0, refer
                    n_false=int(np.count_nonzero(stats["hits"][keep] == 0)))
         if surface:
             out["surface"] = surface_distances(kept_mask, reference, spacing, tolerances_mm=tolerances_mm)
+    if scan is not None:
+        from .density import label_report, row_of
+        scan = scan.to(dev).contiguous()
+        kw = dict(percentiles_permille=percentiles_permille, band_edges_hu=band_edges_hu)
+        lobes = {}
+        if out["lobes"]:
+            top = max(out["lobes"])
+            whole, inside = label_report(scan, lobe, top, **kw), label_report(scan, lobe, top, mask=kept_mask, **kw)
+            lobes = {v: {"parenchyma": row_of(whole, v - 1), "lesion": row_of(inside, v - 1)} for v in out["lobes"]}
+        out["density"] = {"lesions": label_report(scan, labels, n_kept, **kw), "lobes": lobes}
     return out

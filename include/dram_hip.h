@@ -821,6 +821,40 @@ int dram_cc_relabel(const int32_t* labels, const int32_t* lut, int n, int32_t* o
                     void* stream);
 int dram_lobe_burden(const uint8_t* mask, const uint8_t* lobe, int64_t* counts, int64_t nvox, void* stream);
 
+/* ---- lesion density report at inference (csrc/density.hip): the Hounsfield statistics of a lesion or a lobe, what a consumer
+ *      otherwise does on the host with scipy.ndimage.sum_labels / minimum / maximum / histogram over the whole scan.  Volumes
+ *      are contiguous on the DEVICE, 1 <= nvox < 2^31; the scan int16, masks uint8 (non-zero = set), labels uint8 or int32.
+ *      Null pointers and refused sizes are DRAM_EINVAL before anything is launched.  None of the entries synchronises, allocates
+ *      or reads device memory from the host; every output is initialised by the entry.  Everything is integers, accumulated by
+ *      integer atomics and integer reductions: no result depends on their order (the same bits every run).
+ * dram_label_density: voxel v contributes to label k = labels[v] iff 1 <= k <= n and (mask == NULL or mask[v] != 0); a label
+ *   outside 0..n is skipped.  labels: uint8 (label_kind 0, n <= 255) or int32 (label_kind 1).  Per label (n each):
+ *   count[k-1], sum[k-1] = sum of scan, sumsq[k-1] = sum of scan^2 (exact int64: at most 2^30 * 2^31), vmin[k-1], vmax[k-1];
+ *   a label without voxels gets {0, 0, 0, 32767, -32768}.  hist (n rows of nbins + 2 int64, NULL iff nbins == 0): row k-1, entry 0
+ *   counts scan < lo, entry 1 + (scan - lo) / width counts lo <= scan < lo + nbins * width, entry nbins + 1 the rest (the
+ *   below-range test comes first: no negative dividend is divided).  Refused: n < 1; label_kind 0 with n > 255; nbins outside
+ *   0..4096; width < 1 with nbins > 0; n * (nbins + 2) >= 2^31; lo + nbins * width above int32; hist and nbins not NULL / 0
+ *   together; a scan or int32 labels off their natural alignment.  16-byte loads where scan, labels and mask are 16-byte aligned,
+ *   any alignment and any nvox work.
+ * dram_label_density_plan: which of the entry's two kernels a call takes, a function of these three arguments alone, answered
+ *   without a GPU: 0 = the table of the call (n * (7 + nbins + 2) words, n * 7 without a histogram) fits in LDS and is kept per
+ *   block; 1 = runs of equal labels are reduced within a wave and sent to global memory.  Negative (DRAM_EINVAL) for arguments
+ *   that dram_label_density refuses.
+ * dram_hist_summary: per row k of such a histogram (total c = the sum of the row, below 2^52):
+ *   pct[k*nq + i]: rank = max(1, (q[i] * c + 999) / 1000) in int64 (nearest rank, q per mille in 0..1000); the lower edge
+ *     lo + (b-1) * width of the first in-range bin b at which the running count reaches rank; INT32_MIN if it is reached in the
+ *     underflow entry, INT32_MAX if only in the overflow entry, INT32_MAX for c == 0.  With width 1: the exact percentile.
+ *   bands[k*(ne+1) + i]: the count of values in [edges[i-1], edges[i]), band 0 from the underflow entry on and band ne up to and
+ *     including the overflow entry; the bands of a row sum to c.  Every edge is lo + j * width for some 0 <= j <= nbins, strictly
+ *     ascending, else DRAM_EINVAL.  q_permille (nq <= 16) and edges (ne <= 15) are HOST arrays and travel in the kernel arguments;
+ *     nq and ne may be 0 with pct / bands NULL (bands given with ne == 0: the row totals).  One block per row, one launch. ---- */
+int dram_label_density_plan(int label_kind, int n, int nbins);
+int dram_label_density(const int16_t* scan, const void* labels, int label_kind, const uint8_t* mask, int n, int64_t* count,
+                       int64_t* sum, int64_t* sumsq, int32_t* vmin, int32_t* vmax, int64_t* hist, int lo, int width, int nbins,
+                       int64_t nvox, void* stream);
+int dram_hist_summary(const int64_t* hist, int n, int lo, int width, int nbins, const int32_t* q_permille, int nq,
+                      const int32_t* edges, int ne, int32_t* pct, int64_t* bands, void* stream);
+
 /* ---- surface-distance metrics at inference (Hausdorff, its percentiles, average symmetric surface distance, surface Dice):
  *      what a consumer otherwise does on the host with scipy.ndimage.distance_transform_edt and binary_erosion.  Volumes are
  *      contiguous [D,H,W] on the DEVICE, D*H*W < 2^31; masks uint8 (non-zero = set).  Null pointers and refused sizes are
