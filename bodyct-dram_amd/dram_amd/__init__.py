@@ -23,6 +23,9 @@ _LESIONS = ("label_components", "component_stats", "remove_small", "lobe_burden"
 # the lesion density report of `density`, the same way
 _DENSITY = ("label_density", "hist_summary", "label_report")
 
+# the heat-map evaluation curves of `curves`, the same way
+_CURVES = ("score_tables", "curves_from_tables", "heatmap_curves")
+
 # the surface-distance metrics of `surface`, the same way
 _SURFACE = ("distance_transform", "mask_surface", "surface_distances")
 
@@ -33,7 +36,7 @@ _VESSELS = ("gaussian_derivative_taps", "hessian", "vesselness", "vessel_mask", 
 _INFERENCE = ("tta_views",)
 
 __all__ = ["_lib", "functional", "modules", "optim", "Adam", "AdamW", "SGD", "RAdam", "AdaBound", *_AUGMENT, *_LOSSES, *_LESIONS,
-           *_DENSITY, *_SURFACE, *_VESSELS, *_INFERENCE]
+           *_DENSITY, *_CURVES, *_SURFACE, *_VESSELS, *_INFERENCE]
 
 
 def __getattr__(name):
@@ -49,6 +52,9 @@ def __getattr__(name):
     if name in _DENSITY:
         from . import density
         return getattr(density, name)
+    if name in _CURVES:
+        from . import curves
+        return getattr(curves, name)
     if name in _SURFACE:
         from . import surface
         return getattr(surface, name)

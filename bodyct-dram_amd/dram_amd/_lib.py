@@ -173,6 +173,9 @@ SIGNATURES = {
     "dram_label_density_plan": (I, [I, I, I]),
     "dram_label_density": (I, [P, P, I, P, I, P, P, P, P, P, P, I, I, I, L, P]),
     "dram_hist_summary": (I, [P, I, I, I, I, P, I, P, I, P, P, P]),
+    # heat-map evaluation curves: the joint histogram of score bin x class x region
+    "dram_score_hist_plan": (I, [I, I, I]),
+    "dram_score_hist": (I, [P, P, P, P, I, I, P, P, L, P]),
     # surface-distance metrics: exact Euclidean distance transform, mask surface, compaction over a surface
     "dram_edt_max_dim": (I, []),
     "dram_edt_ws_bytes": (Z, [I, I, I]),

@@ -160,7 +160,7 @@ class LobeInference:
         self.post_window, self.post_scaler = (int(post_window[0]), int(post_window[1])), float(post_scaler)
 
     @torch.no_grad()
-    def run(self, scan, lobe, spacing, vessel=None, lesion=None, original_spacing=None, original_size=None):
+    def run(self, scan, lobe, spacing, vessel=None, lesion=None, original_spacing=None, original_size=None, curves=None):
         """`vessel` (uint8 [D,H,W], optional): the vessel mask of LesionSegTest.run; with it (or with `lesion`) the result also
         holds the post-processed mask `mask_post` = mask & (windowed scan > brightness threshold) & ~vessel (job_runner.py:1006-1010).
         `vessel` may also be a callable `fn(scan_dev, lobe_dev, spacing) -> uint8 [D,H,W]` that produces the mask; it is called once
@@ -169,7 +169,11 @@ class LobeInference:
         computed at the working resolution unless `original_spacing` and `original_size` ((z, y, x), the scan's metadata) are
         given: then, like job_runner.py:1016-1032, the masks (nearest neighbour), the scan and the heat map (linear) first go
         back to the original grid (`resample_volume`; result key "original": mask / mask_post / lesion / scan / htp there) and
-        the four metrics are those of the resampled masks."""
+        the four metrics are those of the resampled masks.
+        `curves` (a number of bins, optional; needs `lesion`): adds "curves" and "curves_post", the evaluation curves of the heat
+        map over all thresholds (see `post_process`)."""
+        if curves is not None and lesion is None:
+            raise ValueError("curves needs the reference mask: pass lesion=")
         dev = next(self.model.parameters()).device
         scan = torch.as_tensor(scan).to(device=dev, dtype=torch.int16).contiguous()
         lobe = torch.as_tensor(lobe).to(device=dev, dtype=torch.uint8).contiguous()
@@ -255,7 +259,7 @@ class LobeInference:
             res.update(spread=spread, views=self.views)
         if vessel is not None or lesion is not None or original_size is not None:
             res.update(self.post_process(scan, lobe, htp, th, vessel, lesion, mask, spacing=spacing,
-                                         original_spacing=original_spacing, original_size=original_size))
+                                         original_spacing=original_spacing, original_size=original_size, curves=curves))
         return res
 
     def _tta_group(self, xg, lobe, htp, spread, carr, L, D, H, W, st):
@@ -292,11 +296,21 @@ class LobeInference:
 
     @torch.no_grad()
     def post_process(self, scan, lobe, htp, th, vessel=None, lesion=None, mask=None, spacing=None, original_spacing=None,
-                     original_size=None):
+                     original_size=None, curves=None):
         """The tail of LesionSegTest.run (job_runner.py:1006-1037) on the device: brightness gate
         `binary_cam(w_scan[lobe > 0], 0.75)` on the scan windowed with windowing()'s default span, lesion_pred_post =
         lesion_pred & (w_scan > th) & ~(vessel > 0), the resampling to the scan's original grid when `original_spacing` /
-        `original_size` are given (job_runner.py:1016-1032), and IOU / Dice against the reference lesion mask (utils.py:437-446)."""
+        `original_size` are given (job_runner.py:1016-1032), and IOU / Dice against the reference lesion mask (utils.py:437-446).
+        `curves=nbins` (a power of two in 2..4096; needs `lesion`) adds what the reference does not have, the same judgement at
+        every threshold instead of the one Otsu point (`dram_amd.curves.heatmap_curves`: ROC-AUC, average precision, the Dice /
+        IoU sweep and its best point, a calibration table; one row per lobe label 1..highest present, then the lungs pooled):
+        "curves" for the heat map as it is and "curves_post" with the gate behind `mask_post`, (w_scan > brightness threshold) &
+        ~vessel.  Both are computed on the grid of the IoU / Dice metrics: the working grid, or with `original_size` the original
+        one, from the linearly resampled heat map and the nearest-resampled reference, lobe map and gate.  On the original grid
+        the reported `dice` (of a nearest-resampled mask) is therefore not a point of this curve (a linearly resampled map, then
+        thresholded); on the working grid `dice` is the curve's value at the cut below `threshold`, up to the bin width."""
+        if curves is not None and lesion is None:
+            raise ValueError("curves needs the reference mask: pass lesion=")
         if (original_spacing is None) != (original_size is None) or (original_size is not None and spacing is None):
             raise ValueError("post_process: spacing, original_spacing and original_size go together")
         dev = htp.device
@@ -327,6 +341,20 @@ class LobeInference:
                 orig["lesion"] = lesion = back(lesion, "nearest")
             out["original"] = orig
             mask, post, n = orig["mask"], orig["mask_post"], orig["mask"].numel()
+        if curves is not None:
+            from .curves import heatmap_curves
+            # the gate alone: with th = -inf the prediction term of dram_lesion_post is true wherever the score is not NaN, and a NaN
+            # score is in bin 0 (never predicted) with or without a gate
+            gate = torch.empty(htp.shape, dtype=torch.uint8, device=dev)
+            call("dram_lesion_post", htp.data_ptr(), scan.data_ptr(), None if vessel is None else vessel.data_ptr(), None,
+                 gate.data_ptr(), float("-inf"), self.post_window[0], self.post_window[1], float(th_scan), htp.numel(), st)
+            n_regions = max(1, int(lobe.max()))
+            score, regions = htp, lobe
+            if original_size is not None:
+                score, regions, gate = orig["htp"], back(lobe, "nearest"), back(gate, "nearest")
+            n_cal = min(16, int(curves))
+            out["curves"] = heatmap_curves(score, lesion, regions, n_regions, None, curves, n_cal)
+            out["curves_post"] = heatmap_curves(score, lesion, regions, n_regions, gate, curves, n_cal)
         if lesion is not None:
             counts = torch.empty(8, dtype=torch.int64, device=dev)
             call("dram_mask_overlap", mask.data_ptr(), lesion.data_ptr(), counts.data_ptr(), n, st)

@@ -855,6 +855,31 @@ int dram_label_density(const int16_t* scan, const void* labels, int label_kind, 
 int dram_hist_summary(const int64_t* hist, int n, int lo, int width, int nbins, const int32_t* q_permille, int nq,
                       const int32_t* edges, int ne, int32_t* pct, int64_t* bands, void* stream);
 
+/* ---- heat-map evaluation curves at inference (csrc/curves.hip): the joint histogram of score bin x class x region of a
+ *      probability map against a reference mask, from which ROC, precision / recall, the Dice sweep and a calibration table are
+ *      exact host arithmetic (dram_amd/curves.py) -- what a consumer otherwise does with sklearn on every lung voxel.  Volumes are
+ *      contiguous on the DEVICE, 1 <= nvox < 2^31; score fp32, ref / region / gate uint8.  Null score, ref or hist and refused
+ *      sizes are DRAM_EINVAL before anything is launched.  Neither entry synchronises, allocates or reads device memory from the
+ *      host; every output is initialised by the entry.  Everything is integers, accumulated by integer atomics and integer
+ *      reductions: the same bits every run.
+ * dram_score_hist: voxel v goes to region r = region[v] iff 1 <= r <= nregions (label 0 and labels above nregions are skipped;
+ *   region == NULL requires nregions == 1 and puts every voxel in region 1), class c = (ref[v] != 0), and with s = score[v] bin
+ *     0                         if gate != NULL && gate[v] == 0, or if !(s >= 0.0f) (NaN and negative scores; -0.0f passes),
+ *     nbins                     if s >= 1.0f (+inf too),
+ *     1 + (int)(s * nbins)      otherwise (nbins is a power of two: the fp32 product is exact, so this is 1 + floor(s * nbins)).
+ *   hist: int64 [nregions][2][nbins + 1], the counts.  conf (may be NULL): the same shape; entry b >= 1 is the sum over the
+ *   voxels of bin b of q = (uint32)(fminf(s, 1.0f) * 16777216.0f) (exact product, truncated, q <= 2^24, sums below 2^55); entry
+ *   0 of every row is 0.  gate may be NULL (every voxel on).  Refused: nregions outside 1..255; nbins not a power of two in
+ *   2..4096; region == NULL with nregions != 1; a score off its natural alignment.  16-byte loads where score, ref, region and
+ *   gate are 16-byte aligned, any alignment and any nvox work.
+ * dram_score_hist_plan: which of the entry's two paths a call takes, a function of these three arguments alone, answered
+ *   without a GPU: 0 = the table (nregions * 2 * (nbins + 1) words, three times that with conf) fits in 128 KiB of LDS and is
+ *   kept per block; 1 = it does not, and the aggregated updates go to global memory.  Negative (DRAM_EINVAL) for the nregions
+ *   and nbins that dram_score_hist refuses. ---- */
+int dram_score_hist_plan(int nregions, int nbins, int with_conf);
+int dram_score_hist(const float* score, const uint8_t* ref, const uint8_t* region, const uint8_t* gate, int nregions, int nbins,
+                    int64_t* hist, int64_t* conf, int64_t nvox, void* stream);
+
 /* ---- surface-distance metrics at inference (Hausdorff, its percentiles, average symmetric surface distance, surface Dice):
  *      what a consumer otherwise does on the host with scipy.ndimage.distance_transform_edt and binary_erosion.  Volumes are
  *      contiguous [D,H,W] on the DEVICE, D*H*W < 2^31; masks uint8 (non-zero = set).  Null pointers and refused sizes are
