@@ -385,8 +385,24 @@ __global__ __launch_bounds__(256) void masked_mean_bwd_kernel(const float* __res
     for (int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x; e < S; e += stride) dx[row * S + e] = g * m[(int64_t)n * S + e];
 }
 
-static inline bool vec4_ok(const void* a, const void* b, int64_t S) {
-    return S % 4 == 0 && ((uintptr_t)a % 16 == 0) && ((uintptr_t)b % 16 == 0);
+// Which kernel a 1x1x1 conv call launches, decided in one place for the entry points and for dram_conv3d_k1_fwd_choice /
+// dram_conv3d_k1_bwd_choice (values: include/dram_hip.h).  Host arithmetic only; *_mis: the pointer is not 16-byte aligned.
+//   forward and backward-data: the float4 kernel when the rows are whole 16-byte pieces (S % 4 == 0) and both the tensor read
+//   and the tensor written are aligned, the scalar kernel otherwise; MAXCO output channels per pass either way.
+//   backward-weights: 16-byte rows of dy and x -> the multi-output kernel for Cout > 1 (while its channel tiles fit
+//   gridDim.z), the one-output float4 kernel otherwise; the scalar kernel for everything else.
+enum { K1_FWD_SCALAR = 0, K1_FWD_VEC = 1 };
+enum { K1_DGRAD_SCALAR = 0, K1_DGRAD_VEC = 1, K1_WGRAD_SCALAR = 2, K1_WGRAD_VEC = 3, K1_WGRAD_MULTI = 4 };
+
+static inline int k1_fwd_choice(bool x_mis, bool y_mis, int64_t S) {
+    return S % 4 == 0 && !x_mis && !y_mis ? K1_FWD_VEC : K1_FWD_SCALAR;
+}
+static inline int k1_dgrad_choice(bool dy_mis, bool dx_mis, int64_t S) {
+    return S % 4 == 0 && !dy_mis && !dx_mis ? K1_DGRAD_VEC : K1_DGRAD_SCALAR;
+}
+static inline int k1_wgrad_choice(bool dy_mis, bool x_mis, int Cin, int Cout, int64_t S) {
+    if (S % 4 != 0 || dy_mis || x_mis) return K1_WGRAD_SCALAR;
+    return Cout > 1 && cdiv(Cin, WM_CT) * cdiv(Cout, WM_CO) <= 65535 ? K1_WGRAD_MULTI : K1_WGRAD_VEC;
 }
 
 }  // namespace dram
@@ -398,7 +414,7 @@ static int conv1x1_fwd_run(const char* who, const float* x, const float* coef, i
     DRAM_REQUIRE(x && w && y, "%s: null pointer", who);
     DRAM_REQUIRE(N > 0 && N <= 65535 && Cin > 0 && Cout > 0 && S > 0, "%s: bad dimensions", who);
     hipStream_t st = (hipStream_t)stream;
-    const bool vec = vec4_ok(x, y, S);
+    const bool vec = k1_fwd_choice(!aligned16(x), !aligned16(y), S) == K1_FWD_VEC;
     for (int co0 = 0; co0 < Cout; co0 += K1_MAXCO) {
         const int nco = (Cout - co0) < K1_MAXCO ? (Cout - co0) : K1_MAXCO;
         if (vec) {
@@ -434,8 +450,15 @@ static int conv1x1_bwd_run(const float* dy, const float* x, const float* coef, i
     DRAM_REQUIRE(dy && x && w, "conv3d_k1_bwd: null pointer");
     DRAM_REQUIRE(N > 0 && N <= 65535 && Cin > 0 && Cout > 0 && S > 0, "conv3d_k1_bwd: bad dimensions");
     hipStream_t st = (hipStream_t)stream;
+    if (dw || dbias) {   // (checked before backward-data is launched: a refused call writes nothing)
+        DRAM_REQUIRE(ws, "conv3d_k1_bwd: workspace is null");
+        if (ws_bytes < dram_conv3d_k1_bwd_ws_bytes(N, Cin, Cout, S)) {
+            set_error("conv3d_k1_bwd: workspace too small");
+            return DRAM_EWS;
+        }
+    }
     if (dx) {
-        const bool vec = vec4_ok(dy, dx, S);
+        const bool vec = k1_dgrad_choice(!aligned16(dy), !aligned16(dx), S) == K1_DGRAD_VEC;
         for (int co0 = 0; co0 < Cout; co0 += K1_MAXCO) {
             const int nco = (Cout - co0) < K1_MAXCO ? (Cout - co0) : K1_MAXCO;
             if (vec) {
@@ -448,22 +471,17 @@ static int conv1x1_bwd_run(const float* dy, const float* x, const float* coef, i
         }
     }
     if (dw || dbias) {
-        DRAM_REQUIRE(ws, "conv3d_k1_bwd: workspace is null");
-        if (ws_bytes < dram_conv3d_k1_bwd_ws_bytes(N, Cin, Cout, S)) {
-            set_error("conv3d_k1_bwd: workspace too small");
-            return DRAM_EWS;
-        }
         int nblk = (int)cdiv64(S, WG_VPB);
         float* part = (float*)ws;
         static_assert(WG_VPB == 2048, "conv1x1_wgrad_vec_kernel: two float4 per thread");
         static_assert(WM_VPB % WG_VPB == 0, "the multi-output kernel's partials fit the workspace sized for WG_VPB");
-        const bool vec = (S % 4) == 0 && ((((uintptr_t)dy) | ((uintptr_t)x)) & 15) == 0;
-        const int ci_tiles = cdiv(Cin, WM_CT), co_tiles = cdiv(Cout, WM_CO);
-        if (vec && Cout > 1 && ci_tiles * co_tiles <= 65535) {
+        const int route = k1_wgrad_choice(!aligned16(dy), !aligned16(x), Cin, Cout, S);
+        if (route == K1_WGRAD_MULTI) {
+            const int ci_tiles = cdiv(Cin, WM_CT), co_tiles = cdiv(Cout, WM_CO);
             nblk = (int)cdiv64(S, WM_VPB);
             hipLaunchKernelGGL(conv1x1_wgrad_multi_kernel, dim3(nblk, N, ci_tiles * co_tiles), dim3(256), 0, st, dy, x, part, Cin, Cout,
                                S, nblk, ci_tiles, coef, relu);
-        } else if (vec)
+        } else if (route == K1_WGRAD_VEC)
             hipLaunchKernelGGL(conv1x1_wgrad_vec_kernel, dim3(nblk, N), dim3(256), 0, st, dy, x, part, Cin, Cout, S, nblk, coef, relu);
         else
             hipLaunchKernelGGL(conv1x1_wgrad_kernel, dim3(nblk, N), dim3(256), 0, st, dy, x, part, Cin, Cout, S, nblk, coef, relu);
@@ -483,6 +501,17 @@ extern "C" int dram_conv3d_k1_bwd_lazy(const float* dy, const float* x, const fl
                                        float* dw, float* dbias, void* ws, size_t ws_bytes, int N, int Cin, int Cout, int64_t S,
                                        void* stream) {
     return conv1x1_bwd_run(dy, x, coef, relu, w, dx, dw, dbias, ws, ws_bytes, N, Cin, Cout, S, stream);
+}
+
+extern "C" int dram_conv3d_k1_fwd_choice(int x_mis, int y_mis, int64_t S) {
+    DRAM_REQUIRE(S > 0, "conv3d_k1_fwd_choice: bad dimensions");
+    return k1_fwd_choice(x_mis != 0, y_mis != 0, S);
+}
+
+extern "C" int dram_conv3d_k1_bwd_choice(int dy_mis, int x_mis, int dx_mis, int Cin, int Cout, int64_t S, int which) {
+    DRAM_REQUIRE(Cin > 0 && Cout > 0 && S > 0, "conv3d_k1_bwd_choice: bad dimensions");
+    DRAM_REQUIRE(which == 0 || which == 1, "conv3d_k1_bwd_choice: which must be 0 (backward-data) or 1 (backward-weights)");
+    return which == 0 ? k1_dgrad_choice(dy_mis != 0, dx_mis != 0, S) : k1_wgrad_choice(dy_mis != 0, x_mis != 0, Cin, Cout, S);
 }
 
 extern "C" size_t dram_channel_sum_ws_bytes(int N, int C, int64_t S) {

@@ -60,6 +60,8 @@ SIGNATURES = {
     "dram_conv3d_k1_fwd": (I, [P, P, P, P, I, I, I, L, P]),
     "dram_conv3d_k1_bwd_ws_bytes": (Z, [I, I, I, L]),
     "dram_conv3d_k1_bwd": (I, [P, P, P, P, P, P, P, Z, I, I, I, L, P]),
+    "dram_conv3d_k1_fwd_choice": (I, [I, I, L]),
+    "dram_conv3d_k1_bwd_choice": (I, [I, I, I, I, I, L, I]),
     "dram_masked_mean_ws_bytes": (Z, [I, I, L]),
     "dram_masked_mean_fwd": (I, [P, P, P, P, P, Z, I, I, L, P]),
     "dram_masked_mean_bwd": (I, [P, P, P, P, I, I, L, P]),

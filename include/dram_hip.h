@@ -235,9 +235,23 @@ int dram_crop_concat_bwd(const float* dout, float* dt1, float* dt2, int N, int C
 int dram_conv3d_k1_fwd(const float* x, const float* w, const float* bias, float* y,
                        int N, int Cin, int Cout, int64_t S, void* stream);
 size_t dram_conv3d_k1_bwd_ws_bytes(int N, int Cin, int Cout, int64_t S);
-/* dx[N,Cin,S] (may be NULL), dw[Cout,Cin], dbias[Cout] (may be NULL). */
+/* dx[N,Cin,S], dw[Cout,Cin], dbias[Cout]: each may be NULL and is then not computed; the others do not depend on which are
+ * asked for.  dx is overwritten, whatever it held.  ws is needed (non-NULL, at least dram_conv3d_k1_bwd_ws_bytes) when dw or
+ * dbias is asked for; a smaller one returns DRAM_EWS before anything is launched.  The call writes per-block partial sums to
+ * the front of ws and nothing behind dram_conv3d_k1_bwd_ws_bytes; on the multi-output route (choice 4 below) they are
+ * N * ceil(S / 8192) * Cout * (Cin + 1) floats and the rest of ws is not written.  dw and dbias are fp64 sums of those partials in a fixed order: the same call
+ * gives the same bits. */
 int dram_conv3d_k1_bwd(const float* dy, const float* x, const float* w, float* dx, float* dw, float* dbias,
                        void* ws, size_t ws_bytes, int N, int Cin, int Cout, int64_t S, void* stream);
+/* Which kernel the 1x1x1 conv entry points (plain and lazy) launch: host arithmetic only, the rule the launches go through.
+ * *_mis: non-zero when that tensor's base pointer is not 16-byte aligned (y / dx: the tensor written).
+ *   _fwd_choice: 0 = conv1x1_fwd_kernel<false> (scalar), 1 = conv1x1_fwd_kernel<true> (float4).
+ *   _bwd_choice: which = 0, backward-data (x_mis, Cin, Cout unused): 0 = conv1x1_dgrad_kernel<false>, 1 = <true>;
+ *                which = 1, backward-weights (dx_mis unused): 2 = conv1x1_wgrad_kernel (scalar), 3 = conv1x1_wgrad_vec_kernel
+ *                (one output channel), 4 = conv1x1_wgrad_multi_kernel.
+ * Negative on bad sizes or an unknown `which`. */
+int dram_conv3d_k1_fwd_choice(int x_mis, int y_mis, int64_t S);
+int dram_conv3d_k1_bwd_choice(int dy_mis, int x_mis, int dx_mis, int Cin, int Cout, int64_t S, int which);
 
 /* ---- lobe-masked mean: pooling_dense_features (models.py:37-49, default branch) ----
  * out[n,c] = sum_s x[n,c,s]*m[n,s] / sum_s m[n,s];  msum[n] = sum_s m[n,s] is also returned. */
