@@ -23,6 +23,9 @@ _LESIONS = ("label_components", "component_stats", "remove_small", "lobe_burden"
 # the lesion density report of `density`, the same way
 _DENSITY = ("label_density", "hist_summary", "label_report")
 
+# the lesion distribution report of `distribution`, the same way
+_DISTRIBUTION = ("lung_depth", "label_depth", "lesion_distribution")
+
 # the heat-map evaluation curves of `curves`, the same way
 _CURVES = ("score_tables", "curves_from_tables", "heatmap_curves")
 
@@ -36,7 +39,7 @@ _VESSELS = ("gaussian_derivative_taps", "hessian", "vesselness", "vessel_mask", 
 _INFERENCE = ("tta_views",)
 
 __all__ = ["_lib", "functional", "modules", "optim", "Adam", "AdamW", "SGD", "RAdam", "AdaBound", *_AUGMENT, *_LOSSES, *_LESIONS,
-           *_DENSITY, *_CURVES, *_SURFACE, *_VESSELS, *_INFERENCE]
+           *_DENSITY, *_DISTRIBUTION, *_CURVES, *_SURFACE, *_VESSELS, *_INFERENCE]
 
 
 def __getattr__(name):
@@ -52,6 +55,9 @@ def __getattr__(name):
     if name in _DENSITY:
         from . import density
         return getattr(density, name)
+    if name in _DISTRIBUTION:
+        from . import distribution
+        return getattr(distribution, name)
     if name in _CURVES:
         from . import curves
         return getattr(curves, name)

@@ -175,6 +175,9 @@ SIGNATURES = {
     "dram_label_density_plan": (I, [I, I, I]),
     "dram_label_density": (I, [P, P, I, P, I, P, P, P, P, P, P, I, I, I, L, P]),
     "dram_hist_summary": (I, [P, I, I, I, I, P, I, P, I, P, P, P]),
+    # lesion distribution report: per-label reduction of a depth map and of the voxel positions
+    "dram_label_depth_plan": (I, [I, I, I, I]),
+    "dram_label_depth": (I, [P, P, I, P, I, P, P, P, P, P, P, I, I, P, P, I, I, I, I, I, I, P]),
     # heat-map evaluation curves: the joint histogram of score bin x class x region
     "dram_score_hist_plan": (I, [I, I, I]),
     "dram_score_hist": (I, [P, P, P, P, I, I, P, P, L, P]),

@@ -108,7 +108,8 @@ def lobe_burden(mask, lobe):
 
 
 def lesion_report(mask, lobe, spacing, connectivity=1, min_volume_mm3=0.0, reference=None, surface=False, tolerances_mm=(),
-                  scan=None, percentiles_permille=(150, 500, 850), band_edges_hu=(-950, -750, -300)):
+                  scan=None, percentiles_permille=(150, 500, 850), band_edges_hu=(-950, -750, -300), distribution=False, depth=None,
+                  shells_mm=(5.0, 10.0, 20.0), zones=(3, 2, 1), box=None, subpleural_mm=3.0):
     """The lesion-wise report of a [D,H,W] lesion mask (e.g. `LobeInference.run(...)["mask_post"]`, or the "original" entries
     on the scan's own grid) with its lobe map and voxel spacing (z, y, x) in mm.
 
@@ -125,7 +126,11 @@ def lesion_report(mask, lobe, spacing, connectivity=1, min_volume_mm3=0.0, refer
     and with `scan` (int16 [D,H,W], Hounsfield units): density = {"lesions": `density.label_report` over the kept components,
     one row per lesion in the order of volumes_ml, "lobes": {label: {"parenchyma": the report row of the whole lobe, "lesion":
     that of the lobe's voxels inside the kept mask}}} at `percentiles_permille` and `band_edges_hu`.  Without `scan` nothing of
-    that is computed and the result has no such key."""
+    that is computed and the result has no such key;
+    and with `distribution=True`: distribution = `distribution.lesion_distribution` of the kept mask and its components (depth
+    below the lung surface, peripheral share, centroids and positional zones per lobe, for both lungs and per lesion, "lesions"
+    in the order of volumes_ml) at `depth`, `shells_mm`, `zones`, `box`, `percentiles_permille` and `subpleural_mm`.  Without
+    the keyword nothing of that is computed and the result has no such key."""
     mask = _device_u8(mask)
     dev = mask.device
     if scan is not None:
@@ -173,4 +178,9 @@ def lesion_report(mask, lobe, spacing, connectivity=1, min_volume_mm3=0.0, refer
             whole, inside = label_report(scan, lobe, top, **kw), label_report(scan, lobe, top, mask=kept_mask, **kw)
             lobes = {v: {"parenchyma": row_of(whole, v - 1), "lesion": row_of(inside, v - 1)} for v in out["lobes"]}
         out["density"] = {"lesions": label_report(scan, labels, n_kept, **kw), "lobes": lobes}
+    if distribution:
+        from .distribution import lesion_distribution
+        out["distribution"] = lesion_distribution(kept_mask, lobe, spacing, labels=labels, n=n_kept, depth=depth, shells_mm=shells_mm,
+                                                  zones=zones, box=box, percentiles_permille=percentiles_permille,
+                                                  subpleural_mm=subpleural_mm)
     return out

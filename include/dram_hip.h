@@ -869,6 +869,49 @@ int dram_label_density(const int16_t* scan, const void* labels, int label_kind, 
 int dram_hist_summary(const int64_t* hist, int n, int lo, int width, int nbins, const int32_t* q_permille, int nq,
                       const int32_t* edges, int ne, int32_t* pct, int64_t* bands, void* stream);
 
+/* ---- lesion distribution report at inference (csrc/distribution.hip): where in the lung the lesions lie -- per label of a label
+ *      volume the reduction of a depth map (the distance of every voxel from the lung surface, dram_edt of the non-lung voxels)
+ *      and of the voxel positions, what a consumer otherwise does on the host with scipy.ndimage.sum_labels / minimum /
+ *      center_of_mass over a distance transform.  Volumes are contiguous [D,H,W] on the DEVICE, D * H * W < 2^31; depth fp32,
+ *      labels uint8 (label_kind 0, n <= 255) or int32 (label_kind 1), mask uint8 or NULL.  Null pointers and refused sizes are
+ *      DRAM_EINVAL before anything is launched.  The entry does not synchronise, allocate or read device memory from the host;
+ *      every output is initialised by the entry.  Everything is integers, accumulated by integer atomics and integer
+ *      reductions: no result depends on their order (the same bits every run).
+ * dram_label_depth: voxel v = (z*H + y)*W + x with depth d = depth[v] contributes to label k = labels[v] iff
+ *     1 <= k <= n (a label outside 0..n is skipped),  mask == NULL or mask[v] != 0,  and  d >= 0.0f
+ *   (NaN and negative depths are skipped entirely; -0.0f and +inf pass).  Per label, over its contributing voxels:
+ *   count[k-1]   their number.
+ *   qsum[k-1]    the sum of q = (uint32)(fminf(d, 2097152.0f) * 1024.0f): the depth in 1/1024 mm, the fp32 product exact and then
+ *                truncated; q <= 2^31, so the sums stay below 2^62.
+ *   dmin[k-1], dmax[k-1]  the minimum and the maximum of the bit pattern of d taken as an unsigned integer, which orders
+ *                depths as their values do for every d >= +0.0f (-0.0f counts with its own pattern 0x80000000, above +inf).
+ *                A label without contributing voxels gets {count, qsum, dmin, dmax} = {0, 0, 0x7f800000, 0}.
+ *   possum[(k-1)*3 + a]  the sums of the voxel indices z, y, x (a = 0, 1, 2).
+ *   hist (n rows of nbins + 2 int64; NULL iff nbins == 0): the row layout that dram_hist_summary takes with lo = 0, width = 1.
+ *                Entry 0 is always 0.  With b = d * bins_per_mm in fp32 (bins_per_mm one of 1, 2, 4, 8, 16: the product is
+ *                exact) the voxel counts in entry nbins + 1 if b >= (float)nbins -- the comparison comes before the conversion,
+ *                so +inf lands there -- else in entry 1 + (int)b.  nbins in 0..4096.
+ *   zones (n rows of nz*ny*nx int64): the positional zone of index i along an axis with the pair [a0, a1) of the HOST array
+ *                box = {z0, z1, y0, y1, x0, x1} and nzones_axis zones is
+ *                    ((clamp(i, a0, a1 - 1) - a0) * nzones_axis) / (a1 - a0)        (integer division),
+ *                the zone of a voxel (zz*ny + zy)*nx + zx, and the voxel counts in that entry of its label's row.  Index 0 is
+ *                the low-index end of an axis.  nz, ny, nx each in 1..8.  zones is NULL iff nz*ny*nx == 1 and box == NULL; zones
+ *                given without a box takes the whole volume {0, D, 0, H, 0, W} as the box.
+ *   Refused: n < 1; label_kind other than 0, 1, or 0 with n > 255; nbins outside 0..4096; bins_per_mm not one of the five when
+ *   nbins > 0; hist and nbins not NULL / 0 together; nz, ny or nx outside 1..8; zones and box not together as above; a0 >= a1 on
+ *   an axis; n * (nbins + 2), n * nz*ny*nx or n * 3 at or above 2^31; D, H or W < 1 or D * H * W >= 2^31; depth or int32 labels
+ *   off their natural alignment.  16-byte loads where depth, labels and mask are 16-byte aligned; any alignment and any size
+ *   work.
+ * dram_label_depth_plan: which of the entry's two kernels a call takes, a function of these four arguments alone (nzones = the
+ *   entries of a zones row, nz*ny*nx, or 0 for zones == NULL; 0..512), answered without a GPU: 0 = the table of the call
+ *   (n * (11 + nbins + 2 + nzones) 32-bit words, without the nbins + 2 when nbins == 0) fits in LDS, is kept per block and
+ *   flushed once; 1 = runs of equal labels are reduced within a wave and sent to global memory with integer atomics.  Negative
+ *   (DRAM_EINVAL) for arguments that dram_label_depth refuses. ---- */
+int dram_label_depth_plan(int label_kind, int n, int nbins, int nzones);
+int dram_label_depth(const float* depth, const void* labels, int label_kind, const uint8_t* mask, int n, int64_t* count,
+                     int64_t* qsum, uint32_t* dmin, uint32_t* dmax, int64_t* possum, int64_t* hist, int bins_per_mm, int nbins,
+                     int64_t* zones, const int32_t* box, int nz, int ny, int nx, int D, int H, int W, void* stream);
+
 /* ---- heat-map evaluation curves at inference (csrc/curves.hip): the joint histogram of score bin x class x region of a
  *      probability map against a reference mask, from which ROC, precision / recall, the Dice sweep and a calibration table are
  *      exact host arithmetic (dram_amd/curves.py) -- what a consumer otherwise does with sklearn on every lung voxel.  Volumes are
