@@ -35,11 +35,14 @@ _SURFACE = ("distance_transform", "mask_surface", "surface_distances")
 # the pseudo-vessel mask of `vessels`, the same way
 _VESSELS = ("gaussian_derivative_taps", "hessian", "vesselness", "vessel_mask", "pseudo_vessel_mask")
 
+# the edge-aware heat-map refinement of `refine`, the same way
+_REFINE = ("guided_filter", "refine_heatmap")
+
 # the views of test-time augmentation at inference (`inference`), the same way
 _INFERENCE = ("tta_views",)
 
 __all__ = ["_lib", "functional", "modules", "optim", "Adam", "AdamW", "SGD", "RAdam", "AdaBound", *_AUGMENT, *_LOSSES, *_LESIONS,
-           *_DENSITY, *_DISTRIBUTION, *_CURVES, *_SURFACE, *_VESSELS, *_INFERENCE]
+           *_DENSITY, *_DISTRIBUTION, *_CURVES, *_SURFACE, *_VESSELS, *_REFINE, *_INFERENCE]
 
 
 def __getattr__(name):
@@ -67,6 +70,9 @@ def __getattr__(name):
     if name in _VESSELS:
         from . import vessels
         return getattr(vessels, name)
+    if name in _REFINE:
+        from . import refine
+        return getattr(refine, name)
     if name in _INFERENCE:
         from . import inference
         return getattr(inference, name)

@@ -194,6 +194,10 @@ SIGNATURES = {
     "dram_hessian_norm_max": (I, [P, P, L, P, P]),
     "dram_vesselness": (I, [P, L, ctypes.c_double, ctypes.c_double, P, P, I, P, P]),
     "dram_vessel_mask": (I, [P, P, F, P, L, P]),
+    # heat-map refinement: the masked 3-D guided filter
+    "dram_guided_max_radius": (I, []),
+    "dram_guided_ws_bytes": (Z, [I, I, I]),
+    "dram_guided_filter": (I, [P, I, ctypes.c_double, ctypes.c_double, P, P, P, ctypes.c_double, I, I, I, P, P, P, Z, P]),
     # test-time augmentation for the per-lobe inference (views: host array of V x {perm[3], flip[3]})
     "dram_tta_expand": (I, [P, P, I, I, P, I, P]),
     "dram_tta_combine": (I, [P, P, P, I, I, P, I, P]),

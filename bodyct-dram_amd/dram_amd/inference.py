@@ -28,6 +28,12 @@ signed-permutation views (`tta_views`; the flips and 90-degree rotations the mod
 map is the mean of the V sigmoid maps and the result gains `spread`, their population standard deviation -- both formed at the
 chunk's resolution, then resized and pasted like the single-view map (include/dram_hip.h, "test-time augmentation";
 csrc/infer_tta.hip).  `tta=None` (the default) is the path described above, unchanged.
+
+`LobeInference(refine=...)` adds an edge-aware refinement of the finished heat map, which the reference does not have either:
+the masked 3-D guided filter of `dram_amd.refine`, guided by the scan inside the lobes.  The result gains `htp_refined`,
+`threshold_refined` and `mask_refined`, and `post_process` the same judgement of the refined map beside that of the map as it
+is.  Whether it improves a metric on real scans has not been measured; with `curves=` a user with labels measures it in one
+call.  `refine=None` (the default) changes nothing.
 """
 import ctypes
 import itertools
@@ -136,12 +142,17 @@ class LobeInference:
     tta: None (default: one view, the path above), "flip", "full" or a sequence of (perm, flip) views (`tta_views`): the chunks
     are cropped once, every view of them goes through the model in batches of `tta_batch` chunks, "htp" is the mean of the
     views' sigmoid maps and the result gains "spread" (float32 [D,H,W], their population standard deviation resized and pasted
-    like the heat map, zero outside the lobes) and "views"; "input" stays the canonical chunks.  Only with head="sigmoid"."""
+    like the heat map, zero outside the lobes) and "views"; "input" stays the canonical chunks.  Only with head="sigmoid".
+    refine: None (default), True (the defaults of `dram_amd.refine.refine_heatmap`) or a dict with any of radius_mm, eps, window,
+    iterations: once the heat map is complete (either head, with or without tta) it is refined, and the result gains
+    "htp_refined", "threshold_refined" (`binary_cam` on the refined map inside the lobes) and "mask_refined"."""
+
+    REFINE_KEYS = ("radius_mm", "eps", "window", "iterations")
 
     MAX_CHUNKS = 8     # chunks per kernel call / model batch (csrc/infer.hip MAX_CHUNKS)
 
     def __init__(self, model, resample_size=80, window=(-1000.0, -300.0), border_mm=5.0, max_labels=255,
-                 post_window=(-1150, 350), post_scaler=0.75, head="sigmoid", tta=None, tta_batch=8):
+                 post_window=(-1150, 350), post_scaler=0.75, head="sigmoid", tta=None, tta_batch=8, refine=None):
         if not 1 <= int(max_labels) <= 255:
             raise ValueError("max_labels must be in 1..255 (uint8 label map)")
         if head not in ("sigmoid", "cam"):
@@ -154,6 +165,12 @@ class LobeInference:
         if isinstance(tta_batch, bool) or not isinstance(tta_batch, (int, np.integer)) or tta_batch < 1:
             raise ValueError("tta_batch must be a positive integer (chunks per model call)")
         self.tta_batch = int(tta_batch)
+        if refine is None or refine is True:
+            self.refine = None if refine is None else {}
+        elif isinstance(refine, dict) and set(refine) <= set(self.REFINE_KEYS):
+            self.refine = dict(refine)
+        else:
+            raise ValueError(f"refine must be None, True or a dict with keys among {self.REFINE_KEYS}")
         self.model, self.R, self.window, self.border, self.max_labels = model, int(resample_size), window, border_mm, int(max_labels)
         # the brightness gate of LesionSegTest.run: windowing()'s default span (utils.py:189, job_runner.py:1006) and the 0.75
         # on its Otsu threshold (job_runner.py:1007)
@@ -211,6 +228,8 @@ class LobeInference:
                 res["lobe_cls"] = {}
             if spread is not None:
                 res.update(spread=spread, views=self.views)
+            if self.refine is not None:
+                res.update(htp_refined=torch.zeros_like(htp), threshold_refined=0.0, mask_refined=torch.zeros_like(res["mask"]))
             return res
         R = self.R
         x = torch.empty((len(chunks), 1, R, R, R), dtype=torch.float32, device=dev)
@@ -257,9 +276,20 @@ class LobeInference:
             res.update(lobe_cls={c[6]: int(k) for c, k in zip(chunks, cls_h)}, pool=torch.cat(pools), lobe_mask=lobe_mask)
         if spread is not None:
             res.update(spread=spread, views=self.views)
+        refined = None
+        if self.refine is not None:
+            from .refine import refine_heatmap
+            htp_r = refine_heatmap(htp, scan, lobe, spacing, **self.refine)
+            call("dram_lung_hist256", htp_r.data_ptr(), lobe.data_ptr(), hist.data_ptr(), ssum.data_ptr(), htp_r.numel(), st)
+            th_r = binary_cam_threshold(hist[:256].cpu().numpy())
+            mask_r = torch.empty((D, H, W), dtype=torch.uint8, device=dev)
+            call("dram_threshold_mask", htp_r.data_ptr(), mask_r.data_ptr(), float(th_r), htp_r.numel(), st)
+            res.update(htp_refined=htp_r, threshold_refined=th_r, mask_refined=mask_r)
+            refined = (htp_r, th_r, mask_r)
         if vessel is not None or lesion is not None or original_size is not None:
             res.update(self.post_process(scan, lobe, htp, th, vessel, lesion, mask, spacing=spacing,
-                                         original_spacing=original_spacing, original_size=original_size, curves=curves))
+                                         original_spacing=original_spacing, original_size=original_size, curves=curves,
+                                         refined=refined))
         return res
 
     def _tta_group(self, xg, lobe, htp, spread, carr, L, D, H, W, st):
@@ -296,7 +326,7 @@ class LobeInference:
 
     @torch.no_grad()
     def post_process(self, scan, lobe, htp, th, vessel=None, lesion=None, mask=None, spacing=None, original_spacing=None,
-                     original_size=None, curves=None):
+                     original_size=None, curves=None, refined=None):
         """The tail of LesionSegTest.run (job_runner.py:1006-1037) on the device: brightness gate
         `binary_cam(w_scan[lobe > 0], 0.75)` on the scan windowed with windowing()'s default span, lesion_pred_post =
         lesion_pred & (w_scan > th) & ~(vessel > 0), the resampling to the scan's original grid when `original_spacing` /
@@ -308,7 +338,11 @@ class LobeInference:
         ~vessel.  Both are computed on the grid of the IoU / Dice metrics: the working grid, or with `original_size` the original
         one, from the linearly resampled heat map and the nearest-resampled reference, lobe map and gate.  On the original grid
         the reported `dice` (of a nearest-resampled mask) is therefore not a point of this curve (a linearly resampled map, then
-        thresholded); on the working grid `dice` is the curve's value at the cut below `threshold`, up to the bin width."""
+        thresholded); on the working grid `dice` is the curve's value at the cut below `threshold`, up to the bin width.
+        `refined` = (htp_refined, threshold_refined, mask_refined) of a `refine=` run adds, under the same conditions as the keys
+        above and computed the same way from the refined map: "mask_refined_post" (the same gate), "iou_refined", "dice_refined",
+        "iou_refined_post", "dice_refined_post", "curves_refined", "curves_refined_post", and under "original" "htp_refined"
+        (linear), "mask_refined" and "mask_refined_post" (nearest)."""
         if curves is not None and lesion is None:
             raise ValueError("curves needs the reference mask: pass lesion=")
         if (original_spacing is None) != (original_size is None) or (original_size is not None and spacing is None):
@@ -326,6 +360,12 @@ class LobeInference:
         call("dram_lesion_post", htp.data_ptr(), scan.data_ptr(), None if vessel is None else vessel.data_ptr(), None,
              post.data_ptr(), float(th), self.post_window[0], self.post_window[1], float(th_scan), n, st)
         out = {"mask_post": post, "threshold_scan": th_scan}
+        if refined is not None:
+            htp_r, th_r, mask_r = refined
+            post_r = torch.empty(htp.shape, dtype=torch.uint8, device=dev)
+            call("dram_lesion_post", htp_r.data_ptr(), scan.data_ptr(), None if vessel is None else vessel.data_ptr(), None,
+                 post_r.data_ptr(), float(th_r), self.post_window[0], self.post_window[1], float(th_scan), n, st)
+            out["mask_refined_post"] = post_r
         if mask is None and (lesion is not None or original_size is not None):
             mask = torch.empty(htp.shape, dtype=torch.uint8, device=dev)
             call("dram_threshold_mask", htp.data_ptr(), mask.data_ptr(), float(th), n, st)
@@ -340,6 +380,10 @@ class LobeInference:
             if lesion is not None:
                 orig["lesion"] = lesion = back(lesion, "nearest")
             out["original"] = orig
+            if refined is not None:
+                orig.update(htp_refined=back(htp_r, "linear"), mask_refined=back(mask_r, "nearest"),
+                            mask_refined_post=back(post_r, "nearest"))
+                htp_r, mask_r, post_r = orig["htp_refined"], orig["mask_refined"], orig["mask_refined_post"]
             mask, post, n = orig["mask"], orig["mask_post"], orig["mask"].numel()
         if curves is not None:
             from .curves import heatmap_curves
@@ -355,6 +399,9 @@ class LobeInference:
             n_cal = min(16, int(curves))
             out["curves"] = heatmap_curves(score, lesion, regions, n_regions, None, curves, n_cal)
             out["curves_post"] = heatmap_curves(score, lesion, regions, n_regions, gate, curves, n_cal)
+            if refined is not None:
+                out["curves_refined"] = heatmap_curves(htp_r, lesion, regions, n_regions, None, curves, n_cal)
+                out["curves_refined_post"] = heatmap_curves(htp_r, lesion, regions, n_regions, gate, curves, n_cal)
         if lesion is not None:
             counts = torch.empty(8, dtype=torch.int64, device=dev)
             call("dram_mask_overlap", mask.data_ptr(), lesion.data_ptr(), counts.data_ptr(), n, st)
@@ -363,6 +410,12 @@ class LobeInference:
             s = 1e-5                                                        # the smooth term of job_runner.py:1033-1037
             out.update(iou=(c[0] + s) / (c[1] + s), dice=(2.0 * c[0] + s) / (c[2] + c[3] + s),
                        iou_post=(c[4] + s) / (c[5] + s), dice_post=(2.0 * c[4] + s) / (c[6] + c[7] + s))
+            if refined is not None:
+                call("dram_mask_overlap", mask_r.data_ptr(), lesion.data_ptr(), counts.data_ptr(), n, st)
+                call("dram_mask_overlap", post_r.data_ptr(), lesion.data_ptr(), counts[4:].data_ptr(), n, st)
+                c = [int(v) for v in counts.cpu()]
+                out.update(iou_refined=(c[0] + s) / (c[1] + s), dice_refined=(2.0 * c[0] + s) / (c[2] + c[3] + s),
+                           iou_refined_post=(c[4] + s) / (c[5] + s), dice_refined_post=(2.0 * c[4] + s) / (c[6] + c[7] + s))
         return out
 
 

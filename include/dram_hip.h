@@ -1007,6 +1007,40 @@ int dram_vesselness(const float* h6, int64_t S, double alpha, double beta, const
                     double* eig, void* stream);
 int dram_vessel_mask(const float* vmax, const uint8_t* lobe, float threshold, uint8_t* mask, int64_t n, void* stream);
 
+/* ---- heat-map refinement (csrc/guided.hip; no counterpart in the reference): the masked 3-D guided filter (He, Sun and Tang)
+ *      of the heat map, guided by the scan and restricted to a region (the lung).  Closed form, deterministic, nothing trained.
+ *      Volumes are contiguous [D,H,W] on the DEVICE, S = D*H*W < 2^31.  The entry does not synchronise, allocate or read device
+ *      memory from the host.
+ * Inputs: guide G, either the int16 scan (DRAM_GUIDE_INT16) or a float32 volume (DRAM_GUIDE_FLOAT32); input P, float32, the heat
+ *   map; region M, uint8, nonzero = inside; radius r = (rz, ry, rx) in voxels (a HOST array), each 0 <= r <=
+ *   dram_guided_max_radius(); eps > 0.
+ *   The guide value of an int16 scan is formed on load in fp64 as g = clamp((hu - lo) / (hi - lo), 0, 1); it is never
+ *   materialised.  A float32 guide is taken as it is (lo and hi are not read).
+ *   The window W(c) is the box c +- r, cut at the volume's edge.  All arithmetic is fp64 on the fp32 or int16 inputs; the
+ *   products g*g and g*p are formed in fp64, where they are exact; no operation is fused into a multiply-add.
+ *   1. For every c, over q in W(c) with M(q) != 0:  N = count, Sg = sum g, Sp = sum p, Sgg = sum g*g, Sgp = sum g*p.  Voxels with
+ *      M = 0 are selected out, not multiplied by zero: a NaN or Inf outside the region reaches no output.
+ *   2. Where M(c) != 0 (there N >= 1):  mg = Sg/N, mp = Sp/N, a = (Sgp/N - mg*mp) / ((Sgg/N - mg*mg) + eps), b = mp - a*mg.
+ *      Elsewhere a and b are not defined and are never read.
+ *   3. Where M(c) != 0:  A = (sum of a over W(c), M != 0) / N, B the same for b, q(c) = (float)(A*g(c) + B).  Elsewhere q(c) = 0.
+ *      Every voxel of q is written.
+ *   Every sum is a direct window sum, separable x, then y, then z, each axis added in ascending order from +0 with +0 for a
+ *   voxel outside M or outside the volume; so a value depends on nothing but its window, and the call on any box that holds
+ *   every voxel of M gives the bits of the whole-volume call.  No floating-point atomics: two calls on the same input give the
+ *   same bits.  Everything that crosses memory between the passes is fp64.
+ * dram_guided_max_radius() = 16 serves 8 mm at 0.5 mm spacing; a larger radius is refused, not clamped.
+ * dram_guided_filter: ab ([2][S] fp64, may be NULL) receives a and b of step 2, 0 where M == 0.  ws: dram_guided_ws_bytes(D, H,
+ *   W) bytes (twelve fp64 volumes); ws and ab 16-byte aligned.  Refused before anything is launched: a null required pointer,
+ *   an unknown guide_kind, refused sizes, eps <= 0 or not finite, a radius negative or above the cap, DRAM_GUIDE_INT16 with
+ *   hi <= lo or a window that is not finite, a misaligned pointer (all DRAM_EINVAL); a workspace that is too small (DRAM_EWS).
+ *   dram_guided_ws_bytes and dram_guided_max_radius answer without a GPU, the former 0 for sizes that the filter refuses. ---- */
+#define DRAM_GUIDE_INT16 0
+#define DRAM_GUIDE_FLOAT32 1
+int dram_guided_max_radius(void);
+size_t dram_guided_ws_bytes(int D, int H, int W);
+int dram_guided_filter(const void* guide, int guide_kind, double lo, double hi, const float* p, const uint8_t* mask, const int* radius,
+                       double eps, int D, int H, int W, float* q, double* ab, void* ws, size_t ws_bytes, void* stream);
+
 /* ---- test-time augmentation for the per-lobe inference (csrc/infer_tta.hip; no counterpart in the reference): the chunks go
  *      through the model in V orientations, the heat map is the mean of the V sigmoid maps and the spread map their standard
  *      deviation.
