@@ -1,7 +1,8 @@
 // The training losses and their targets on the device, gfx950.  In this order: the pieces every section shares; the fused
 // IntRegRefineLoss; the pieces of the affine-consistency losses; IntRegLoss (the hinge with an
 // entropy term instead of the pseudo-label term); the two voxel-wise segmentation losses on a target that is given
-// (BootBinCrossEntropy, BinaryCrossEntropySmooth); the regression targets of a batch; the C entry points.
+// (BootBinCrossEntropy, BinaryCrossEntropySmooth) and the per-sample Tversky + focal loss on logits (SegOverlap); the regression
+// targets of a batch; the C entry points.
 //
 // Every loss is a streaming pass that leaves one tuple of partial sums per block, a one-block kernel that adds the partials
 // in a fixed order and forms the scalars, and a streaming backward.  No atomics anywhere: the same input gives the same
@@ -15,6 +16,7 @@
 //   seg_load_groups     the groups of four elements a lane of a segmentation kernel owns, by element index, with a per-tensor
 //                       alignment flag and a ragged tail (seg_load4 / seg_store4)
 // loss_partial_kernel and the masked smooth-L1 kernels predate these and keep their fp32 chunk sums (block_sum_256).
+#include <cmath>
 #include <type_traits>
 
 #include "common.h"
@@ -762,7 +764,164 @@ __global__ __launch_bounds__(256) void bce_smooth_bwd_kernel(const float* __rest
 static inline int64_t seg_blocks(int64_t n) { return cdiv64(n, SEG_CHUNK); }
 static inline bool seg_kind_ok(int kind) { return kind == DRAM_SEG_MASK_U8 || kind == DRAM_SEG_MASK_F32; }
 // whether a tensor of this kind may be read one group (four elements) per access
-static inline int seg_vec(const void* b, int kind) { return ((uintptr_t)b & (kind == DRAM_SEG_MASK_U8 ? 3 : 15)) == 0; }
+__host__ __device__ static inline int seg_vec(const void* b, int kind) {
+    return ((uintptr_t)b & (kind == DRAM_SEG_MASK_U8 ? 3 : 15)) == 0;
+}
+
+
+// ---- SegOverlap: per-sample Tversky + focal loss on LOGITS with a target that is given (no reference counterpart) ---------
+//   p = sigmoid(z),  -log p = softplus(-z),  -log(1 - p) = softplus(z);  1 - p is never formed by subtraction
+//   per sample n, V = {voi set} (every voxel without a voi):  TP = sum_V p [t],  SP = sum_V p,  ST = sum_V [t],  M = |V|
+//   TI = (TP + s) / ((1 - a - b) TP + a SP + b ST + s),   F = (1 / M) sum_V alpha_t (1 - p_t)^gamma (-log p_t)
+//   out[0] = sum_n (1 - TI_n),  out[1] = (1 / N) sum_n F_n;  M = 0: TI = 1, F = 0
+// With u = -z where t is set and u = z elsewhere (the logit of the WRONG class): -log p_t = softplus(u), -log(1 - p_t) =
+// softplus(-u), so one voxel costs one expf (e = exp(-|z|), shared by the sigmoid and both softplus: softplus(x) = max(x, 0)
+// + log1p(e)), one log1pf and one expf for the power.
+// Forward: the layout of the BCE pair above, once per sample: grid (blocks of SEG_CHUNK elements, N), so a block never
+// leaves its sample; the groups a lane owns are counted from the SAMPLE's first element and the per-tensor alignment flag
+// is that of the sample's base, so any S and any base address give the same bits.  One fp64 tuple per block; one block
+// then adds each sample's tuples (one wave per sample, sample_totals) and the per-sample terms in index order.
+// Backward: one pass with the same ownership; per sample it reads the three coefficients the finish kernel left in `state`.
+constexpr int OVL_NSUM = 5;            // per (sample, block): TP, SP, ST, M, sum of the focal terms
+constexpr int OVL_STATE = 5;           // floats per sample: 1 - TI, F, then the backward's c_set, c_unset, 1 / (N M)
+
+// One voxel: p q = d p / d z, p, the focal term f and d f / d z.  a1 = alpha, a0 = 1 - alpha.
+__device__ __forceinline__ void ovl_voxel(float z, bool set, float a1, float a0, float gamma, float& pq, float& p, float& f,
+                                          float& dfz) {
+    float q;
+    sigmoid_pq(z, p, q);
+    pq = p * q;
+    const float l = log1pf(expf(-fabsf(z)));             // softplus(-|z|)
+    const float u = set ? -z : z;
+    const float nlp = fmaxf(u, 0.f) + l;                 // -log p_t       = softplus(u)
+    const float nlq = fmaxf(-u, 0.f) + l;                // -log(1 - p_t)  = softplus(-u)
+    const float w = (set ? a1 : a0) * expf(-gamma * nlq);     // alpha_t (1 - p_t)^gamma
+    f = w * nlp;
+    // d f / d u = alpha_t (1 - p_t)^gamma (gamma p_t (-log p_t) + (1 - p_t)),  d u / d z = -+ 1
+    const float dfu = w * (gamma * (set ? p : q) * nlp + (set ? q : p));
+    dfz = set ? -dfu : dfu;
+}
+
+// KV and voi are not used where HV is false (no volume of interest: every voxel counts)
+template <int KT, int KV, bool HV>
+__global__ __launch_bounds__(256) void seg_overlap_partial_kernel(const float* __restrict__ z,
+                                                                  const typename SegMask<KT>::type* __restrict__ t,
+                                                                  const typename SegMask<KV>::type* __restrict__ voi,
+                                                                  double* __restrict__ part, int64_t S, float a1, float a0,
+                                                                  float gamma) {
+    __shared__ double red[OVL_NSUM][4];
+    const int64_t base = (int64_t)blockIdx.y * S;
+    z += base; t += base; voi += base;
+    float zv[SEG_UNROLL][4], tv[SEG_UNROLL][4], vv[SEG_UNROLL][4];
+    int cnt[SEG_UNROLL];
+    int64_t at[SEG_UNROLL];
+    if constexpr (HV)
+        seg_load_groups(S, cnt, at, SegSrc(z, seg_vec(z, DRAM_SEG_MASK_F32), zv), SegSrc(t, seg_vec(t, KT), tv),
+                        SegSrc(voi, seg_vec(voi, KV), vv));
+    else
+        seg_load_groups(S, cnt, at, SegSrc(z, seg_vec(z, DRAM_SEG_MASK_F32), zv), SegSrc(t, seg_vec(t, KT), tv));
+    double acc[OVL_NSUM] = {0.0, 0.0, 0.0, 0.0, 0.0};
+#pragma unroll
+    for (int u = 0; u < SEG_UNROLL; ++u) {
+        float s[OVL_NSUM] = {0.f, 0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+            if (e >= cnt[u]) continue;
+            if constexpr (HV)
+                if (vv[u][e] == 0.f) continue;
+            const bool set = tv[u][e] != 0.f;
+            float pq, p, f, dfz;
+            ovl_voxel(zv[u][e], set, a1, a0, gamma, pq, p, f, dfz);
+            s[0] += set ? p : 0.f;
+            s[1] += p;
+            s[2] += set ? 1.f : 0.f;
+            s[3] += 1.f;
+            s[4] += f;
+        }
+#pragma unroll
+        for (int q = 0; q < OVL_NSUM; ++q) acc[q] += s[q];
+    }
+    block_partials<OVL_NSUM>(acc, red, part + ((size_t)blockIdx.y * gridDim.x + blockIdx.x) * OVL_NSUM);
+}
+
+// tot (SEG_TOTALS doubles per sample): TP, SP, ST, M, the focal sum, 1 - TI, F, 0.  state: OVL_STATE floats per sample.
+// 1 - TI = (a (SP - TP) + b (ST - TP)) / denominator: the difference of the two, formed without the cancellation near TI = 1.
+__global__ __launch_bounds__(256) void seg_overlap_finish_kernel(const double* __restrict__ part, int N, int nblk, double a,
+                                                                 double b, double smooth, double* __restrict__ tot,
+                                                                 float* __restrict__ out, float* __restrict__ state) {
+    __shared__ double red[2][4];
+    for (int n = threadIdx.x >> 6; n < N; n += 4) {
+        double v[OVL_NSUM];
+        sample_totals<OVL_NSUM>(part, n, nblk, v);
+        if ((threadIdx.x & 63) != 0) continue;
+        const double TP = v[0], SP = v[1], ST = v[2], M = v[3];
+        const double num = TP + smooth, den = (1.0 - a - b) * TP + a * SP + b * ST + smooth;      // den >= num > 0
+        const bool any = M > 0.0;
+        const double loss = (a * (SP - TP) + b * (ST - TP)) / den, F = any ? v[4] / M : 0.0;
+        double* o = tot + (size_t)n * SEG_TOTALS;
+#pragma unroll
+        for (int q = 0; q < OVL_NSUM; ++q) o[q] = v[q];
+        o[5] = loss; o[6] = F; o[7] = 0.0;
+        float* c = state + (size_t)n * OVL_STATE;
+        c[0] = (float)loss; c[1] = (float)F;
+        c[2] = (float)(-(den - num * (1.0 - b)) / (den * den));       // d (1 - TI) / d TP + d (1 - TI) / d SP: t set
+        c[3] = (float)(num * a / (den * den));                        // d (1 - TI) / d SP: t not set
+        c[4] = any ? (float)(1.0 / ((double)N * M)) : 0.f;
+    }
+    __syncthreads();
+    double s[2] = {0.0, 0.0}, r[2];
+    for (int n = threadIdx.x; n < N; n += 256) {
+        s[0] += tot[(size_t)n * SEG_TOTALS + 5];
+        s[1] += tot[(size_t)n * SEG_TOTALS + 6];
+    }
+    block_totals<2>(s, red, r);
+    if (threadIdx.x == 0) { out[0] = (float)r[0]; out[1] = (float)(r[1] / (double)N); }
+}
+
+// dz = gout[0] d out[0] / dz + gout[1] d out[1] / dz: each product with gout last (one rounding each), then one addition;
+// exactly +0 outside the volume of interest.
+template <int KT, int KV, bool HV>
+__global__ __launch_bounds__(256) void seg_overlap_bwd_kernel(const float* __restrict__ z,
+                                                              const typename SegMask<KT>::type* __restrict__ t,
+                                                              const typename SegMask<KV>::type* __restrict__ voi,
+                                                              const float* __restrict__ state, const float* __restrict__ gout,
+                                                              float* __restrict__ dz, int64_t S, float a1, float a0,
+                                                              float gamma) {
+    const int64_t base = (int64_t)blockIdx.y * S;
+    z += base; t += base; voi += base; dz += base;
+    const float g0 = gout[0], g1 = gout[1];
+    const float* c = state + (size_t)blockIdx.y * OVL_STATE;
+    const float cset = c[2], cunset = c[3], cf = c[4];
+    float zv[SEG_UNROLL][4], tv[SEG_UNROLL][4], vv[SEG_UNROLL][4];
+    int cnt[SEG_UNROLL];
+    int64_t at[SEG_UNROLL];
+    if constexpr (HV)
+        seg_load_groups(S, cnt, at, SegSrc(z, seg_vec(z, DRAM_SEG_MASK_F32), zv), SegSrc(t, seg_vec(t, KT), tv),
+                        SegSrc(voi, seg_vec(voi, KV), vv));
+    else
+        seg_load_groups(S, cnt, at, SegSrc(z, seg_vec(z, DRAM_SEG_MASK_F32), zv), SegSrc(t, seg_vec(t, KT), tv));
+    const bool vecd = seg_vec(dz, DRAM_SEG_MASK_F32) != 0;
+#pragma unroll
+    for (int u = 0; u < SEG_UNROLL; ++u) {
+        if (cnt[u] == 0) continue;
+        float d[4] = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+            if (e >= cnt[u]) continue;
+            if constexpr (HV)
+                if (vv[u][e] == 0.f) continue;
+            const bool set = tv[u][e] != 0.f;
+            float pq, p, f, dfz;
+            ovl_voxel(zv[u][e], set, a1, a0, gamma, pq, p, f, dfz);
+            {
+#pragma clang fp contract(off)         // two rounded products, then their sum: no fma may merge a product into the sum
+                const float d0 = g0 * (pq * (set ? cset : cunset)), d1 = g1 * (cf * dfz);
+                d[e] = d0 + d1;
+            }
+        }
+        seg_store4(dz, at[u], vecd, cnt[u], d);
+    }
+}
 
 
 // ---- regression targets of a batch (IntRegLoss.get_labels, dram/metrics.py:122-138; weight 172-174; keep 326-327) --------
@@ -1057,6 +1216,64 @@ extern "C" int dram_bce_smooth_bwd(const float* p, const void* t, int t_kind, in
                            seg_vec(dp, DRAM_SEG_MASK_F32));
     });
     return check_launch("bce_smooth_bwd");
+}
+
+extern "C" size_t dram_seg_overlap_ws_bytes(int N, int64_t S) {
+    if (N <= 0 || S <= 0) return 0;
+    return ((size_t)N * SEG_TOTALS + (size_t)N * seg_blocks(S) * OVL_NSUM) * sizeof(double);
+}
+
+extern "C" int dram_seg_overlap_state_floats(int N) { return OVL_STATE * (N > 0 ? N : 0); }
+
+// launch(Int<KT>, Int<KV>, has-voi, typed t, typed voi): the instantiation of a SegOverlap kernel; without a voi the
+// target stands in for the pointer nobody reads
+template <class F> static inline void with_overlap_masks(const void* t, int t_kind, const void* voi, int voi_kind, F&& launch) {
+    with_mask(t, t_kind, [&](auto KT, auto tp) {
+        if (!voi) launch(KT, KT, std::false_type(), tp, tp);
+        else with_mask(voi, voi_kind, [&](auto KV, auto vp) { launch(KT, KV, std::true_type(), tp, vp); });
+    });
+}
+
+#define OVL_REQUIRE_COMMON(who)                                                                                          \
+    DRAM_REQUIRE(N >= 0 && S >= 0, who ": negative dimension");                                                          \
+    DRAM_REQUIRE(N <= 65535 && S <= ((int64_t)1 << 40), who ": more than 65535 samples or 2^40 elements per sample");    \
+    DRAM_REQUIRE(seg_kind_ok(t_kind) && (!voi || seg_kind_ok(voi_kind)), who ": mask kind must be 0 (uint8) or 2 (float32)"); \
+    DRAM_REQUIRE(alpha >= 0.0 && alpha <= 1.0, who ": alpha must lie in [0, 1]");                                       \
+    DRAM_REQUIRE(gamma >= 0.0 && std::isfinite(gamma), who ": gamma must be finite and not negative")
+
+extern "C" int dram_seg_overlap_fwd(const float* z, const void* t, const void* voi, int t_kind, int voi_kind, int N,
+                                    int64_t S, double a, double b, double smooth, double alpha, double gamma, float* out,
+                                    float* state, void* ws, size_t ws_bytes, void* stream) {
+    OVL_REQUIRE_COMMON("seg_overlap_fwd");
+    DRAM_REQUIRE(a >= 0.0 && b >= 0.0 && std::isfinite(a) && std::isfinite(b), "seg_overlap_fwd: a and b must be finite and not negative");
+    DRAM_REQUIRE(smooth > 0.0 && std::isfinite(smooth), "seg_overlap_fwd: the smoothing term must be finite and positive");
+    if (N == 0 || S == 0) return DRAM_OK;
+    DRAM_REQUIRE(z && t && out && state && ws, "seg_overlap_fwd: null pointer");
+    LOSS_REQUIRE_WS("seg_overlap_fwd", ws, 8, ws_bytes, dram_seg_overlap_ws_bytes(N, S));
+    hipStream_t st = (hipStream_t)stream;
+    const int nblk = (int)seg_blocks(S);
+    double* tot = (double*)ws;
+    double* part = tot + (size_t)N * SEG_TOTALS;
+    with_overlap_masks(t, t_kind, voi, voi_kind, [&](auto KT, auto KV, auto HV, auto tp, auto vp) {
+        hipLaunchKernelGGL((seg_overlap_partial_kernel<KT.value, KV.value, HV.value>), dim3(nblk, N), dim3(256), 0, st, z, tp, vp,
+                           part, S, (float)alpha, (float)(1.0 - alpha), (float)gamma);
+    });
+    hipLaunchKernelGGL(seg_overlap_finish_kernel, dim3(1), dim3(256), 0, st, (const double*)part, N, nblk, a, b, smooth, tot, out,
+                       state);
+    return check_launch("seg_overlap_fwd");
+}
+
+extern "C" int dram_seg_overlap_bwd(const float* z, const void* t, const void* voi, int t_kind, int voi_kind, int N,
+                                    int64_t S, double alpha, double gamma, const float* state, const float* gout, float* dz,
+                                    void* stream) {
+    OVL_REQUIRE_COMMON("seg_overlap_bwd");
+    if (N == 0 || S == 0) return DRAM_OK;
+    DRAM_REQUIRE(z && t && state && gout && dz, "seg_overlap_bwd: null pointer");
+    with_overlap_masks(t, t_kind, voi, voi_kind, [&](auto KT, auto KV, auto HV, auto tp, auto vp) {
+        hipLaunchKernelGGL((seg_overlap_bwd_kernel<KT.value, KV.value, HV.value>), dim3((unsigned)seg_blocks(S), N), dim3(256), 0,
+                           (hipStream_t)stream, z, tp, vp, state, gout, dz, S, (float)alpha, (float)(1.0 - alpha), (float)gamma);
+    });
+    return check_launch("seg_overlap_bwd");
 }
 
 extern "C" size_t dram_intreg_targets_ws_bytes(int N, int64_t S) {

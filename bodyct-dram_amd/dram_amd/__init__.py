@@ -15,7 +15,7 @@ _AUGMENT = ("GaussianBlur", "RandomMaskOut", "RandomFlip", "RandomRotate90", "Ga
             "EnsembleScanAugmentation")
 
 # the segmentation losses of `losses`, the same way
-_LOSSES = ("BootBinCrossEntropy", "BinaryCrossEntropySmooth")
+_LOSSES = ("BootBinCrossEntropy", "BinaryCrossEntropySmooth", "TverskyLoss", "SoftDiceLoss", "FocalLoss")
 
 # the lesion-wise report of `lesions`, the same way
 _LESIONS = ("label_components", "component_stats", "remove_small", "lobe_burden", "lesion_report")

@@ -136,6 +136,11 @@ SIGNATURES = {
     "dram_boot_bce_bwd": (I, [P, P, P, I, I, L, ctypes.c_double, P, P, P, P]),
     "dram_bce_smooth_fwd": (I, [P, P, I, L, ctypes.c_double, P, P, P, Z, P]),
     "dram_bce_smooth_bwd": (I, [P, P, I, L, ctypes.c_double, P, P, P, P]),
+    # per-sample Tversky + focal loss on logits with a given target
+    "dram_seg_overlap_ws_bytes": (Z, [I, L]),
+    "dram_seg_overlap_state_floats": (I, [I]),
+    "dram_seg_overlap_fwd": (I, [P, P, P, I, I, I, L] + [ctypes.c_double] * 5 + [P, P, P, Z, P]),
+    "dram_seg_overlap_bwd": (I, [P, P, P, I, I, I, L, ctypes.c_double, ctypes.c_double, P, P, P, P]),
     "dram_affine_sample_fwd": (I, [P, P, P, I, I, I, I, I, P]),
     "dram_affine_sample_bwd": (I, [P, P, P, I, I, I, I, I, P]),
     # measured ceilings (bench.py)

@@ -1286,6 +1286,70 @@ def bce_smooth(p, t, smooth):
     return BCESmoothFn.apply(p, t, smooth)
 
 
+def _seg_overlap_args(logits, target, voi):
+    """The checked tensors of a SegOverlap call: (z, t, t kind, voi or None, voi kind, N, S).  The first dimension is the
+    sample; a 5-d tensor is [N,1,D,H,W]."""
+    z = _chk(logits, "seg_overlap logits")
+    if z.dim() < 1 or (z.dim() == 5 and z.shape[1] != 1):
+        raise ValueError(f"seg_overlap logits: expected [N, ...] with one channel, got shape {tuple(z.shape)}")
+    t, kt = _seg_mask(target, "seg_overlap target", z)
+    voi, kv = (None, 0) if voi is None else _seg_mask(voi, "seg_overlap voi", z)
+    N = z.shape[0]
+    return z, t, kt, voi, kv, N, (z.numel() // N if N else 0)
+
+
+def _seg_overlap_launch(z, t, kt, voi, kv, N, S, a, b, smooth, alpha, gamma):
+    """(out[2], state, fp64 workspace) of a SegOverlap forward; a batch of no elements is (0, 0), nothing is launched."""
+    dev = z.device
+    out = torch.zeros(2, dtype=torch.float32, device=dev) if N * S == 0 else torch.empty(2, dtype=torch.float32, device=dev)
+    state = torch.empty(max(_lib.lib.dram_seg_overlap_state_floats(N), 1), dtype=torch.float32, device=dev)
+    ws = torch.empty(max(int(_lib.lib.dram_seg_overlap_ws_bytes(N, S)) // 8, 8), dtype=torch.float64, device=dev)
+    call("dram_seg_overlap_fwd", _p(z), _p(t), _p(voi), kt, kv, N, S, float(a), float(b), float(smooth), float(alpha),
+         float(gamma), _p(out), _p(state), _p(ws), ws.numel() * 8, _stream())
+    return out, state, ws
+
+
+def seg_overlap_totals(logits, target, voi=None, alpha=.5, gamma=2.0):
+    """The fp64 per-sample totals of a SegOverlap forward as the finish kernel leaves them at the head of the workspace, an
+    [N, 5] device tensor: TP, SP, ST, M and the sum of the focal terms (for tests and diagnostics)."""
+    z, t, kt, voi, kv, N, S = _seg_overlap_args(logits.detach(), target, voi)
+    ws = _seg_overlap_launch(z, t, kt, voi, kv, N, S, .5, .5, 1.0, alpha, gamma)[2]
+    return ws[:8 * N].view(N, 8)[:, :5] if N * S else torch.zeros((N, 5), dtype=torch.float64, device=z.device)
+
+
+class SegOverlapFn(Function):
+    """(sum_n (1 - TI_n), mean_n F_n): the per-sample Tversky and focal terms of include/dram_hip.h (SegOverlap) on logits
+    and a given target.  One streaming pass and a one-block finish forward, one streaming pass backward; what is saved is
+    z, t, voi and five floats per sample -- no per-voxel intermediate -- and nothing is read back."""
+
+    @staticmethod
+    def forward(ctx, logits, target, voi, a, b, smooth, alpha, gamma):
+        z, t, kt, voi, kv, N, S = _seg_overlap_args(logits, target, voi)
+        out, state, _ = _seg_overlap_launch(z, t, kt, voi, kv, N, S, a, b, smooth, alpha, gamma)
+        ctx.save_for_backward(z, t, state, *(() if voi is None else (voi,)))
+        ctx.args = (kt, kv, N, S, float(alpha), float(gamma))
+        return out
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, gout):
+        z, t, state, *rest = ctx.saved_tensors
+        voi = rest[0] if rest else None
+        gout = _chk(gout, "seg_overlap grad_output", 1)
+        if gout.numel() != 2:
+            raise ValueError(f"seg_overlap grad_output: expected two elements, got shape {tuple(gout.shape)}")
+        kt, kv, N, S, alpha, gamma = ctx.args
+        dz = torch.empty_like(z)
+        call("dram_seg_overlap_bwd", _p(z), _p(t), _p(voi), kt, kv, N, S, alpha, gamma, _p(state), _p(gout), _p(dz), _stream())
+        return dz, None, None, None, None, None, None, None
+
+
+def seg_overlap(logits, target, voi=None, a=.5, b=.5, smooth=1.0, alpha=.5, gamma=2.0):
+    """Returns a [2] tensor: (sum over samples of 1 - Tversky index, mean over samples of the focal term) of the logits
+    [N,1,D,H,W] against `target` inside `voi` (float32, uint8 or bool of the logits' shape; voi None: every voxel)."""
+    return SegOverlapFn.apply(logits, target, voi, a, b, smooth, alpha, gamma)
+
+
 # --------------------------------------------------------------------------- PCM local attention
 PCM_RELU, PCM_L2NORM = 1, 2
 # merge_type -> (flags, scale_mode); reference models.py:259-331 (dot-product family)

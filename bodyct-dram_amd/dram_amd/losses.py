@@ -1,10 +1,15 @@
-"""The reference's two voxel-wise segmentation losses (dram/metrics.py:10-72) on the device, for a target the caller gives:
-fine-tuning on real voxel labels, where the fused IntRegRefineLoss (train_step.DeviceIntRegRefineLoss) derives its target
-from the prediction itself.  Constructor and call signatures are the reference's; the work is `functional.boot_bce` /
-`functional.bce_smooth` (kernels dram_boot_bce_* / dram_bce_smooth_* of csrc/loss.hip).  There is no CPU path.
+"""Segmentation losses on the device for a target the caller gives: fine-tuning on real voxel labels, where the fused
+IntRegRefineLoss (train_step.DeviceIntRegRefineLoss) derives its target from the prediction itself.  There is no CPU path.
 
-Neither class fits DataParallelTrainer(loss_fn=...): that contract is two terms, a per-sample sum and a share-weighted batch
-mean, and these are a single mean over the whole batch."""
+BootBinCrossEntropy and BinaryCrossEntropySmooth are the reference's two voxel-wise losses (dram/metrics.py:10-72) on
+probabilities, constructor and call signatures the reference's; the work is `functional.boot_bce` / `functional.bce_smooth`
+(kernels dram_boot_bce_* / dram_bce_smooth_* of csrc/loss.hip).  Neither fits DataParallelTrainer(loss_fn=...): that
+contract is two terms, a per-sample sum and a share-weighted batch mean, and these are a single mean over the whole batch
+whose class-balance weight is a statistic of that batch.
+
+TverskyLoss, SoftDiceLoss and FocalLoss have no reference counterpart.  They take LOGITS, every quantity of theirs is per
+sample (include/dram_hip.h, SegOverlap; `functional.seg_overlap`, kernels dram_seg_overlap_*), and the pair of them is
+what does fit the trainer: train_step.DeviceSegOverlapLoss."""
 from . import functional as HF
 
 
@@ -35,3 +40,37 @@ class BinaryCrossEntropySmooth:
 
     def __call__(self, probs, targets):
         return HF.bce_smooth(probs, targets, self.smooth)
+
+
+class TverskyLoss:
+    """loss = TverskyLoss(a, b, smooth)(logits, target, voi=None): the mean over samples of 1 - TI_n,
+    TI_n = (TP + smooth) / (TP + a FP + b FN + smooth) with the soft counts of sample n inside voi (a weighs false
+    positives, b false negatives).  logits [N,1,D,H,W] float32 on the device, target and voi of the same shape (float32,
+    uint8 or bool; non-zero is set; voi None: every voxel).  Returns a 0-dim tensor, differentiable in the logits."""
+
+    def __init__(self, a=0.5, b=0.5, smooth=1.0):
+        self.a, self.b, self.smooth = a, b, smooth
+
+    def __call__(self, logits, target, voi=None):
+        n = max(logits.shape[0], 1)
+        return HF.seg_overlap(logits, target, voi, self.a, self.b, self.smooth, 0.5, 0.0)[0] / n
+
+
+class SoftDiceLoss(TverskyLoss):
+    """SoftDiceLoss(smooth) = TverskyLoss(0.5, 0.5, smooth): the mean over samples of 1 - (2 TP + 2 smooth) /
+    (sum p + sum t + 2 smooth)."""
+
+    def __init__(self, smooth=1.0):
+        super().__init__(0.5, 0.5, smooth)
+
+
+class FocalLoss:
+    """loss = FocalLoss(alpha, gamma)(logits, target, voi=None): the mean over samples of the sample's mean inside voi of
+    -alpha_t (1 - p_t)^gamma log p_t (alpha_t = alpha where the target is set, 1 - alpha elsewhere).  gamma = 0 with
+    alpha = 0.5 is half the plain binary cross-entropy.  Tensors as TverskyLoss's.  Returns a 0-dim tensor."""
+
+    def __init__(self, alpha=0.5, gamma=2.0):
+        self.alpha, self.gamma = alpha, gamma
+
+    def __call__(self, logits, target, voi=None):
+        return HF.seg_overlap(logits, target, voi, 0.5, 0.5, 1.0, self.alpha, self.gamma)[1]

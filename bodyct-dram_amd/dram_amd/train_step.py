@@ -16,6 +16,10 @@ come from the device masks by one more kernel pair of csrc/loss.hip (`Batch.on_d
 `DeviceIntRegLoss` / `DeviceIntRegAffLoss` are the reference's two losses without the pseudo-label refinement
 (metrics.py:75-308: the same hinge plus an entropy term, one more kernel pair of csrc/loss.hip); they take the places of
 `DeviceIntRegRefineLoss` / `DeviceIntRegAffRefineLoss` unchanged.
+
+`DeviceSegOverlapLoss` is the supervised one, with no counterpart in the reference: a per-sample Tversky term and a
+per-sample focal term on the logits against voxel labels that are GIVEN (`Batch.supervised`), one more kernel pair of
+csrc/loss.hip.  It has the same call signature and decomposes over micro-batches and ranks exactly.
 """
 import math
 
@@ -90,10 +94,28 @@ class Batch:
         b._ctss_dev = ctss_dev
         return b
 
+    @classmethod
+    def supervised(cls, images, lobes, labels):
+        """A batch for supervised fine-tuning (DeviceSegOverlapLoss): the images, the lobe masks and the GIVEN voxel labels,
+        which take the place of `lesions`.  No CT severity scores and no host read: `ctss`, `targets`, `weight` and `keep`
+        are None, so `micro()` and `augmented()` work and the IntReg losses, which need them, refuse such a batch."""
+        b = object.__new__(cls)
+        b.images, b.lobes, b.lesions = images, lobes, labels
+        b.ctss = b.targets = b.weight = b.keep = b._ctss_dev = None
+        return b
+
+    def require_targets(self, who):
+        """The IntReg losses' precondition: a batch built from CT severity scores (regression band, class weight, switch)."""
+        if self.targets is None or self.weight is None or self.keep is None:
+            raise ValueError(f"{who} needs the regression targets of a batch built from CT severity scores; this batch is "
+                             f"Batch.supervised(...) and carries voxel labels only (use DeviceSegOverlapLoss)")
+
     def ctss_device(self):
         """The CT severity scores as an int32 tensor on the batch's device: uploaded at the first call, kept after that
         (micro-batches take slices of it), so that `on_device` batches derived from this one need no upload of their own."""
         dev = getattr(self, "_ctss_dev", None)
+        if dev is None and self.ctss is None:
+            raise ValueError("this batch has no CT severity scores (Batch.supervised)")
         if dev is None:
             dev = self._ctss_dev = torch.tensor([int(c) for c in self.ctss], dtype=torch.int32).to(self.images.device)
         return dev
@@ -102,7 +124,7 @@ class Batch:
         b = object.__new__(Batch)
         b.images, b.lobes, b.lesions = self.images[lo:hi], self.lobes[lo:hi], self.lesions[lo:hi]
         b.ctss = None if self.ctss is None else self.ctss[lo:hi]
-        b.targets, b.weight, b.keep = self.targets[lo:hi], self.weight[lo:hi], self.keep[lo:hi]
+        b.targets, b.weight, b.keep = (None if v is None else v[lo:hi] for v in (self.targets, self.weight, self.keep))
         dev = getattr(self, "_ctss_dev", None)
         b._ctss_dev = None if dev is None else dev[lo:hi]
         return b
@@ -151,6 +173,7 @@ class DeviceIntRegRefineLoss:
         """`refined`: the model's second output when it differs from `dense` (DC3DATGeneric).  Two fused HIP
         kernels (csrc/loss.hip); like every other op of the path there is no CPU fallback (CPU tensors raise)."""
         from . import functional as HF
+        batch.require_targets("DeviceIntRegRefineLoss")
         out = HF.intreg_refine_loss(dense, batch.lobes, batch.lesions, batch.keep, batch.targets, batch.weight,
                                     self.smoothing, refined=refined)
         return out[0], out[1]
@@ -173,7 +196,35 @@ class DeviceIntRegLoss:
     def __call__(self, dense, batch, refined=None):
         """One fused HIP kernel each way (csrc/loss.hip); no CPU fallback (CPU tensors raise)."""
         from . import functional as HF
+        batch.require_targets("DeviceIntRegLoss")
         out = HF.intreg_enc_loss(dense if refined is None else refined, batch.lobes, batch.lesions, batch.targets, batch.weight)
+        return out[0], out[1]
+
+
+class DeviceSegOverlapLoss:
+    """Supervised fine-tuning on given voxel labels: the per-sample Tversky and focal terms of include/dram_hip.h
+    (SegOverlap; functional.seg_overlap, one HIP kernel each way and a one-block finish) on the model's logits, with
+    `batch.lesions` as the target and `batch.lobes` as the volume of interest (a batch of Batch.supervised; any Batch
+    works).  `a`, `b` weigh false positives and false negatives (0.5, 0.5: soft Dice), `smooth` is added to numerator and
+    denominator, `alpha`, `gamma` are the focal term's.  Returns (tversky_sum, focal_mean):
+
+      tversky_sum = sum over the samples of 1 - TI_n        focal_mean = mean over the samples of F_n
+
+    The call signature is DeviceIntRegLoss's, so it goes into DataParallelTrainer(loss_fn=...) as it is, and `refined` is
+    used when given.  Every quantity is per sample -- no statistic of the batch enters either term -- so both terms
+    decompose over micro-batches and ranks with NO deviation: the first adds up, the second adds up under the trainer's
+    share = len(micro) / n_global weighting.  The first term is therefore a sum over the GLOBAL batch: a mean Dice loss of
+    weight w wants loss_factors[0] = w / n_global (the losses.TverskyLoss / SoftDiceLoss / FocalLoss classes return the
+    means directly, for use outside the trainer)."""
+
+    def __init__(self, a=0.5, b=0.5, smooth=1.0, alpha=0.5, gamma=2.0):
+        self.a, self.b, self.smooth, self.alpha, self.gamma = a, b, smooth, alpha, gamma
+
+    def __call__(self, dense, batch, refined=None):
+        """No CPU fallback (CPU tensors raise)."""
+        from . import functional as HF
+        out = HF.seg_overlap(dense if refined is None else refined, batch.lesions, batch.lobes, self.a, self.b, self.smooth,
+                             self.alpha, self.gamma)
         return out[0], out[1]
 
 
@@ -439,6 +490,7 @@ class DeviceIntRegAffRefineLoss:
         given T the call reads nothing back from the device: the transformed copy's regression targets come from
         `Batch.on_device`, the scores from `batch.ctss_device()` (uploaded once per batch)."""
         from . import functional as HF
+        batch.require_targets("DeviceIntRegAffRefineLoss")
         T = self.draw() if transform is None else transform
         aff_images = T({"#image": batch.images})["#image"]
         aff_lobes = T({"#reference": batch.lobes})["#reference"].contiguous()
@@ -497,6 +549,7 @@ class DeviceIntRegAffLoss:
     def __call__(self, model, batch, transform=None):
         """`transform`: as DeviceIntRegAffRefineLoss.__call__."""
         from . import functional as HF
+        batch.require_targets("DeviceIntRegAffLoss")
         T = self.draw() if transform is None else transform
         aff_images = T({"#image": batch.images})["#image"]
         aff_lobes = T({"#reference": batch.lobes})["#reference"].contiguous()

@@ -627,6 +627,48 @@ int dram_bce_smooth_fwd(const float* p, const void* t, int t_kind, int64_t n, do
 int dram_bce_smooth_bwd(const float* p, const void* t, int t_kind, int64_t n, double smooth, const float* state,
                         const float* gout, float* dp, void* stream);
 
+/* ---- SegOverlap: a per-sample Tversky (soft Dice) term and a focal term on LOGITS, for a target that is given.  No
+ *      reference counterpart: this is the supervised loss that fits the data-parallel trainer's two-term contract.
+ * z[N][S]: float32 logits, one channel, S = D*H*W.  t[N][S]: the target, voi[N][S]: the volume of interest, each float32
+ * (DRAM_SEG_MASK_F32) or uint8 (DRAM_SEG_MASK_U8) with its own kind; "set" means non-zero.  voi may be NULL: every voxel
+ * counts (voi_kind is then ignored).  Any base address, any S.
+ * Parameters: a, b >= 0 the Tversky weights of false positives and false negatives (a = b = 0.5: soft Dice); s > 0 the
+ * smoothing term; alpha in [0, 1] and gamma >= 0 the focal term (gamma = 0, alpha = 0.5: half the plain BCE).
+ * Per voxel, never forming 1 - p by subtraction:
+ *   p = sigmoid(z),   log p = -softplus(-z),   log(1 - p) = -softplus(z)
+ * Per sample n, with V_n = {v : voi[n][v] set}:
+ *   TP = sum_V p [t],   SP = sum_V p,   ST = sum_V [t],   M = |V_n|
+ *   TI_n = (TP + s) / ((1 - a - b) TP + a SP + b ST + s)
+ *   F_n  = (1 / M) sum_V -alpha_t (1 - p_t)^gamma log p_t,   t set: p_t = p, alpha_t = alpha;  t unset: p_t = 1 - p,
+ *          alpha_t = 1 - alpha;   (1 - p_t)^gamma = exp(gamma log(1 - p_t))
+ *   M = 0:  TI_n = 1 and F_n = 0 (the sample contributes nothing; no NaN)
+ * out[0] = sum_n (1 - TI_n)      a SUM over samples (the trainer's rule for a first term)
+ * out[1] = (1 / N) sum_n F_n     a MEAN over samples (its rule for every later term)
+ * Every quantity is per sample, so micro-batches and ranks add up exactly: sum_k out_k[0] = out[0] and
+ * sum_k (N_k / N) out_k[1] = out[1] for any split of the batch into parts k.
+ * Per-voxel values are fp32 (|z| up to 100 and beyond gives finite values and gradients), every sum is fp64: one block per
+ * dram_seg_loss_chunk() elements OF ONE SAMPLE writes one tuple of fp64 partials, one block adds them in a fixed order.  No
+ * atomics: the bits depend on the values alone -- not on alignment, mask kind or run.
+ * fwd: out[2] as above; state = dram_seg_overlap_state_floats(N) device floats for the backward, five per sample:
+ *   1 - TI_n, F_n, d(1 - TI_n)/d(TP + SP) (a voxel with t set), d(1 - TI_n)/d SP (t unset), 1 / (N M) (0 where M = 0);
+ *   ws = dram_seg_overlap_ws_bytes(N, S) bytes, 8-byte aligned; on return it starts with 8 doubles per sample:
+ *   TP, SP, ST, M, sum_V of the focal terms, 1 - TI_n, F_n, 0.
+ * bwd: dz = gout[0] d out[0]/dz + gout[1] d out[1]/dz in closed form,
+ *   d out[0]/dz = p (1 - p) ([t] c_set + [not t] c_unset),   c_set = -(Den - (TP + s)(1 - b)) / Den^2,  c_unset = (TP + s) a / Den^2
+ *   d out[1]/dz = -+ alpha_t (1 - p_t)^gamma (gamma p_t (-log p_t) + 1 - p_t) / (N M)      (- where t is set)
+ *   each product with gout formed last (one fp32 rounding), then one addition; exactly +0 outside V_n.  t, voi: no gradient.
+ * Negative N or S, N > 65535, S > 2^40, an unknown kind, a, b or gamma negative or not finite, s <= 0 or not finite, alpha
+ * outside [0, 1] and (for N S > 0) a null required pointer are DRAM_EINVAL, a short workspace DRAM_EWS, all before anything
+ * is launched or written; N S == 0 launches nothing and leaves out, state and dz alone.  The two size queries need no
+ * device. ---- */
+size_t dram_seg_overlap_ws_bytes(int N, int64_t S);
+int dram_seg_overlap_state_floats(int N);
+int dram_seg_overlap_fwd(const float* z, const void* t, const void* voi, int t_kind, int voi_kind, int N, int64_t S,
+                         double a, double b, double smooth, double alpha, double gamma, float* out, float* state, void* ws,
+                         size_t ws_bytes, void* stream);
+int dram_seg_overlap_bwd(const float* z, const void* t, const void* voi, int t_kind, int voi_kind, int N, int64_t S,
+                         double alpha, double gamma, const float* state, const float* gout, float* dz, void* stream);
+
 /* Rotate3DXOneShot (data_transforms.py:1186-1208): F.grid_sample(x, F.affine_grid(theta, x.size())) with the defaults
  * (trilinear, zeros padding, align_corners=False); theta12 = HOST pointer to the row-major [3][4] matrix shared by all
  * samples.  Backward = the scatter adjoint (float atomics: summation order not fixed, like ATen's). */
