@@ -38,11 +38,14 @@ _VESSELS = ("gaussian_derivative_taps", "hessian", "vesselness", "vessel_mask", 
 # the edge-aware heat-map refinement of `refine`, the same way
 _REFINE = ("guided_filter", "refine_heatmap")
 
+# the result contact sheet of `sheet`, the same way
+_SHEET = ("sheet_layout", "pick_slices", "sheet_occupancy", "result_sheet", "save_sheet")
+
 # the views of test-time augmentation at inference (`inference`), the same way
 _INFERENCE = ("tta_views",)
 
 __all__ = ["_lib", "functional", "modules", "optim", "Adam", "AdamW", "SGD", "RAdam", "AdaBound", *_AUGMENT, *_LOSSES, *_LESIONS,
-           *_DENSITY, *_DISTRIBUTION, *_CURVES, *_SURFACE, *_VESSELS, *_REFINE, *_INFERENCE]
+           *_DENSITY, *_DISTRIBUTION, *_CURVES, *_SURFACE, *_VESSELS, *_REFINE, *_SHEET, *_INFERENCE]
 
 
 def __getattr__(name):
@@ -73,6 +76,9 @@ def __getattr__(name):
     if name in _REFINE:
         from . import refine
         return getattr(refine, name)
+    if name in _SHEET:
+        from . import sheet
+        return getattr(sheet, name)
     if name in _INFERENCE:
         from . import inference
         return getattr(inference, name)

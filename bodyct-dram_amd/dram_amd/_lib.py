@@ -203,6 +203,9 @@ SIGNATURES = {
     "dram_guided_max_radius": (I, []),
     "dram_guided_ws_bytes": (Z, [I, I, I]),
     "dram_guided_filter": (I, [P, I, ctypes.c_double, ctypes.c_double, P, P, P, ctypes.c_double, I, I, I, P, P, P, Z, P]),
+    # result contact sheet: planes of the zoomed coordinate mask, the rendered sheet (layers: host array of dram_sheet_layer)
+    "dram_sheet_occupancy": (I, [P, I, I, I, I, I, I, I, P, P]),
+    "dram_sheet_render": (I, [P, I, I, I, P, P, I, P, I, I, I, I, I, I, I, I, I, I, ctypes.c_double, P, P]),
     # test-time augmentation for the per-lobe inference (views: host array of V x {perm[3], flip[3]})
     "dram_tta_expand": (I, [P, P, I, I, P, I, P]),
     "dram_tta_combine": (I, [P, P, P, I, I, P, I, P]),

@@ -292,6 +292,35 @@ class LobeInference:
                                          refined=refined))
         return res
 
+    SHEET_TITLES = {"mask": "pred_lesion", "mask_post": "pred_lesion_post", "lesion": "lesion", "htp": "pred_cam"}
+
+    @torch.no_grad()
+    def sheet(self, res, scan, lesion=None, original=False, **kw):
+        """The screenshot sheet of archive_results (job_runner.py:897-904) from a result of `run`: the windowed scan on top, then
+        one row each for res["mask"], res["mask_post"] when the run produced it, `lesion` when given, and res["htp"] through the
+        jet map; the slices are taken through the reference's coord_mask, pred > 0 | ref > 0.  `dram_amd.sheet.result_sheet` does
+        the work and `kw` goes to it (num_slices, alpha, flip_axis, zoom_size, coord_axis, colormap, style, ...; `titles`
+        defaults to the reference's).  original=True draws the original-grid volumes of res["original"] instead (a run with
+        original_size=; its resampled scan and reference are used, `scan` and `lesion` are not read).  Returns what result_sheet
+        returns: None for an empty coord_mask, else the dict with "sheet" on the device.  `run` and `res` are left as they are."""
+        from .sheet import result_sheet
+        if original:
+            if "original" not in res:
+                raise ValueError("sheet: original=True needs a run with original_spacing= and original_size=")
+            src = res["original"]
+            scan, lesion = src["scan"], src.get("lesion")
+        else:
+            src = res
+            dev = res["htp"].device
+            scan = torch.as_tensor(scan).to(device=dev, dtype=torch.int16).contiguous()
+            if lesion is not None:
+                lesion = torch.as_tensor(lesion).to(device=dev, dtype=torch.uint8).contiguous()
+        layers = {"mask": src["mask"], "mask_post": src.get("mask_post"), "lesion": lesion, "htp": src["htp"]}
+        names = [k for k in ("mask", "mask_post", "lesion", "htp") if layers[k] is not None]
+        kw.setdefault("titles", [self.SHEET_TITLES[k] for k in names])
+        coord = [src["mask"]] + ([lesion] if lesion is not None else [])
+        return result_sheet(scan, [[layers[k]] for k in names], coord, **kw)
+
     def _tta_group(self, xg, lobe, htp, spread, carr, L, D, H, W, st):
         """Test-time augmentation for one group of L chunks (csrc/infer_tta.hip): all V views in one launch, the V * L viewed
         chunks through the model in batches of tta_batch -- a batch may end inside one view and start the next --, then mean

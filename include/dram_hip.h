@@ -1083,6 +1083,97 @@ size_t dram_guided_ws_bytes(int D, int H, int W);
 int dram_guided_filter(const void* guide, int guide_kind, double lo, double hi, const float* p, const uint8_t* mask, const int* radius,
                        double eps, int D, int H, int W, float* q, double* ab, void* ws, size_t ws_bytes, void* stream);
 
+/* ---- result contact sheet (csrc/sheet.hip): the screenshot sheet of archive_results (job_runner.py:897-904), written by
+ *      draw_mask_tile_singleview_heatmap (utils.py:542-620) and, with contours, draw_mask_tile_single_view (utils.py:464-539).
+ *      Volumes are contiguous [D,H,W] on the DEVICE, n = (D, H, W), D*H*W < 2^31.  ca = coord_axis in 0..2; a < b are the two other
+ *      axes: a tile's rows run along a, its columns along b (np.take along ca).  flip_axis in 0..2, or -1 for none.  zoom_size
+ *      > 0, or 0 for none (the reference's zoom_size=None).  Everything below the drawing step is the reference's numpy / scipy
+ *      geometry and is reproduced exactly; all outputs are integers.
+ * 1. Flip (utils.py:547-552).  F[p] = V[p'] with p'[flip_axis] = n[flip_axis] - 1 - p[flip_axis]: the image, every layer and the
+ *    coordinate mask.  Plane numbers (the flags of dram_sheet_occupancy, the slice ids of dram_sheet_render) count in F.
+ * 2. Zoom (utils.py:556-577, ndimage.zoom(v, ratio, order), mode "constant", grid_mode off).  ratio = 1 along ca and zoom_size /
+ *    max(n[a], n[b]) (one fp64 division) along a and b.  Per axis the output extent is zn = round-half-even(n * ratio) (one fp64
+ *    product); a zoomed extent of 0 is refused.  Output index o reads the input coordinate c = o * step with step = (n - 1) /
+ *    (zn - 1), the quotient rounded to fp64 before the product, and c = 0 when zn == 1.  The mode is "constant": where the
+ *    rounded product exceeds n - 1 -- only the last index can, by one rounding -- that output index reads nothing and is 0 in
+ *    either order, whatever the other axis does (scipy 1.15.3 blanks the last row or column of such a zoom; so does this).
+ *      order 0 (coordinate mask, every layer): the voxel min(floor(c + 0.5), n - 1).
+ *      order 1 (image): i0 = min(floor(c), n - 1), i1 = min(i0 + 1, n - 1), t = c - i0; v = v0 * (1 - t) + v1 * t in fp64, both
+ *        products rounded on their own; separable, axis a first, then axis b on the unrounded fp64 results; the sum becomes uint8
+ *        as floor(v + 0.5).  Along ca the map is the identity (t = 0, the lerp returns v0): plane k of the result depends on
+ *        plane k of the source alone.
+ * 3. Pad (utils.py:566-569).  Each zoomed plane is centred in a zoom_size x zoom_size tile of zeros: (zoom_size - zn) / 2 (floor)
+ *    in front, the rest behind; zn <= zoom_size always, so the reference's crop never cuts.  Without a zoom a tile is the raw
+ *    plane n[a] x n[b].  The pad comes before the drawing: a heat-map row shows the colour of value 0 there.
+ * 4. Slice choice (utils.py:579-592) is the host's (dram_amd.sheet.pick_slices) from the flags of dram_sheet_occupancy: flag[k] !=
+ *    0 iff plane k of the ZOOMED coordinate mask holds a non-zero voxel -- under a nearest-neighbour down-zoom a plane's only
+ *    voxel can be skipped.
+ * 5. Layout (utils.py:595-614).  Slice j gives column j: the grey tile (the zoomed image on three channels) on top, below it one
+ *    rendered tile per row; columns left to right; the sheet is padded with zeros to sheet_width, (sheet_width - cur) / 2 (floor)
+ *    on the left (sheet_width 0: no pad).  Sheet: uint8 [(1 + n_rows) * th][max(sheet_width, num_slices * tw)][3].
+ * 6. 8-bit sources, formed on load, before the zoom (job_runner.py:897-901):
+ *      image DRAM_SHEET_INT16  windowing(scan, (wmin, wmax), (0, 255)).astype(uint8) (utils.py:189-198): clip, fp64 quotient, * 255,
+ *                              + 0, truncation (windowed_scan and scan_bin of csrc/volume_math.h); DRAM_SHEET_U8: as it is.
+ *      layer DRAM_SHEET_MASK   uint8, 255 where non-zero (the reference passes mask * 255)
+ *            DRAM_SHEET_U8     uint8, as it is
+ *            DRAM_SHEET_UNIT   float32 through windowing(h, (0, 1)): numpy stays in fp32 there -- clip to [0, 1], / 1.0f, * 255.0f
+ *                              (one fp32 product), + 0.0f, truncation.  NaN maps to 0: OUR definition, numpy's cast of NaN is
+ *                              undefined.
+ * 7. Drawing.  PARITY UNPINNED: OpenCV is not available here, so nothing of this step is checked against it; it is defined here.
+ *    With a = (float)alpha and b = (float)(1.0 - alpha) (the difference in fp64), blend(x, y) = sat(rne((float)x * a + (float)y * b)):
+ *    fp32, the two products rounded on their own, one addition, round half to even, clamped to 0..255.
+ *      DRAM_SHEET_HEATMAP (draw_2d_heatmap, utils.py:634-644: applyColorMap + addWeighted): per channel, start from the grey value
+ *        and for every layer of the row in order  value = blend(map[layer value][channel], value).  The colour map is a
+ *        256-entry table from a closed form, t = i / 255.0 in fp64, entry = rne(255.0 * c):
+ *          DRAM_SHEET_JET     c = clamp(1.5 - |4 t - k|, 0, 1), k = 3, 2, 1 for r, g, b
+ *          DRAM_SHEET_SUMMER  (r, g, b) = (t, 0.5 + 0.5 t, 0.4)
+ *        every operation in fp64, rounded on its own, in the order written (t first, then 4 t, the difference, the absolute value,
+ *        1.5 minus it, the clamp, the product with 255): on jet's ramps 255 c is a half-integer in exact arithmetic, so the
+ *        entry is what these roundings leave.
+ *        not OpenCV's tables.
+ *      DRAM_SHEET_CONTOUR (draw_2d, utils.py:623-631): painted = the grey value on three channels; every layer of the row in order
+ *        paints its colour over it: thickness -1 at every pixel of the zoomed, padded layer that is non-zero; thickness 1 at
+ *        those of them that have a 4-neighbour which is zero or lies outside the tile.  value = blend(painted, grey).  This is
+ *        OUR definition of an outline, not OpenCV's findContours / drawContours.
+ *    Other deviations: channels are stored in RGB order (the reference builds BGR for cv2.imwrite), and titles are not
+ *    rasterised (cv2.putText's Hershey font is not reproduced); the host returns every tile's rectangle instead.
+ * dram_sheet_occupancy: up to DRAM_SHEET_MAX_MASKS uint8 masks (`masks`: a HOST array of n_masks device pointers), ORed on load;
+ *   flags: n[ca] device int32, every one written (0 or 1).  Planes, rows and, along x, bytes that the order-0 zoom does not
+ *   sample are not looked at; rows that it skips are not read.  The flags are cleared and then set with plain vector stores of
+ *   the value 1, so concurrent writers agree.  W <= DRAM_SHEET_MAX_W.
+ * dram_sheet_render: the whole sheet in one launch, every byte written.  `layers`: a HOST array of the rows' layers, row after
+ *   row; row_layers[r] = the number of layers of row r (>= 1); slice_ids: num_slices plane numbers in F.  Both tables travel in
+ *   the kernel arguments.  A layer's colour and thickness are read by DRAM_SHEET_CONTOUR only.
+ * Refused before anything is launched (DRAM_EINVAL): a null required pointer, sizes not positive or D*H*W >= 2^31, W above the
+ *   cap (occupancy), an axis, kind, style, colour map or thickness not listed here, zoom_size < 0, a zoomed extent of 0, wmax
+ *   <= wmin for an int16 image, alpha outside [0, 1] or not finite, counts outside 1 .. their caps, a slice id outside
+ *   0 .. n[ca] - 1, 0 < sheet_width < num_slices * tw, a float32 layer that is not 4-byte or an int16 image that is not 2-byte
+ *   aligned.  Neither entry synchronises, allocates or reads device memory from the host. ---- */
+#define DRAM_SHEET_MAX_MASKS 4
+#define DRAM_SHEET_MAX_W 32768
+#define DRAM_SHEET_MAX_ROWS 8
+#define DRAM_SHEET_MAX_LAYERS 16
+#define DRAM_SHEET_MAX_SLICES 16
+#define DRAM_SHEET_INT16 0
+#define DRAM_SHEET_U8 1
+#define DRAM_SHEET_MASK 2
+#define DRAM_SHEET_UNIT 3
+#define DRAM_SHEET_HEATMAP 0
+#define DRAM_SHEET_CONTOUR 1
+#define DRAM_SHEET_JET 0
+#define DRAM_SHEET_SUMMER 1
+typedef struct dram_sheet_layer {
+    const void* data;          /* device, [D,H,W] */
+    int kind;                  /* DRAM_SHEET_MASK | DRAM_SHEET_U8 | DRAM_SHEET_UNIT */
+    int thickness;             /* -1 or 1 */
+    unsigned char color[4];    /* r, g, b, unused */
+} dram_sheet_layer;
+int dram_sheet_occupancy(const void* const* masks, int n_masks, int D, int H, int W, int coord_axis, int flip_axis, int zoom_size,
+                         int* flags, void* stream);
+int dram_sheet_render(const void* image, int image_kind, int wmin, int wmax, const dram_sheet_layer* layers, const int* row_layers,
+                      int n_rows, const int* slice_ids, int num_slices, int D, int H, int W, int coord_axis, int flip_axis,
+                      int zoom_size, int sheet_width, int style, int colormap, double alpha, uint8_t* sheet, void* stream);
+
 /* ---- test-time augmentation for the per-lobe inference (csrc/infer_tta.hip; no counterpart in the reference): the chunks go
  *      through the model in V orientations, the heat map is the mean of the V sigmoid maps and the spread map their standard
  *      deviation.
