@@ -26,6 +26,9 @@ _DENSITY = ("label_density", "hist_summary", "label_report")
 # the lesion distribution report of `distribution`, the same way
 _DISTRIBUTION = ("lung_depth", "label_depth", "lesion_distribution")
 
+# the lesion shape report of `shape`, the same way
+_SHAPE = ("label_shape", "crossings", "euler_number", "crofton_weights", "lesion_shape")
+
 # the heat-map evaluation curves of `curves`, the same way
 _CURVES = ("score_tables", "curves_from_tables", "heatmap_curves")
 
@@ -45,7 +48,7 @@ _SHEET = ("sheet_layout", "pick_slices", "sheet_occupancy", "result_sheet", "sav
 _INFERENCE = ("tta_views",)
 
 __all__ = ["_lib", "functional", "modules", "optim", "Adam", "AdamW", "SGD", "RAdam", "AdaBound", *_AUGMENT, *_LOSSES, *_LESIONS,
-           *_DENSITY, *_DISTRIBUTION, *_CURVES, *_SURFACE, *_VESSELS, *_REFINE, *_SHEET, *_INFERENCE]
+           *_DENSITY, *_DISTRIBUTION, *_SHAPE, *_CURVES, *_SURFACE, *_VESSELS, *_REFINE, *_SHEET, *_INFERENCE]
 
 
 def __getattr__(name):
@@ -64,6 +67,9 @@ def __getattr__(name):
     if name in _DISTRIBUTION:
         from . import distribution
         return getattr(distribution, name)
+    if name in _SHAPE:
+        from . import shape
+        return getattr(shape, name)
     if name in _CURVES:
         from . import curves
         return getattr(curves, name)

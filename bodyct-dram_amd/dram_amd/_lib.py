@@ -183,6 +183,9 @@ SIGNATURES = {
     # lesion distribution report: per-label reduction of a depth map and of the voxel positions
     "dram_label_depth_plan": (I, [I, I, I, I]),
     "dram_label_depth": (I, [P, P, I, P, I, P, P, P, P, P, P, I, I, P, P, I, I, I, I, I, I, P]),
+    # lesion shape report: per-label 2x2x2 configuration histogram and second-order moments
+    "dram_label_shape_plan": (I, [I, I]),
+    "dram_label_shape": (I, [P, I, I, P, P, I, I, I, P]),
     # heat-map evaluation curves: the joint histogram of score bin x class x region
     "dram_score_hist_plan": (I, [I, I, I]),
     "dram_score_hist": (I, [P, P, P, P, I, I, P, P, L, P]),

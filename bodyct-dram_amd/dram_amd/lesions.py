@@ -109,7 +109,7 @@ def lobe_burden(mask, lobe):
 
 def lesion_report(mask, lobe, spacing, connectivity=1, min_volume_mm3=0.0, reference=None, surface=False, tolerances_mm=(),
                   scan=None, percentiles_permille=(150, 500, 850), band_edges_hu=(-950, -750, -300), distribution=False, depth=None,
-                  shells_mm=(5.0, 10.0, 20.0), zones=(3, 2, 1), box=None, subpleural_mm=3.0):
+                  shells_mm=(5.0, 10.0, 20.0), zones=(3, 2, 1), box=None, subpleural_mm=3.0, shape=False):
     """The lesion-wise report of a [D,H,W] lesion mask (e.g. `LobeInference.run(...)["mask_post"]`, or the "original" entries
     on the scan's own grid) with its lobe map and voxel spacing (z, y, x) in mm.
 
@@ -130,7 +130,10 @@ def lesion_report(mask, lobe, spacing, connectivity=1, min_volume_mm3=0.0, refer
     and with `distribution=True`: distribution = `distribution.lesion_distribution` of the kept mask and its components (depth
     below the lung surface, peripheral share, centroids and positional zones per lobe, for both lungs and per lesion, "lesions"
     in the order of volumes_ml) at `depth`, `shells_mm`, `zones`, `box`, `percentiles_permille` and `subpleural_mm`.  Without
-    the keyword nothing of that is computed and the result has no such key."""
+    the keyword nothing of that is computed and the result has no such key;
+    and with `shape=True`: shape = `shape.lesion_shape` over the kept components (surface area, Euler number, sphericity,
+    principal axes), one row per lesion in the order of volumes_ml.  Without the keyword nothing of that is computed and the
+    result has no such key."""
     mask = _device_u8(mask)
     dev = mask.device
     if scan is not None:
@@ -183,4 +186,7 @@ def lesion_report(mask, lobe, spacing, connectivity=1, min_volume_mm3=0.0, refer
         out["distribution"] = lesion_distribution(kept_mask, lobe, spacing, labels=labels, n=n_kept, depth=depth, shells_mm=shells_mm,
                                                   zones=zones, box=box, percentiles_permille=percentiles_permille,
                                                   subpleural_mm=subpleural_mm)
+    if shape:
+        from .shape import lesion_shape
+        out["shape"] = lesion_shape(labels, n_kept, spacing)
     return out

@@ -954,6 +954,35 @@ int dram_label_depth(const float* depth, const void* labels, int label_kind, con
                      int64_t* qsum, uint32_t* dmin, uint32_t* dmax, int64_t* possum, int64_t* hist, int bins_per_mm, int nbins,
                      int64_t* zones, const int32_t* box, int nz, int ny, int nx, int D, int H, int W, void* stream);
 
+/* ---- lesion shape report at inference (csrc/shape.hip; host arithmetic in dram_amd/shape.py): per label k = 1..n of a label
+ *      volume the histogram of its 2x2x2 neighbourhood configurations and the moments of its voxel positions up to second order,
+ *      from which surface area, Euler number, sphericity and principal axes are host arithmetic -- what a consumer otherwise
+ *      does on the host with a regionprops-style pass.  labels is a contiguous [D,H,W] volume on the DEVICE, uint8 (label_kind 0,
+ *      n <= 255) or int32 (label_kind 1); a voxel with a label outside 0..n belongs to nobody.  Null pointers and refused sizes
+ *      are DRAM_EINVAL before anything is launched.  The entry does not synchronise, allocate or read device memory from the
+ *      host; both outputs are initialised by the entry.  Everything is integers, accumulated by integer atomics: no result
+ *      depends on their order (the same bits every run).
+ * dram_label_shape:
+ *   cfg (n rows of 256 int64): cells lie over the zero-padded volume, cell (z, y, x) for z in -1..D-1, y in -1..H-1, x in
+ *                -1..W-1, (D+1)(H+1)(W+1) of them; a cell covers the eight voxels (z+dz, y+dy, x+dx), dz, dy, dx in {0, 1}.  Bit
+ *                dz*4 + dy*2 + dx of the cell's configuration c for label k is set iff that voxel lies inside the volume and
+ *                carries k.  cfg[(k-1)*256 + c] counts the cells whose configuration for k is c, c in 1..255; entry 0 is always
+ *                0.  A cell whose corners carry several labels counts once in the row of each, with that label's
+ *                configuration.  Entry 255 is not counted cell by cell: it is solved from
+ *                sum_c popcount(c) * cfg[c] = 8 * count, which holds because every voxel lies in eight cells.
+ *   mom (n rows of 10 int64): {count, sum z, sum y, sum x, sum z^2, sum y^2, sum x^2, sum zy, sum zx, sum yx} over the label's
+ *                voxels, in voxel indices.  A label without voxels gets zeros in both tables.
+ *   Refused: n < 1; label_kind other than 0, 1, or 0 with n > 255; D, H or W < 1 or > 32768 (every sum then stays below 2^62);
+ *   D * H * W >= 2^31; n * 256 >= 2^31; int32 labels off their natural alignment.  16-byte loads for every piece of a row that
+ *   is 16-byte aligned and wholly inside the row; any alignment and any size work.
+ * dram_label_shape_plan: which of the entry's two kernels a call takes, a function of these two arguments alone, answered
+ *   without a GPU: 0 = the table of the call (n <= 24: n * 276 32-bit words) fits in LDS beside the staged rows, is kept per
+ *   block and flushed once; 1 = contributions are reduced within a wave over runs of equal (label, configuration) and of equal
+ *   labels and sent to global memory with integer atomics.  Negative (DRAM_EINVAL) for arguments that dram_label_shape
+ *   refuses. ---- */
+int dram_label_shape_plan(int label_kind, int n);
+int dram_label_shape(const void* labels, int label_kind, int n, int64_t* cfg, int64_t* mom, int D, int H, int W, void* stream);
+
 /* ---- heat-map evaluation curves at inference (csrc/curves.hip): the joint histogram of score bin x class x region of a
  *      probability map against a reference mask, from which ROC, precision / recall, the Dice sweep and a calibration table are
  *      exact host arithmetic (dram_amd/curves.py) -- what a consumer otherwise does with sklearn on every lung voxel.  Volumes are
