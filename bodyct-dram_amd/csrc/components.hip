@@ -13,7 +13,7 @@
 // ever lowered (atomicMin in cc_merge, the root in cc_flatten).  A `find` therefore follows strictly decreasing indices and ends
 // at a fixed point; nothing depends on the order in which the atomics land, since the root of a component is its minimum index
 // whatever the shape of the tree was.  Numbering roots in raster order is scipy.ndimage.label's numbering.
-#include "common.h"
+#include "label_stream.h"
 
 namespace dram {
 
@@ -204,7 +204,7 @@ __global__ __launch_bounds__(256) void cc_stats_kernel(const int* __restrict__ l
     const bool valid = l >= 1 && l <= n;
     const bool hit = valid && other && other[i];
     unsigned long long todo = __ballot(valid);
-    while (todo) {                                         // wave-uniform; every round clears at least the leader's bit
+    while (todo) {                                         // wave-uniform; the rounds of wave_reduce_by_key (label_stream.h)
         const int lead = __shfl(l, __ffsll((long long)todo) - 1, 64);
         const bool mine = valid && l == lead;
         const unsigned long long m = __ballot(mine), mh = __ballot(mine && hit);
@@ -251,7 +251,8 @@ __global__ __launch_bounds__(256) void cc_relabel_kernel(const int* labels, cons
 // ---- per-lobe burden: counts[v] = {voxels with lobe == v, of which mask != 0}
 // The pattern of chunk_hist_kernel (prep.hip): one LDS table per wave, then one 64-bit atomic per occupied entry and block.  A
 // lobe map is long runs of one value, so a thread keeps the pair of its current value in registers and goes to LDS only when
-// the value changes.  16-byte groups where both buffers are 16-byte aligned, the rest element by element.
+// the value changes.  16-byte groups where both buffers are 16-byte aligned, the rest element by element.  The 32-bit LDS counts
+// cannot wrap for the reason given in label_stream.h.
 struct BurdenRun {
     unsigned* table;        // this wave's [256][2]
     int value;              // -1: nothing pending
@@ -276,13 +277,10 @@ __global__ __launch_bounds__(256) void lobe_burden_kernel(const uint8_t* __restr
     __syncthreads();
     BurdenRun run{table[threadIdx.x >> 6], -1, 0, 0};
     const long long stride = (long long)gridDim.x * 256, t0 = (long long)blockIdx.x * 256 + threadIdx.x;
-    // a block covers at most cdiv(2^31, gridDim.x) voxels (2^19 at the 4096 blocks of the largest volume; 8 groups per thread
-    // below that): the 32-bit LDS counts cannot wrap
     for (long long g = t0; g < groups; g += stride) {
         const uint4 lv = reinterpret_cast<const uint4*>(lobe)[g], mv = reinterpret_cast<const uint4*>(mask)[g];
-        const unsigned lw[4] = {lv.x, lv.y, lv.z, lv.w}, mw[4] = {mv.x, mv.y, mv.z, mv.w};
 #pragma unroll
-        for (int k = 0; k < 16; ++k) run.add((lw[k >> 2] >> (8 * (k & 3))) & 0xffu, (mw[k >> 2] >> (8 * (k & 3))) & 0xffu);
+        for (int k = 0; k < 16; ++k) run.add(byte_of(lv, k), byte_of(mv, k));
     }
     for (long long e = groups * 16 + t0; e < nvox; e += stride) run.add(lobe[e], mask[e]);
     run.flush();

@@ -5,7 +5,7 @@
 //
 // dram_score_hist serves two regimes, chosen by dram_score_hist_plan from (nregions, nbins, with_conf) alone:
 //   CURVES_LDS     the table of the call -- nregions * 2 * (nbins + 1) entries of one 32-bit count and, with conf, one 64-bit sum --
-//                  fits in CURVES_LDS_WORDS of LDS (5 lobes at 1024 bins with conf are 120 KiB).  One table per block; at the end
+//                  fits in LABEL_LDS_WORDS of LDS (5 lobes at 1024 bins with conf are 120 KiB).  One table per block; at the end
 //                  one 64-bit global atomic per occupied entry.
 //   CURVES_GLOBAL  it does not fit (5 lobes at 4096 bins): the same aggregated updates go to global memory as 64-bit atomics.
 // What keeps either from serialising on the few low-score bins that hold almost every lung voxel is done before the atomic, in two
@@ -19,14 +19,13 @@
 // 16 voxels per thread with 16-byte loads where score, ref, region and gate are 16-byte aligned; one voxel per thread otherwise
 // and for the last nvox % 16 voxels.  A group of 16 whose region bytes are all zero (outside the lungs: most of a scan) costs
 // its 16 region bytes and nothing else.
-#include "common.h"
+#include "label_stream.h"
 
 namespace dram {
 
 constexpr int CURVES_LDS = 0, CURVES_GLOBAL = 1;
+static_assert(CURVES_LDS == LABEL_LDS && CURVES_GLOBAL == LABEL_WAVE, "label_regime and stream_geometry (label_stream.h) decide between them");
 constexpr int CURVES_MAX_BINS = 4096;
-constexpr int CURVES_LDS_WORDS = 32768;      // 128 of the CU's 160 KiB
-constexpr int CURVES_BIG_BYTES = 16384;      // a table above this: 1024 threads and one block per CU instead of 256 and eight
 constexpr int CURVES_PEEL = 2;               // keys per send that are looked at for a wave-wide sum
 constexpr int CURVES_GROUP = 8;              // lanes that must share a key for the sum to pay
 
@@ -61,8 +60,7 @@ __device__ __forceinline__ unsigned curves_q(float s) { return (unsigned)(fminf(
 
 extern __shared__ unsigned long long curves_lds[];
 
-// CURVES_LDS: the block's table {conf[E] (64-bit, only with conf), count[E] (32-bit)}.  A call covers fewer than 2^31 voxels, so
-// the 32-bit counts cannot wrap.
+// CURVES_LDS: the block's table {conf[E] (64-bit, only with conf), count[E] (32-bit)}.
 template <bool CONF>
 struct CurveLdsTable {
     unsigned long long* lconf;
@@ -153,12 +151,7 @@ __device__ __forceinline__ void curves_step(Table& t, CurveRun& run, bool valid,
     }
 }
 
-__device__ __forceinline__ unsigned curves_byte(const uint4& v, int k) {
-    const unsigned w = (k >> 2) == 0 ? v.x : ((k >> 2) == 1 ? v.y : ((k >> 2) == 2 ? v.z : v.w));
-    return (w >> (8 * (k & 3))) & 0xffu;
-}
-
-// Both loops run a wave-uniform number of laps (the bound is tested on the wave's first index), and every cross-lane step sits
+// The lap bounds of both loops are wave-uniform, as those of stream_labels (label_stream.h) are, and every cross-lane step sits
 // under wave-uniform conditions only.
 template <class Table, bool CONF>
 __global__ __launch_bounds__(1024) void score_hist_kernel(const CurveArgs a) {
@@ -187,11 +180,11 @@ __global__ __launch_bounds__(1024) void score_hist_kernel(const CurveArgs a) {
                               s[2].x, s[2].y, s[2].z, s[2].w, s[3].x, s[3].y, s[3].z, s[3].w};
 #pragma unroll
         for (int k = 0; k < 16; ++k) {
-            const int r = (int)curves_byte(rv, k);
+            const int r = (int)byte_of(rv, k);
             const bool valid = live && r >= 1 && r <= a.nregions;
-            const bool on = !a.gate || curves_byte(gv, k) != 0;
+            const bool on = !a.gate || byte_of(gv, k) != 0;
             const int b = curves_bin(sc[k], on, a.nbins, a.fbins);
-            const int key = ((r - 1) * 2 + (curves_byte(cv, k) != 0 ? 1 : 0)) * a.row + b;
+            const int key = ((r - 1) * 2 + (byte_of(cv, k) != 0 ? 1 : 0)) * a.row + b;
             curves_step<CONF>(table, run, valid, key, (CONF && b > 0) ? curves_q(sc[k]) : 0u);
         }
     }
@@ -224,20 +217,7 @@ static inline int64_t curves_lds_words(int nregions, int nbins, bool conf) {
     return (int64_t)nregions * 2 * (nbins + 1) * (conf ? 3 : 1);
 }
 
-static inline int curves_regime(int nregions, int nbins, bool conf) {
-    return curves_lds_words(nregions, nbins, conf) <= CURVES_LDS_WORDS ? CURVES_LDS : CURVES_GLOBAL;
-}
-
-template <class Table, bool CONF>
-static int curves_launch(const CurveArgs& a, unsigned grid, unsigned threads, size_t lds, hipStream_t st) {
-    if (lds > 65536) {
-        static LdsAttrOnce once;
-        const int rc = ensure_dynamic_lds((const void*)score_hist_kernel<Table, CONF>, lds, once, "score_hist");
-        if (rc != DRAM_OK) return rc;
-    }
-    hipLaunchKernelGGL((score_hist_kernel<Table, CONF>), dim3(grid), dim3(threads), lds, st, a);
-    return DRAM_OK;
-}
+static inline int curves_regime(int nregions, int nbins, bool conf) { return label_regime(curves_lds_words(nregions, nbins, conf)); }
 
 }  // namespace dram
 
@@ -264,23 +244,16 @@ extern "C" int dram_score_hist(const float* score, const uint8_t* ref, const uin
     const bool vec = aligned16(score) && aligned16(ref) && (!region || aligned16(region)) && (!gate || aligned16(gate));
     CurveArgs a{score, ref, region, gate, (unsigned long long*)hist, (unsigned long long*)conf, nregions, nbins, nbins + 1,
                 (float)nbins, (long long)nvox, vec ? nvox / 16 : 0};
-    const int64_t work = a.groups > 0 ? a.groups : nvox;
     const bool with_conf = conf != nullptr;
+    const StreamLaunch g = stream_geometry(curves_lds_words(nregions, nbins, with_conf), nvox, a.groups, 2048);
+    const char* who = "score_hist";
     int rc;
-    if (curves_regime(nregions, nbins, with_conf) == CURVES_LDS) {
-        const size_t lds = (size_t)curves_lds_words(nregions, nbins, with_conf) * 4;
-        const bool big = lds > (size_t)CURVES_BIG_BYTES;
-        const unsigned threads = big ? 1024 : 256;
-        const int64_t want = cdiv64(work, threads * 4), cap = big ? 256 : 2048;
-        const unsigned grid = (unsigned)(want > cap ? cap : want);
-        rc = with_conf ? curves_launch<CurveLdsTable<true>, true>(a, grid, threads, lds, st)
-                       : curves_launch<CurveLdsTable<false>, false>(a, grid, threads, lds, st);
-    } else {
-        const int64_t want = cdiv64(work, 256 * 4);
-        const unsigned grid = (unsigned)(want > 2048 ? 2048 : want);
-        rc = with_conf ? curves_launch<CurveGlobalTable<true>, true>(a, grid, 256, 0, st)
-                       : curves_launch<CurveGlobalTable<false>, false>(a, grid, 256, 0, st);
-    }
+    if (curves_regime(nregions, nbins, with_conf) == CURVES_LDS)
+        rc = with_conf ? launch_stream<score_hist_kernel<CurveLdsTable<true>, true>>(a, g, st, who)
+                       : launch_stream<score_hist_kernel<CurveLdsTable<false>, false>>(a, g, st, who);
+    else
+        rc = with_conf ? launch_stream<score_hist_kernel<CurveGlobalTable<true>, true>>(a, g, st, who)
+                       : launch_stream<score_hist_kernel<CurveGlobalTable<false>, false>>(a, g, st, who);
     if (rc != DRAM_OK) return rc;
     return check_launch("score_hist");
 }

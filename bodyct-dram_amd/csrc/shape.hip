@@ -20,9 +20,9 @@
 //               staged rows and flushed once with one 64-bit global atomic per occupied entry.
 //   SHAPE_WAVE  otherwise (component labels).  A thread merges the run of equal (label, configuration) along x and the run of
 //               its owned voxels of one label; at the end of a work item the lanes of a wave that hold the same pending
-//               (label, configuration), or the same label, are reduced together (a ballot elects the leader, as in
-//               density.hip) and the leader sends the global atomics.  A run that ends inside an item is sent directly.
-#include "common.h"
+//               (label, configuration), or the same label, are reduced together (wave_reduce_by_key, label_stream.h) and the
+//               group's first lane sends the global atomics.  A run that ends inside an item is sent directly.
+#include "label_stream.h"
 #include <type_traits>
 
 namespace dram {
@@ -101,38 +101,13 @@ struct ShapeRun {
     }
 };
 
-// Called by all 64 lanes of a wave together.  Every round serves the lanes whose pending entry carries the leader's key and
-// clears at least the leader's bit, so each loop ends after at most 64 rounds.
+// Called by all 64 lanes of a wave together: the pending configuration counts by key, then the pending moments by label.
 __device__ __forceinline__ void shape_wave_flush(const ShapeSink<unsigned long long>& sink, const ShapeRun& run, unsigned z, unsigned y) {
-    const int lane = threadIdx.x & 63;
-    unsigned long long todo = __ballot(run.key >= 0);
-    while (todo) {                                         // wave-uniform
-        const int lead = __shfl(run.key, __ffsll((long long)todo) - 1, 64);
-        const bool mine = run.key == lead;
-        const unsigned long long m = __ballot(mine);
-        unsigned c = mine ? run.kcnt : 0u;
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) c += __shfl_xor(c, o, 64);
-        if (lane == __ffsll((long long)m) - 1) sink.add_cfg(lead, c);
-        todo &= ~m;
-    }
-    unsigned long long v[SHAPE_MOM];
-    run.moments(z, y, v);
-    todo = __ballot(run.label > 0);
-    while (todo) {                                         // wave-uniform
-        const int lead = __shfl(run.label, __ffsll((long long)todo) - 1, 64);
-        const bool mine = run.label == lead;
-        const unsigned long long m = __ballot(mine);
-        unsigned long long r[SHAPE_MOM];
-#pragma unroll
-        for (int e = 0; e < SHAPE_MOM; ++e) {
-            r[e] = mine ? v[e] : 0ull;
-#pragma unroll
-            for (int o = 32; o > 0; o >>= 1) r[e] += __shfl_xor(r[e], o, 64);
-        }
-        if (lane == __ffsll((long long)m) - 1) sink.add_mom(lead, r);
-        todo &= ~m;
-    }
+    wave_reduce_by_key(run.key >= 0, run.key, WaveSums<unsigned, 1>{{run.kcnt}},
+                       [&](int key, const WaveSums<unsigned, 1>& c) { sink.add_cfg(key, c.v[0]); });
+    WaveSums<unsigned long long, SHAPE_MOM> m;
+    run.moments(z, y, m.v);
+    wave_reduce_by_key(run.label > 0, run.label, m, [&](int label, const WaveSums<unsigned long long, SHAPE_MOM>& r) { sink.add_mom(label, r.v); });
 }
 
 extern __shared__ unsigned shape_lds[];
@@ -271,7 +246,7 @@ __global__ __launch_bounds__(256) void label_shape_kernel(const ShapeArgs a) {
 }
 
 static inline bool shape_labels_ok(int label_kind, int n) {
-    return (label_kind == 0 || label_kind == 1) && n >= 1 && !(label_kind == 0 && n > 255) && (int64_t)n * 256 < (1LL << 31);
+    return label_kind_ok(label_kind, n) && (int64_t)n * 256 < (1LL << 31);
 }
 
 static inline int shape_regime(int n) { return n <= SHAPE_LDS_LABELS ? SHAPE_LDS : SHAPE_WAVE; }

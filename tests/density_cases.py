@@ -183,6 +183,19 @@ def _wave(name):
     return c
 
 
+def _wave_extremes():
+    """The two extremes of the keyed wave reduction in one block: int32 labels, n = 64 and 4096 bins (n * (7 + 4098) words: past
+    the LDS regime as it stands), 2 x 1024 + 5 voxels.  The 64 lanes of the first wave each hold another label for their 16
+    voxels (64 rounds, each a group of one lane), those of the second all hold label 7 (one round, the full butterfly), and the
+    last 5 voxels go element by element."""
+    labels = np.concatenate([1 + np.arange(1024) // 16, np.full(1024, 7), [3, 0, 64, 3, 1]]).astype(np.int32)
+    return _case(_hu(np.random.default_rng(61), labels.size), labels, 64, bins=FULL_BINS)
+
+
+# regime 1 by their own n and bins
+WAVE_ONLY = {"wave_64_groups_and_one": _wave_extremes}
+
+
 def _seam_cases():
     """For each regime the largest n or nbins it takes and the first one past it."""
     out = {}
@@ -197,7 +210,7 @@ def _seam_cases():
 
 @functools.lru_cache(maxsize=None)
 def names():
-    return tuple(BASE) + tuple(k + "/wave" for k in WAVE_OF) + tuple(_seam_cases())
+    return tuple(BASE) + tuple(k + "/wave" for k in WAVE_OF) + tuple(WAVE_ONLY) + tuple(_seam_cases())
 
 
 # what each seam case must report as its regime
@@ -208,7 +221,12 @@ NAMES_WITHOUT_LIBRARY = tuple(BASE)
 
 @functools.lru_cache(maxsize=None)
 def case(name):
-    c = _wave(name[:-5]) if name.endswith("/wave") else (BASE[name]() if name in BASE else _seam_cases()[name]())
+    if name.endswith("/wave"):
+        c = _wave(name[:-5])
+    elif name in WAVE_ONLY:
+        c = WAVE_ONLY[name]()
+    else:
+        c = BASE[name]() if name in BASE else _seam_cases()[name]()
     for key in ("scan", "labels", "mask"):
         if c[key] is not None:
             c[key].setflags(write=False)

@@ -140,6 +140,19 @@ def _zones(zones, box, shape=(5, 7, 9), seed=50):
     return _small(seed, shape, 3, np.uint8, zones=zones, box=box)
 
 
+def _wave_extremes():
+    """The two extremes of the keyed wave reduction in one block: int32 labels, n = 64 and 4096 bins (past the LDS regime as it
+    stands), 2 x 1024 + 5 voxels.  The 64 lanes of the first wave each hold another label for their 16 voxels (64 rounds, each a
+    group of one lane), those of the second all hold label 7 (one round, the full butterfly), and the last 5 voxels go element
+    by element."""
+    labels = np.concatenate([1 + np.arange(1024) // 16, np.full(1024, 7), [3, 0, 64, 3, 1]]).astype(np.int32)
+    return _case(_edt((1, 1, labels.size), 61), labels, 64, nbins=4096, zones=(1, 1, 5))
+
+
+# regime 1 by their own n and bins
+WAVE_ONLY = {"wave_64_groups_and_one": _wave_extremes}
+
+
 def _seam(label_kind, n, nbins, zones, seed, size):
     """Every label 1..n occurs where n allows it, the last one for certain."""
     rng = np.random.default_rng(seed)
@@ -217,12 +230,17 @@ NAMES_WITHOUT_LIBRARY = tuple(BASE)
 
 @functools.lru_cache(maxsize=None)
 def names():
-    return tuple(BASE) + tuple(k + "/wave" for k in WAVE_OF) + tuple(SEAM_REGIMES)
+    return tuple(BASE) + tuple(k + "/wave" for k in WAVE_OF) + tuple(WAVE_ONLY) + tuple(SEAM_REGIMES)
 
 
 @functools.lru_cache(maxsize=None)
 def case(name):
-    c = _wave(name[:-5]) if name.endswith("/wave") else (BASE[name]() if name in BASE else _seam_cases()[name]())
+    if name.endswith("/wave"):
+        c = _wave(name[:-5])
+    elif name in WAVE_ONLY:
+        c = WAVE_ONLY[name]()
+    else:
+        c = BASE[name]() if name in BASE else _seam_cases()[name]()
     for key in ("depth", "labels", "mask"):
         if c[key] is not None:
             c[key].setflags(write=False)

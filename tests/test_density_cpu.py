@@ -16,7 +16,7 @@ ROOT = os.path.abspath(os.path.join(os.path.dirname(__file__), ".."))
 ENTRY_ARGS = {"dram_label_density_plan": 3, "dram_label_density": 16, "dram_hist_summary": 12}
 
 
-@pytest.mark.parametrize("name", DC.NAMES_WITHOUT_LIBRARY)
+@pytest.mark.parametrize("name", DC.NAMES_WITHOUT_LIBRARY + tuple(DC.WAVE_ONLY))
 def test_restatement_moments_and_histogram_like_scipy(name):
     ndimage = pytest.importorskip("scipy.ndimage")
     c = DC.case(name)
@@ -209,5 +209,5 @@ def test_plan_is_a_function_of_its_arguments_and_refuses_what_the_entry_refuses(
     for name, want in DC.SEAM_REGIMES.items():
         assert DC.regime(name) == want, name
     assert {DC.regime(name) for name in DC.names()} == {0, 1}
-    assert all(DC.regime(name) == 1 for name in DC.names() if name.endswith("/wave"))
+    assert all(DC.regime(name) == 1 for name in DC.names() if name.endswith("/wave") or name in DC.WAVE_ONLY)
     assert all(DC.regime(name) == 0 for name in DC.NAMES_WITHOUT_LIBRARY)

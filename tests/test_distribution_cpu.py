@@ -64,7 +64,7 @@ def test_plan_is_monotone_refuses_what_the_entry_refuses_and_needs_no_gpu():
         assert by_bins == sorted(by_bins) and by_zones == sorted(by_zones), n
     for name, want in XC.SEAM_REGIMES.items():
         assert XC.regime(name) == want, name
-    assert all(XC.regime(name) == 1 for name in XC.names() if name.endswith("/wave"))
+    assert all(XC.regime(name) == 1 for name in XC.names() if name.endswith("/wave") or name in XC.WAVE_ONLY)
     assert all(XC.regime(name) == 0 for name in XC.NAMES_WITHOUT_LIBRARY)
 
 

@@ -58,7 +58,7 @@ def test_label_density_matches_the_restatement(name):
     assert _same(gpu_density(c), got)                                                          # no dependence on the order of the atomics
     if name in DC.SEAM_REGIMES:
         assert DC.regime(name) == DC.SEAM_REGIMES[name]
-    if name.endswith("/wave"):
+    if name.endswith("/wave") or name in DC.WAVE_ONLY:
         assert DC.regime(name) == 1
 
 

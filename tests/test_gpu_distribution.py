@@ -62,7 +62,7 @@ def test_label_depth_matches_the_restatement(name):
     _assert_tables_equal(gpu_tables(c), got)                                                   # no dependence on the order of the atomics
     if name in XC.SEAM_REGIMES:
         assert XC.regime(name) == XC.SEAM_REGIMES[name]
-    if name.endswith("/wave"):
+    if name.endswith("/wave") or name in XC.WAVE_ONLY:
         assert XC.regime(name) == 1
 
 
