@@ -35,6 +35,53 @@ def make_chunks(seed=11, with_vessel=True):
     return chunks
 
 
+# Output sizes for the other `rows` regimes of chunk_prepare_kernel (rows = min(64, cdiv(2048, Wo)) output rows per block):
+# (2,70,33): rows = 63, three blocks per sample whose spans are 2079 elements, so 16-byte output quads straddle the block seams;
+# (3,5,300): the x table takes two strides of 256 threads, rows = 7; (1,3,2048): one row per block at the largest Wo accepted
+ROW_REGIME_SIZES = [(2, 70, 33), (3, 5, 300), (1, 3, 2048)]
+MAX_WO = 2048
+
+
+def prepare_rows(out_size):
+    """(rows per block, blocks per sample) as dram_chunk_prepare chooses them."""
+    rows = min(64, -(-2048 // out_size[2]))
+    return rows, -(-out_size[0] * out_size[1] // rows)
+
+
+# dram_chunk_hist256 with N = 2 runs per = 512 blocks per sample; a block covers 256 groups of 8 elements per lap
+HIST_LAP = 512 * 256 * 8
+HIST_SHAPES = [(3, 5, 7), (9, 300, 391)]        # 105 elements: chunk 1 starts neither 8- nor 16-aligned, and is longer than a lap
+
+
+def hist_second_lap_start():
+    """Index inside chunk 1 of the first element of the second lap: laps count from the 8-aligned group that holds the chunk's
+    first element."""
+    off = int(np.prod(HIST_SHAPES[0]))
+    return (off // 8) * 8 + HIST_LAP - off
+
+
+def make_hist_chunks(seed=12):
+    """Two chunks for the histogram alone: HU uniform in [-2048, 1500], chunk 1's lobe a seeded ellipsoid (values {0, 2}) that
+    reaches into the last rows of the last slice, i.e. into the second lap."""
+    rng = np.random.default_rng(seed)
+    chunks = []
+    for shape in HIST_SHAPES:
+        scan = rng.integers(-2048, 1501, size=shape).astype(np.int16)
+        grid = np.meshgrid(*[np.arange(n, dtype=np.float64) for n in shape], indexing="ij", sparse=True)
+        centre = [(n - 1) * f + rng.uniform(-0.02, 0.02) * n for n, f in zip(shape, (0.62, 0.62, 0.5))]
+        radius = [f * n for n, f in zip(shape, (0.7, 0.5, 0.55))]
+        lobe = (sum(((g - c) / r) ** 2 for g, c, r in zip(grid, centre, radius)) < 1.0).astype(np.uint8) * np.uint8(2)
+        chunks.append({"#image": scan, "#lobe_reference": lobe, "meta": {"spacing": (1.0, 0.7, 0.7)}})
+    return chunks
+
+
+def hist_expected(chunk):
+    """The 256-bin histogram of binary_cam's 8-bit view inside the lobe."""
+    w = O.windowing(chunk["#image"], from_span=PSEUDO_WINDOW, to_span=(0, 1))[chunk["#lobe_reference"] > 0]
+    view = O.windowing(w, from_span=(0, 1), to_span=(0, 255)).astype(np.uint8)
+    return np.bincount(view, minlength=256)
+
+
 def oracle_prepare(chunk, out_size, plan):
     """One chunk the reference's way on the host.  plan(spacing, size) -> (required_spacing, new_size).  Returns the dict of
     [D,H,W] float32 arrays and the threshold."""

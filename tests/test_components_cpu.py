@@ -9,6 +9,7 @@ import numpy as np
 import pytest
 
 import component_cases as CC
+import component_large_cases as CL
 import components_restatement as CR
 
 ROOT = os.path.abspath(os.path.join(os.path.dirname(__file__), ".."))
@@ -114,6 +115,103 @@ def test_report_restatement_end_to_end_small():
     assert rep["lobes"] == {1: {"voxels": 96, "lesion_voxels": 3, "ratio": 3 / 96, "ctss": 2},
                             2: {"voxels": 96, "lesion_voxels": 8, "ratio": 8 / 96, "ctss": 3}}
     assert (rep["n_reference"], rep["n_found"], rep["sensitivity"], rep["n_false"]) == (2, 1, 0.5, 1)
+
+
+@pytest.mark.parametrize("connectivity", CL.CONNECTIVITIES)
+@pytest.mark.parametrize("name", list(CL.GENERATORS))
+def test_large_case_constructions_label_like_the_flood_fill(name, connectivity):
+    """The expectations of the whole-scan masks are built, not computed: at SMALL every generator's (labels, n) is the flood
+    fill's, at all three connectivities (lattice_gap also with a gap that lies inside SMALL)."""
+    variants = [CL.GENERATORS[name](CL.SMALL, connectivity)]
+    if name == "lattice_gap":
+        variants.append(CL.lattice_gap(CL.SMALL, connectivity, gap=(CL.TILE, 2 * CL.TILE)))
+        assert variants[1][0].sum() < variants[0][0].sum() and not variants[1][0].ravel()[CL.TILE:2 * CL.TILE].any()
+    for mask, labels, n in variants:
+        assert mask.shape == CL.SMALL and mask.dtype == np.uint8 and labels.dtype == np.int32 and mask.any()
+        ref, n_ref = CR.label(mask, connectivity)
+        assert n == n_ref and np.array_equal(labels, ref)
+    if name == "tiled_random":
+        assert n > 6 and np.bincount(labels.ravel())[1:].max() >= 8            # more than one per cell; shapes, not single voxels
+
+
+def test_large_masks_reach_the_laps_they_are_built_for():
+    """What the GPU tests rely on, asserted on the masks themselves: more than two laps of 1024 tiles, uneven and empty tile
+    counts, a whole lap of zeros between populated ones, labels far above one lap's, components that cross tiles."""
+    tiles = CL.tiles_of(CL.LARGE)
+    assert tiles == 2095 and tiles > 2 * CL.TILE and CL.LARGE[2] % 64 != 0
+    mask, labels, n = CL.large("lattice_thinned")
+    counts = CL.tile_counts(mask, CL.LARGE)                                   # every set voxel is a root
+    assert n == mask.sum() == labels.max() and n > 65536
+    assert counts.size == tiles and len(set(counts.tolist())) > 1 and (counts == 0).any()
+    assert counts[:1024].any() and counts[1024:2048].any() and counts[2048:].any()
+    assert not mask[1::2].any() and not mask[:, 1::2].any() and not mask[:, :, 1::2].any()   # no two set voxels touch
+    for c in (2, 3):
+        assert CL.large("lattice_thinned", c)[2] == n and np.array_equal(CL.large("lattice_thinned", c)[1], labels)
+    mask, labels, n = CL.large("lattice_gap")
+    counts = CL.tile_counts(mask, CL.LARGE)
+    assert counts[:1024].sum() > 0 and not counts[1024:2048].any() and counts[2048:].sum() > 0
+    assert mask.ravel()[:CL.GAP[0]].any() and mask.ravel()[CL.GAP[1]:].any() and n == counts.sum() > 1024
+    for c in CL.CONNECTIVITIES:
+        mask, labels, n = CL.large("tiled_random", c)
+        flat = labels.ravel()
+        assert n == labels.max() > 5120 and np.array_equal(np.unique(flat), np.arange(n + 1))
+        first = np.full(n + 1, flat.size, dtype=np.int64)
+        last = np.zeros(n + 1, dtype=np.int64)
+        np.minimum.at(first, flat, np.arange(flat.size))
+        np.maximum.at(last, flat, np.arange(flat.size))
+        assert np.all(np.diff(first[1:]) > 0)                                 # numbered in raster order of the first voxels
+        crossing = (first[1:] // CL.TILE) != (last[1:] // CL.TILE)            # voxels in another tile than the root's
+        other_lap = (first[1:] // (CL.TILE * CL.TILE)) != (last[1:] // (CL.TILE * CL.TILE))
+        assert crossing.sum() > n // 4 and other_lap.any()
+        roots = np.zeros(flat.size, dtype=bool)
+        roots[first[1:]] = True
+        counts = CL.tile_counts(roots, CL.LARGE)
+        assert counts[:1024].any() and counts[1024:2048].any() and counts[2048:].any() and len(set(counts.tolist())) > 2
+    assert CL.large("tiled_random", 1)[2] > CL.large("tiled_random", 2)[2] > CL.large("tiled_random", 3)[2]
+    for name in ("comb_large", "comb_large_mirrored"):
+        mask, labels, n = CL.large(name)
+        assert n == 1 and np.array_equal(labels, mask) and mask[0, 0].all() and mask[1, 1].sum() == 1
+        assert mask[:, :, 0 if name.endswith("mirrored") else -1].all()
+
+
+@pytest.mark.parametrize("name", CL.STATS_CASES)
+def test_vectorised_stats_equal_the_restatement(name):
+    mask, labels, n = CL.GENERATORS[name](CL.SMALL, 1)
+    other = CL.other_mask(CL.SMALL)
+    for oth in (None, other):
+        v, b, h = CL.stats(labels, n, oth)
+        v_ref, b_ref, h_ref = CR.stats(labels, n, oth)
+        assert v.dtype == np.int64 and b.dtype == np.int32 and np.array_equal(v, v_ref) and np.array_equal(b, b_ref)
+        assert (h is None and h_ref is None) or (h.dtype == np.int64 and np.array_equal(h, h_ref))
+    bad = labels.copy()
+    bad[0, 0, 0], bad[4, 19, 38], bad[2, 3, 4] = n + 1, -3, n             # outside 1..n twice, and the last label itself
+    for a, b in zip(CL.stats(bad, n, other), CR.stats(bad, n, other)):
+        assert np.array_equal(a, b)
+    # the large expectation: n above one block of cc_stats_init, rows that are no multiple of a wave
+    labels, n = CL.large(name)[1:]
+    v, b, h = CL.stats(labels, n, CL.other_mask(CL.LARGE))
+    assert n > 256 and v.sum() == np.count_nonzero(labels) and 0 < h.sum() < v.sum() and v.min() >= 1
+    assert np.all(b[:, 0::2] < b[:, 1::2]) and np.all(b[:, 1::2] <= np.array(CL.LARGE))
+
+
+def test_relabel_case_is_what_it_claims():
+    labels, lut, n, expected, mask = CL.relabel_case()
+    cap = CL.RELABEL_CAP
+    assert labels.size == CL.RELABEL_NVOX == cap + 300 and lut.size == n + 1 == 1001
+    outside = np.flatnonzero((labels < 0) | (labels > n))
+    assert outside.tolist() == sorted(CL.RELABEL_BAD)
+    below, above = labels[outside] < 0, labels[outside] > n
+    for lo, hi in ((0, 256), (cap - 256, cap), (cap, cap + 256), (CL.RELABEL_NVOX - 300, CL.RELABEL_NVOX)):
+        here = (outside >= lo) & (outside < hi)
+        assert (here & below).any() and (here & above).any(), (lo, hi)      # both kinds in every region
+    assert not expected[outside].any() and not mask[outside].any()
+    rng = np.random.default_rng(1)
+    for i in np.concatenate([rng.integers(0, labels.size, 2000), np.arange(cap - 50, cap + 50), outside]):
+        want = int(lut[labels[i]]) if 0 <= labels[i] <= n else 0
+        assert expected[i] == want and mask[i] == (want != 0)
+    assert (labels == n).sum() >= 2 and lut[n] != 0 and (expected[cap:] == lut[n]).any()
+    assert 0 < (lut == 0).sum() < n and (lut < 0).any() and (lut > n).any()
+    assert 0 < mask[cap:].sum() < 300 and 0 < mask[:cap].mean() < 1       # the second lap's outputs are not all one value
 
 
 def _header_functions():

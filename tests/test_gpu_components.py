@@ -7,6 +7,7 @@ import pytest
 import torch
 
 import component_cases as CC
+import component_large_cases as CL
 import components_restatement as CR
 
 pytestmark = pytest.mark.gpu
@@ -125,6 +126,62 @@ def test_cc_relabel_lut_aliasing_and_single_outputs():
     out3 = torch.full(labels.shape, -7, dtype=torch.int32, device="cuda")
     call("dram_cc_relabel", _dev(bad).data_ptr(), lut_d.data_ptr(), n, out3.data_ptr(), None, nvox, _st())
     assert np.array_equal(out3.cpu().numpy(), expect)
+
+
+@pytest.mark.parametrize("name,connectivity", CL.LABEL_CASES)
+def test_cc_label_past_one_scan_lap(name, connectivity):
+    """2095 tiles: cc_scan_kernel walks laps of 1024, 1024 and 47 tile counts with its carry, cc_rank / cc_final see block
+    offsets and rank codes from every lap (tests/component_large_cases.py; expectations by construction)."""
+    mask, ref, n_ref = CL.large(name, connectivity)
+    labels, n = gpu_label(mask, connectivity)
+    assert n == n_ref
+    assert np.array_equal(labels, ref)
+
+
+@pytest.mark.parametrize("with_other", [False, True])
+@pytest.mark.parametrize("name", CL.STATS_CASES)
+def test_cc_stats_with_many_components_and_rows_off_the_wave(name, with_other):
+    """n far above 256 (cc_stats_init_kernel in many blocks), W = 260 (groups of a wave span rows)."""
+    _, labels, n = CL.large(name, 1)
+    other = CL.other_mask(CL.LARGE) if with_other else None
+    voxels, bbox, hits = gpu_stats(labels, n, other)
+    v_ref, b_ref, h_ref = CL.stats(labels, n, other)
+    assert np.array_equal(voxels, v_ref) and np.array_equal(bbox, b_ref)
+    assert (hits is None and h_ref is None) or np.array_equal(hits, h_ref)
+
+
+def test_cc_relabel_past_the_grid_cap():
+    """16384 x 256 + 300 elements: the second lap of the grid-stride loop, labels outside 0..n in the first block, on both
+    sides of the lap seam and in the ragged tail.  Separate outputs, one output at a time, in place; a guard band after
+    every output."""
+    from dram_amd._lib import call
+    labels, lut, n, ref_labels, ref_mask = CL.relabel_case()
+    nvox, guard = labels.size, 64
+    lut_d = _dev(lut)
+
+    def buffers():
+        lab = torch.full((nvox + guard,), -7, dtype=torch.int32, device="cuda")
+        lab[:nvox] = _dev(labels)
+        return (lab, torch.full((nvox + guard,), -7, dtype=torch.int32, device="cuda"),
+                torch.full((nvox + guard,), 9, dtype=torch.uint8, device="cuda"))
+
+    def check(out, msk):
+        if out is not None:
+            assert np.array_equal(out[:nvox].cpu().numpy(), ref_labels) and bool((out[nvox:] == -7).all())
+        if msk is not None:
+            assert np.array_equal(msk[:nvox].cpu().numpy(), ref_mask) and bool((msk[nvox:] == 9).all())
+
+    lab, out, msk = buffers()
+    call("dram_cc_relabel", lab.data_ptr(), lut_d.data_ptr(), n, out.data_ptr(), msk.data_ptr(), nvox, _st())
+    check(out, msk)
+    assert np.array_equal(lab[:nvox].cpu().numpy(), labels)                      # the input is left alone
+    _, out, msk = buffers()
+    call("dram_cc_relabel", lab.data_ptr(), lut_d.data_ptr(), n, out.data_ptr(), None, nvox, _st())
+    call("dram_cc_relabel", lab.data_ptr(), lut_d.data_ptr(), n, None, msk.data_ptr(), nvox, _st())
+    check(out, msk)
+    _, _, msk = buffers()
+    call("dram_cc_relabel", lab.data_ptr(), lut_d.data_ptr(), n, lab.data_ptr(), msk.data_ptr(), nvox, _st())   # in place
+    check(lab, msk)
 
 
 def test_remove_small_renumbers_in_the_old_order():

@@ -128,6 +128,93 @@ def test_chunk_hist256_per_sample():
         assert got[i].sum() == int((lobe > 0).sum())
 
 
+def test_chunk_hist256_past_one_lap():
+    """N = 2, so 512 blocks per sample; chunk 1 starts at element 105 and holds 1,055,700: the stride loop of
+    chunk_hist_kernel takes a second, partly filled step, and the lobe has voxels in both (asserted on the host)."""
+    chunks = PC.make_hist_chunks()
+    start = PC.hist_second_lap_start()
+    lobe1 = chunks[1]["#lobe_reference"].ravel()
+    assert lobe1[:start].any() and lobe1[start:].any()
+    packed = ChunkLoader(PC.OUT_SIZES[0], PC.WINDOW).pack(chunks)
+    assert packed.offsets == [0, 105]
+    st = torch.cuda.current_stream().cuda_stream
+    hist = torch.full((2, 256), -1, dtype=torch.int64, device="cuda")
+    _lib.call("dram_chunk_hist256", packed.d_scans.data_ptr(), packed.d_lobes.data_ptr(), packed.d_table.data_ptr(), 2,
+              hist.data_ptr(), *PC.PSEUDO_WINDOW, st)
+    got = hist.cpu().numpy()
+    for i, c in enumerate(chunks):
+        assert np.array_equal(got[i], PC.hist_expected(c)), i
+        assert got[i].sum() == int((c["#lobe_reference"] > 0).sum())
+    one = torch.full((256,), -1, dtype=torch.int64, device="cuda")
+    scan_d, lobe_d = torch.as_tensor(chunks[1]["#image"]).cuda(), torch.as_tensor(chunks[1]["#lobe_reference"]).cuda()
+    _lib.call("dram_scan_hist256", scan_d.data_ptr(), lobe_d.data_ptr(), one.data_ptr(), *PC.PSEUDO_WINDOW, scan_d.numel(), st)
+    assert np.array_equal(got[1], one.cpu().numpy())
+
+
+@pytest.mark.parametrize("with_vessel", [True, False])
+@pytest.mark.parametrize("out_size", PC.ROW_REGIME_SIZES)
+def test_ragged_batch_is_bit_exact_in_every_rows_regime(out_size, with_vessel):
+    """rows = 63 with output quads shared by two blocks, an x table of two strides with rows = 7, one row per block at
+    Wo = 2048 (tests/preprocess_cases.py: ROW_REGIME_SIZES)."""
+    chunks = _chunks() if with_vessel else [{k: v for k, v in c.items() if k != "#vessel_reference"} for c in _chunks()]
+    got = _device(out_size, chunks)
+    ref = _oracle(out_size)
+    assert ("#vessel_reference" in got) == with_vessel
+    for i, (r, th) in enumerate(ref):
+        assert got["threshold"][i] == th, (i, got["threshold"][i], th)
+        for k in KEYS[:3 + with_vessel]:
+            g = got[k][i, 0]
+            assert g.shape == tuple(out_size) and g.dtype == np.float32
+            assert np.array_equal(g, r[k]), (i, k, int((g != r[k]).sum()), float(np.abs(g - r[k]).max()))
+    assert 0 < got["#pseudo_lesion_reference"].mean() < 1 and (got["#image"] != 0).any()
+
+
+def _prepare_raw(packed, th, out_size, outs, vessel=True):
+    """dram_chunk_prepare itself on four output pointers (image, lobe, lesion, vessel); returns the status."""
+    Do, Ho, Wo = out_size
+    return _lib.lib.dram_chunk_prepare(packed.d_scans.data_ptr(), packed.d_lobes.data_ptr(), packed.d_vessels.data_ptr() if vessel else None,
+                                       packed.d_table.data_ptr(), th.data_ptr(), len(packed), Do, Ho, Wo, float(PC.WINDOW[0]),
+                                       float(PC.WINDOW[1]), *PC.PSEUDO_WINDOW, outs[0], outs[1], outs[2], outs[3] if vessel else None,
+                                       torch.cuda.current_stream().cuda_stream)
+
+
+def test_an_output_row_above_the_cap_is_refused_and_nothing_is_written():
+    out_size = (1, 2, PC.MAX_WO + 1)
+    loader = ChunkLoader(PC.OUT_SIZES[0], PC.WINDOW)
+    packed = loader.pack(_chunks())
+    th = torch.full((len(packed),), 0.5, dtype=torch.float64, device="cuda")
+    out = torch.full((4, len(packed)) + out_size, -7.0, device="cuda")
+    assert _prepare_raw(packed, th, out_size, [o.data_ptr() for o in out]) != 0
+    assert b"Wo up to 2048" in _lib.lib.dram_last_error()
+    torch.cuda.synchronize()
+    assert bool((out == -7).all())
+    at_cap = (1, 2, PC.MAX_WO)                                                       # one less is accepted and fills every output
+    assert _prepare_raw(packed, th, at_cap, [o.data_ptr() for o in out]) == 0
+    torch.cuda.synchronize()
+    filled = out.view(4, -1)[:, :len(packed) * 2 * PC.MAX_WO]
+    assert bool((filled != -7).all()) and bool((out.view(4, -1)[:, len(packed) * 2 * PC.MAX_WO:] == -7).all())
+
+
+def test_outputs_one_float_off_16_bytes_give_the_same_bits():
+    """Every output pointer 4 bytes past a 16-byte boundary: each quad takes the element-wise stores.  Same bits as the aligned
+    run, guard words on both sides of every output untouched."""
+    out_size = PC.ROW_REGIME_SIZES[0]
+    loader = ChunkLoader(out_size, PC.WINDOW, PC.PSEUDO_WINDOW, PC.PSEUDO_SCALER)
+    packed = loader.pack(_chunks())
+    aligned = loader(packed)
+    n = aligned["#image"].numel()
+    front, back = 5, 27                                                              # 20 bytes: one float past 16-byte alignment
+    bufs = [torch.full((front + n + back,), -7.0, device="cuda") for _ in range(4)]
+    ptrs = [b.data_ptr() + 4 * front for b in bufs]
+    assert all(b.data_ptr() % 16 == 0 for b in bufs) and all(p % 16 == 4 for p in ptrs)
+    assert _prepare_raw(packed, aligned["threshold"], out_size, ptrs) == 0
+    torch.cuda.synchronize()
+    for k, b in zip(KEYS, bufs):
+        assert torch.equal(b[front:front + n].view(torch.int32), aligned[k].reshape(-1).view(torch.int32)), k
+        assert bool((b[:front] == -7).all()) and bool((b[front + n:] == -7).all()), k
+    assert bool((aligned["#image"] != 0).any()) and bool((aligned["#vessel_reference"] != 0).any())
+
+
 def test_outputs_do_not_depend_on_the_packing_order():
     fwd = _device(PC.OUT_SIZES[1], _chunks())
     rev = _device(PC.OUT_SIZES[1], _chunks()[::-1])

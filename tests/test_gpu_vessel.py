@@ -134,6 +134,18 @@ def test_norm_max_is_exact():
     assert gpu_norm_max(np.zeros_like(h6), None) == np.float32(1.0)
 
 
+@pytest.mark.parametrize("variant", ["no_lobe", "lobe_holds_the_maximum", "lobe_leaves_it_out"])
+def test_norm_max_past_the_grid_cap(variant):
+    """4096 x 256 + 300 voxels: the grid-stride loop takes a second, ragged lap.  The largest norm lies in that lap; a lobe map
+    that leaves it out makes the answer the first lap's largest (tests/vessel_cases.py: norm_max_large)."""
+    h6, lobes = VC.norm_max_large()
+    lobe = lobes[variant]
+    norms = VR.frobenius32(h6)
+    at = VC.NORM_MAX_FIRST_LAP if variant == "lobe_leaves_it_out" else VC.NORM_MAX_SECOND_LAP
+    c = gpu_norm_max(h6, lobe)
+    assert c == VR.frangi_c(h6, lobe) == np.float32(0.5) * norms[at]
+
+
 @functools.lru_cache(maxsize=None)
 def _e2e_device():
     from dram_amd.vessels import vesselness

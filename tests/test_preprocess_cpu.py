@@ -9,7 +9,7 @@ import pytest
 import torch
 
 import preprocess_cases as PC
-from dram_amd.preprocess import TABLE_DTYPE, ChunkLoader, resample_plan
+from dram_amd.preprocess import MAX_WO, TABLE_DTYPE, ChunkLoader, resample_plan
 
 
 def test_resample_plan_matches_the_reference_for_every_mode(golden_dir):
@@ -87,6 +87,47 @@ def test_last_bit_steps_exist_for_both_output_sizes():
             req, _ = resample_plan("fixed_size", None, out, np.asarray(spacing), shape)
             n += sum(float(req[a]) / float(spacing[a]) != shape[a] / out[a] for a in range(3))
         assert n >= 1, out
+
+
+def test_row_regime_sizes_are_the_regimes_they_name():
+    """rows below 64, spans that are no multiple of 4, an x table longer than one stride, one row per block at the cap; and the
+    oracle prepares all six chunks at each size quickly (it is vectorised)."""
+    assert [PC.prepare_rows(s) for s in PC.OUT_SIZES] == [(64, 2), (64, 1)]              # what the suite had before
+    assert [PC.prepare_rows(s) for s in PC.ROW_REGIME_SIZES] == [(63, 3), (7, 3), (1, 3)]
+    rows, blocks = PC.prepare_rows(PC.ROW_REGIME_SIZES[0])
+    assert rows * PC.ROW_REGIME_SIZES[0][2] == 2079 and 2079 % 4 and blocks * rows > 2 * 70 > (blocks - 1) * rows
+    assert PC.ROW_REGIME_SIZES[1][2] > 256 and PC.ROW_REGIME_SIZES[2][2] == PC.MAX_WO == MAX_WO
+    chunks = PC.make_chunks()
+    for out in PC.ROW_REGIME_SIZES:
+        plan = lambda spacing, size: resample_plan("fixed_size", None, out, spacing, size)
+        set_voxels = dict.fromkeys(("#image", "#lobe_reference", "#pseudo_lesion_reference", "#vessel_reference"), 0)
+        for c in chunks:
+            ref, th = PC.oracle_prepare(c, out, plan)
+            assert set(ref) == set(set_voxels) and 0 < th < 1
+            assert all(v.shape == out and v.dtype == np.float32 for v in ref.values())
+            for k, v in ref.items():
+                set_voxels[k] += np.count_nonzero(v)
+        print(out, set_voxels)
+        assert all(n > 100 for n in set_voxels.values()), (out, set_voxels)     # no output of the batch is all background
+
+
+def test_hist_chunks_fill_a_second_lap():
+    chunks = PC.make_hist_chunks()
+    assert [c["#image"].shape for c in chunks] == PC.HIST_SHAPES
+    off, size = chunks[0]["#image"].size, chunks[1]["#image"].size
+    assert off == 105 and off % 8 and off % 16 and PC.HIST_LAP == 512 * 256 * 8
+    start = PC.hist_second_lap_start()
+    assert 0 < start < size < start + PC.HIST_LAP and (off + start) % 8 == 0 and (off + start) // 8 - off // 8 == 512 * 256
+    lobe = chunks[1]["#lobe_reference"].ravel()
+    assert lobe[:start].any() and lobe[start:].any() and not lobe.all() and chunks[0]["#lobe_reference"].any()
+    for c in chunks:
+        h = PC.hist_expected(c)
+        assert h.shape == (256,) and h.sum() == np.count_nonzero(c["#lobe_reference"])
+    first, second = (dict(chunks[1], **{"#image": chunks[1]["#image"].ravel()[sl], "#lobe_reference": lobe[sl]})
+                     for sl in (slice(0, start), slice(start, None)))
+    whole = PC.hist_expected(chunks[1])
+    assert np.array_equal(PC.hist_expected(first) + PC.hist_expected(second), whole)
+    assert PC.hist_expected(second).sum() > 100 and (PC.hist_expected(first) != whole).any()   # one lap alone is another answer
 
 
 def test_argument_errors():

@@ -157,6 +157,29 @@ def test_hessian_cases_cover_the_tiles():
         assert v.min() < -1150 and v.max() > 350, name          # values outside the clip window are present
 
 
+def test_norm_max_case_puts_its_maxima_where_it_says():
+    """The planted Hessian is the largest norm and lies past 4096 x 256 voxels; once the lobe leaves it out the largest is the
+    one planted in the first lap; both laps hold lobe voxels; the three expectations differ where they must."""
+    h6, lobes = VC.norm_max_large()
+    S, cap = h6.shape[1], VC.NORM_MAX_CAP
+    assert S == VC.NORM_MAX_S == cap + 300 and h6.dtype == np.float32
+    norms = VR.frobenius32(h6)
+    assert norms.argmax() == VC.NORM_MAX_SECOND_LAP >= cap
+    assert norms[:cap].argmax() == VC.NORM_MAX_FIRST_LAP and norms[VC.NORM_MAX_FIRST_LAP] > 2 * np.delete(norms, [
+        VC.NORM_MAX_FIRST_LAP, VC.NORM_MAX_SECOND_LAP]).max()
+    assert norms[VC.NORM_MAX_SECOND_LAP] > 2 * norms[VC.NORM_MAX_FIRST_LAP]
+    assert list(lobes) == ["no_lobe", "lobe_holds_the_maximum", "lobe_leaves_it_out"] and lobes["no_lobe"] is None
+    holds, leaves = lobes["lobe_holds_the_maximum"], lobes["lobe_leaves_it_out"]
+    assert holds[VC.NORM_MAX_SECOND_LAP] and not leaves[VC.NORM_MAX_SECOND_LAP] and leaves[VC.NORM_MAX_FIRST_LAP]
+    for lobe in (holds, leaves):
+        assert lobe.dtype == np.uint8 and 0 < (lobe[:cap] > 0).mean() < 1 and 0 < (lobe[cap:] > 0).sum() < 300 and lobe.max() > 1
+    half = np.float32(0.5)
+    assert VR.frangi_c(h6) == VR.frangi_c(h6, holds) == half * norms[VC.NORM_MAX_SECOND_LAP]
+    assert VR.frangi_c(h6, leaves) == half * norms[VC.NORM_MAX_FIRST_LAP] == half * norms[leaves > 0].max()
+    # the norm is the fp64 expression rounded once (exact integers here)
+    assert norms[VC.NORM_MAX_SECOND_LAP] == np.float32(np.sqrt(100.0 ** 2 + 200.0 ** 2 + 150.0 ** 2 + 2 * (50.0 ** 2 + 75.0 ** 2 + 25.0 ** 2)))
+
+
 def test_argument_errors_are_reported_without_a_gpu():
     from dram_amd import _lib
     q, S = 16, 5 * 7 * 9

@@ -114,6 +114,30 @@ def vesselness_h6():
     return h
 
 
+NORM_MAX_CAP = 4096 * 256                # voxels of one lap of hessian_norm_max_kernel at its grid cap
+NORM_MAX_S = NORM_MAX_CAP + 300
+NORM_MAX_FIRST_LAP, NORM_MAX_SECOND_LAP = 777_777, NORM_MAX_CAP + 123
+
+
+@functools.lru_cache(maxsize=None)
+def norm_max_large():
+    """(h6 [6, NORM_MAX_S] float32, {variant: lobe or None}): seeded Hessians of modest size, the largest norm of all planted in
+    the second lap of the grid-stride loop and the second largest in the first.  Variants: no lobe map; a lobe map that holds
+    the planted voxel of the second lap; one that leaves it out (and everything near it), so that the maximum is the first
+    lap's."""
+    rng = np.random.default_rng(8)
+    h = rng.normal(size=(6, NORM_MAX_S)).astype(np.float32) * np.float32(3.0)
+    h[:, NORM_MAX_SECOND_LAP] = np.array([100, -200, 150, 50, -75, 25], dtype=np.float32)
+    h[:, NORM_MAX_FIRST_LAP] = np.array([-60, 90, 30, -45, 20, 10], dtype=np.float32)
+    inside = (rng.random(NORM_MAX_S) < 0.5).astype(np.uint8) * rng.integers(1, 6, size=NORM_MAX_S).astype(np.uint8)
+    inside[[NORM_MAX_FIRST_LAP, NORM_MAX_SECOND_LAP]] = 2
+    outside = inside.copy()
+    outside[NORM_MAX_SECOND_LAP - 40:NORM_MAX_SECOND_LAP + 40] = 0
+    for a in (h, inside, outside):
+        a.setflags(write=False)
+    return h, {"no_lobe": None, "lobe_holds_the_maximum": inside, "lobe_leaves_it_out": outside}
+
+
 def _jacobi_rotate(app, aqq, apq, arp, arq):
     """csrc/vessel_device.h: jacobi_rotate, operation for operation, on arrays."""
     with np.errstate(all="ignore"):
