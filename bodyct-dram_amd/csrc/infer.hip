@@ -82,7 +82,8 @@ __global__ __launch_bounds__(256) void label_bboxes_kernel(const uint8_t* __rest
     }
 }
 
-// out[l][R][R][R]: windowed, lobe-masked crop resampled to R^3
+// out[l][R][R][R]: windowed, lobe-masked crop resampled to R^3.  The 8-term combination is Trilinear::combine's (lobe_chunk.h),
+// written out: through the shared form hipcc fuses other products of it, and the result differs in the last bit.
 __global__ __launch_bounds__(256) void lobe_chunks_kernel(const int16_t* __restrict__ scan,
                                                           const uint8_t* __restrict__ lobe, float* __restrict__ out,
                                                           ChunkList cl, int H, int W, int R, float wmin, float wmax) {
@@ -115,25 +116,11 @@ __global__ __launch_bounds__(256) void lobe_chunks_kernel(const int16_t* __restr
 __global__ __launch_bounds__(256) void lobe_paste_kernel(const float* __restrict__ dense,
                                                          const uint8_t* __restrict__ lobe, float* __restrict__ htp,
                                                          ChunkList cl, int H, int W, int R) {
-    const int l = blockIdx.y;
-    const Chunk c = cl.c[l];
-    const int e = blockIdx.x * 256 + threadIdx.x;
-    if (e >= c.dz * c.dy * c.dx) return;
-    const int x = e % c.dx, y = (e / c.dx) % c.dy, z = e / (c.dx * c.dy);
-    const size_t o = ((size_t)(c.z0 + z) * H + (c.y0 + y)) * W + (c.x0 + x);
-    if (lobe[o] != c.label) return;
-    int z0, z1, y0, y1, x0, x1;
-    float a0, a1, b0, b1, c0, c1;
-    ac_index(R, c.dz, z, z0, z1, a0, a1);
-    ac_index(R, c.dy, y, y0, y1, b0, b1);
-    ac_index(R, c.dx, x, x0, x1, c0, c1);
-    const float* p = dense + (size_t)l * R * R * R;
-    auto at = [&](int zz, int yy, int xx) -> float {
-        const float d = p[((size_t)zz * R + yy) * R + xx];
-        return 1.f / (1.f + expf(-d));                            // F.sigmoid before the resize, job_runner.py:765
-    };
-    htp[o] = a0 * (b0 * (c0 * at(z0, y0, x0) + c1 * at(z0, y0, x1)) + b1 * (c0 * at(z0, y1, x0) + c1 * at(z0, y1, x1))) +
-             a1 * (b0 * (c0 * at(z1, y0, x0) + c1 * at(z1, y0, x1)) + b1 * (c0 * at(z1, y1, x0) + c1 * at(z1, y1, x1)));
+    const CropVoxel v = crop_voxel(cl, lobe, H, W);
+    if (!v.mine) return;
+    const Trilinear t(R, v.c, v.z, v.y, v.x);
+    const ChunkField d{dense + (size_t)v.l * R * R * R, R};
+    htp[v.o] = t.combine([&](int z, int y, int x) { return paste_sigmoid(d(z, y, x)); });
 }
 
 // hist[b] = #{v : lobe[v] > 0, uint8(clip(htp[v],0,1)*255) == b}; also sum of htp inside the lungs (fp64) and the count
@@ -142,22 +129,15 @@ __global__ __launch_bounds__(256) void lung_hist_kernel(const float* __restrict_
                                                         size_t n) {
     __shared__ unsigned lh[256];
     __shared__ double lsum[4];
-    lh[threadIdx.x] = 0;
-    __syncthreads();
     double s = 0.0;
-    const size_t stride = (size_t)gridDim.x * 256;
-    for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < n; i += stride) {
-        if (lobe[i] > 0) {
-            const float v = htp[i];
-            const float w = fminf(fmaxf(v, 0.f), 1.f) * 255.f;
-            atomicAdd(&lh[(int)w], 1u);
-            s += (double)v;
-        }
-    }
+    hist256_count(lh, n, [&](size_t i) { return lobe[i] > 0; }, [&](size_t i) {
+        const float v = htp[i];
+        s += (double)v;
+        return (int)(fminf(fmaxf(v, 0.f), 1.f) * 255.f);
+    });
     s = wave_sum_d(s);
     if ((threadIdx.x & 63) == 0) lsum[threadIdx.x >> 6] = s;
-    __syncthreads();
-    if (lh[threadIdx.x]) atomicAdd(&hist[threadIdx.x], (unsigned long long)lh[threadIdx.x]);
+    hist256_flush(lh, hist);
     if (threadIdx.x == 0) atomicAdd(sum, lsum[0] + lsum[1] + lsum[2] + lsum[3]);
 }
 
@@ -172,16 +152,9 @@ __global__ void threshold_kernel(const float* __restrict__ htp, uint8_t* __restr
 __global__ __launch_bounds__(256) void scan_hist_kernel(const int16_t* __restrict__ scan, const uint8_t* __restrict__ lobe,
                                                         unsigned long long* __restrict__ hist, int wmin, int wmax, size_t n) {
     __shared__ unsigned lh[256];
-    lh[threadIdx.x] = 0;
-    __syncthreads();
-    const size_t stride = (size_t)gridDim.x * 256;
-    for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < n; i += stride) {
-        if (lobe[i] > 0) {
-            atomicAdd(&lh[scan_bin(windowed_scan((int)scan[i], wmin, wmax))], 1u);
-        }
-    }
-    __syncthreads();
-    if (lh[threadIdx.x]) atomicAdd(&hist[threadIdx.x], (unsigned long long)lh[threadIdx.x]);
+    hist256_count(lh, n, [&](size_t i) { return lobe[i] > 0; },
+                  [&](size_t i) { return scan_bin(windowed_scan((int)scan[i], wmin, wmax)); });
+    hist256_flush(lh, hist);
 }
 
 // lesion_pred = htp > th (job_runner.py:1004);  lesion_pred_post = lesion_pred & (w_scan > th_scan) & ~(vessel > 0) (1008-1010)
@@ -287,12 +260,10 @@ extern "C" int dram_lobe_paste(const float* dense, const uint8_t* lobe, float* h
     DRAM_REQUIRE(dense && lobe && htp, "lobe_paste: null pointer");
     DRAM_REQUIRE(R > 0, "lobe_paste: bad resample size");
     ChunkList cl;
-    int rc = fill_chunks("lobe_paste", cl, chunks, L, D, H, W);
+    dim3 grid;
+    const int rc = crop_grid("lobe_paste", cl, grid, chunks, L, D, H, W);
     if (rc) return rc;
-    const int64_t mx = max_chunk_voxels(cl, L);
-    DRAM_REQUIRE(mx < 0x7fffffffLL, "lobe_paste: chunk too large");
-    hipLaunchKernelGGL(lobe_paste_kernel, dim3((unsigned)cdiv64(mx, 256), L), dim3(256), 0, (hipStream_t)stream, dense,
-                       lobe, htp, cl, H, W, R);
+    hipLaunchKernelGGL(lobe_paste_kernel, grid, dim3(256), 0, (hipStream_t)stream, dense, lobe, htp, cl, H, W, R);
     return check_launch("lobe_paste");
 }
 
@@ -303,15 +274,13 @@ extern "C" int dram_lung_hist256(const float* htp, const uint8_t* lobe, unsigned
     hipStream_t st = (hipStream_t)stream;
     (void)hipMemsetAsync(hist, 0, 256 * sizeof(unsigned long long), st);
     (void)hipMemsetAsync(sum, 0, sizeof(double), st);
-    const unsigned grid = (unsigned)(cdiv64(n, 256 * 16) < 2048 ? cdiv64(n, 256 * 16) : 2048);
-    hipLaunchKernelGGL(lung_hist_kernel, dim3(grid ? grid : 1), dim3(256), 0, st, htp, lobe, hist, sum, (size_t)n);
+    hipLaunchKernelGGL(lung_hist_kernel, dim3(stream_grid(n, 16, 2048)), dim3(256), 0, st, htp, lobe, hist, sum, (size_t)n);
     return check_launch("lung_hist256");
 }
 
 extern "C" int dram_threshold_mask(const float* htp, uint8_t* mask, float th, int64_t n, void* stream) {
     DRAM_REQUIRE(htp && mask && n > 0, "threshold_mask: bad arguments");
-    const unsigned grid = (unsigned)(cdiv64(n, 256) < 4096 ? cdiv64(n, 256) : 4096);
-    hipLaunchKernelGGL(threshold_kernel, dim3(grid), dim3(256), 0, (hipStream_t)stream, htp, mask, th, (size_t)n);
+    hipLaunchKernelGGL(threshold_kernel, dim3(stream_grid(n, 1, 4096)), dim3(256), 0, (hipStream_t)stream, htp, mask, th, (size_t)n);
     return check_launch("threshold_mask");
 }
 
@@ -321,8 +290,7 @@ extern "C" int dram_scan_hist256(const int16_t* scan, const uint8_t* lobe, unsig
     DRAM_REQUIRE(scan && lobe && hist && n > 0 && wmax > wmin, "scan_hist256: bad arguments");
     hipStream_t st = (hipStream_t)stream;
     (void)hipMemsetAsync(hist, 0, 256 * sizeof(unsigned long long), st);
-    const unsigned grid = (unsigned)(cdiv64(n, 256 * 16) < 2048 ? cdiv64(n, 256 * 16) : 2048);
-    hipLaunchKernelGGL(scan_hist_kernel, dim3(grid ? grid : 1), dim3(256), 0, st, scan, lobe, hist, wmin, wmax, (size_t)n);
+    hipLaunchKernelGGL(scan_hist_kernel, dim3(stream_grid(n, 16, 2048)), dim3(256), 0, st, scan, lobe, hist, wmin, wmax, (size_t)n);
     return check_launch("scan_hist256");
 }
 
@@ -330,9 +298,8 @@ extern "C" int dram_scan_hist256(const int16_t* scan, const uint8_t* lobe, unsig
 extern "C" int dram_lesion_post(const float* htp, const int16_t* scan, const uint8_t* vessel, uint8_t* pred, uint8_t* post,
                                 float th, int wmin, int wmax, double th_scan, int64_t n, void* stream) {
     DRAM_REQUIRE(htp && scan && post && n > 0 && wmax > wmin, "lesion_post: bad arguments");
-    const unsigned grid = (unsigned)(cdiv64(n, 256) < 4096 ? cdiv64(n, 256) : 4096);
-    hipLaunchKernelGGL(lesion_post_kernel, dim3(grid), dim3(256), 0, (hipStream_t)stream, htp, scan, vessel, pred, post, th,
-                       wmin, wmax, th_scan, (size_t)n);
+    hipLaunchKernelGGL(lesion_post_kernel, dim3(stream_grid(n, 1, 4096)), dim3(256), 0, (hipStream_t)stream, htp, scan, vessel, pred,
+                       post, th, wmin, wmax, th_scan, (size_t)n);
     return check_launch("lesion_post");
 }
 
@@ -341,8 +308,7 @@ extern "C" int dram_mask_overlap(const uint8_t* a, const uint8_t* b, unsigned lo
     DRAM_REQUIRE(a && b && counts && n > 0, "mask_overlap: bad arguments");
     hipStream_t st = (hipStream_t)stream;
     (void)hipMemsetAsync(counts, 0, 4 * sizeof(unsigned long long), st);
-    const unsigned grid = (unsigned)(cdiv64(n, 256 * 16) < 2048 ? cdiv64(n, 256 * 16) : 2048);
-    hipLaunchKernelGGL(mask_overlap_kernel, dim3(grid ? grid : 1), dim3(256), 0, st, a, b, counts, (size_t)n);
+    hipLaunchKernelGGL(mask_overlap_kernel, dim3(stream_grid(n, 16, 2048)), dim3(256), 0, st, a, b, counts, (size_t)n);
     return check_launch("mask_overlap");
 }
 

@@ -56,17 +56,9 @@ __device__ __forceinline__ int pool_argmax(const float* __restrict__ row, int C)
     return idx;
 }
 
-// relu(trilinear_ac(p)(z, y, x)) of crop voxel (z, y, x); p: one R^3 channel.  lobe_paste_kernel's index rule and combination.
+// relu(trilinear_ac(p)(z, y, x)) of crop voxel (z, y, x); p: one R^3 channel.  F.relu AFTER the resize (job_runner.py:993-995)
 __device__ __forceinline__ float cam_value(const float* __restrict__ p, const Chunk& c, int R, int z, int y, int x) {
-    int z0, z1, y0, y1, x0, x1;
-    float a0, a1, b0, b1, c0, c1;
-    ac_index(R, c.dz, z, z0, z1, a0, a1);
-    ac_index(R, c.dy, y, y0, y1, b0, b1);
-    ac_index(R, c.dx, x, x0, x1, c0, c1);
-    auto at = [&](int zz, int yy, int xx) -> float { return p[((size_t)zz * R + yy) * R + xx]; };
-    const float v = a0 * (b0 * (c0 * at(z0, y0, x0) + c1 * at(z0, y0, x1)) + b1 * (c0 * at(z0, y1, x0) + c1 * at(z0, y1, x1))) +
-                    a1 * (b0 * (c0 * at(z1, y0, x0) + c1 * at(z1, y0, x1)) + b1 * (c0 * at(z1, y1, x0) + c1 * at(z1, y1, x1)));
-    return fmaxf(v, 0.f);                                         // F.relu AFTER the resize (job_runner.py:993-995)
+    return fmaxf(Trilinear(R, c, z, y, x).combine(ChunkField{p, R}), 0.f);
 }
 
 // blockIdx.y = chunk; a capped grid strides over the dz * dy * dx voxels of the box, outside-lobe voxels included
@@ -85,8 +77,8 @@ __global__ __launch_bounds__(256) void lobe_cam_max_kernel(const float* __restri
     const int64_t stride = (int64_t)gridDim.x * 256;
     float m = 0.f;
     for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += stride) {
-        const int e = (int)i;
-        const int x = e % c.dx, y = (e / c.dx) % c.dy, z = e / (c.dx * c.dy);
+        int z, y, x;
+        crop_decode(c, (int)i, z, y, x);
         m = fmaxf(m, cam_value(p, c, R, z, y, x));
     }
     m = block_max_256(m, red);
@@ -94,26 +86,19 @@ __global__ __launch_bounds__(256) void lobe_cam_max_kernel(const float* __restri
     if (threadIdx.x == 0) atomicMax(reinterpret_cast<unsigned*>(max_out + l), __float_as_uint(m));
 }
 
-// One thread per voxel of the largest box.  A voxel carries one label, so it is written by the chunk of that label alone:
-// chunks with different labels may overlap (as in lobe_paste_kernel).  v / m is the IEEE quotient: 0 / 0 = NaN when the whole
-// channel is <= 0 over the box, as in the reference.
+// crop_voxel's walk.  v / m is the IEEE quotient: 0 / 0 = NaN when the whole channel is <= 0 over the box, as in the reference.
 __global__ __launch_bounds__(256) void lobe_cam_paste_kernel(const float* __restrict__ dense, const uint8_t* __restrict__ lobe,
                                                              float* __restrict__ htp, ChunkList cl,
                                                              const int* __restrict__ cls_in, const float* __restrict__ max_in,
                                                              int C, int H, int W, int R) {
-    const int l = blockIdx.y;
-    const Chunk c = cl.c[l];
-    const int e = blockIdx.x * 256 + threadIdx.x;
-    if (e >= c.dz * c.dy * c.dx) return;
-    const int x = e % c.dx, y = (e / c.dx) % c.dy, z = e / (c.dx * c.dy);
-    const size_t o = ((size_t)(c.z0 + z) * H + (c.y0 + y)) * W + (c.x0 + x);
-    if (lobe[o] != c.label) return;
-    const int cls = cls_in[l];
+    const CropVoxel v = crop_voxel(cl, lobe, H, W);
+    if (!v.mine) return;
+    const int cls = cls_in[v.l];
     if (cls == 0) {                                               // `if cls_pred < 1e-7: dense_out.zero_()`, job_runner.py:999
-        htp[o] = 0.f;
+        htp[v.o] = 0.f;
         return;
     }
-    htp[o] = cam_value(dense + ((size_t)l * C + cls) * R * R * R, c, R, z, y, x) / max_in[l];
+    htp[v.o] = cam_value(dense + ((size_t)v.l * C + cls) * R * R * R, v.c, R, v.z, v.y, v.x) / max_in[v.l];
 }
 
 }  // namespace dram
@@ -140,15 +125,13 @@ extern "C" int dram_lobe_cam_max(const float* dense, const float* pool, const in
     DRAM_REQUIRE(dense && pool && cls_out && max_out, "lobe_cam_max: null pointer");
     DRAM_REQUIRE(R > 0 && R <= 1024 && C > 0, "lobe_cam_max: bad resample size or channel count");
     ChunkList cl;
-    int rc = fill_chunks("lobe_cam_max", cl, chunks, L, 0x7fffffff, 0x7fffffff, 0x7fffffff);   // only the sizes are used
+    dim3 grid;
+    const int rc = crop_grid("lobe_cam_max", cl, grid, chunks, L, 0x7fffffff, 0x7fffffff, 0x7fffffff,   // only the sizes are used
+                             CAM_MAX_VOXELS_PER_THREAD, CAM_MAX_GRID_CAP);
     if (rc) return rc;
-    const int64_t mx = max_chunk_voxels(cl, L);
-    DRAM_REQUIRE(mx < 0x7fffffffLL, "lobe_cam_max: chunk too large");
     hipStream_t st = (hipStream_t)stream;
     (void)hipMemsetAsync(max_out, 0, (size_t)L * sizeof(float), st);
-    const int64_t want = cdiv64(mx, 256 * CAM_MAX_VOXELS_PER_THREAD);
-    const unsigned grid = (unsigned)(want < CAM_MAX_GRID_CAP ? want : CAM_MAX_GRID_CAP);
-    hipLaunchKernelGGL(lobe_cam_max_kernel, dim3(grid, L), dim3(256), 0, st, dense, pool, cl, C, R, cls_out, max_out);
+    hipLaunchKernelGGL(lobe_cam_max_kernel, grid, dim3(256), 0, st, dense, pool, cl, C, R, cls_out, max_out);
     return check_launch("lobe_cam_max");
 }
 
@@ -157,11 +140,9 @@ extern "C" int dram_lobe_cam_paste(const float* dense, const uint8_t* lobe, floa
     DRAM_REQUIRE(dense && lobe && htp && cls && max, "lobe_cam_paste: null pointer");
     DRAM_REQUIRE(R > 0 && R <= 1024 && C > 0, "lobe_cam_paste: bad resample size or channel count");
     ChunkList cl;
-    int rc = fill_chunks("lobe_cam_paste", cl, chunks, L, D, H, W);
+    dim3 grid;
+    const int rc = crop_grid("lobe_cam_paste", cl, grid, chunks, L, D, H, W);
     if (rc) return rc;
-    const int64_t mx = max_chunk_voxels(cl, L);
-    DRAM_REQUIRE(mx < 0x7fffffffLL, "lobe_cam_paste: chunk too large");
-    hipLaunchKernelGGL(lobe_cam_paste_kernel, dim3((unsigned)cdiv64(mx, 256), L), dim3(256), 0, (hipStream_t)stream, dense, lobe,
-                       htp, cl, cls, max, C, H, W, R);
+    hipLaunchKernelGGL(lobe_cam_paste_kernel, grid, dim3(256), 0, (hipStream_t)stream, dense, lobe, htp, cl, cls, max, C, H, W, R);
     return check_launch("lobe_cam_paste");
 }

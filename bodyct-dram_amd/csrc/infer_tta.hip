@@ -1,7 +1,7 @@
 // Test-time augmentation around the model call of the per-lobe inference (include/dram_hip.h, "test-time augmentation"), gfx950.
 //   tta_expand       every signed-permutation view of every R^3 chunk in one launch (data movement only)
 //   tta_combine      mean and population standard deviation over the views of sigmoid(dense), at the chunk's resolution, one pass
-//   lobe_paste_prob  lobe_paste_kernel (infer.hip) without the sigmoid, for one or two fields in one walk over the crop
+//   lobe_paste_prob  the paste of infer.hip without the sigmoid, for one or two fields in one walk over the crop
 //
 // A view reads a chunk along another axis than it writes, so one side of a plain gather (dram_spatial_permute_flip,
 // resample.hip: contiguous stores, loads with a lane stride of the moved axis) runs at a lane stride of R or R^2 floats.  That
@@ -186,7 +186,7 @@ __global__ __launch_bounds__(TTA_THREADS) void tta_combine_kernel(const float* _
 #pragma unroll
             for (int r = 0; r < TTA_PER; ++r) {
                 const float d = turn ? (ok[r] ? img[u][at[r]] : 0.f) : ld[u][r];
-                p[r][g + u] = 1.f / (1.f + expf(-d));                      // lobe_paste_kernel's expression (infer.hip)
+                p[r][g + u] = paste_sigmoid(d);
             }
         }
         __syncthreads();
@@ -208,31 +208,15 @@ __global__ __launch_bounds__(TTA_THREADS) void tta_combine_kernel(const float* _
     }
 }
 
-// lobe_paste_kernel (infer.hip) on fields that are probabilities already: the same crop walk, lobe test, align-corners indices
-// and 8-term combination; prob2 / htp2 (both or neither) ride along on the same indices and weights.
+// crop_voxel's walk pasting fields that are probabilities already; prob2 / htp2 (both or neither) ride along on the same taps.
 __global__ __launch_bounds__(256) void lobe_paste_prob_kernel(const float* __restrict__ prob, const float* __restrict__ prob2,
                                                               const uint8_t* __restrict__ lobe, float* __restrict__ htp,
                                                               float* __restrict__ htp2, ChunkList cl, int H, int W, int R) {
-    const int l = blockIdx.y;
-    const Chunk c = cl.c[l];
-    const int e = blockIdx.x * 256 + threadIdx.x;
-    if (e >= c.dz * c.dy * c.dx) return;
-    const int x = e % c.dx, y = (e / c.dx) % c.dy, z = e / (c.dx * c.dy);
-    const size_t o = ((size_t)(c.z0 + z) * H + (c.y0 + y)) * W + (c.x0 + x);
-    if (lobe[o] != c.label) return;
-    int z0, z1, y0, y1, x0, x1;
-    float a0, a1, b0, b1, c0, c1;
-    ac_index(R, c.dz, z, z0, z1, a0, a1);
-    ac_index(R, c.dy, y, y0, y1, b0, b1);
-    ac_index(R, c.dx, x, x0, x1, c0, c1);
-    auto resize = [&](const float* field) -> float {
-        const float* p = field + (size_t)l * R * R * R;
-        auto at = [&](int zz, int yy, int xx) -> float { return p[((size_t)zz * R + yy) * R + xx]; };
-        return a0 * (b0 * (c0 * at(z0, y0, x0) + c1 * at(z0, y0, x1)) + b1 * (c0 * at(z0, y1, x0) + c1 * at(z0, y1, x1))) +
-               a1 * (b0 * (c0 * at(z1, y0, x0) + c1 * at(z1, y0, x1)) + b1 * (c0 * at(z1, y1, x0) + c1 * at(z1, y1, x1)));
-    };
-    htp[o] = resize(prob);
-    if (prob2) htp2[o] = resize(prob2);
+    const CropVoxel v = crop_voxel(cl, lobe, H, W);
+    if (!v.mine) return;
+    const Trilinear t(R, v.c, v.z, v.y, v.x);
+    htp[v.o] = t.combine(ChunkField{prob + (size_t)v.l * R * R * R, R});
+    if (prob2) htp2[v.o] = t.combine(ChunkField{prob2 + (size_t)v.l * R * R * R, R});
 }
 
 // views: host array of V x {perm[3], flip[3]}
@@ -299,11 +283,9 @@ extern "C" int dram_lobe_paste_prob(const float* prob, const float* prob2, const
     DRAM_REQUIRE((prob2 == nullptr) == (htp2 == nullptr), "lobe_paste_prob: prob2 and htp2 go together");
     DRAM_REQUIRE(R >= 2, "lobe_paste_prob: bad resample size");
     ChunkList cl;
-    int rc = fill_chunks("lobe_paste_prob", cl, chunks, L, D, H, W);
+    dim3 grid;
+    const int rc = crop_grid("lobe_paste_prob", cl, grid, chunks, L, D, H, W);
     if (rc) return rc;
-    const int64_t mx = max_chunk_voxels(cl, L);
-    DRAM_REQUIRE(mx < 0x7fffffffLL, "lobe_paste_prob: chunk too large");
-    hipLaunchKernelGGL(lobe_paste_prob_kernel, dim3((unsigned)cdiv64(mx, 256), L), dim3(256), 0, (hipStream_t)stream, prob,
-                       prob2, lobe, htp, htp2, cl, H, W, R);
+    hipLaunchKernelGGL(lobe_paste_prob_kernel, grid, dim3(256), 0, (hipStream_t)stream, prob, prob2, lobe, htp, htp2, cl, H, W, R);
     return check_launch("lobe_paste_prob");
 }

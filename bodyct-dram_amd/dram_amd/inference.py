@@ -133,6 +133,24 @@ def resample_volume(vol, spacing, required_spacing, new_size, interpolator="line
     return out
 
 
+def crop_list(boxes, shape, spacing, border, max_labels):
+    """The crops from the labels' boxes, boxes[label - 1] = (min z, y, x, max z, y, x) inclusive, min > max for an absent label
+    (dram_label_bboxes): one [z0, y0, x0, dz, dy, dx, label] per label present in 1..max_labels, ascending, the box widened by
+    ceil(border / spacing) voxels per axis and clipped to the volume (find_crops, utils.py:244-254)."""
+    chunks = []
+    for label in range(1, max_labels + 1):
+        lo, hi = boxes[label - 1][:3], boxes[label - 1][3:]
+        if hi[0] < lo[0]:
+            continue                                                         # label absent (np.unique(lobe)[1:])
+        start, stop = [], []
+        for l, h, size, sp in zip(lo, hi, shape, spacing):
+            pad = int(math.ceil(border / sp)) if border > 0 else 0
+            start.append(max(0, int(l) - pad))
+            stop.append(min(int(size), int(h) + 1 + pad))
+        chunks.append(start + [b - a for a, b in zip(start, stop)] + [label])
+    return chunks
+
+
 class LobeInference:
     """model: a models.DC3D on the GPU.  run(scan_i16, lobe_u8, spacing) -> dict.  Every label 1..max_labels
     present in the uint8 lobe map is visited in ascending order (evaluate_scan: `np.unique(lobe)[1:]`,
@@ -196,94 +214,26 @@ class LobeInference:
         lobe = torch.as_tensor(lobe).to(device=dev, dtype=torch.uint8).contiguous()
         if scan.dim() != 3 or scan.shape != lobe.shape:
             raise ValueError("scan and lobe must be [D,H,W] arrays of the same shape")
-        D, H, W = scan.shape
         if callable(vessel):
             vessel = vessel(scan, lobe, spacing)
-        st = torch.cuda.current_stream().cuda_stream
-        boxes = torch.empty(self.max_labels * 6, dtype=torch.int32, device=dev)
-        call("dram_label_bboxes", lobe.data_ptr(), boxes.data_ptr(), self.max_labels, D, H, W, st)
-        top = int(lobe.max()) if self.max_labels < 255 else 0             # (a second small sync only when labels are capped)
-        if top > self.max_labels:
-            raise ValueError(f"lobe map holds label {top} > max_labels={self.max_labels}: it would be left out of the "
-                             f"heat map while still counting in the lesion ratio")
-        boxes = boxes.cpu().numpy().reshape(self.max_labels, 6)            # the only sync before the model: 6 ints per label
-        chunks = []
-        for label in range(1, self.max_labels + 1):
-            lo, hi = boxes[label - 1, :3], boxes[label - 1, 3:]
-            if hi[0] < lo[0]:
-                continue                                                     # label absent (np.unique(lobe)[1:])
-            start, stop = [], []
-            for ax, (l, h, size, sp) in enumerate(zip(lo, hi, (D, H, W), spacing)):   # find_crops, utils.py:244-254
-                pad = int(math.ceil(self.border / sp)) if self.border > 0 else 0
-                start.append(max(0, int(l) - pad))
-                stop.append(min(size, int(h) + 1 + pad))
-            chunks.append(start + [b - a for a, b in zip(start, stop)] + [label])
-        htp = torch.zeros((D, H, W), dtype=torch.float32, device=dev)
-        cam = self.head == "cam"
-        spread = None if self.views is None else torch.zeros((D, H, W), dtype=torch.float32, device=dev)
+        chunks = crop_list(self._label_boxes(lobe), scan.shape, spacing, self.border, self.max_labels)
+        out = {"htp": torch.zeros(scan.shape, dtype=torch.float32, device=dev)}
+        if self.views is not None:
+            out.update(spread=torch.zeros_like(out["htp"]), views=self.views)
         if not chunks:
-            res = {"htp": htp, "mask": torch.zeros((D, H, W), dtype=torch.uint8, device=dev), "threshold": 0.0,
-                   "lesion_ratio": 0.0, "ctss": 0, "chunks": []}
-            if cam:
-                res["lobe_cls"] = {}
-            if spread is not None:
-                res.update(spread=spread, views=self.views)
-            if self.refine is not None:
-                res.update(htp_refined=torch.zeros_like(htp), threshold_refined=0.0, mask_refined=torch.zeros_like(res["mask"]))
-            return res
-        R = self.R
-        x = torch.empty((len(chunks), 1, R, R, R), dtype=torch.float32, device=dev)
-        if cam:   # the resampled lobe masks, and per chunk: pooled channels, class, maximum of the class's map over the crop
-            lobe_mask = torch.empty((len(chunks), 1, R, R, R), dtype=torch.float32, device=dev)
-            cls = torch.empty(len(chunks), dtype=torch.int32, device=dev)
-            cmax = torch.empty(len(chunks), dtype=torch.float32, device=dev)
-            pools = []
-        was_training = self.model.training
-        self.model.eval()
-        try:
-            for g0 in range(0, len(chunks), self.MAX_CHUNKS):
-                grp = chunks[g0:g0 + self.MAX_CHUNKS]
-                L = len(grp)
-                carr = (ctypes.c_int * (7 * L))(*[v for c in grp for v in c])
-                xg = x[g0:g0 + L]
-                call("dram_lobe_chunks", scan.data_ptr(), lobe.data_ptr(), xg.data_ptr(), carr, L, D, H, W, R,
-                     float(self.window[0]), float(self.window[1]), st)
-                if cam:
-                    self._cam_group(xg, lobe_mask[g0:g0 + L], cls[g0:g0 + L], cmax[g0:g0 + L], pools, lobe, htp, carr, L, D, H, W, st)
-                    continue
-                if spread is not None:
-                    self._tta_group(xg, lobe, htp, spread, carr, L, D, H, W, st)
-                    continue
-                _, dense = self.model(xg, None)   # one batch of L lobe chunks; the 2nd output is used (job_runner.py:764)
-                call("dram_lobe_paste", dense.contiguous().data_ptr(), lobe.data_ptr(), htp.data_ptr(), carr, L, D, H, W, R, st)
-        finally:
-            self.model.train(was_training)
-        hist = torch.empty(256 + (len(chunks) if cam else 0), dtype=torch.int64, device=dev)
-        ssum = torch.empty(1, dtype=torch.float64, device=dev)
-        call("dram_lung_hist256", htp.data_ptr(), lobe.data_ptr(), hist.data_ptr(), ssum.data_ptr(), htp.numel(), st)
-        if cam:
-            hist[256:].copy_(cls)                                            # the classes ride along with the histogram read-back
-        hist_h = hist.cpu().numpy()
-        hist_h, cls_h = hist_h[:256], hist_h[256:]
-        n_lung = int(hist_h.sum())
-        th = binary_cam_threshold(hist_h)
-        mask = torch.empty((D, H, W), dtype=torch.uint8, device=dev)
-        call("dram_threshold_mask", htp.data_ptr(), mask.data_ptr(), float(th), htp.numel(), st)
+            return self._empty_result(out)
+        self._run_groups(chunks, scan, lobe, out)
+        htp = out["htp"]
+        th, mask, ssum, n_lung, cls_h = self._judge(htp, lobe, out.pop("cls", None))
         ratio = float(ssum.item()) / max(n_lung, 1)                          # (htp * (lobe>0)).sum() / (lobe>0).sum()
-        res = {"htp": htp, "mask": mask, "threshold": th, "lesion_ratio": ratio, "ctss": ratio_to_label(ratio),
-               "chunks": chunks, "input": x}
-        if cam:
-            res.update(lobe_cls={c[6]: int(k) for c, k in zip(chunks, cls_h)}, pool=torch.cat(pools), lobe_mask=lobe_mask)
-        if spread is not None:
-            res.update(spread=spread, views=self.views)
+        res = {"htp": htp, "mask": mask, "threshold": th, "lesion_ratio": ratio, "ctss": ratio_to_label(ratio), "chunks": chunks, **out}
+        if self.head == "cam":
+            res.update(lobe_cls={c[6]: int(k) for c, k in zip(chunks, cls_h)}, pool=torch.cat(out["pool"]))
         refined = None
         if self.refine is not None:
             from .refine import refine_heatmap
             htp_r = refine_heatmap(htp, scan, lobe, spacing, **self.refine)
-            call("dram_lung_hist256", htp_r.data_ptr(), lobe.data_ptr(), hist.data_ptr(), ssum.data_ptr(), htp_r.numel(), st)
-            th_r = binary_cam_threshold(hist[:256].cpu().numpy())
-            mask_r = torch.empty((D, H, W), dtype=torch.uint8, device=dev)
-            call("dram_threshold_mask", htp_r.data_ptr(), mask_r.data_ptr(), float(th_r), htp_r.numel(), st)
+            th_r, mask_r = self._judge(htp_r, lobe)[:2]
             res.update(htp_refined=htp_r, threshold_refined=th_r, mask_refined=mask_r)
             refined = (htp_r, th_r, mask_r)
         if vessel is not None or lesion is not None or original_size is not None:
@@ -291,6 +241,67 @@ class LobeInference:
                                          original_spacing=original_spacing, original_size=original_size, curves=curves,
                                          refined=refined))
         return res
+
+    def _label_boxes(self, lobe):
+        """dram_label_bboxes on the host, [max_labels, 6]: the only sync before the model (a second small one when labels are capped)."""
+        D, H, W = lobe.shape
+        boxes = torch.empty(self.max_labels * 6, dtype=torch.int32, device=lobe.device)
+        call("dram_label_bboxes", lobe.data_ptr(), boxes.data_ptr(), self.max_labels, D, H, W, torch.cuda.current_stream().cuda_stream)
+        top = int(lobe.max()) if self.max_labels < 255 else 0
+        if top > self.max_labels:
+            raise ValueError(f"lobe map holds label {top} > max_labels={self.max_labels}: it would be left out of the "
+                             f"heat map while still counting in the lesion ratio")
+        return boxes.cpu().numpy().reshape(self.max_labels, 6)
+
+    def _empty_result(self, out):
+        """No label in the map: an all-zero heat map judged by hand (there is no histogram to take a threshold from)."""
+        mask = torch.zeros(out["htp"].shape, dtype=torch.uint8, device=out["htp"].device)
+        res = {"mask": mask, "threshold": 0.0, "lesion_ratio": 0.0, "ctss": 0, "chunks": [], **out}
+        if self.head == "cam":
+            res["lobe_cls"] = {}
+        if self.refine is not None:
+            res.update(htp_refined=torch.zeros_like(out["htp"]), threshold_refined=0.0, mask_refined=torch.zeros_like(mask))
+        return res
+
+    def _run_groups(self, chunks, scan, lobe, out):
+        """Crops every chunk to R^3 (out["input"]) and takes the chunks through the model and into out["htp"] in groups of up to
+        MAX_CHUNKS, by the group method of the head; what else a head produces per chunk joins `out` (its group method says)."""
+        R, dev, st = self.R, scan.device, torch.cuda.current_stream().cuda_stream
+        D, H, W = scan.shape
+        x = out["input"] = torch.empty((len(chunks), 1, R, R, R), dtype=torch.float32, device=dev)
+        if self.head == "cam":
+            out.update(lobe_mask=torch.empty_like(x), cls=torch.empty(len(chunks), dtype=torch.int32, device=dev),
+                       cmax=torch.empty(len(chunks), dtype=torch.float32, device=dev), pool=[])
+        group = self._cam_group if self.head == "cam" else self._sigmoid_group if self.views is None else self._tta_group
+        was_training = self.model.training
+        self.model.eval()
+        try:
+            for g0 in range(0, len(chunks), self.MAX_CHUNKS):
+                grp = chunks[g0:g0 + self.MAX_CHUNKS]
+                sl, L = slice(g0, g0 + len(grp)), len(grp)
+                carr = (ctypes.c_int * (7 * L))(*[v for c in grp for v in c])
+                call("dram_lobe_chunks", scan.data_ptr(), lobe.data_ptr(), x[sl].data_ptr(), carr, L, D, H, W, R,
+                     float(self.window[0]), float(self.window[1]), st)
+                group(out, sl, lobe, carr, L, D, H, W, st)
+        finally:
+            self.model.train(was_training)
+        out.pop("cmax", None)
+
+    def _judge(self, htp, lobe, ride=None):
+        """The judgement of a finished map: `binary_cam` on its 8-bit histogram inside the lungs (job_runner.py:1003-1005), mask =
+        htp > threshold.  Returns (threshold, mask, the map's fp64 sum inside the lungs, still on the device, the lungs' voxel
+        count, `ride` on the host): a few device integers that ride along with the histogram's read-back, this step's one sync."""
+        st = torch.cuda.current_stream().cuda_stream
+        hist = torch.empty(256 + (0 if ride is None else len(ride)), dtype=torch.int64, device=htp.device)
+        ssum = torch.empty(1, dtype=torch.float64, device=htp.device)
+        call("dram_lung_hist256", htp.data_ptr(), lobe.data_ptr(), hist.data_ptr(), ssum.data_ptr(), htp.numel(), st)
+        if ride is not None:
+            hist[256:].copy_(ride)
+        hist_h = hist.cpu().numpy()
+        th = binary_cam_threshold(hist_h[:256])
+        mask = torch.empty(htp.shape, dtype=torch.uint8, device=htp.device)
+        call("dram_threshold_mask", htp.data_ptr(), mask.data_ptr(), float(th), htp.numel(), st)
+        return th, mask, ssum, int(hist_h[:256].sum()), hist_h[256:]
 
     SHEET_TITLES = {"mask": "pred_lesion", "mask_post": "pred_lesion_post", "lesion": "lesion", "htp": "pred_cam"}
 
@@ -321,11 +332,17 @@ class LobeInference:
         coord = [src["mask"]] + ([lesion] if lesion is not None else [])
         return result_sheet(scan, [[layers[k]] for k in names], coord, **kw)
 
-    def _tta_group(self, xg, lobe, htp, spread, carr, L, D, H, W, st):
+    def _sigmoid_group(self, out, sl, lobe, carr, L, D, H, W, st):
+        """evaluate_scan for chunks `sl` of out["input"] (L of them, `carr` their boxes): the model's 2nd output
+        (job_runner.py:764), sigmoid, resize, paste into out["htp"].  The other two group methods take the same arguments."""
+        _, dense = self.model(out["input"][sl], None)
+        call("dram_lobe_paste", dense.contiguous().data_ptr(), lobe.data_ptr(), out["htp"].data_ptr(), carr, L, D, H, W, self.R, st)
+
+    def _tta_group(self, out, sl, lobe, carr, L, D, H, W, st):
         """Test-time augmentation for one group of L chunks (csrc/infer_tta.hip): all V views in one launch, the V * L viewed
         chunks through the model in batches of tta_batch -- a batch may end inside one view and start the next --, then mean
-        and spread over the views at the chunk's resolution and both pasted in one walk over the crops."""
-        R, V = self.R, len(self.views)
+        and spread over the views at the chunk's resolution and both pasted in one walk over the crops (out["spread"])."""
+        R, V, xg = self.R, len(self.views), out["input"][sl]
         varr = (ctypes.c_int * (6 * V))(*[a for perm, flip in self.views for a in perm + flip])
         xv = torch.empty((V * L, 1, R, R, R), dtype=torch.float32, device=xg.device)
         call("dram_tta_expand", xg.data_ptr(), xv.data_ptr(), L, R, varr, V, st)
@@ -334,23 +351,24 @@ class LobeInference:
             dense[b0:b0 + self.tta_batch].copy_(self.model(xv[b0:b0 + self.tta_batch], None)[1])
         mean = torch.empty((2, L, R, R, R), dtype=torch.float32, device=xg.device)
         call("dram_tta_combine", dense.data_ptr(), mean[0].data_ptr(), mean[1].data_ptr(), L, R, varr, V, st)
-        call("dram_lobe_paste_prob", mean[0].data_ptr(), mean[1].data_ptr(), lobe.data_ptr(), htp.data_ptr(), spread.data_ptr(),
-             carr, L, D, H, W, R, st)
+        call("dram_lobe_paste_prob", mean[0].data_ptr(), mean[1].data_ptr(), lobe.data_ptr(), out["htp"].data_ptr(),
+             out["spread"].data_ptr(), carr, L, D, H, W, R, st)
 
-    def _cam_group(self, xg, mg, cls, cmax, pools, lobe, htp, carr, L, D, H, W, st):
+    def _cam_group(self, out, sl, lobe, carr, L, D, H, W, st):
         """The lobe-wise class head of LesionSegTest.run (job_runner.py:985-1004) for one batch of L chunks: the model sees the
-        image chunk and the resampled lobe mask, the dense output is pooled over that mask, and the class, the maximum of its
-        ReLU'd map over the crop and the paste follow on the device (csrc/infer_cam.hip)."""
+        image chunk and the resampled lobe mask (out["lobe_mask"]), the dense output is pooled over that mask (out["pool"], one
+        [L, C] tensor per group), and the class (out["cls"]), the maximum of its ReLU'd map over the crop (out["cmax"]) and the
+        paste follow on the device (csrc/infer_cam.hip)."""
         import models
-        R = self.R
+        R, mg, cls, cmax = self.R, out["lobe_mask"][sl], out["cls"][sl], out["cmax"][sl]
         call("dram_lobe_chunk_masks", lobe.data_ptr(), mg.data_ptr(), carr, L, D, H, W, R, st)
-        _, dense = self.model(xg, mg)                                        # the 2nd output (job_runner.py:985)
+        _, dense = self.model(out["input"][sl], mg)                          # the 2nd output (job_runner.py:985)
         dense = dense.contiguous()
         C = int(dense.shape[1])
         pool = models.pooling_dense_features(dense, mg).contiguous()         # [L, C]: masked mean (models.py:45-47)
-        pools.append(pool)
+        out["pool"].append(pool)
         call("dram_lobe_cam_max", dense.data_ptr(), pool.data_ptr(), carr, L, C, R, cls.data_ptr(), cmax.data_ptr(), st)
-        call("dram_lobe_cam_paste", dense.data_ptr(), lobe.data_ptr(), htp.data_ptr(), carr, cls.data_ptr(), cmax.data_ptr(),
+        call("dram_lobe_cam_paste", dense.data_ptr(), lobe.data_ptr(), out["htp"].data_ptr(), carr, cls.data_ptr(), cmax.data_ptr(),
              L, C, D, H, W, R, st)
 
     @torch.no_grad()
@@ -385,66 +403,56 @@ class LobeInference:
         hist = torch.empty(256, dtype=torch.int64, device=dev)
         call("dram_scan_hist256", scan.data_ptr(), lobe.data_ptr(), hist.data_ptr(), self.post_window[0], self.post_window[1], n, st)
         th_scan = binary_cam_threshold(hist.cpu().numpy(), self.post_scaler)
-        post = torch.empty(htp.shape, dtype=torch.uint8, device=dev)
-        call("dram_lesion_post", htp.data_ptr(), scan.data_ptr(), None if vessel is None else vessel.data_ptr(), None,
-             post.data_ptr(), float(th), self.post_window[0], self.post_window[1], float(th_scan), n, st)
-        out = {"mask_post": post, "threshold_scan": th_scan}
+
+        def gated(score, cut):
+            post = torch.empty(score.shape, dtype=torch.uint8, device=dev)
+            call("dram_lesion_post", score.data_ptr(), scan.data_ptr(), None if vessel is None else vessel.data_ptr(), None,
+                 post.data_ptr(), float(cut), self.post_window[0], self.post_window[1], float(th_scan), score.numel(), st)
+            return post
+
+        # the heat map as it is and, when given, the refined one; `infix` tells their result keys apart
+        judged = [{"infix": "", "htp": htp, "th": th, "mask": mask}]
         if refined is not None:
-            htp_r, th_r, mask_r = refined
-            post_r = torch.empty(htp.shape, dtype=torch.uint8, device=dev)
-            call("dram_lesion_post", htp_r.data_ptr(), scan.data_ptr(), None if vessel is None else vessel.data_ptr(), None,
-                 post_r.data_ptr(), float(th_r), self.post_window[0], self.post_window[1], float(th_scan), n, st)
-            out["mask_refined_post"] = post_r
-        if mask is None and (lesion is not None or original_size is not None):
-            mask = torch.empty(htp.shape, dtype=torch.uint8, device=dev)
-            call("dram_threshold_mask", htp.data_ptr(), mask.data_ptr(), float(th), n, st)
+            judged.append({"infix": "_refined", "htp": refined[0], "th": refined[1], "mask": refined[2]})
+        out = {"threshold_scan": th_scan}
+        for m in judged:
+            m["post"] = out[f"mask{m['infix']}_post"] = gated(m["htp"], m["th"])
+            if m["mask"] is None and (lesion is not None or original_size is not None):
+                m["mask"] = torch.empty(htp.shape, dtype=torch.uint8, device=dev)
+                call("dram_threshold_mask", m["htp"].data_ptr(), m["mask"].data_ptr(), float(m["th"]), n, st)
         if lesion is not None:
             lesion = torch.as_tensor(lesion).to(device=dev, dtype=torch.uint8).contiguous()
             if lesion.shape != htp.shape:
                 raise ValueError("lesion mask and scan must have the same shape")
         if original_size is not None:
             back = lambda v, how: resample_volume(v, spacing, original_spacing, original_size, how)
-            orig = {"mask": back(mask, "nearest"), "mask_post": back(post, "nearest"), "scan": back(scan, "linear"),
-                    "htp": back(htp, "linear")}
+            orig = out["original"] = {"scan": back(scan, "linear")}
             if lesion is not None:
                 orig["lesion"] = lesion = back(lesion, "nearest")
-            out["original"] = orig
-            if refined is not None:
-                orig.update(htp_refined=back(htp_r, "linear"), mask_refined=back(mask_r, "nearest"),
-                            mask_refined_post=back(post_r, "nearest"))
-                htp_r, mask_r, post_r = orig["htp_refined"], orig["mask_refined"], orig["mask_refined_post"]
-            mask, post, n = orig["mask"], orig["mask_post"], orig["mask"].numel()
+            for m in judged:
+                m.update(htp=back(m["htp"], "linear"), mask=back(m["mask"], "nearest"), post=back(m["post"], "nearest"))
+                orig.update({f"htp{m['infix']}": m["htp"], f"mask{m['infix']}": m["mask"], f"mask{m['infix']}_post": m["post"]})
         if curves is not None:
             from .curves import heatmap_curves
-            # the gate alone: with th = -inf the prediction term of dram_lesion_post is true wherever the score is not NaN, and a NaN
-            # score is in bin 0 (never predicted) with or without a gate
-            gate = torch.empty(htp.shape, dtype=torch.uint8, device=dev)
-            call("dram_lesion_post", htp.data_ptr(), scan.data_ptr(), None if vessel is None else vessel.data_ptr(), None,
-                 gate.data_ptr(), float("-inf"), self.post_window[0], self.post_window[1], float(th_scan), htp.numel(), st)
-            n_regions = max(1, int(lobe.max()))
-            score, regions = htp, lobe
+            # the gate alone: with a cut of -inf the prediction term of dram_lesion_post is true wherever the score is not NaN, and a
+            # NaN score is in bin 0 (never predicted) with or without a gate
+            gate, regions, n_regions = gated(htp, float("-inf")), lobe, max(1, int(lobe.max()))
             if original_size is not None:
-                score, regions, gate = orig["htp"], back(lobe, "nearest"), back(gate, "nearest")
+                regions, gate = back(lobe, "nearest"), back(gate, "nearest")
             n_cal = min(16, int(curves))
-            out["curves"] = heatmap_curves(score, lesion, regions, n_regions, None, curves, n_cal)
-            out["curves_post"] = heatmap_curves(score, lesion, regions, n_regions, gate, curves, n_cal)
-            if refined is not None:
-                out["curves_refined"] = heatmap_curves(htp_r, lesion, regions, n_regions, None, curves, n_cal)
-                out["curves_refined_post"] = heatmap_curves(htp_r, lesion, regions, n_regions, gate, curves, n_cal)
+            for m in judged:
+                out[f"curves{m['infix']}"] = heatmap_curves(m["htp"], lesion, regions, n_regions, None, curves, n_cal)
+                out[f"curves{m['infix']}_post"] = heatmap_curves(m["htp"], lesion, regions, n_regions, gate, curves, n_cal)
         if lesion is not None:
-            counts = torch.empty(8, dtype=torch.int64, device=dev)
-            call("dram_mask_overlap", mask.data_ptr(), lesion.data_ptr(), counts.data_ptr(), n, st)
-            call("dram_mask_overlap", post.data_ptr(), lesion.data_ptr(), counts[4:].data_ptr(), n, st)
-            c = [int(v) for v in counts.cpu()]
             s = 1e-5                                                        # the smooth term of job_runner.py:1033-1037
-            out.update(iou=(c[0] + s) / (c[1] + s), dice=(2.0 * c[0] + s) / (c[2] + c[3] + s),
-                       iou_post=(c[4] + s) / (c[5] + s), dice_post=(2.0 * c[4] + s) / (c[6] + c[7] + s))
-            if refined is not None:
-                call("dram_mask_overlap", mask_r.data_ptr(), lesion.data_ptr(), counts.data_ptr(), n, st)
-                call("dram_mask_overlap", post_r.data_ptr(), lesion.data_ptr(), counts[4:].data_ptr(), n, st)
+            for m in judged:
+                counts = torch.empty(8, dtype=torch.int64, device=dev)
+                call("dram_mask_overlap", m["mask"].data_ptr(), lesion.data_ptr(), counts.data_ptr(), lesion.numel(), st)
+                call("dram_mask_overlap", m["post"].data_ptr(), lesion.data_ptr(), counts[4:].data_ptr(), lesion.numel(), st)
                 c = [int(v) for v in counts.cpu()]
-                out.update(iou_refined=(c[0] + s) / (c[1] + s), dice_refined=(2.0 * c[0] + s) / (c[2] + c[3] + s),
-                           iou_refined_post=(c[4] + s) / (c[5] + s), dice_refined_post=(2.0 * c[4] + s) / (c[6] + c[7] + s))
+                out.update({f"iou{m['infix']}": (c[0] + s) / (c[1] + s), f"dice{m['infix']}": (2.0 * c[0] + s) / (c[2] + c[3] + s),
+                            f"iou{m['infix']}_post": (c[4] + s) / (c[5] + s),
+                            f"dice{m['infix']}_post": (2.0 * c[4] + s) / (c[6] + c[7] + s)})
         return out
 
 

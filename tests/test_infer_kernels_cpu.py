@@ -71,6 +71,32 @@ def test_bboxes_ref_with_border_and_clamp_is_find_crops(name, extra):
         assert not present
 
 
+@pytest.mark.parametrize("border", [5.0, 0.0])
+@pytest.mark.parametrize("spacing", [(2.5, 1.0, 1.0), (1.0, 0.7, 0.7)])
+def test_crop_list_is_find_crops_per_label(spacing, border):
+    """dram_amd.inference.crop_list on the boxes of a (20, 30, 40) map == O.find_crops(lobe == label, spacing, border) for
+    every label present, in ascending order: label 1 touches the volume's first and last voxel along every axis (the pad is
+    clipped on both sides), label 3 is absent between 2 and 4, label 4 is one voxel, and label 9 above max_labels = 6 is not
+    listed (LobeInference.run refuses such a map itself)."""
+    from dram_amd.inference import crop_list
+    shape = (20, 30, 40)
+    lobe = np.zeros(shape, dtype=np.uint8)
+    lobe[0, 0, 0] = lobe[-1, -1, -1] = lobe[8:12, 10:20, 5:9] = 1
+    lobe[3:9, 12:17, 20:33] = 2
+    lobe[10, 15, 20] = 4
+    lobe[15:18, 2:6, 30:38] = 6
+    lobe[12:14, 22:26, 1:4] = 9
+    chunks = crop_list(K.bboxes_ref(lobe, 6), shape, spacing, border, 6)
+    assert [c[6] for c in chunks] == [1, 2, 4, 6] and all(len(c) == 7 and all(type(v) is int for v in c) for c in chunks)
+    for c in chunks:
+        sl = O.find_crops(lobe == c[6], spacing, border)
+        assert [s.start for s in sl] == c[:3] and [s.stop - s.start for s in sl] == c[3:6]
+    assert chunks[0][:6] == [0, 0, 0, 20, 30, 40]
+    if border == 0:
+        assert chunks[2][3:6] == [1, 1, 1]
+    assert crop_list(K.bboxes_ref(np.zeros(shape, dtype=np.uint8), 6), shape, spacing, border, 6) == []
+
+
 def test_bbox_band_map_boxes_by_hand():
     """The boxes the band map is built to give, written out."""
     b = K.bboxes_ref(K.bbox_band_map(32), 6)
