@@ -29,6 +29,9 @@ _DISTRIBUTION = ("lung_depth", "label_depth", "lesion_distribution")
 # the lesion shape report of `shape`, the same way
 _SHAPE = ("label_shape", "crossings", "euler_number", "crofton_weights", "lesion_shape")
 
+# the lesion texture report of `texture`, the same way
+_TEXTURE = ("label_glcm", "glcm_features", "lesion_texture")
+
 # the heat-map evaluation curves of `curves`, the same way
 _CURVES = ("score_tables", "curves_from_tables", "heatmap_curves")
 
@@ -48,7 +51,7 @@ _SHEET = ("sheet_layout", "pick_slices", "sheet_occupancy", "result_sheet", "sav
 _INFERENCE = ("tta_views",)
 
 __all__ = ["_lib", "functional", "modules", "optim", "Adam", "AdamW", "SGD", "RAdam", "AdaBound", *_AUGMENT, *_LOSSES, *_LESIONS,
-           *_DENSITY, *_DISTRIBUTION, *_SHAPE, *_CURVES, *_SURFACE, *_VESSELS, *_REFINE, *_SHEET, *_INFERENCE]
+           *_DENSITY, *_DISTRIBUTION, *_SHAPE, *_TEXTURE, *_CURVES, *_SURFACE, *_VESSELS, *_REFINE, *_SHEET, *_INFERENCE]
 
 
 def __getattr__(name):
@@ -70,6 +73,9 @@ def __getattr__(name):
     if name in _SHAPE:
         from . import shape
         return getattr(shape, name)
+    if name in _TEXTURE:
+        from . import texture
+        return getattr(texture, name)
     if name in _CURVES:
         from . import curves
         return getattr(curves, name)

@@ -186,6 +186,9 @@ SIGNATURES = {
     # lesion shape report: per-label 2x2x2 configuration histogram and second-order moments
     "dram_label_shape_plan": (I, [I, I]),
     "dram_label_shape": (I, [P, I, I, P, P, I, I, I, P]),
+    # lesion texture report: per-label grey-level co-occurrence tables in the 13 directions
+    "dram_label_glcm_plan": (I, [I, I, I, I]),
+    "dram_label_glcm": (I, [P, P, I, P, I, I, I, I, I, P, I, I, I, P]),
     # heat-map evaluation curves: the joint histogram of score bin x class x region
     "dram_score_hist_plan": (I, [I, I, I]),
     "dram_score_hist": (I, [P, P, P, P, I, I, P, P, L, P]),

@@ -109,7 +109,7 @@ def lobe_burden(mask, lobe):
 
 def lesion_report(mask, lobe, spacing, connectivity=1, min_volume_mm3=0.0, reference=None, surface=False, tolerances_mm=(),
                   scan=None, percentiles_permille=(150, 500, 850), band_edges_hu=(-950, -750, -300), distribution=False, depth=None,
-                  shells_mm=(5.0, 10.0, 20.0), zones=(3, 2, 1), box=None, subpleural_mm=3.0, shape=False):
+                  shells_mm=(5.0, 10.0, 20.0), zones=(3, 2, 1), box=None, subpleural_mm=3.0, shape=False, texture=False):
     """The lesion-wise report of a [D,H,W] lesion mask (e.g. `LobeInference.run(...)["mask_post"]`, or the "original" entries
     on the scan's own grid) with its lobe map and voxel spacing (z, y, x) in mm.
 
@@ -133,9 +133,16 @@ def lesion_report(mask, lobe, spacing, connectivity=1, min_volume_mm3=0.0, refer
     the keyword nothing of that is computed and the result has no such key;
     and with `shape=True`: shape = `shape.lesion_shape` over the kept components (surface area, Euler number, sphericity,
     principal axes), one row per lesion in the order of volumes_ml.  Without the keyword nothing of that is computed and the
-    result has no such key."""
+    result has no such key;
+    and with `scan` and `texture=True` (the defaults of `texture.label_glcm`) or `texture=dict(levels=, lo=, width=, distance=)`:
+    texture = {"lesions": `texture.lesion_texture` over the kept components (Haralick features of the grey-level co-occurrence
+    tables), rows in the order of volumes_ml, "lobes": {label: {"parenchyma": the row of the whole lobe, "lesion": that of the
+    lobe's voxels inside the kept mask}}}, the layout of `density`.  `texture` without `scan` is a ValueError.  Without the
+    keyword nothing of that is computed and the result has no such key."""
     mask = _device_u8(mask)
     dev = mask.device
+    if texture and scan is None:
+        raise ValueError("lesion_report: texture needs the scan")
     if scan is not None:
         scan = torch.as_tensor(scan)
         if scan.dtype != torch.int16 or scan.shape != mask.shape:
@@ -189,4 +196,17 @@ def lesion_report(mask, lobe, spacing, connectivity=1, min_volume_mm3=0.0, refer
     if shape:
         from .shape import lesion_shape
         out["shape"] = lesion_shape(labels, n_kept, spacing)
+    if texture:
+        from .density import row_of
+        from .texture import lesion_texture
+        scan = scan.to(dev).contiguous()
+        kw = {} if texture is True else dict(texture)
+        if set(kw) - {"levels", "lo", "width", "distance"}:
+            raise ValueError("lesion_report: texture takes levels, lo, width and distance")
+        lobes = {}
+        if out["lobes"]:
+            top = max(out["lobes"])
+            whole, inside = lesion_texture(scan, lobe, top, **kw), lesion_texture(scan, lobe, top, mask=kept_mask, **kw)
+            lobes = {v: {"parenchyma": row_of(whole, v - 1), "lesion": row_of(inside, v - 1)} for v in out["lobes"]}
+        out["texture"] = {"lesions": lesion_texture(scan, labels, n_kept, **kw), "lobes": lobes}
     return out

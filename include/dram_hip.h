@@ -983,6 +983,37 @@ int dram_label_depth(const float* depth, const void* labels, int label_kind, con
 int dram_label_shape_plan(int label_kind, int n);
 int dram_label_shape(const void* labels, int label_kind, int n, int64_t* cfg, int64_t* mom, int D, int H, int W, void* stream);
 
+/* ---- lesion texture report at inference (csrc/texture.hip; host arithmetic in dram_amd/texture.py): per label k = 1..n of a
+ *      label volume and per direction of the half 26-neighbourhood the grey-level co-occurrence table (GLCM) of the scan, from
+ *      which Haralick's second-order statistics (angular second moment, entropy, contrast, correlation, ...) are host
+ *      arithmetic -- what a consumer otherwise does on the host with 13 shifted copies of the scan and a scatter-add per label.
+ *      scan (int16) and labels are contiguous [D,H,W] volumes on the DEVICE, labels uint8 (label_kind 0, n <= 255) or int32
+ *      (label_kind 1), mask uint8 or NULL; a voxel with a label outside 1..n, or with mask == 0, belongs to nobody.  Null
+ *      pointers and refused sizes are DRAM_EINVAL before anything is launched.  The entry does not synchronise, allocate or
+ *      read device memory from the host; the output is initialised by the entry.  Everything is integers, accumulated by
+ *      integer atomics: no result depends on their order (the same bits every run).
+ * dram_label_glcm:
+ *   grey level   a voxel of value v has level g = min(max((v - lo) / width, 0), levels - 1) in integer arithmetic: values below
+ *                lo fall in level 0, values at or above lo + levels * width in level levels - 1.
+ *   directions   the 13 offsets (dz, dy, dx) of the half 26-neighbourhood in lexicographic order, the first non-zero component
+ *                positive: 0 (0,0,1)  1 (0,1,-1)  2 (0,1,0)  3 (0,1,1)  4 (1,-1,-1)  5 (1,-1,0)  6 (1,-1,1)  7 (1,0,-1)  8 (1,0,0)
+ *                9 (1,0,1)  10 (1,1,-1)  11 (1,1,0)  12 (1,1,1); each is multiplied by `distance`.  They are VOXEL offsets: under
+ *                anisotropic spacing the directions have different physical lengths.
+ *   glcm (n x 13 x levels x levels int64): entry [(k-1), dir, g(p), g(q)] counts the ordered pairs (p, q = p + distance *
+ *                offset[dir]) of voxels that both lie inside the volume, both carry label k and both pass the mask.  The table
+ *                is not symmetrised: the host adds the transpose.  A label without pairs gets zeros.
+ *   Refused: n < 1; label_kind other than 0, 1, or 0 with n > 255; levels outside 2..32; distance outside 1..4; width < 1; D, H
+ *   or W < 1 or > 32768; D * H * W >= 2^31; n * 13 * levels^2 >= 2^31; int32 labels or the int16 scan off their natural
+ *   alignment.  16-byte loads of the scan and of int32 labels (8-byte loads of uint8 labels and of the mask) for every piece of
+ *   eight voxels of a row that is so aligned and wholly inside the row; any alignment and any size work.
+ * dram_label_glcm_plan: which of the entry's two kernels a call takes, a function of these four arguments alone, answered
+ *   without a GPU: 0 = the table of the call (n * 13 * levels^2 <= 24576 32-bit words) fits in LDS beside the staged planes,
+ *   is kept per block and flushed once; 1 = runs of equal (label, direction, g(p), g(q)) are reduced within a wave and sent to
+ *   global memory with integer atomics.  Negative (DRAM_EINVAL) for arguments that dram_label_glcm refuses. ---- */
+int dram_label_glcm_plan(int label_kind, int n, int levels, int distance);
+int dram_label_glcm(const int16_t* scan, const void* labels, int label_kind, const uint8_t* mask, int n, int lo, int width,
+                    int levels, int distance, int64_t* glcm, int D, int H, int W, void* stream);
+
 /* ---- heat-map evaluation curves at inference (csrc/curves.hip): the joint histogram of score bin x class x region of a
  *      probability map against a reference mask, from which ROC, precision / recall, the Dice sweep and a calibration table are
  *      exact host arithmetic (dram_amd/curves.py) -- what a consumer otherwise does with sklearn on every lung voxel.  Volumes are
